@@ -10,8 +10,17 @@ Contract (one JSON line on rank 0):
 A "step" is one complete sort of one batch of synthetic keys already resident in HBM.  Every
 step sorts its own pre-generated input buffer (seed = step index), so no restore copy sits in
 the timed region (the reference restores inputs outside its timed call, lsb/sort.cu:141-146).
+At most INPUT_RING input buffers are held at once: with more steps than that, the timed steps run
+in chunks of INPUT_RING, and the next chunk's inputs are generated between chunks with the clock
+stopped (value and ms_per_step are over the K timed steps only).
 
-Also reported on the same line:
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the
+outputs (--dump-outputs DIR) and print the line (value, ms_per_step, step_ms_device).
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy in
+float64 (the u32 keys exactly): the whole array up to DUMP_MAX elements, above that a fixed
+seeded sample of DUMP_MAX positions (the same positions in every run of the same size).
+
+With --full, also reported on the same line (as before this option existed):
   verified     -- the LAST timed step's output checked on the device outside the timed region (sortedness + the
                   multiset checksum of its input, taken before the sort)
   also         -- N = 1, default workload only: BASELINE.json configs[2] (LSB pairs), configs[3] (MSB Zipf keys), MSB
@@ -23,8 +32,10 @@ Also reported on the same line:
                   measured live with hipEvents on the launch stream during the timed steps.
   cpu_baseline -- the reference's CPU check sort (std::sort) timed on this host on a bounded
                   sample of the same workload (oracle/cpu_baseline.cpp; checker only).
+  whole_sort, kernels_ms_total, box, stages_ms_serialised and the communicator self-test under `rccl`.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -36,6 +47,9 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md
 LSB_BYTES_PER_KEY = {False: 48, True: 80}       # (4 + 8) x 4 passes; pairs (4 + 16) x 4
 DOWNSWEEP_BYTES_PER_KEY = {False: 8, True: 16}  # read + write keys (+ values) per launch
+INPUT_RING = 16                 # input buffers held at once (4 GiB each at 2^30 keys; twice that with values)
+DUMP_MAX = 1 << 21              # elements per dumped array (8 B each in float64)
+DUMP_SEED = 20240917
 
 
 def parse_args():
@@ -67,7 +81,33 @@ def parse_args():
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="launch plumbing only (CPU, gloo): spawn the ranks, rendezvous, one all_reduce, rank 0 prints a "
                          "JSON line with n_gpus -- what tests/test_bench_launch.py runs where there is no GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the `also` workloads, the CPU baseline, per-kernel roofline, "
+                         "the device-side check of the last step, box facts, stage breakdown, communicator self-test")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64)")
     return ap.parse_args()
+
+
+def dump_sample_index(count):
+    """Positions dumped from an output of `count` elements: all of them up to DUMP_MAX, else one seeded position in each
+    of DUMP_MAX equal strata (sorted, distinct, identical from run to run for the same count)."""
+    import numpy as np
+    if count <= DUMP_MAX:
+        return np.arange(count, dtype=np.int64)
+    stride = count // DUMP_MAX
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.arange(DUMP_MAX, dtype=np.int64) * stride + rng.integers(0, stride, DUMP_MAX, dtype=np.int64)
+
+
+def dump_outputs(torch, out_dir, arrays):
+    """arrays: {name: (1-D int32 device tensor holding u32 bit patterns, count)} -> out_dir/<name>.npy in float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (t, count) in arrays.items():
+        idx = dump_sample_index(int(count))
+        sel = t[:count].index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), sel.cpu().numpy().view(np.uint32).astype(np.float64))
 
 
 def self_launch(args):
@@ -324,16 +364,19 @@ def main():
     # the five arrays of the `also` workloads are allocated FIRST, the way a long-lived caller holds its sort buffers from start-up
     # on: what the pairs sort takes depends on where its arrays lie (profiles/README.md, round 3), and arrays allocated after the
     # headline's 23 x 4 GiB of inputs have been freed landed on the slow side in every run (4.0-4.2 ms per downsweep against 3.3)
-    also_wanted = (world == 1 and not args.force_sharded and not args.one_rank_rccl and algo == "lsb" and not args.pairs
-                   and args.dist == "uniform" and not args.no_also and args.also_steps > 0)
+    also_wanted = (args.full and world == 1 and not args.force_sharded and not args.one_rank_rccl and algo == "lsb"
+                   and not args.pairs and args.dist == "uniform" and not args.no_also and args.also_steps > 0)
     also_bufs = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(5)] if also_wanted and not args.also_late_alloc else None
-    # one input buffer per step (4 GiB each at 2^30): nothing but the sort runs in the timed region
-    inputs = [gen(n, seed=i, start=rank * n, device=dev) for i in range(total)]
+    # one input buffer per step (4 GiB each at 2^30): nothing but the sort runs in the timed region.  At most INPUT_RING of
+    # them at a time; slot i % ring holds step i's input (holds[slot] = that step), refilled between chunks of timed steps
+    ring = min(total, INPUT_RING)
+    inputs = [gen(n, seed=i, start=rank * n, device=dev) for i in range(ring)]
     alt = torch.empty(n, dtype=torch.int32, device=dev)
     vals = vals_alt = None
     if args.pairs:
-        vals = [gs.generate_enumerated_values(n, device=dev) for _ in range(total)]
+        vals = [gs.generate_enumerated_values(n, device=dev) for _ in range(ring)]
         vals_alt = torch.empty(n, dtype=torch.int32, device=dev)
+    holds = list(range(ring))
 
     sharded_path = world > 1 or args.force_sharded
     comm_info = None
@@ -341,7 +384,7 @@ def main():
         # what the COMMUNICATOR says (not argv), and a start-up check that it delivers a 1 GiB + 4 byte message whole
         from gpu_sort_amd import sharded as _sh
         comm_info = {"ranks": dist.get_world_size(), "backend": dist.get_backend(), "rank0_device": str(dev)}
-        if not args.rehearse_on_one_gpu:
+        if args.full and not args.rehearse_on_one_gpu:
             comm_info["selftest_words_per_rank"] = _sh.communicator_selftest(dev)      # MAX_MSG words; raises on a truncated message
             try:        # informational: a message above the cap (the sorter never sends one)
                 _sh.communicator_selftest(dev, elements=(1 << 28) + 1)
@@ -369,42 +412,78 @@ def main():
     last = {}
 
     def one_step(i):
+        s = i % ring
         if sharded_path:
-            sk, sv, cnt = runner.sort(inputs[i], vals[i] if args.pairs else None)
+            sk, sv, cnt = runner.sort(inputs[s], vals[s] if args.pairs else None)
+            last["sharded"] = (sk, sv, cnt)
             if args.verify:
                 checks.append(runner.verify(sk, cnt, pre[i])[0])
             return
+        res_v = None
         if algo == "lsb":
-            dk = gs.DoubleBuffer(inputs[i], alt)
+            dk = gs.DoubleBuffer(inputs[s], alt)
             if args.pairs:
-                dv = gs.DoubleBuffer(vals[i], vals_alt)
+                dv = gs.DoubleBuffer(vals[s], vals_alt)
                 gs.DeviceRadixSort.SortPairs(temp, nbytes, dk, dv, n, key_type=gs.GS_KEY_U32)
+                res_v = dv.Current()
             else:
                 gs.DeviceRadixSort.SortKeys(temp, nbytes, dk, n, key_type=gs.GS_KEY_U32)
             res = dk.Current()
         else:
-            seq = gs.rdxsrt_unstable_sort(inputs[i], vals[i] if args.pairs else None, n, alt, vals_alt,
+            seq = gs.rdxsrt_unstable_sort(inputs[s], vals[s] if args.pairs else None, n, alt, vals_alt,
                                           pre_allocated_dm=temp, synchronize=False)
             res = seq.sorted_keys
-        last["res"] = res
+            res_v = seq.sorted_values if args.pairs else None
+        last["res"], last["vals"] = res, res_v
         if args.verify:
-            checks.append(res)
+            pending.append((i, res))
 
     def barrier():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
 
-    last_pre = None
-    if not sharded_path:
-        last_pre = gs.check_sorted(inputs[total - 1])[1:]     # multiset checksum of the LAST timed step's input
-    pre = None
-    if args.verify and not sharded_path:
-        pre = [gs.check_sorted(inputs[i])[1:] for i in range(total)]
-    elif args.verify:
-        pre = [runner.input_checksum(inputs[i]) for i in range(total)]
+    # multiset checksums of inputs, taken when they are generated: every step's with --verify, else (--full) the LAST
+    # timed step's, for the check of its output
+    pre = {}
+
+    def note_pre(i):
+        s = i % ring
+        if args.verify:
+            pre[i] = runner.input_checksum(inputs[s]) if sharded_path else gs.check_sorted(inputs[s])[1:]
+        elif args.full and not sharded_path and i == total - 1:
+            pre[i] = gs.check_sorted(inputs[s])[1:]
+
+    def refill(i0):
+        """inputs (and values) of steps i0 .. i0 + ring - 1 into their slots, exactly as they were first generated"""
+        for i in range(i0, min(i0 + ring, total)):
+            s = i % ring
+            gen(n, seed=i, start=rank * n, device=dev, out=inputs[s])
+            if args.pairs:
+                gs.generate_enumerated_values(n, device=dev, out=vals[s])
+            holds[s] = i
+            note_pre(i)
+
+    # --verify, single-GPU paths: outputs checked before their slots are refilled (outside the timed region)
+    pending = []
+
+    def settle_checks():
+        for i, res in pending:
+            inv, s, x = gs.check_sorted(res)
+            checks.append(inv == 0 and (s, x) == pre[i])
+        pending.clear()
+
+    def ensure(i):
+        if holds[i % ring] != i:
+            settle_checks()
+            refill(i)
+            barrier()
+
+    for i in range(ring):
+        note_pre(i)
 
     for i in range(warmup):
+        ensure(i)
         one_step(i)
     barrier()
     # N > 1 (or the one-rank RCCL group): whether finishing group g while groups g+1.. are in flight pays depends on
@@ -428,20 +507,30 @@ def main():
             probe[g] = round(float(t.item()), 3)
         runner.groups = min(probe, key=probe.get)
         barrier()
-    prof = gs.KernelProfile()
+    # --full: per-kernel hipEvent spans on the launch stream during the timed steps (roofline, kernels_ms_total)
+    prof = gs.KernelProfile() if args.full else None
     # BASELINE.md sections 3-4 / SURVEY.md 8d: besides the wall clock over the K steps (the contract's `value`), every
     # step is bracketed by an event pair on the stream the sort is enqueued on -> median and min of the per-step device time
     step_events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
-    t0 = time.perf_counter()
-    with prof:
-        for i in range(warmup, total):
-            ea, eb = step_events[i - warmup]
-            ea.record()
-            one_step(i)
-            eb.record()
-    barrier()
-    elapsed = time.perf_counter() - t0
-    kernels = prof.read()
+    elapsed = 0.0
+    i = warmup
+    while i < total:                     # one chunk: the consecutive steps whose inputs are in their slots
+        ensure(i)
+        j = i
+        while j < total and holds[j % ring] == j:
+            j += 1
+        t0 = time.perf_counter()
+        with prof if prof is not None else contextlib.nullcontext():
+            for k in range(i, j):
+                ea, eb = step_events[k - warmup]
+                ea.record()
+                one_step(k)
+                eb.record()
+        barrier()
+        elapsed += time.perf_counter() - t0
+        i = j
+    settle_checks()
+    kernels = prof.read() if prof is not None else {}
     step_ms = sorted(a.elapsed_time(b) for a, b in step_events)
 
     if world > 1:
@@ -449,13 +538,27 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # outside the timed region: one more sharded sort with a host synchronisation after every stage and the
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (rank 0's slice when sharded), before anything else runs on it
+        if sharded_path:
+            sk, sv, cnt = last["sharded"]
+            outs = {"sorted_keys": (sk, int(cnt))}
+            if args.pairs:
+                outs["sorted_values"] = (sv, int(cnt))
+        else:
+            outs = {"sorted_keys": (last["res"], n)}
+            if args.pairs:
+                outs["sorted_values"] = (last["vals"], n)
+        dump_outputs(torch, args.dump_outputs, outs)
+
+    # outside the timed region (--full): one more sharded sort with a host synchronisation after every stage and the
     # exchange as ONE collective, so that the exchange time is broken out (max over ranks)
     stages = None
     groups_used = runner.last.get("groups") if sharded_path and runner.last else None
-    if sharded_path and not args.algo:
+    if args.full and sharded_path and not args.algo:
         runner.stage_times = {}
-        runner.sort(inputs[-1], vals[-1] if args.pairs else None)
+        s = (total - 1) % ring                  # the last step's slot
+        runner.sort(inputs[s], vals[s] if args.pairs else None)
         st, runner.stage_times = runner.stage_times, None
         if st:
             names = ["first_pass_ms", "exchange_ms", "finish_ms"]
@@ -465,16 +568,11 @@ def main():
             stages = {k: round(float(v), 3) for k, v in zip(names, t.tolist())}
 
     verified = None
-    if not sharded_path and not args.verify:
+    if args.full and not sharded_path and not args.verify:
         # the last timed step's output, checked outside the timed region: sorted + same multiset as its input
         inv, sm, xr = gs.check_sorted(last["res"])
-        verified = inv == 0 and (sm, xr) == last_pre
-    if args.verify and not sharded_path:
-        verified = True
-        for j, res in enumerate(checks):
-            inv, s, x = gs.check_sorted(res)
-            verified = verified and inv == 0 and (s, x) == pre[j]
-    elif args.verify:
+        verified = inv == 0 and (sm, xr) == pre[total - 1]
+    if args.verify:
         verified = all(checks)
 
     if comm_info is not None and sharded_path and runner.last:
@@ -492,7 +590,7 @@ def main():
         roofline = None
         whole = None
         census = None
-        if algo == "msb" and not sharded_path:
+        if args.full and algo == "msb" and not sharded_path:
             # the MSB path's bytes are data-dependent -> from the census of the last timed sort (what every
             # level partitioned / handed to local sorts); the roofline entry is the kernel group that took the most time
             from gpu_sort_amd.msb import msb_census, msb_algorithmic_bytes
@@ -526,13 +624,13 @@ def main():
                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                         "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(avg_ms, 4),
                         "launches": cnt}
-        if algo == "lsb" and world == 1 and not sharded_path:
+        if args.full and algo == "lsb" and world == 1 and not sharded_path:
             gbs = LSB_BYTES_PER_KEY[args.pairs] * n / (ms_per_step * 1e-3) / 1e9
             whole = {"algorithmic_bytes_per_key": LSB_BYTES_PER_KEY[args.pairs], "achieved_GBps": round(gbs, 1),
                      "frac_of_peak": round(gbs / HBM_PEAK_GBS, 4),
                      "logical_GBps_cub_style": round(8 * n / (ms_per_step * 1e-3) / 1e9, 1)}
         also = None
-        if (world == 1 and not sharded_path and algo == "lsb" and not args.pairs and args.dist == "uniform"
+        if (args.full and world == 1 and not sharded_path and algo == "lsb" and not args.pairs and args.dist == "uniform"
                 and not args.no_also and args.also_steps > 0):
             inputs.clear()
             last.clear()
@@ -541,7 +639,7 @@ def main():
             torch.cuda.empty_cache()
             also = also_configs(gs, torch, dev, n, args.also_steps, args.log2n, also_bufs)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(min(args.cpu_sample_log2, args.log2n), args.pairs)
         line = {
             "metric": "Gkeys/s sorting 2^30 uint32 keys; achieved HBM GB/s vs roofline",
@@ -560,8 +658,9 @@ def main():
                                      if sharded_path else algo),
                        "distribution": args.dist, "parallelism": "single" if not sharded_path else f"msb_bucket_shard{world}"},
             "stages_ms_serialised": stages, "rccl": comm_info,
-            "roofline": roofline, "whole_sort": whole, "cpu_baseline": cpu, "also": also, "box": box_facts(torch, dev),
-            "kernels_ms_total": {k: [round(v[0], 3), v[1]] for k, v in kernels.items()},
+            "roofline": roofline, "whole_sort": whole, "cpu_baseline": cpu, "also": also,
+            "box": box_facts(torch, dev) if args.full else None, "full": bool(args.full),
+            "kernels_ms_total": {k: [round(v[0], 3), v[1]] for k, v in kernels.items()} if args.full else None,
         }
         if verified is not None:
             line["verified"] = bool(verified)

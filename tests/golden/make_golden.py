@@ -10,6 +10,9 @@ the masked key -- the InitializeSolution rule (test_device_radix_sort.cu
 :634-693): an independent implementation, NOT oracle.c and NOT the GPU path.
 
 Run from the repo root in the build container:  python tests/golden/make_golden.py
+`python tests/golden/make_golden.py mt` writes only tests/golden/mt19937_ref_stream.npz: the first words of the
+reference's MT19937 after init_by_array{0x123,0x234,0x345,0x456} and after init_genrand(12345), so that the
+oracle's generator is pinned against the reference's output where the reference tree is not at hand.
 """
 import ctypes as C
 import os
@@ -25,12 +28,27 @@ SIZES = [0, 1, 2, 255, 256, 257, 6911, 6912, 6913, 8191, 8192, 8193, (1 << 14) +
 FULL = ((0, 32), (1, 31), (15, 17))
 
 
-def ref_stream(nwords):
+def ref_stream(nwords, seed=None):
+    """MT19937 words of the reference's build: after init_by_array{0x123,...} or, given `seed`, init_genrand(seed)."""
     R = C.CDLL(REF)
     R.ref_mt_genrand_int32.restype = C.c_uint32
-    init = (C.c_uint32 * 4)(0x123, 0x234, 0x345, 0x456)
-    R.ref_mt_init_by_array(init, 4)
+    if seed is None:
+        init = (C.c_uint32 * 4)(0x123, 0x234, 0x345, 0x456)
+        R.ref_mt_init_by_array(init, 4)
+    else:
+        R.ref_mt_init_genrand.argtypes = [C.c_uint32]
+        R.ref_mt_init_genrand(seed)
     return np.array([R.ref_mt_genrand_int32() for _ in range(nwords)], dtype=np.uint32)
+
+
+MT_GENRAND_SEED = 12345
+
+
+def main_mt():
+    path = os.path.join(ROOT, "tests", "golden", "mt19937_ref_stream.npz")
+    np.savez_compressed(path, by_array=ref_stream(5000), genrand_seed=np.array(MT_GENRAND_SEED, dtype=np.uint32),
+                        by_genrand=ref_stream(2000, MT_GENRAND_SEED))
+    print(path, os.path.getsize(path), "bytes")
 
 
 def random_bits(stream, n, entropy_reduction):
@@ -76,4 +94,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main_mt() if sys.argv[1:] == ["mt"] else main()

@@ -15,18 +15,21 @@ def test_mt19937_known_answer(oracle):
 
 
 def test_mt19937_matches_reference_build(oracle):
-    R = oracle.ref_mersenne()
-    if R is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    init = (C.c_uint32 * 4)(0x123, 0x234, 0x345, 0x456)
-    R.ref_mt_init_by_array(init, 4)
+    # the reference build's words, recorded in tests/golden/mt19937_ref_stream.npz (make_golden.py mt); when oracle/_ref
+    # is built here as well, the live reference library is held against the same words
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mt19937_ref_stream.npz"))
+    seed = int(ref["genrand_seed"])
     oracle.lib().orc_mt_init_cub_default()
-    for _ in range(5000):
-        assert R.ref_mt_genrand_int32() == oracle.lib().orc_mt_genrand_int32()
-    R.ref_mt_init_genrand(12345)
-    oracle.lib().orc_mt_init_genrand(12345)
-    for _ in range(2000):
-        assert R.ref_mt_genrand_int32() == oracle.lib().orc_mt_genrand_int32()
+    assert [oracle.lib().orc_mt_genrand_int32() for _ in range(ref["by_array"].size)] == ref["by_array"].tolist()
+    oracle.lib().orc_mt_init_genrand(seed)
+    assert [oracle.lib().orc_mt_genrand_int32() for _ in range(ref["by_genrand"].size)] == ref["by_genrand"].tolist()
+    R = oracle.ref_mersenne()
+    if R is not None:
+        init = (C.c_uint32 * 4)(0x123, 0x234, 0x345, 0x456)
+        R.ref_mt_init_by_array(init, 4)
+        assert [R.ref_mt_genrand_int32() for _ in range(ref["by_array"].size)] == ref["by_array"].tolist()
+        R.ref_mt_init_genrand(seed)
+        assert [R.ref_mt_genrand_int32() for _ in range(ref["by_genrand"].size)] == ref["by_genrand"].tolist()
 
 
 def test_random_bits_matches_golden_inputs(oracle, golden):

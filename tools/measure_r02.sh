@@ -5,19 +5,19 @@ set -e
 export TMPDIR=/tmp
 R=$PWD
 O=$R/gpurun_out/${GS_MEASURE_TAG:-r02_v1}; mkdir -p $O
-python bench.py --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err
 echo bench-done
-python bench.py --pairs --no-cpu-baseline > $O/bench_pairs.json 2>> $O/bench.err
-python bench.py --algo msb --no-cpu-baseline > $O/bench_msb.json 2>> $O/bench.err
-python bench.py --algo msb --dist zipf --no-cpu-baseline > $O/bench_msb_zipf.json 2>> $O/bench.err
-python bench.py --algo msb --pairs --no-cpu-baseline > $O/bench_msb_pairs.json 2>> $O/bench.err
-python bench.py --dist zipf --no-cpu-baseline > $O/bench_lsb_zipf.json 2>> $O/bench.err
-python bench.py --force-sharded --verify --no-cpu-baseline > $O/bench_sharded1.json 2>> $O/bench.err
+python bench.py --full --pairs --no-cpu-baseline > $O/bench_pairs.json 2>> $O/bench.err
+python bench.py --full --algo msb --no-cpu-baseline > $O/bench_msb.json 2>> $O/bench.err
+python bench.py --full --algo msb --dist zipf --no-cpu-baseline > $O/bench_msb_zipf.json 2>> $O/bench.err
+python bench.py --full --algo msb --pairs --no-cpu-baseline > $O/bench_msb_pairs.json 2>> $O/bench.err
+python bench.py --full --dist zipf --no-cpu-baseline > $O/bench_lsb_zipf.json 2>> $O/bench.err
+python bench.py --full --force-sharded --verify --no-cpu-baseline > $O/bench_sharded1.json 2>> $O/bench.err
 (cd gpu-sort_amd/drivers && ./msb_sharded --log2n 30 --reps 3 2>/dev/null | tail -1) > $O/msb_sharded_cpp_one_rank.json
 echo variants-done
 prof() { # name, bench args...
   local name=$1; shift
-  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -- python3 $R/bench.py "$@" --steps 3 --warmup 1 --no-cpu-baseline > $O/profiled_bench_$name.json 2> $O/prof_$name.err)
+  (cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -- python3 $R/bench.py --full "$@" --steps 3 --warmup 1 --no-cpu-baseline > $O/profiled_bench_$name.json 2> $O/prof_$name.err)
 }
 prof lsb
 prof pairs --pairs

@@ -5,11 +5,11 @@ set -e
 export TMPDIR=/tmp
 R=$PWD
 O=$R/gpurun_out/${GS_MEASURE_TAG:-r03_v1}; mkdir -p $O
-python bench.py --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err
 echo bench-done
 prof() { # name, bench args...
   local name=$1; shift
-  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -- python3 $R/bench.py "$@" --steps 3 --warmup 1 --no-cpu-baseline --no-also > $O/profiled_bench_$name.json 2> $O/prof_$name.err)
+  (cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -- python3 $R/bench.py --full "$@" --steps 3 --warmup 1 --no-cpu-baseline --no-also > $O/profiled_bench_$name.json 2> $O/prof_$name.err)
 }
 prof lsb
 prof pairs --pairs
