@@ -17,6 +17,7 @@ from ._lib import (GpuSortError, GS_KEY_U32, GS_KEY_I32, GS_KEY_F32, GS_KEY_U64,
 from .lsb import DoubleBuffer, DeviceRadixSort, DeviceSegmentedRadixSort, sortKeysGPU, sortPairsGPU, lsb_pass_kernels
 from .datagen import (generate_random_keys, generate_uniform_keys, generate_zipf_keys, generate_enumerated_values,
                       check_sorted, check_pairs_enumerated)
-from .msb import RDXSRT_SortedSequence, rdxsrt_unstable_sort, rdxsrt_unstable_sort_keys, rdxsrt_unstable_sort_pairs
+from .msb import (RDXSRT_SortedSequence, rdxsrt_unstable_sort, rdxsrt_unstable_sort_keys, rdxsrt_unstable_sort_pairs,
+                  rdxsrt_unstable_sort_large)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -35,6 +35,7 @@
 #endif
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace gs {
 
@@ -341,7 +342,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void lsb_scan_kernel(uint32_t *__rest
 //   4. keys (and values) go to LDS at their tile rank and are read back in rank
 //      order: consecutive lanes hit consecutive addresses inside a digit run.
 // Two (pairs) or three (keys only) block barriers per tile.
-template <bool HAS_VALUES>
+// OFF64: the 64-bit pass (lsb_downsweep64): gbase holds absolute u64 element offsets instead of u32 ones.
+template <bool HAS_VALUES, bool OFF64 = false>
 struct DownsweepSmem {
     uint32_t whist[LSB_WAVES][RADIX];                     // wave-private digit counters, then bases (byte offsets)
 #ifdef GS_EXP_ALLWAVE_KEYS
@@ -349,7 +351,7 @@ struct DownsweepSmem {
 #else
     uint16_t wbase[HAS_VALUES ? LSB_WAVES : 1][RADIX];    // pairs: tile-absolute base of (wave, digit), < 8192
 #endif
-    uint32_t gbase[RADIX];                                // global offset of digit run - tile-local start
+    std::conditional_t<OFF64, uint64_t, uint32_t> gbase[RADIX];   // global offset of digit run - tile-local start
     uint32_t stage[LSB_TILE * (HAS_VALUES ? 2 : 1)];      // tile in rank order; pairs interleaved {key,val}
     uint32_t dead;                                        // pipelined pass only: wave 0's wait gave up -> the tile stores nothing
 };
@@ -384,14 +386,17 @@ __device__ uint32_t gs_phase_buf[131072 * 16];   // [block][phase], n <= 2^30
 // PIPE = true: the tile is one block of lsb_pipe_pass_kernel; its chunk's scanned counts come from the scanner
 // role as {tag, value} granules (`sc`), its in-chunk prefixes from the upsweep role (`prefix16`), both published
 // write-through inside the same launch and read here with agent-scope loads.
+// OFF64 = true: the tile belongs to one slice (< 2^31 keys) of a larger array (lsb_downsweep64_kernel): the spine,
+// prefix16 and totals are the slice's own, and dbase[d] is the absolute u64 output offset of the slice's run of digit
+// d, so the global base of a digit run is dbase[d] + (signed 32-bit in-slice offset) and the stores index with 64 bits.
 constexpr uint32_t PIPE_SPIN_LIMIT = 1u << 18;   // polls (each >= one memory round trip) before a wait gives up
 
-template <bool HAS_VALUES, bool TAIL, int TW, bool BIG, bool PIPE>
-__device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES> &sm, const uint32_t t,
+template <bool HAS_VALUES, bool TAIL, int TW, bool BIG, bool PIPE, bool OFF64 = false>
+__device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES, OFF64> &sm, const uint32_t t,
     const uint32_t *__restrict__ keys_in, uint32_t *__restrict__ keys_out, const uint32_t *__restrict__ vals_in,
     uint32_t *__restrict__ vals_out, const uint32_t *__restrict__ spine, const uint16_t *__restrict__ prefix16,
     const uint32_t *__restrict__ totals, const PassParams &p, const uint64_t *__restrict__ sc, uint32_t tag,
-    uint32_t *__restrict__ error_word, const uint32_t tid_ = threadIdx.x)
+    uint32_t *__restrict__ error_word, const uint32_t tid_ = threadIdx.x, const uint64_t *__restrict__ dbase = nullptr)
 {
 #ifdef GS_EXP_ALLWAVE_KEYS
     constexpr bool ALLWAVE = true;          // experiment: every wave computes its own bases for keys too (no second barrier)
@@ -473,7 +478,13 @@ __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES> &sm, co
     // (after the key loads are in flight) wave 0, lane l: global start of digits 4l..4l+3 (exclusive scan of the totals)
     // (TAIL: inclusive scan; the tile's own counts are subtracted later)
     uint32_t dstart[4] = {0, 0, 0, 0};
-    if (w == 0) {
+    if constexpr (OFF64) {
+        // digit starts are dbase[d] (added in publish_gbase); TAIL: the slice's run of d ends at dbase[d] + totals[d]
+        if (TAIL && w == 0) {
+            const uint4 tot = reinterpret_cast<const uint4 *>(totals)[lane];
+            dstart[0] = tot.x; dstart[1] = tot.y; dstart[2] = tot.z; dstart[3] = tot.w;
+        }
+    } else if (w == 0) {
         const uint4 tot = reinterpret_cast<const uint4 *>(totals)[lane];
         const uint32_t lane_sum = tot.x + tot.y + tot.z + tot.w;
         const uint32_t ex = wave_inclusive_scan(lane_sum) - lane_sum;
@@ -539,11 +550,16 @@ __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES> &sm, co
                     if ((dmax & 3u) == (uint32_t)q) g[q] += pads;
             }
         }
-        if (!BIG) {   // byte offsets (mod 2^32; exact once the slot is added)
+        if constexpr (OFF64) {   // in-slice offsets are in (-2^13, 2^31): signed 32-bit
 #pragma unroll
-            for (int q = 0; q < 4; ++q) g[q] <<= 2;
+            for (int q = 0; q < 4; ++q) sm.gbase[4 * lane + q] = dbase[4 * lane + q] + (uint64_t)(int64_t)(int32_t)g[q];
+        } else {
+            if (!BIG) {   // byte offsets (mod 2^32; exact once the slot is added)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) g[q] <<= 2;
+            }
+            reinterpret_cast<uint4 *>(sm.gbase)[lane] = make_uint4(g[0], g[1], g[2], g[3]);
         }
-        reinterpret_cast<uint4 *>(sm.gbase)[lane] = make_uint4(g[0], g[1], g[2], g[3]);
     };
 
     // 2. rank inside the wave (the LDS count of round i is consumed one round later, so
@@ -708,9 +724,13 @@ __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES> &sm, co
         } else {
             k = sm.stage[slot];
         }
-        const uint32_t g = sm.gbase[digit(k)];
+        const auto g = sm.gbase[digit(k)];
         if (!TAIL || slot < valid) {
-            if (BIG) {
+            if constexpr (OFF64) {
+                const uint64_t dst = g + slot;
+                keys_out[dst] = tw_out(k);
+                if (HAS_VALUES) vals_out[dst] = v;
+            } else if (BIG) {
                 const uint32_t dst = g + slot;
                 keys_out[dst] = tw_out(k);
                 if (HAS_VALUES) vals_out[dst] = v;
@@ -784,6 +804,24 @@ __global__ __launch_bounds__(LSB_THREADS, HAS_VALUES ? 4 : 6) void lsb_downsweep
 #endif
     downsweep_tile<HAS_VALUES, TAIL, TW, BIG, false>(sm, t, keys_in, keys_out, vals_in, vals_out, spine, prefix16, totals, p,
                                                      nullptr, 0u, nullptr);
+}
+
+// The downsweep of one slice of the 64-bit pass (gs_large.hip): keys_in / vals_in point at the slice, keys_out / vals_out at
+// the whole output range, dbase[256] holds the slice's absolute u64 digit starts in it.  Same tile code as above.
+template <bool HAS_VALUES, bool TAIL, int TW>
+__global__ __launch_bounds__(LSB_THREADS, HAS_VALUES ? 4 : 6) void lsb_downsweep64_kernel(
+    const uint32_t n_, const uint32_t shift_, const uint32_t bits_, const uint32_t grid_,
+    const uint32_t *__restrict__ keys_in, uint32_t *__restrict__ keys_out, const uint32_t *__restrict__ totals,
+    const uint32_t *__restrict__ spine, const uint16_t *__restrict__ prefix16, const uint32_t *__restrict__ vals_in,
+    uint32_t *__restrict__ vals_out, const uint64_t *__restrict__ dbase, PassParams p)
+{
+    __shared__ __attribute__((aligned(16))) DownsweepSmem<HAS_VALUES, true> sm;
+    p.n = n_; p.shift = shift_; p.bits = bits_; p.grid = grid_;
+    const uint32_t full_tiles = p.n / (uint32_t)LSB_TILE;
+    if (!TAIL && blockIdx.x >= full_tiles) return;
+    const uint32_t t = TAIL ? full_tiles : tile_of_item_wide(blockIdx.x, full_tiles);
+    downsweep_tile<HAS_VALUES, TAIL, TW, true, false, true>(sm, t, keys_in, keys_out, vals_in, vals_out, spine, prefix16, totals, p,
+                                                            nullptr, 0u, nullptr, threadIdx.x, dbase);
 }
 
 
@@ -1108,6 +1146,40 @@ int lsb_downsweep(const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint
 #undef GS_DS
     }
     if (p.n % (uint32_t)LSB_TILE) launch_downsweep_tail(kin, kout, vin, vout, totals, p, s);   // the partial last tile
+    return (int)hipGetLastError();
+}
+
+template <int TW>
+static void launch_downsweep64(const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, const uint32_t *spine,
+                               const uint16_t *prefix16, const uint32_t *totals, const uint64_t *dbase, const PassParams &p, hipStream_t s)
+{
+    const dim3 block(LSB_THREADS), grid(p.ds_grid);
+    if (vin)
+        hipLaunchKernelGGL((lsb_downsweep64_kernel<true, false, TW>), grid, block, 0, s, p.n, p.shift, p.bits, p.grid, kin, kout,
+                           totals, spine, prefix16, vin, vout, dbase, p);
+    else
+        hipLaunchKernelGGL((lsb_downsweep64_kernel<false, false, TW>), grid, block, 0, s, p.n, p.shift, p.bits, p.grid, kin, kout,
+                           totals, spine, prefix16, vin, vout, dbase, p);
+}
+
+int lsb_downsweep64(const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, const uint32_t *spine,
+                    const uint16_t *prefix16, const uint32_t *totals, const uint64_t *dbase, const PassParams &p, hipStream_t s)
+{
+    KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
+    if (p.n >= (uint32_t)LSB_TILE) {   // full tiles
+        const int tw = (p.f32_in || p.f32_out) ? 2 : ((p.xor_in | p.xor_out) ? 1 : 0);
+        if (tw == 2) launch_downsweep64<2>(kin, kout, vin, vout, spine, prefix16, totals, dbase, p, s);
+        else if (tw == 1) launch_downsweep64<1>(kin, kout, vin, vout, spine, prefix16, totals, dbase, p, s);
+        else launch_downsweep64<0>(kin, kout, vin, vout, spine, prefix16, totals, dbase, p, s);
+    }
+    if (p.n % (uint32_t)LSB_TILE) {    // the partial last tile: one block, the general variant
+        if (vin)
+            hipLaunchKernelGGL((lsb_downsweep64_kernel<true, true, 2>), dim3(1), dim3(LSB_THREADS), 0, s, p.n, p.shift, p.bits, p.grid,
+                               kin, kout, totals, (const uint32_t *)nullptr, (const uint16_t *)nullptr, vin, vout, dbase, p);
+        else
+            hipLaunchKernelGGL((lsb_downsweep64_kernel<false, true, 2>), dim3(1), dim3(LSB_THREADS), 0, s, p.n, p.shift, p.bits, p.grid,
+                               kin, kout, totals, (const uint32_t *)nullptr, (const uint16_t *)nullptr, vin, vout, dbase, p);
+    }
     return (int)hipGetLastError();
 }
 

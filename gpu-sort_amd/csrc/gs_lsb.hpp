@@ -113,6 +113,10 @@ int lsb_upsweep(const uint32_t *keys, uint32_t *spine, uint16_t *prefix16, const
 int lsb_scan(uint32_t *spine, uint32_t *totals, uint32_t grid, hipStream_t s);
 int lsb_downsweep(const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, const uint32_t *spine,
                   const uint16_t *prefix16, const uint32_t *totals, const PassParams &p, hipStream_t s);
+// the downsweep of one slice (p.n < 2^31 keys) of the 64-bit pass (gs_large.hip): spine / prefix16 / totals are the slice's
+// own (lsb_upsweep + lsb_scan on it), dbase[256] the absolute u64 start of the slice's run of each digit in kout / vout
+int lsb_downsweep64(const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, const uint32_t *spine,
+                    const uint16_t *prefix16, const uint32_t *totals, const uint64_t *dbase, const PassParams &p, hipStream_t s);
 
 // gs_wide.hip: digit totals of the last wide pass inside its workspace
 const uint32_t *wide_totals_ptr(void *d_temp, uint64_t n);

@@ -54,6 +54,31 @@ def rdxsrt_unstable_sort(dev_keys, dev_values, key_count, dev_sorted_keys_out, d
                                  which(sv.value, dev_values, dev_sorted_values_out) if has_values else None)
 
 
+def rdxsrt_unstable_sort_large(dev_keys, dev_values, key_count, dev_keys_alt, dev_values_alt, pre_allocated_dm=None, stream=None,
+                               key_type=_lib.GS_KEY_U32, synchronize=True):
+    """rdxsrt_unstable_sort for key counts of 2^32 and more (gs_msb_sort_large_u32, key_count < 2^40; the branch the reference
+    left commented out, gpu_radix_sort.h:526-529).  32-bit keys, no or 32-bit values; ascending, unstable.  dev_keys_alt /
+    dev_values_alt are scratch of the same size; the result is ALWAYS in dev_keys / dev_values.  The call blocks the host
+    (it reads bucket sizes back) and cannot be captured into a graph."""
+    _check_buf(dev_keys, key_count, "dev_keys")
+    _check_buf(dev_keys_alt, key_count, "dev_keys_alt")
+    has_values = dev_values is not None
+    if has_values:
+        _check_buf(dev_values, key_count, "dev_values")
+        _check_buf(dev_values_alt, key_count, "dev_values_alt")
+    need = lib.gs_msb_large_temp_bytes(key_count, int(has_values))
+    dm = pre_allocated_dm
+    if dm is None:
+        dm = torch.empty(max(need, 1), dtype=torch.uint8, device=dev_keys.device)
+        if stream is not None and not synchronize:
+            dm.record_stream(stream)   # see rdxsrt_unstable_sort
+    err = lib.gs_msb_sort_large_u32(dm.data_ptr(), dm.numel(), dev_keys.data_ptr(), dev_values.data_ptr() if has_values else None,
+                                    key_count, dev_keys_alt.data_ptr(), dev_values_alt.data_ptr() if has_values else None, key_type,
+                                    _stream_ptr(stream), int(synchronize))
+    check(err, "gs_msb_sort_large_u32")
+    return RDXSRT_SortedSequence(dev_keys, dev_values if has_values else None)
+
+
 def rdxsrt_unstable_sort_keys(keys, key_count=None, device="cuda"):
     """Host array in, sorted host array out (gpu_radix_sort.h:511-541)."""
     keys = np.ascontiguousarray(keys)

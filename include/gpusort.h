@@ -20,6 +20,8 @@
  *   - counts are 64-bit in the signature; the current kernels index with
  *     32-bit offsets, so num_items must be < 2^32 (the reference caps at
  *     int / unsigned, device_radix_sort.cuh:599,606, gpu_radix_sort.h:526).
+ *     The one exception is gs_msb_sort_large_u32 (num_items < 2^40), the
+ *     branch the reference left commented out (gpu_radix_sort.h:526-529).
  */
 #ifndef GPUSORT_H_
 #define GPUSORT_H_
@@ -181,6 +183,23 @@ size_t gs_msb_wide_temp_bytes(uint64_t num_items, int key_bytes, int val_bytes);
 int gs_msb_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys, void *d_vals, uint64_t num_items,
                      void *d_keys_alt, void *d_vals_alt, int key_bytes, int val_bytes,
                      void **d_sorted_keys, void **d_sorted_vals, int key_type, void *stream, int synchronize);
+
+/* The same sort as gs_msb_sort_u32 for num_items of 2^32 and more (up to 2^40): 32-bit keys (GS_KEY_U32 / I32 / F32) with
+ * no (d_vals NULL) or 32-bit values; d_keys_alt / d_vals_alt are scratch of the same size; ascending, unstable; the result
+ * is ALWAYS in the caller's input arrays d_keys / d_vals.  One stable partition on the top byte with 64-bit offsets
+ * (keys -> alternates), then the buckets are finished in groups of < 2^32 keys by gs_msb_finish_u32; a bucket larger than
+ * a group is partitioned again on its next byte.  Arrays of up to one group (2^31 keys) simply take
+ * gs_msb_sort_u32.  The call BLOCKS the host: it reads the 256 bucket counts back after the first pass, and again after
+ * every partition of an oversized bucket; with `synchronize` it also waits for the end of the sort.  While `stream` is
+ * being captured into a HIP graph it returns hipErrorStreamCaptureUnsupported and enqueues nothing.
+ * Errors: hipErrorInvalidValue for a NULL or too-small workspace, overlapping arrays, a bad key_type or
+ * num_items >= 2^40; a synchronous call whose finish overflowed a device-side list returns hipErrorUnknown.
+ * gs_msb_large_temp_bytes is a pure host function.                                                                    */
+size_t gs_msb_large_temp_bytes(uint64_t num_items, int has_values);
+int    gs_msb_sort_large_u32(void *d_temp, size_t temp_bytes,
+                             uint32_t *d_keys, uint32_t *d_vals, uint64_t num_items,
+                             uint32_t *d_keys_alt, uint32_t *d_vals_alt,
+                             int key_type, void *stream, int synchronize);
 
 /* Census of the last gs_msb_sort_u32 that used d_temp (read back after synchronising `stream`): what every level
  * partitioned and what it handed to local sorts.  SURVEY.md 8d: the MSB path's algorithmic bytes are data-dependent --

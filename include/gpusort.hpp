@@ -373,6 +373,38 @@ RDXSRT_SortedSequence<KeyT, ValueT> rdxsrt_unstable_sort(KeyT *dev_keys, ValueT 
     }
 }
 
+// The same sort for key counts of 2^32 and more (gs_msb_sort_large_u32, key_count < 2^40): the branch the reference left
+// commented out (gpu_radix_sort.h:526-529).  32-bit keys, none (ValueT = NullType) or 32-bit values; dev_keys_alt /
+// dev_values_alt are scratch of the same size; the result is always in dev_keys / dev_values.  Synchronous; the scratch
+// is allocated per call.  Failures are reported like rdxsrt_unstable_sort's: on stderr, and {nullptr, nullptr} returned.
+namespace gpusort {
+template <typename KeyT, typename ValueT = NullType>
+RDXSRT_SortedSequence<KeyT, ValueT> rdxsrt_unstable_sort_large(KeyT *dev_keys, ValueT *dev_values, unsigned long long key_count,
+                                                               KeyT *dev_keys_alt, ValueT *dev_values_alt, hipStream_t stream = nullptr)
+{
+    constexpr bool keys_only = std::is_same<ValueT, NullType>::value;
+    static_assert(sizeof(KeyT) == 4, "32-bit keys");
+    static_assert(keys_only || sizeof(ValueT) == 4, "no or 32-bit values");
+    const bool pairs = !keys_only && dev_values != nullptr;
+    const size_t tb = gs_msb_large_temp_bytes((uint64_t)key_count, pairs ? 1 : 0);
+    void *temp = nullptr;
+    int err = (int)hipMalloc(&temp, tb ? tb : 1);
+    if (err != 0) {
+        report_failure("rdxsrt_unstable_sort_large: scratch allocation", err);
+        return RDXSRT_SortedSequence<KeyT, ValueT>{nullptr, nullptr};
+    }
+    err = gs_msb_sort_large_u32(temp, tb, reinterpret_cast<uint32_t *>(dev_keys), pairs ? reinterpret_cast<uint32_t *>(dev_values) : nullptr,
+                                (uint64_t)key_count, reinterpret_cast<uint32_t *>(dev_keys_alt),
+                                pairs ? reinterpret_cast<uint32_t *>(dev_values_alt) : nullptr, KeyTraits<KeyT>::type, stream, 1);
+    (void)hipFree(temp);
+    if (err != 0) {
+        report_failure("rdxsrt_unstable_sort_large", err);
+        return RDXSRT_SortedSequence<KeyT, ValueT>{nullptr, nullptr};
+    }
+    return RDXSRT_SortedSequence<KeyT, ValueT>{dev_keys, pairs ? dev_values : nullptr};
+}
+}  // namespace gpusort
+
 // Host-pointer conveniences (gpu_radix_sort.h:511-587): allocate, copy in, sort, copy the
 // result back from the INPUT device arrays, free.  The reference's versions return void and check nothing; these keep
 // the signature, check every runtime call, and on ANY failure (allocation, copy, sort) leave the output arrays
