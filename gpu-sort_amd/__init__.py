@@ -18,6 +18,6 @@ from .lsb import DoubleBuffer, DeviceRadixSort, DeviceSegmentedRadixSort, sortKe
 from .datagen import (generate_random_keys, generate_uniform_keys, generate_zipf_keys, generate_enumerated_values,
                       check_sorted, check_pairs_enumerated)
 from .msb import (RDXSRT_SortedSequence, rdxsrt_unstable_sort, rdxsrt_unstable_sort_keys, rdxsrt_unstable_sort_pairs,
-                  rdxsrt_unstable_sort_large)
+                  rdxsrt_unstable_sort_large, rdxsrt_unstable_sort_large_wide)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -49,6 +49,8 @@ SIGNATURES = {
     "gs_msb_sort_wide": (i32, [vp, sz, vp, vp, u64, vp, vp, i32, i32, pp, pp, i32, vp, i32]),
     "gs_msb_large_temp_bytes": (sz, [u64, i32]),
     "gs_msb_sort_large_u32": (i32, [vp, sz, vp, vp, u64, vp, vp, i32, vp, i32]),
+    "gs_msb_large_wide_temp_bytes": (sz, [u64, i32, i32]),
+    "gs_msb_sort_large_wide": (i32, [vp, sz, vp, vp, u64, vp, vp, i32, i32, i32, vp, i32]),
     "gs_msb_census": (i32, [vp, u64, i32, vp, vp]),
     "gs_msb_capacities": (None, [u64, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "gs_msb_classify_upto": (i32, [vp, sz, vp, vp, u64, i32, i32, vp]),
@@ -66,6 +68,8 @@ SIGNATURES = {
     "gs_generate_u32": (i32, [vp, u64, i32, u64, u64, i32, vp]),
     "gs_check_sorted_u32": (i32, [vp, u64, i32, vp, vp]),
     "gs_check_pairs_enumerated_u32": (i32, [vp, vp, vp, u64, vp, vp]),
+    "gs_check_sorted_u64": (i32, [vp, u64, i32, vp, vp]),
+    "gs_check_pairs_enumerated_wide": (i32, [vp, vp, vp, u64, i32, vp, vp]),
     "gs_profile_create": (vp, []),
     "gs_profile_destroy": (None, [vp]),
     "gs_profile_begin": (None, [vp]),

@@ -11,6 +11,9 @@
 //      by all of them on the stream;
 //   3. a bucket larger than a group is partitioned again by the 64-bit pass on its next byte and planned the same
 //      way (skewed inputs only).  After the last byte a range is sorted; only the twiddle is undone.
+// gs_msb_sort_large_wide is the same planner for the wide element types: the pass is the wide
+// LSB pass per slice (wide_slice_count / wide_slice_scatter: wide_downsweep64_kernel), keys keep their representation,
+// and groups are finished by msb_wide_finish (the wide MSB levels, started from the group's counts).
 #include "gs_device.hpp"
 #include "gs_lsb.hpp"
 #include <cstdlib>
@@ -34,8 +37,9 @@ static uint64_t large_limit()
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// workspace of the 64-bit pass over m keys in slices of S: per slice its spine and prefix16 (gs_lsb.hip layout), then
-// the slices' digit totals [slices][256] u32, the digit starts [slices][256] u64 and the bucket sizes [256] u64
+// workspace of the 64-bit pass over m elements in slices of S: per slice its spine and prefix16 (the layout of gs_lsb.hip's
+// pass, or of gs_wide.hip's for the wide element types), then the slices' digit totals [slices][256] u32, the digit starts
+// [slices][256] u64 and the bucket sizes [256] u64
 struct LargePassWs {
     char *slice_ws;          // slice i: spine at slice_ws + i * per_slice, prefix16 behind it
     size_t per_slice, spine_bytes;
@@ -44,26 +48,27 @@ struct LargePassWs {
     uint64_t *counts;
 };
 static inline uint64_t large_slices(uint64_t m, uint64_t S) { return m ? (m + S - 1) / S : 1; }
-static inline void large_slice_bytes(uint64_t S, size_t &spine, size_t &prefix)
+static inline void large_slice_bytes(uint64_t S, bool wide, size_t &spine, size_t &prefix)
 {
+    if (wide) { wide_slice_bytes(S, spine, prefix); return; }
     const PassParams p = lsb_make_params(S, 24, 8);
     spine = align256((size_t)RADIX * p.grid * sizeof(uint32_t));
     prefix = align256((size_t)p.num_tiles * RADIX * sizeof(uint16_t));
 }
 // (every slice is carved at the size of a full one: the last one is never larger)
-static size_t large_pass_bytes(uint64_t m, uint64_t S)
+static size_t large_pass_bytes(uint64_t m, uint64_t S, bool wide)
 {
     size_t sp, pf;
-    large_slice_bytes(S, sp, pf);
+    large_slice_bytes(S, wide, sp, pf);
     const uint64_t ns = large_slices(m, S);
     return (size_t)ns * (sp + pf) + align256((size_t)ns * RADIX * sizeof(uint32_t)) + align256((size_t)ns * RADIX * sizeof(uint64_t)) +
            align256(RADIX * sizeof(uint64_t));
 }
-static LargePassWs large_pass_carve(void *temp, uint64_t m, uint64_t S)
+static LargePassWs large_pass_carve(void *temp, uint64_t m, uint64_t S, bool wide)
 {
     LargePassWs w;
     size_t pf;
-    large_slice_bytes(S, w.spine_bytes, pf);
+    large_slice_bytes(S, wide, w.spine_bytes, pf);
     w.per_slice = w.spine_bytes + pf;
     const uint64_t ns = large_slices(m, S);
     char *c = (char *)temp;
@@ -107,46 +112,10 @@ __global__ __launch_bounds__(256) void large_untwiddle_kernel(const uint32_t *sr
         dst[i] = twiddle_out(src[i], f32, x);
 }
 
-// The 64-bit pass: stable partition of m keys (and values) on the byte at `shift`, kin -> kout, with key_type's twiddle
-// applied on read (GS_KEY_U32: none); the bucket sizes are copied to h_counts (the call waits for them).
-static int large_pass(void *temp, uint64_t S, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, uint64_t m,
-                      int shift, int key_type, uint64_t *h_counts, hipStream_t s)
-{
-    const LargePassWs w = large_pass_carve(temp, m, S);
-    const uint64_t ns = large_slices(m, S);
-    int e;
-    for (uint64_t i = 0; i < ns; ++i) {
-        const uint64_t off = i * S, len = m - off < S ? m - off : S;
-        PassParams p = lsb_make_params(len, shift, 8);
-        lsb_twiddle_masks(key_type, 0, true, false, p);
-        uint32_t *spine = (uint32_t *)(w.slice_ws + i * w.per_slice);
-        uint16_t *prefix16 = (uint16_t *)(w.slice_ws + i * w.per_slice + w.spine_bytes);
-        if ((e = lsb_upsweep(kin + off, spine, prefix16, p, s))) return e;
-        if ((e = lsb_scan(spine, w.totals + i * RADIX, p.grid, s))) return e;
-    }
-    {
-        KernelTimer kt(GS_K_OTHER, s);
-        hipLaunchKernelGGL(large_offsets_kernel, dim3(1), dim3(RADIX), 0, s, (const uint32_t *)w.totals, (uint32_t)ns,
-                           (unsigned long long *)w.dbase, (unsigned long long *)w.counts);
-    }
-    for (uint64_t i = 0; i < ns; ++i) {
-        const uint64_t off = i * S, len = m - off < S ? m - off : S;
-        PassParams p = lsb_make_params(len, shift, 8);
-        lsb_twiddle_masks(key_type, 0, true, false, p);
-        const uint32_t *spine = (const uint32_t *)(w.slice_ws + i * w.per_slice);
-        const uint16_t *prefix16 = (const uint16_t *)(w.slice_ws + i * w.per_slice + w.spine_bytes);
-        if ((e = lsb_downsweep64(kin + off, kout, vin ? vin + off : nullptr, vout, spine, prefix16, w.totals + i * RADIX,
-                                 w.dbase + i * RADIX, p, s)))
-            return e;
-    }
-    hipError_t he = hipMemcpyAsync(h_counts, w.counts, RADIX * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
-    if (he == hipSuccess) he = hipStreamSynchronize(s);
-    return (int)he;
-}
-
 struct LargeCtx {
-    uint32_t *k[2], *v[2];   // [0] = the caller's arrays (where the result goes), [1] = the alternates
-    bool pairs;
+    char *k[2], *v[2];       // [0] = the caller's arrays (where the result goes), [1] = the alternates
+    int kb, vb;              // element sizes: key bytes (4 | 8), value bytes (0: keys only)
+    bool wide;               // the wide kernel set (gs_msb_sort_large_wide); otherwise u32 keys with no or u32 values
     int key_type;
     uint64_t L;              // group size and slice size
     char *pass_ws;
@@ -156,44 +125,106 @@ struct LargeCtx {
     int synchronize;
 };
 
+// The 64-bit pass: stable partition of m elements on the byte at `shift`, kin -> kout, with key_type's twiddle applied on
+// read.  The u32 path keeps its keys twiddled (GS_KEY_U32: none); the wide path writes them back in their own representation.
+// The bucket sizes are copied to h_counts (the call waits for them).
+static int large_pass(const LargeCtx &c, const char *kin, char *kout, const char *vin, char *vout, uint64_t m, int shift, int key_type,
+                      uint64_t *h_counts)
+{
+    const uint64_t S = c.L;
+    const hipStream_t s = c.s;
+    const LargePassWs w = large_pass_carve(c.pass_ws, m, S, c.wide);
+    const uint64_t ns = large_slices(m, S);
+    int e;
+    for (uint64_t i = 0; i < ns; ++i) {
+        const uint64_t off = i * S, len = m - off < S ? m - off : S;
+        uint32_t *spine = (uint32_t *)(w.slice_ws + i * w.per_slice);
+        uint16_t *prefix16 = (uint16_t *)(w.slice_ws + i * w.per_slice + w.spine_bytes);
+        if (c.wide) {
+            if ((e = wide_slice_count(kin + off * c.kb, len, c.kb, shift, key_type, spine, prefix16, w.totals + i * RADIX, s))) return e;
+            continue;
+        }
+        PassParams p = lsb_make_params(len, shift, 8);
+        lsb_twiddle_masks(key_type, 0, true, false, p);
+        if ((e = lsb_upsweep((const uint32_t *)kin + off, spine, prefix16, p, s))) return e;
+        if ((e = lsb_scan(spine, w.totals + i * RADIX, p.grid, s))) return e;
+    }
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(large_offsets_kernel, dim3(1), dim3(RADIX), 0, s, (const uint32_t *)w.totals, (uint32_t)ns,
+                           (unsigned long long *)w.dbase, (unsigned long long *)w.counts);
+    }
+    for (uint64_t i = 0; i < ns; ++i) {
+        const uint64_t off = i * S, len = m - off < S ? m - off : S;
+        const uint32_t *spine = (const uint32_t *)(w.slice_ws + i * w.per_slice);
+        const uint16_t *prefix16 = (const uint16_t *)(w.slice_ws + i * w.per_slice + w.spine_bytes);
+        if (c.wide) {
+            if ((e = wide_slice_scatter(kin + off * c.kb, kout, vin ? vin + off * c.vb : nullptr, vout, len, c.kb, c.vb, shift, key_type,
+                                        spine, prefix16, w.dbase + i * RADIX, s)))
+                return e;
+            continue;
+        }
+        PassParams p = lsb_make_params(len, shift, 8);
+        lsb_twiddle_masks(key_type, 0, true, false, p);
+        if ((e = lsb_downsweep64((const uint32_t *)kin + off, (uint32_t *)kout, vin ? (const uint32_t *)vin + off : nullptr,
+                                 (uint32_t *)vout, spine, prefix16, w.totals + i * RADIX, w.dbase + i * RADIX, p, s)))
+            return e;
+    }
+    hipError_t he = hipMemcpyAsync(h_counts, w.counts, RADIX * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    return (int)he;
+}
+
 static int large_copy_back(const LargeCtx &c, uint64_t off, uint64_t m)
 {
-    hipError_t e = hipMemcpyAsync(c.k[0] + off, c.k[1] + off, m * sizeof(uint32_t), hipMemcpyDeviceToDevice, c.s);
-    if (e == hipSuccess && c.pairs) e = hipMemcpyAsync(c.v[0] + off, c.v[1] + off, m * sizeof(uint32_t), hipMemcpyDeviceToDevice, c.s);
+    hipError_t e = hipMemcpyAsync(c.k[0] + off * c.kb, c.k[1] + off * c.kb, m * c.kb, hipMemcpyDeviceToDevice, c.s);
+    if (e == hipSuccess && c.vb) e = hipMemcpyAsync(c.v[0] + off * c.vb, c.v[1] + off * c.vb, m * c.vb, hipMemcpyDeviceToDevice, c.s);
     return (int)e;
 }
 
-// finish the group [off, off + m) that lies in buffer `b`, its buckets (by the byte just partitioned) sized gcounts
-static int large_finish_group(const LargeCtx &c, int b, uint64_t off, uint64_t m, const uint64_t *gcounts)
+// finish the group [off, off + m) that lies in buffer `b`, its buckets (by the byte at `shift`, just partitioned) sized gcounts
+static int large_finish_group(const LargeCtx &c, int b, uint64_t off, uint64_t m, const uint64_t *gcounts, int shift)
 {
     const int o = b ^ 1;
-    int e = gs_msb_finish_u32(c.fin_ws, c.fin_bytes, c.k[b] + off, c.pairs ? c.v[b] + off : nullptr, c.k[o] + off,
-                              c.pairs ? c.v[o] + off : nullptr, m, gcounts, 1, c.key_type, c.s, c.synchronize);
+    char *kb_ = c.k[b] + off * c.kb, *ko = c.k[o] + off * c.kb;
+    char *vb_ = c.vb ? c.v[b] + off * c.vb : nullptr, *vo = c.vb ? c.v[o] + off * c.vb : nullptr;
+    int e, res = o;   // the buffer the result lands in
+    if (c.wide) {
+        // the levels below `shift` only: the result lands in either buffer, by the parity of the bytes left (msb_wide_levels)
+        int in_src = 0;
+        e = msb_wide_finish(c.fin_ws, kb_, vb_, ko, vo, m, c.kb, c.vb, gcounts, shift, c.key_type, c.s, c.synchronize, &in_src);
+        if (in_src) res = b;
+    } else {
+        e = gs_msb_finish_u32(c.fin_ws, c.fin_bytes, (uint32_t *)kb_, (uint32_t *)vb_, (uint32_t *)ko, (uint32_t *)vo, m, gcounts, 1,
+                              c.key_type, c.s, c.synchronize);
+    }
     if (e) return e;
-    return o == 0 ? 0 : large_copy_back(c, off, m);   // (a split range of odd depth: the result landed in the alternates)
+    return res == 0 ? 0 : large_copy_back(c, off, m);   // (a split range of odd depth: the result landed in the alternates)
 }
 
-// The range [off, off + m) lies in buffer `cur`; its keys agree on every byte above `shift` (twiddled form).  Partition it on
-// the byte at `shift` into the other buffer, then finish its buckets in groups, splitting the ones larger than a group.
+// The range [off, off + m) lies in buffer `cur`; its keys agree on every byte above `shift` (in the twiddled order).  Partition
+// it on the byte at `shift` into the other buffer, then finish its buckets in groups, splitting the ones larger than a group.
 static int large_range(const LargeCtx &c, uint64_t off, uint64_t m, int cur, int shift, int key_type_in)
 {
     uint64_t counts[RADIX];
     const int nb = cur ^ 1;
-    int e = large_pass(c.pass_ws, c.L, c.k[cur] + off, c.k[nb] + off, c.pairs ? c.v[cur] + off : nullptr,
-                       c.pairs ? c.v[nb] + off : nullptr, m, shift, key_type_in, counts, c.s);
+    int e = large_pass(c, c.k[cur] + off * c.kb, c.k[nb] + off * c.kb, c.vb ? c.v[cur] + off * c.vb : nullptr,
+                       c.vb ? c.v[nb] + off * c.vb : nullptr, m, shift, key_type_in, counts);
     if (e) return e;
     if (shift == 0) {
-        // every byte is ordered: the range is sorted, each bucket one value.  Undo the twiddle on the way to the caller's arrays.
+        // every byte is ordered: the range is sorted, each bucket one value.  Wide keys are in their own representation;
+        // u32 keys have their twiddle undone on the way to the caller's arrays.
+        if (c.wide) return nb == 0 ? 0 : large_copy_back(c, off, m);
         PassParams tw{};
         lsb_twiddle_masks(c.key_type, 0, false, true, tw);
         if (nb == 0 && !tw.f32_out && !tw.xor_out) return 0;
         KernelTimer kt(GS_K_OTHER, c.s);
         const uint64_t blocks = (m + 255) / 256;
         hipLaunchKernelGGL(large_untwiddle_kernel, dim3(blocks < 8192 ? (uint32_t)blocks : 8192u), dim3(256), 0, c.s,
-                           (const uint32_t *)(c.k[nb] + off), c.k[0] + off, (unsigned long long)m, tw.f32_out, tw.xor_out);
+                           (const uint32_t *)c.k[nb] + off, (uint32_t *)c.k[0] + off, (unsigned long long)m, tw.f32_out, tw.xor_out);
         if ((e = (int)hipGetLastError())) return e;
-        if (nb == 1 && c.pairs)
-            e = (int)hipMemcpyAsync(c.v[0] + off, c.v[1] + off, m * sizeof(uint32_t), hipMemcpyDeviceToDevice, c.s);
+        if (nb == 1 && c.vb)
+            e = (int)hipMemcpyAsync(c.v[0] + off * c.vb, c.v[1] + off * c.vb, m * c.vb, hipMemcpyDeviceToDevice, c.s);
         return e;
     }
     uint64_t gcounts[RADIX] = {};
@@ -202,12 +233,12 @@ static int large_range(const LargeCtx &c, uint64_t off, uint64_t m, int cur, int
         const uint64_t n_b = counts[b];
         if (n_b == 0) continue;
         if (gsize && (n_b > c.L || gsize + n_b > c.L)) {
-            if ((e = large_finish_group(c, nb, gstart, gsize, gcounts))) return e;
+            if ((e = large_finish_group(c, nb, gstart, gsize, gcounts, shift))) return e;
             for (int q = 0; q < RADIX; ++q) gcounts[q] = 0;
             gsize = 0;
         }
         if (n_b > c.L) {
-            if ((e = large_range(c, at, n_b, nb, shift - 8, GS_KEY_U32))) return e;
+            if ((e = large_range(c, at, n_b, nb, shift - 8, c.wide ? c.key_type : GS_KEY_U32))) return e;
         } else {
             if (gsize == 0) gstart = at;
             gcounts[b] = n_b;
@@ -215,8 +246,49 @@ static int large_range(const LargeCtx &c, uint64_t off, uint64_t m, int cur, int
         }
         at += n_b;
     }
-    if (gsize) e = large_finish_group(c, nb, gstart, gsize, gcounts);
+    if (gsize) e = large_finish_group(c, nb, gstart, gsize, gcounts, shift);
     return e;
+}
+
+static int large_run(LargeCtx &c, void *d_temp, uint64_t num_items, size_t pass_bytes)
+{
+    c.pass_ws = (char *)d_temp;
+    c.fin_ws = (char *)d_temp + align256(pass_bytes);
+    int e = large_range(c, 0, num_items, 0, 8 * c.kb - 8, c.key_type);
+    if (e) return e;
+    if ((e = (int)hipGetLastError())) return e;
+    return c.synchronize ? (int)hipStreamSynchronize(c.s) : 0;
+}
+
+static bool overlaps(const void *a, size_t abytes, const void *b, size_t bbytes)
+{
+    if (!a || !b) return false;
+    const char *x = (const char *)a, *y = (const char *)b;
+    return x < y + bbytes && y < x + abytes;
+}
+
+// no two of the arrays share a byte (sizes: the elements they hold)
+static bool any_overlap(const void *const arr[4], const size_t bytes[4])
+{
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (overlaps(arr[i], bytes[i], arr[j], bytes[j])) return true;
+    return false;
+}
+
+// the call reads bucket sizes back to the host: refused inside a capture (nothing is enqueued); 0 = not capturing
+static int large_capture_check(hipStream_t s)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) return (int)hipGetLastError();
+    return cs != hipStreamCaptureStatusNone ? (int)hipErrorStreamCaptureUnsupported : 0;
+}
+
+// the element types of gs_msb_sort_wide: 64-bit keys with no, 32-bit or 64-bit values, 32-bit keys with 64-bit values
+static bool wide_types_ok(int key_bytes, int val_bytes, int key_type)
+{
+    if (key_bytes == 8) return (val_bytes == 0 || val_bytes == 4 || val_bytes == 8) && key_type >= GS_KEY_U64 && key_type <= GS_KEY_F64;
+    return key_bytes == 4 && val_bytes == 8 && key_type >= GS_KEY_U32 && key_type <= GS_KEY_F32;
 }
 
 }  // namespace gs
@@ -228,13 +300,7 @@ extern "C" {
 size_t gs_msb_large_temp_bytes(uint64_t num_items, int has_values)
 {
     const uint64_t L = large_limit();
-    return align256(large_pass_bytes(num_items, L)) + gs_msb_finish_temp_bytes(L, has_values, 1);
-}
-
-static bool overlaps(const uint32_t *a, const uint32_t *b, uint64_t n)
-{
-    if (!a || !b) return false;
-    return a < b + n && b < a + n;
+    return align256(large_pass_bytes(num_items, L, false)) + gs_msb_finish_temp_bytes(L, has_values, 1);
 }
 
 int gs_msb_sort_large_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys, uint32_t *d_vals, uint64_t num_items,
@@ -248,17 +314,13 @@ int gs_msb_sort_large_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys, uin
     if (!d_keys || !d_keys_alt || (pairs && !d_vals_alt)) return hipErrorInvalidValue;
     if (!d_temp || temp_bytes < gs_msb_large_temp_bytes(num_items, pairs)) return hipErrorInvalidValue;
     {
-        const uint32_t *arr[4] = {d_keys, d_keys_alt, d_vals, pairs ? d_vals_alt : nullptr};
-        for (int i = 0; i < 4; ++i)
-            for (int j = i + 1; j < 4; ++j)
-                if (overlaps(arr[i], arr[j], num_items)) return hipErrorInvalidValue;
+        const void *arr[4] = {d_keys, d_keys_alt, d_vals, pairs ? d_vals_alt : nullptr};
+        const size_t b = num_items * sizeof(uint32_t), bytes[4] = {b, b, b, b};
+        if (any_overlap(arr, bytes)) return hipErrorInvalidValue;
     }
     GS_CLEAR_STALE_ERROR();
     hipStream_t s = (hipStream_t)stream;
-    // the call reads bucket sizes back to the host: not allowed inside a capture, and nothing is enqueued
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) != hipSuccess) return (int)hipGetLastError();
-    if (cs != hipStreamCaptureStatusNone) return hipErrorStreamCaptureUnsupported;
+    if (int ce = large_capture_check(s)) return ce;
 
     const uint64_t L = large_limit();
     if (num_items <= L)   // one group: the plain MSB sort (its workspace fits in the finish's, both sized for L keys)
@@ -266,20 +328,63 @@ int gs_msb_sort_large_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys, uin
                                stream, synchronize);
 
     LargeCtx c;
-    c.k[0] = d_keys; c.k[1] = d_keys_alt;
-    c.v[0] = d_vals; c.v[1] = pairs ? d_vals_alt : nullptr;
-    c.pairs = pairs;
+    c.k[0] = (char *)d_keys; c.k[1] = (char *)d_keys_alt;
+    c.v[0] = (char *)d_vals; c.v[1] = pairs ? (char *)d_vals_alt : nullptr;
+    c.kb = 4; c.vb = pairs ? 4 : 0;
+    c.wide = false;
     c.key_type = key_type;
     c.L = L;
-    c.pass_ws = (char *)d_temp;
-    c.fin_ws = (char *)d_temp + align256(large_pass_bytes(num_items, L));
     c.fin_bytes = gs_msb_finish_temp_bytes(L, pairs, 1);
     c.s = s;
     c.synchronize = synchronize;
-    int e = large_range(c, 0, num_items, 0, 24, key_type);
-    if (e) return e;
-    if ((e = (int)hipGetLastError())) return e;
-    return synchronize ? (int)hipStreamSynchronize(s) : 0;
+    return large_run(c, d_temp, num_items, large_pass_bytes(num_items, L, false));
+}
+
+size_t gs_msb_large_wide_temp_bytes(uint64_t num_items, int key_bytes, int val_bytes)
+{
+    const uint64_t L = large_limit();
+    return align256(large_pass_bytes(num_items, L, true)) + gs_msb_wide_temp_bytes(L, key_bytes, val_bytes);
+}
+
+int gs_msb_sort_large_wide(void *d_temp, size_t temp_bytes, void *d_keys, void *d_vals, uint64_t num_items, void *d_keys_alt,
+                           void *d_vals_alt, int key_bytes, int val_bytes, int key_type, void *stream, int synchronize)
+{
+    // argument checks touch no device
+    if (num_items >= LARGE_MAX) return hipErrorInvalidValue;
+    if (!wide_types_ok(key_bytes, val_bytes, key_type)) return hipErrorInvalidValue;   // (u32, none | u32): gs_msb_sort_large_u32
+    if (num_items == 0) return hipSuccess;
+    const bool pairs = val_bytes != 0;
+    if (pairs != (d_vals != nullptr)) return hipErrorInvalidValue;
+    if (!d_keys || !d_keys_alt || (pairs && !d_vals_alt)) return hipErrorInvalidValue;
+    if (!d_temp || temp_bytes < gs_msb_large_wide_temp_bytes(num_items, key_bytes, val_bytes)) return hipErrorInvalidValue;
+    {
+        const void *arr[4] = {d_keys, d_keys_alt, d_vals, pairs ? d_vals_alt : nullptr};
+        const size_t kb = num_items * (size_t)key_bytes, vb = num_items * (size_t)val_bytes, bytes[4] = {kb, kb, vb, vb};
+        if (any_overlap(arr, bytes)) return hipErrorInvalidValue;
+    }
+    GS_CLEAR_STALE_ERROR();
+    hipStream_t s = (hipStream_t)stream;
+    if (int ce = large_capture_check(s)) return ce;
+
+    const uint64_t L = large_limit();
+    if (num_items <= L) {   // one group: the plain wide MSB sort, whose list overflow is checked here
+        int e = gs_msb_sort_wide(d_temp, temp_bytes, d_keys, d_vals, num_items, d_keys_alt, d_vals_alt, key_bytes, val_bytes, nullptr,
+                                 nullptr, key_type, stream, 0);
+        if (e) return e;
+        return synchronize ? msb_wide_overflow(d_temp, num_items, key_bytes, val_bytes, s) : 0;
+    }
+
+    LargeCtx c;
+    c.k[0] = (char *)d_keys; c.k[1] = (char *)d_keys_alt;
+    c.v[0] = (char *)d_vals; c.v[1] = pairs ? (char *)d_vals_alt : nullptr;
+    c.kb = key_bytes; c.vb = val_bytes;
+    c.wide = true;
+    c.key_type = key_type;
+    c.L = L;
+    c.fin_bytes = gs_msb_wide_temp_bytes(L, key_bytes, val_bytes);
+    c.s = s;
+    c.synchronize = synchronize;
+    return large_run(c, d_temp, num_items, large_pass_bytes(num_items, L, true));
 }
 
 }  // extern "C"

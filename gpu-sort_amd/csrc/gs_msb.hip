@@ -2857,6 +2857,9 @@ static void mw_launch_local_sorts(const MsbWs &ws, int L, const K *sk, K *dk, co
 static size_t mw_lsb_bytes(uint64_t n, int kb, int vb) { return align256(gs_lsb_wide_temp_bytes(n, kb, vb)); }
 
 template <typename K, typename V>
+static int msb_wide_levels(const MsbWs &ws, K *buf_k[2], V *buf_v[2], uint64_t num_items, int f, uint64_t x, hipStream_t s);
+
+template <typename K, typename V>
 static int msb_wide_sort(void *d_temp, K *keys, V *vals, uint64_t num_items, K *keys_alt, V *vals_alt, int key_type, hipStream_t s)
 {
     constexpr bool pairs = !std::is_same<V, MwNoVal>::value;
@@ -2884,11 +2887,24 @@ static int msb_wide_sort(void *d_temp, K *keys, V *vals, uint64_t num_items, K *
     mw_launch_local_sorts<K, V>(ws, 0, keys_alt, keys, vals_alt, vals, f, x, s, true);
     K *buf_k[2] = {keys, keys_alt};
     V *buf_v[2] = {vals, vals_alt};
+    return msb_wide_levels<K, V>(ws, buf_k, buf_v, num_items, f, x, s);
+}
+
+// The byte levels of the wide MSB sort below its level 0, started from the level-1 bucket list that the level-0
+// classification left in `ws` (msb_wide_sort: the top byte; msb_wide_finish: a group of the large sort).  Level 0's output is
+// in buf[1]; level L partitions the byte at ws.key_bits - 8 - 8L from buf[L & 1] into buf[(L + 1) & 1], and its local sorts
+// write buf[R], R = (ws.key_bits / 8) & 1, the buffer of the last level's scatter: every element ends in buf[R] (buf[0] for
+// the whole key of gs_msb_sort_wide).
+template <typename K, typename V>
+static int msb_wide_levels(const MsbWs &ws, K *buf_k[2], V *buf_v[2], uint64_t num_items, int f, uint64_t x, hipStream_t s)
+{
+    constexpr int nclass = 2;
+    const int levels = (int)ws.key_bits / 8, R = levels & 1;
     const uint32_t tiles_all = (uint32_t)((num_items + MW_TILE - 1) / MW_TILE);
     MsbPeek *peek = msb_peek_get(s);           // a 64-bit key has 7 levels below the first; most of them are empty
     uint32_t known_b = 0, known_tiles = 0;
     bool known = false;
-    for (int L = 1; L < KB; ++L) {
+    for (int L = 1; L < levels; ++L) {
         if (peek && peek->armed) {             // see msb_run_levels
             peek->armed = false;
             if (hipEventSynchronize(peek->ev) == hipSuccess) {
@@ -2900,12 +2916,12 @@ static int msb_wide_sort(void *d_temp, K *keys, V *vals, uint64_t num_items, K *
                 known = false;
             }
         }
-        const uint32_t shift = (uint32_t)(key_bits - 8 - 8 * L);
+        const uint32_t shift = ws.key_bits - 8u - 8u * (uint32_t)L;
         const K *sk = buf_k[L & 1];
         K *dk = buf_k[(L + 1) & 1];
         const V *sv = buf_v[L & 1];
         V *dv = buf_v[(L + 1) & 1];
-        const bool last = L == KB - 1;
+        const bool last = L == levels - 1;
         uint32_t max_b = (L == 1) ? (uint32_t)RADIX : ws.max_buckets;
         uint32_t max_tiles = tiles_all + max_b + tiles_all / MSB_ALIGN_MIN_TILES + 1u;
         if (known && L >= 2) {
@@ -2930,9 +2946,45 @@ static int msb_wide_sort(void *d_temp, K *keys, V *vals, uint64_t num_items, K *
         }
         { KernelTimer kt(GS_K_MSB_PARTITION, s);
           hipLaunchKernelGGL((mw_scatter_kernel<K, V>), dim3(max_tiles), dim3(MW_THREADS), 0, s, ws, L, sk, dk, sv, dv, shift, f, x); }
-        if (!last) mw_launch_local_sorts<K, V>(ws, L, (const K *)dk, buf_k[0], (const V *)dv, buf_v[0], f, x, s, true);
+        if (!last) mw_launch_local_sorts<K, V>(ws, L, (const K *)dk, buf_k[R], (const V *)dv, buf_v[R], f, x, s, true);
     }
     return (int)hipGetLastError();
+}
+
+// a group's 256 bucket sizes, handed to the device as kernel arguments (the caller's table may change once the call returns)
+struct MwCounts { uint32_t c[RADIX]; };
+__global__ void mw_counts_kernel(MwCounts c, uint32_t *out)
+{
+    out[threadIdx.x] = c.c[threadIdx.x];
+}
+
+// msb_wide_finish (gs_lsb.hpp): the group's level 0 is its partition on the byte at `shift`.  The workspace is carved with
+// key_bits = shift + 8, so the classification and the levels sort only the bytes up to that one (the bytes above are equal).
+template <typename K, typename V>
+static int msb_wide_finish_t(void *d_temp, K *src_k, V *src_v, K *oth_k, V *oth_v, uint64_t m, const uint64_t *h_counts, int shift,
+                             int key_type, hipStream_t s, MsbWs &ws, int *in_src)
+{
+    constexpr bool pairs = !std::is_same<V, MwNoVal>::value;
+    constexpr int KB = (int)sizeof(K), VB = pairs ? (int)sizeof(V) : 0, nclass = 2;
+    ws = msb_carve((char *)d_temp + mw_lsb_bytes(m, KB, VB), m, pairs, 0, 0, MW_CAP, (uint32_t)shift + 8u);
+    const bool is_float = key_type == GS_KEY_F32 || key_type == GS_KEY_F64;
+    const bool is_signed = key_type == GS_KEY_I32 || key_type == GS_KEY_I64;
+    const int f = is_float ? 1 : 0;
+    const uint64_t x = is_signed ? (KB == 8 ? 0x8000000000000000ull : 0x80000000ull) : 0ull;
+    MwCounts hc;
+    for (int d = 0; d < RADIX; ++d) hc.c[d] = (uint32_t)h_counts[d];
+    uint32_t *counts = (uint32_t *)d_temp;     // (where msb_wide_sort's level-0 pass keeps its workspace)
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL(msb_init_kernel, dim3(1), dim3(64), 0, s, ws, (uint32_t)m);
+      hipLaunchKernelGGL(mw_counts_kernel, dim3(1), dim3(RADIX), 0, s, hc, counts); }
+    { KernelTimer kt(GS_K_MSB_CLASSIFY, s);
+      hipLaunchKernelGGL((msb_classify_kernel<false, false>), dim3(1), dim3(256), 0, s, ws, 0, (const uint32_t *)counts, nclass); }
+    K *buf_k[2] = {oth_k, src_k};
+    V *buf_v[2] = {oth_v, src_v};
+    const int R = (int)(ws.key_bits / 8) & 1;
+    mw_launch_local_sorts<K, V>(ws, 0, src_k, buf_k[R], src_v, buf_v[R], f, x, s, true);
+    *in_src = R;
+    return msb_wide_levels<K, V>(ws, buf_k, buf_v, m, f, x, s);
 }
 
 // cub::DeviceSegmentedRadixSort for the wide element types (dispatch_radix_sort.cuh:321-432 is type-generic): the structure
@@ -3540,3 +3592,32 @@ int gs_msb_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys, void *d_vals
 }
 
 }  // extern "C"
+
+namespace gs {
+
+int msb_wide_finish(void *d_temp, void *src_k, void *src_v, void *oth_k, void *oth_v, uint64_t m, int key_bytes, int val_bytes,
+                    const uint64_t *h_counts, int shift, int key_type, hipStream_t s, int synchronize, int *in_src)
+{
+    MsbWs ws;
+    int e;
+#define GS_MF(K, V) e = msb_wide_finish_t<K, V>(d_temp, (K *)src_k, (V *)src_v, (K *)oth_k, (V *)oth_v, m, h_counts, shift, key_type, s, ws, in_src)
+    if (key_bytes == 8) {
+        if (val_bytes == 0) GS_MF(uint64_t, MwNoVal);
+        else if (val_bytes == 4) GS_MF(uint64_t, uint32_t);
+        else GS_MF(uint64_t, uint64_t);
+    } else {
+        GS_MF(uint32_t, uint64_t);
+    }
+#undef GS_MF
+    if (e) return e;
+    return synchronize ? msb_sync_and_check(ws, s) : 0;
+}
+
+int msb_wide_overflow(void *d_temp, uint64_t n, int key_bytes, int val_bytes, hipStream_t s)
+{
+    const MsbWs ws = msb_carve((char *)d_temp + mw_lsb_bytes(n, key_bytes, val_bytes), n, val_bytes != 0, 0, 0, MW_CAP,
+                               (uint32_t)(8 * key_bytes));
+    return msb_sync_and_check(ws, s);
+}
+
+}  // namespace gs

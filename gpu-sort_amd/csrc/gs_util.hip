@@ -94,6 +94,61 @@ __global__ __launch_bounds__(256) void check_pairs_enum_kernel(const uint32_t *_
     }
 }
 
+// 64-bit keys: result[0] += adjacent inversions in the order of the key type's order-preserving map (sign flip; floats:
+// negative -> all bits, else the sign bit), [1] += sum splitmix64(key), [2] ^= same
+__global__ __launch_bounds__(256) void check_sorted_u64_kernel(const uint64_t *__restrict__ keys, uint64_t n, int f, uint64_t x,
+                                                               unsigned long long *__restrict__ result)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long inv = 0, sum = 0, xr = 0;
+    auto ord = [&](uint64_t k) {
+        if (f) k ^= (uint64_t)((int64_t)k >> 63) | 0x8000000000000000ull;
+        return k ^ x;
+    };
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t a = keys[i];
+        if (i + 1 < n) inv += ord(a) > ord(keys[i + 1]) ? 1u : 0u;
+        const uint64_t h = splitmix64(a);
+        sum += h;
+        xr ^= h;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        inv += __shfl_xor(inv, o, WAVE);
+        sum += __shfl_xor(sum, o, WAVE);
+        xr ^= __shfl_xor(xr, o, WAVE);
+    }
+    if (lane_id() == 0) {
+        if (inv) atomicAdd(&result[0], inv);
+        atomicAdd(&result[1], sum);
+        atomicXor(&result[2], xr);
+    }
+}
+
+// 64-bit values (row ids): result[0] += i with vals[i] >= n or keys_in[vals[i]] != keys_sorted[i] (bitwise; 32- or 64-bit
+// keys), [1] += vals[i]
+__global__ __launch_bounds__(256) void check_pairs_enum_wide_kernel(const void *__restrict__ keys_in, const void *__restrict__ keys_sorted,
+                                                                    const uint64_t *__restrict__ vals, uint64_t n, int key_bytes,
+                                                                    unsigned long long *__restrict__ result)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long bad = 0, sum = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t v = vals[i];
+        if (v >= n) ++bad;
+        else if (key_bytes == 8 ? ((const uint64_t *)keys_in)[v] != ((const uint64_t *)keys_sorted)[i]
+                                : ((const uint32_t *)keys_in)[v] != ((const uint32_t *)keys_sorted)[i]) ++bad;
+        sum += v;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        bad += __shfl_xor(bad, o, WAVE);
+        sum += __shfl_xor(sum, o, WAVE);
+    }
+    if (lane_id() == 0) {
+        if (bad) atomicAdd(&result[0], bad);
+        atomicAdd(&result[1], sum);
+    }
+}
+
 static inline uint32_t stream_grid(uint64_t n)
 {
     const uint64_t b = (n + 255) / 256;
@@ -235,6 +290,35 @@ int gs_check_pairs_enumerated_u32(const uint32_t *d_keys_in, const uint32_t *d_k
     if (num_items == 0) return hipSuccess;
     hipLaunchKernelGGL(check_pairs_enum_kernel, dim3(stream_grid(num_items)), dim3(256), 0, s, d_keys_in,
                        d_keys_sorted, d_vals, num_items, (unsigned long long *)d_result);
+    return (int)hipGetLastError();
+}
+
+int gs_check_sorted_u64(const uint64_t *d_keys, uint64_t num_items, int key_type, uint64_t *d_result, void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (key_type < GS_KEY_U64 || key_type > GS_KEY_F64) return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = zero_async(d_result, 3 * sizeof(uint64_t), s);
+    if (e != hipSuccess) return (int)e;
+    if (num_items == 0) return hipSuccess;
+    const int f = key_type == GS_KEY_F64 ? 1 : 0;
+    const uint64_t x = key_type == GS_KEY_I64 ? 0x8000000000000000ull : 0ull;
+    hipLaunchKernelGGL(check_sorted_u64_kernel, dim3(stream_grid(num_items)), dim3(256), 0, s, d_keys, num_items, f, x,
+                       (unsigned long long *)d_result);
+    return (int)hipGetLastError();
+}
+
+int gs_check_pairs_enumerated_wide(const void *d_keys_in, const void *d_keys_sorted, const uint64_t *d_vals, uint64_t num_items,
+                                   int key_bytes, uint64_t *d_result, void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (key_bytes != 4 && key_bytes != 8) return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = zero_async(d_result, 2 * sizeof(uint64_t), s);
+    if (e != hipSuccess) return (int)e;
+    if (num_items == 0) return hipSuccess;
+    hipLaunchKernelGGL(check_pairs_enum_wide_kernel, dim3(stream_grid(num_items)), dim3(256), 0, s, d_keys_in, d_keys_sorted, d_vals,
+                       num_items, key_bytes, (unsigned long long *)d_result);
     return (int)hipGetLastError();
 }
 

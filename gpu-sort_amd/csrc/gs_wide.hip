@@ -104,121 +104,33 @@ __global__ __launch_bounds__(W_THREADS, 4) void wide_downsweep_kernel(const K *_
                                                                      const uint16_t *__restrict__ prefix16,
                                                                      const uint32_t *__restrict__ totals, WideParams p)
 {
-    constexpr bool HAS_VALUES = !std::is_same<V, NoVal>::value;
+    constexpr bool HAS_VALUES = !std::is_same<V, NoVal>::value, OFF64 = false;
     constexpr size_t ELEM = sizeof(K) > (HAS_VALUES ? sizeof(V) : 1) ? sizeof(K) : sizeof(V);
+    using Off = uint32_t;
     __shared__ uint32_t whist[W_WAVES][RADIX];
     __shared__ uint32_t gbase[RADIX];
     __shared__ __attribute__((aligned(16))) unsigned char stage_raw[W_TILE * ELEM];
-    K *stage_k = reinterpret_cast<K *>(stage_raw);
+    const uint64_t *dbase = nullptr;
+#include "gs_wide_tile.inc"
+}
 
-    const int lane = lane_id(), w = wave_id();
-    const uint32_t t = tile_of_item(blockIdx.x, p.num_tiles);   // XCD-contiguous slices: neighbouring runs meet in one L2
-    const uint64_t tile_base = (uint64_t)t * W_TILE;
-    const uint32_t valid = (p.n - tile_base < (uint64_t)W_TILE) ? (uint32_t)(p.n - tile_base) : (uint32_t)W_TILE;
-    uint32_t *my = whist[w];
-    const uint32_t wbase = (uint32_t)w * (WAVE * W_KPT) + lane;
-
-    // wave 0, lane l: global start of digits 4l..4l+3 and this tile's offset inside them
-    uint32_t g0[4] = {0, 0, 0, 0};
-    if (w == 0) {
-        const uint4 tot = reinterpret_cast<const uint4 *>(totals)[lane];
-        const uint32_t lane_sum = tot.x + tot.y + tot.z + tot.w;
-        const uint32_t ex = wave_inclusive_scan(lane_sum) - lane_sum;
-        const uint32_t *sp = spine + (uint32_t)(4 * lane) * p.grid + t / W_CHUNK;
-        const uint2 pf = reinterpret_cast<const uint2 *>(prefix16 + (size_t)t * RADIX)[lane];
-        g0[0] = ex + sp[0] + (pf.x & 0xffffu);
-        g0[1] = ex + tot.x + sp[p.grid] + (pf.x >> 16);
-        g0[2] = ex + tot.x + tot.y + sp[2 * p.grid] + (pf.y & 0xffffu);
-        g0[3] = ex + tot.x + tot.y + tot.z + sp[3 * p.grid] + (pf.y >> 16);
-    }
-
-    K key[W_KPT];
-    uint32_t pos[W_KPT];
-    const K pad = (K)~(K)0;                     // twiddled all-ones: largest digit, ranked last
-    // unconditional loads from clamped indices (predicated loads are issued one round trip at a time)
-    const K *kin = keys_in + tile_base;
-#pragma unroll
-    for (int i = 0; i < W_KPT; ++i) {
-        const uint32_t idx = wbase + i * WAVE;
-        key[i] = kin[idx < valid ? idx : valid - 1u];
-    }
-#pragma unroll
-    for (int i = 0; i < W_KPT; ++i) {
-        const uint32_t idx = wbase + i * WAVE;
-        const K k = w_twiddle_in<K>(key[i], p.f_in, p.xor_in);
-        key[i] = (idx < valid) ? k : pad;
-    }
-#pragma unroll
-    for (int i = lane; i < RADIX; i += WAVE) my[i] = 0;
-#pragma unroll
-    for (int i = 0; i < W_KPT; ++i) {
-        const uint32_t d = w_digit(key[i], p);
-        uint32_t plo, phi;
-        match_digit(d, plo, phi);
-        const uint32_t lower = count_lower(plo, phi);
-        pos[i] = my[d] + lower;
-        if (lower == 0)
-            __hip_atomic_fetch_add(&my[d], (uint32_t)(__popc(plo) + __popc(phi)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    }
-#pragma unroll
-    for (int i = 0; i < W_KPT; ++i) asm volatile("" : "+v"(pos[i]));
-    __syncthreads();
-    if (w == 0) {
-        uint32_t run[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < W_WAVES; ++j) {
-            const uint4 x = reinterpret_cast<const uint4 *>(whist[j])[lane];
-            run[0] += x.x; run[1] += x.y; run[2] += x.z; run[3] += x.w;
-        }
-        const uint32_t lane_sum = run[0] + run[1] + run[2] + run[3];
-        uint4 e4;
-        e4.x = wave_inclusive_scan(lane_sum) - lane_sum;
-        e4.y = e4.x + run[0];
-        e4.z = e4.y + run[1];
-        e4.w = e4.z + run[2];
-        reinterpret_cast<uint4 *>(gbase)[lane] = make_uint4(g0[0] - e4.x, g0[1] - e4.y, g0[2] - e4.z, g0[3] - e4.w);
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int j = 0; j < W_WAVES; ++j) {
-            const uint4 x = reinterpret_cast<const uint4 *>(whist[j])[lane];
-            reinterpret_cast<uint4 *>(whist[j])[lane] = e4;
-            e4.x += x.x; e4.y += x.y; e4.z += x.z; e4.w += x.w;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < W_KPT; ++i) {
-        pos[i] += my[w_digit(key[i], p)];
-        stage_k[pos[i]] = key[i];
-    }
-    __syncthreads();
-    uint32_t dst[W_KPT];
-#pragma unroll
-    for (int i = 0; i < W_KPT; ++i) {
-        const uint32_t slot = (uint32_t)w * (WAVE * W_KPT) + i * WAVE + lane;   // wave-contiguous (see lsb_downsweep_kernel)
-        const K k = stage_k[slot];
-        dst[i] = gbase[w_digit(k, p)] + slot;
-        if (slot < valid) keys_out[dst[i]] = w_twiddle_out<K>(k, p.f_out, p.xor_out);
-    }
-    if constexpr (HAS_VALUES) {
-        V *stage_v = reinterpret_cast<V *>(stage_raw);
-        V val[W_KPT];
-        const V *vin = vals_in + tile_base;
-#pragma unroll
-        for (int i = 0; i < W_KPT; ++i) {
-            const uint32_t idx = wbase + i * WAVE;
-            val[i] = vin[idx < valid ? idx : valid - 1u];
-        }
-        __syncthreads();                       // everyone is done reading the keys
-#pragma unroll
-        for (int i = 0; i < W_KPT; ++i) stage_v[pos[i]] = val[i];
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < W_KPT; ++i) {
-            const uint32_t slot = (uint32_t)w * (WAVE * W_KPT) + i * WAVE + lane;
-            if (slot < valid) vals_out[dst[i]] = stage_v[slot];
-        }
-    }
+// the downsweep of one slice of the 64-bit pass (gs_large.hip): keys_in / vals_in point at the slice, keys_out / vals_out at
+// the whole output range, dbase[256] holds the slice's absolute u64 digit starts in it
+template <typename K, typename V>
+__global__ __launch_bounds__(W_THREADS, 4) void wide_downsweep64_kernel(const K *__restrict__ keys_in, K *__restrict__ keys_out,
+                                                                       const V *__restrict__ vals_in, V *__restrict__ vals_out,
+                                                                       const uint32_t *__restrict__ spine,
+                                                                       const uint16_t *__restrict__ prefix16,
+                                                                       const uint64_t *__restrict__ dbase, WideParams p)
+{
+    constexpr bool HAS_VALUES = !std::is_same<V, NoVal>::value, OFF64 = true;
+    constexpr size_t ELEM = sizeof(K) > (HAS_VALUES ? sizeof(V) : 1) ? sizeof(K) : sizeof(V);
+    using Off = uint64_t;
+    __shared__ uint32_t whist[W_WAVES][RADIX];
+    __shared__ __attribute__((aligned(16))) uint64_t gbase[RADIX];
+    __shared__ __attribute__((aligned(16))) unsigned char stage_raw[W_TILE * ELEM];
+    const uint32_t *totals = nullptr;
+#include "gs_wide_tile.inc"
 }
 
 // ------------------------------------------------------------------- host --
@@ -275,6 +187,52 @@ static int wide_sort(void *d_temp, void *d_keys[2], void *d_vals[2], int *select
     }
     *selector = sel;
     return hipSuccess;
+}
+
+// ---- the 64-bit pass over the wide element types (gs_large.hip), one slice of < 2^31 elements at a time.  The key type's
+// twiddle only finds the digit: keys are written back in the caller's representation, as the wide MSB levels keep them.
+void wide_slice_bytes(uint64_t S, size_t &spine, size_t &prefix)
+{
+    spine = w_spine_bytes(S);
+    prefix = w_prefix_bytes(S);
+}
+
+static WideParams wide_slice_params(uint64_t len, int shift, int key_bytes, int key_type)
+{
+    WideParams p{};
+    p.n = len; p.num_tiles = w_tiles(len); p.grid = w_grid(len);
+    p.shift = (uint32_t)shift; p.bits = RADIX_BITS; p.mask = RADIX - 1u;
+    p.f_in = p.f_out = (key_type == GS_KEY_F32 || key_type == GS_KEY_F64) ? 1 : 0;
+    p.xor_in = p.xor_out = (key_type == GS_KEY_I32 || key_type == GS_KEY_I64) ? (key_bytes == 8 ? 0x8000000000000000ull : 0x80000000ull) : 0ull;
+    return p;
+}
+
+int wide_slice_count(const void *kin, uint64_t len, int key_bytes, int shift, int key_type, uint32_t *spine, uint16_t *prefix16,
+                     uint32_t *totals, hipStream_t s)
+{
+    const WideParams p = wide_slice_params(len, shift, key_bytes, key_type);
+    { KernelTimer kt(GS_K_LSB_UPSWEEP, s);
+      if (key_bytes == 8) hipLaunchKernelGGL(wide_upsweep_kernel<uint64_t>, dim3(p.grid), dim3(W_THREADS), 0, s, (const uint64_t *)kin, spine, prefix16, p);
+      else hipLaunchKernelGGL(wide_upsweep_kernel<uint32_t>, dim3(p.grid), dim3(W_THREADS), 0, s, (const uint32_t *)kin, spine, prefix16, p); }
+    return lsb_scan(spine, totals, p.grid, s);
+}
+
+int wide_slice_scatter(const void *kin, void *kout, const void *vin, void *vout, uint64_t len, int key_bytes, int val_bytes, int shift,
+                       int key_type, const uint32_t *spine, const uint16_t *prefix16, const uint64_t *dbase, hipStream_t s)
+{
+    const WideParams p = wide_slice_params(len, shift, key_bytes, key_type);
+    KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
+#define GS_W64(K, V) hipLaunchKernelGGL((wide_downsweep64_kernel<K, V>), dim3(p.num_tiles), dim3(W_THREADS), 0, s, (const K *)kin, (K *)kout, \
+                                        (const V *)vin, (V *)vout, spine, prefix16, dbase, p)
+    if (key_bytes == 8) {
+        if (val_bytes == 0) GS_W64(uint64_t, NoVal);
+        else if (val_bytes == 4) GS_W64(uint64_t, uint32_t);
+        else GS_W64(uint64_t, uint64_t);
+    } else {
+        GS_W64(uint32_t, uint64_t);
+    }
+#undef GS_W64
+    return (int)hipGetLastError();
 }
 
 // where a wide pass leaves its digit totals inside the workspace (the MSB path for wide types reads them after its

@@ -55,3 +55,23 @@ def check_pairs_enumerated(d_keys_in, d_keys_sorted, d_vals, num_items=None, str
                                             res.data_ptr(), _stream_ptr(stream)), "gs_check_pairs_enumerated_u32")
     r = res.cpu().numpy().astype("uint64")
     return int(r[0]), int(r[1])
+
+
+def check_sorted_u64(d_keys, num_items=None, key_type=_lib.GS_KEY_U64, stream=None):
+    """64-bit keys -> (adjacent inversions in key_type's order, multiset sum, multiset xor) computed on the device."""
+    n = d_keys.numel() if num_items is None else num_items
+    res = torch.zeros(3, dtype=torch.int64, device=d_keys.device)
+    check(lib.gs_check_sorted_u64(d_keys.data_ptr(), n, key_type, res.data_ptr(), _stream_ptr(stream)), "gs_check_sorted_u64")
+    r = res.cpu().numpy().astype("uint64")
+    return int(r[0]), int(r[1]), int(r[2])
+
+
+def check_pairs_enumerated_wide(d_keys_in, d_keys_sorted, d_vals, num_items=None, stream=None):
+    """64-bit values (row ids), 32- or 64-bit keys -> (mismatches, sum of values mod 2^64) computed on the device."""
+    n = d_keys_in.numel() if num_items is None else num_items
+    res = torch.zeros(2, dtype=torch.int64, device=d_keys_in.device)
+    check(lib.gs_check_pairs_enumerated_wide(d_keys_in.data_ptr(), d_keys_sorted.data_ptr(), d_vals.data_ptr(), n,
+                                             d_keys_in.element_size(), res.data_ptr(), _stream_ptr(stream)),
+          "gs_check_pairs_enumerated_wide")
+    r = res.cpu().numpy().astype("uint64")
+    return int(r[0]), int(r[1])

@@ -149,6 +149,37 @@ def msb_classify_upto(dev_keys, dev_keys_alt, key_count, stop_level, pivot=True,
     return buckets, tasks, dm
 
 
+def rdxsrt_unstable_sort_large_wide(dev_keys, dev_values, key_count, dev_keys_alt, dev_values_alt, key_type=None, pre_allocated_dm=None,
+                                    stream=None, synchronize=True):
+    """rdxsrt_unstable_sort_large for the wide element types (gs_msb_sort_large_wide, key_count < 2^40): int64 / float64 /
+    uint64-as-int64 keys with no, int32 or int64 values, and int32 / float32 keys with int64 values (e.g. row ids of an
+    argsort).  The default key type follows the key dtype, as in rdxsrt_unstable_sort_wide.  Ascending, unstable;
+    dev_keys_alt / dev_values_alt are scratch of the same size; the result is ALWAYS in dev_keys / dev_values.  The call
+    blocks the host (it reads bucket sizes back) and cannot be captured into a graph."""
+    kb = dev_keys.element_size()
+    has_values = dev_values is not None
+    vb = dev_values.element_size() if has_values else 0
+    _check_buf(dev_keys, key_count, "dev_keys", kb)
+    _check_buf(dev_keys_alt, key_count, "dev_keys_alt", kb)
+    if has_values:
+        _check_buf(dev_values, key_count, "dev_values", vb)
+        _check_buf(dev_values_alt, key_count, "dev_values_alt", vb)
+    if key_type is None:
+        key_type = {torch.int64: _lib.GS_KEY_I64, torch.float64: _lib.GS_KEY_F64, torch.int32: _lib.GS_KEY_I32,
+                    torch.float32: _lib.GS_KEY_F32}[dev_keys.dtype]
+    need = lib.gs_msb_large_wide_temp_bytes(key_count, kb, vb)
+    dm = pre_allocated_dm
+    if dm is None:
+        dm = torch.empty(max(need, 1), dtype=torch.uint8, device=dev_keys.device)
+        if stream is not None and not synchronize:
+            dm.record_stream(stream)   # see rdxsrt_unstable_sort
+    err = lib.gs_msb_sort_large_wide(dm.data_ptr(), dm.numel(), dev_keys.data_ptr(), dev_values.data_ptr() if has_values else None,
+                                     key_count, dev_keys_alt.data_ptr(), dev_values_alt.data_ptr() if has_values else None, kb, vb,
+                                     key_type, _stream_ptr(stream), int(synchronize))
+    check(err, "gs_msb_sort_large_wide")
+    return RDXSRT_SortedSequence(dev_keys, dev_values if has_values else None)
+
+
 def rdxsrt_unstable_sort_wide(dev_keys, dev_values, key_count, dev_sorted_keys_out, dev_sorted_values_out, key_type=None,
                               dm=None, stream=None):
     """The wide element types of rdxsrt_unstable_sort (gs_msb_sort_wide): int64 / float64 / uint64-as-int64 key tensors with no,

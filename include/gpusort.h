@@ -20,8 +20,9 @@
  *   - counts are 64-bit in the signature; the current kernels index with
  *     32-bit offsets, so num_items must be < 2^32 (the reference caps at
  *     int / unsigned, device_radix_sort.cuh:599,606, gpu_radix_sort.h:526).
- *     The one exception is gs_msb_sort_large_u32 (num_items < 2^40), the
- *     branch the reference left commented out (gpu_radix_sort.h:526-529).
+ *     The exceptions are gs_msb_sort_large_u32 and gs_msb_sort_large_wide
+ *     (num_items < 2^40), the branch the reference left commented out
+ *     (gpu_radix_sort.h:526-529).
  */
 #ifndef GPUSORT_H_
 #define GPUSORT_H_
@@ -201,6 +202,22 @@ int    gs_msb_sort_large_u32(void *d_temp, size_t temp_bytes,
                              uint32_t *d_keys_alt, uint32_t *d_vals_alt,
                              int key_type, void *stream, int synchronize);
 
+/* The same for the wide element types of gs_msb_sort_wide, for num_items of 2^32 and more (up to 2^40): 64-bit keys
+ * (GS_KEY_U64 / I64 / F64) with no (d_vals NULL, val_bytes 0), 32-bit or 64-bit values, and 32-bit keys (GS_KEY_U32 / I32 /
+ * F32) with 64-bit values -- e.g. row ids for an argsort of a column of more than 2^32 rows.  (u32, none) and (u32, u32) are
+ * gs_msb_sort_large_u32's and return hipErrorInvalidValue.  The contract is gs_msb_sort_large_u32's: ascending, unstable,
+ * the result ALWAYS in d_keys / d_vals, the alternates scratch of the same size, the call blocks the host and refuses
+ * stream capture (hipErrorStreamCaptureUnsupported, nothing enqueued), num_items == 0 needs no arguments.  The first pass
+ * is the wide LSB pass with 64-bit output offsets; groups of <= 2^31 elements are finished by the wide MSB levels.  Arrays
+ * of up to one group take gs_msb_sort_wide.  Errors: hipErrorInvalidValue for a NULL or too-small workspace, a bad
+ * combination of key_bytes / val_bytes / key_type, missing alternates, values without a value alternate, overlapping
+ * arrays (at their element sizes) or num_items >= 2^40; a synchronous call whose finish overflowed a device-side list
+ * returns hipErrorUnknown.  gs_msb_large_wide_temp_bytes is a pure host function.                                    */
+size_t gs_msb_large_wide_temp_bytes(uint64_t num_items, int key_bytes, int val_bytes);
+int    gs_msb_sort_large_wide(void *d_temp, size_t temp_bytes, void *d_keys, void *d_vals, uint64_t num_items,
+                              void *d_keys_alt, void *d_vals_alt, int key_bytes, int val_bytes, int key_type,
+                              void *stream, int synchronize);
+
 /* Census of the last gs_msb_sort_u32 that used d_temp (read back after synchronising `stream`): what every level
  * partitioned and what it handed to local sorts.  SURVEY.md 8d: the MSB path's algorithmic bytes are data-dependent --
  * "the harness must log the per-pass census and compute bytes from it": level 0 moves every key once (12 B/key), a level
@@ -329,6 +346,13 @@ int gs_check_sorted_u32(const uint32_t *d_keys, uint64_t num_items, int descendi
 int gs_check_pairs_enumerated_u32(const uint32_t *d_keys_in, const uint32_t *d_keys_sorted,
                                   const uint32_t *d_vals, uint64_t num_items,
                                   uint64_t *d_result, void *stream);
+/* 64-bit keys (key_type GS_KEY_U64 / I64 / F64): d_result[0] = adjacent inversions in the order the sort produces (the key
+ * type's order-preserving map: -0.0 before +0.0, NaNs by their bits), [1] / [2] = sum / xor of splitmix64(key).       */
+int gs_check_sorted_u64(const uint64_t *d_keys, uint64_t num_items, int key_type, uint64_t *d_result, void *stream);
+/* 64-bit values, 32- or 64-bit keys (key_bytes): d_result[0] = number of i with d_vals[i] >= num_items or
+ * d_keys_in[d_vals[i]] != d_keys_sorted[i] (bitwise), [1] = sum of d_vals mod 2^64.                                   */
+int gs_check_pairs_enumerated_wide(const void *d_keys_in, const void *d_keys_sorted, const uint64_t *d_vals,
+                                   uint64_t num_items, int key_bytes, uint64_t *d_result, void *stream);
 
 /* ------------------------------------------------------ kernel timing hook --
  * Optional per-kernel device timing with hipEvents recorded on the SAME stream

@@ -373,8 +373,9 @@ RDXSRT_SortedSequence<KeyT, ValueT> rdxsrt_unstable_sort(KeyT *dev_keys, ValueT 
     }
 }
 
-// The same sort for key counts of 2^32 and more (gs_msb_sort_large_u32, key_count < 2^40): the branch the reference left
-// commented out (gpu_radix_sort.h:526-529).  32-bit keys, none (ValueT = NullType) or 32-bit values; dev_keys_alt /
+// The same sort for key counts of 2^32 and more (key_count < 2^40): the branch the reference left commented out
+// (gpu_radix_sort.h:526-529).  32-bit keys with none (ValueT = NullType) or 32-bit values take gs_msb_sort_large_u32; 64-bit
+// keys with none, 32-bit or 64-bit values, and 32-bit keys with 64-bit values take gs_msb_sort_large_wide.  dev_keys_alt /
 // dev_values_alt are scratch of the same size; the result is always in dev_keys / dev_values.  Synchronous; the scratch
 // is allocated per call.  Failures are reported like rdxsrt_unstable_sort's: on stderr, and {nullptr, nullptr} returned.
 namespace gpusort {
@@ -383,19 +384,28 @@ RDXSRT_SortedSequence<KeyT, ValueT> rdxsrt_unstable_sort_large(KeyT *dev_keys, V
                                                                KeyT *dev_keys_alt, ValueT *dev_values_alt, hipStream_t stream = nullptr)
 {
     constexpr bool keys_only = std::is_same<ValueT, NullType>::value;
-    static_assert(sizeof(KeyT) == 4, "32-bit keys");
-    static_assert(keys_only || sizeof(ValueT) == 4, "no or 32-bit values");
+    constexpr int KB = (int)sizeof(KeyT), VB = keys_only ? 0 : (int)sizeof(ValueT);
+    static_assert(KB == 4 || KB == 8, "32- or 64-bit keys");
+    static_assert(VB == 0 || VB == 4 || VB == 8, "no, 32-bit or 64-bit values");
+    constexpr bool wide = KB == 8 || VB == 8;
     const bool pairs = !keys_only && dev_values != nullptr;
-    const size_t tb = gs_msb_large_temp_bytes((uint64_t)key_count, pairs ? 1 : 0);
+    const int vb = pairs ? VB : 0;
+    size_t tb;
+    if constexpr (wide) tb = gs_msb_large_wide_temp_bytes((uint64_t)key_count, KB, vb);
+    else tb = gs_msb_large_temp_bytes((uint64_t)key_count, pairs ? 1 : 0);
     void *temp = nullptr;
     int err = (int)hipMalloc(&temp, tb ? tb : 1);
     if (err != 0) {
         report_failure("rdxsrt_unstable_sort_large: scratch allocation", err);
         return RDXSRT_SortedSequence<KeyT, ValueT>{nullptr, nullptr};
     }
-    err = gs_msb_sort_large_u32(temp, tb, reinterpret_cast<uint32_t *>(dev_keys), pairs ? reinterpret_cast<uint32_t *>(dev_values) : nullptr,
-                                (uint64_t)key_count, reinterpret_cast<uint32_t *>(dev_keys_alt),
-                                pairs ? reinterpret_cast<uint32_t *>(dev_values_alt) : nullptr, KeyTraits<KeyT>::type, stream, 1);
+    if constexpr (wide)
+        err = gs_msb_sort_large_wide(temp, tb, dev_keys, pairs ? (void *)dev_values : nullptr, (uint64_t)key_count, dev_keys_alt,
+                                     pairs ? (void *)dev_values_alt : nullptr, KB, vb, KeyTraits<KeyT>::type, stream, 1);
+    else
+        err = gs_msb_sort_large_u32(temp, tb, reinterpret_cast<uint32_t *>(dev_keys), pairs ? reinterpret_cast<uint32_t *>(dev_values) : nullptr,
+                                    (uint64_t)key_count, reinterpret_cast<uint32_t *>(dev_keys_alt),
+                                    pairs ? reinterpret_cast<uint32_t *>(dev_values_alt) : nullptr, KeyTraits<KeyT>::type, stream, 1);
     (void)hipFree(temp);
     if (err != 0) {
         report_failure("rdxsrt_unstable_sort_large", err);
@@ -406,7 +416,8 @@ RDXSRT_SortedSequence<KeyT, ValueT> rdxsrt_unstable_sort_large(KeyT *dev_keys, V
 }  // namespace gpusort
 
 // Host-pointer conveniences (gpu_radix_sort.h:511-587): allocate, copy in, sort, copy the
-// result back from the INPUT device arrays, free.  The reference's versions return void and check nothing; these keep
+// result back from the INPUT device arrays, free.  A key_count above UINT_MAX takes rdxsrt_unstable_sort_large (the
+// reference's commented-out branch): the second device array of each kind is its scratch alternate.  The reference's versions return void and check nothing; these keep
 // the signature, check every runtime call, and on ANY failure (allocation, copy, sort) leave the output arrays
 // UNTOUCHED and say why through report_failure -- the caller never receives stale or half-copied data as if it were sorted.
 template <typename KeyT>
@@ -420,8 +431,10 @@ void rdxsrt_unstable_sort_keys(KeyT *keys, const unsigned long long key_count, K
     if (err) {
         gpusort::report_failure("rdxsrt_unstable_sort_keys: device allocation / copy in", err);
     } else {
-        auto seq = rdxsrt_unstable_sort<KeyT, gpusort::NullType, unsigned int>(dev_keys, nullptr, (unsigned int)key_count,
-                                                                               dev_keys_out, nullptr);
+        auto seq = key_count > 0xffffffffull
+                       ? gpusort::rdxsrt_unstable_sort_large<KeyT, gpusort::NullType>(dev_keys, nullptr, key_count, dev_keys_out, nullptr)
+                       : rdxsrt_unstable_sort<KeyT, gpusort::NullType, unsigned int>(dev_keys, nullptr, (unsigned int)key_count,
+                                                                                      dev_keys_out, nullptr);
         if (seq.sorted_keys) {          // (a failed sort has reported itself and returned {nullptr, nullptr})
             err = (int)hipMemcpy(sorted_keys_out, seq.sorted_keys, sizeof(KeyT) * key_count, hipMemcpyDeviceToHost);
             if (err) gpusort::report_failure("rdxsrt_unstable_sort_keys: copy out", err);
@@ -447,7 +460,8 @@ void rdxsrt_unstable_sort_pairs(KeyT *keys, ValueT *values, const unsigned long 
     if (err) {
         gpusort::report_failure("rdxsrt_unstable_sort_pairs: device allocation / copy in", err);
     } else {
-        auto seq = rdxsrt_unstable_sort<KeyT, ValueT, unsigned int>(dk, dv, (unsigned int)key_count, dko, dvo);
+        auto seq = key_count > 0xffffffffull ? gpusort::rdxsrt_unstable_sort_large<KeyT, ValueT>(dk, dv, key_count, dko, dvo)
+                                             : rdxsrt_unstable_sort<KeyT, ValueT, unsigned int>(dk, dv, (unsigned int)key_count, dko, dvo);
         if (seq.sorted_keys && seq.sorted_values) {
             // both copies into scratch first would double the host memory; instead: keys, then values, and a failure of the
             // second is reported (the keys array then holds sorted keys whose values did not arrive -- said so)
