@@ -146,9 +146,9 @@ size_t gs_lsb_any_temp_bytes(uint64_t num_items, int key_type, int val_bytes)
     if (kb == 0) return 0;
     const size_t n = (size_t)num_items;
     if (kb == 8)   // (u64 sort key, u32 index) through the wide sort: 2 x keys, 2 x indices
-        return any_align(gs_lsb_wide_temp_bytes(num_items, 8, 4)) + 2 * any_align(n * 8) + 2 * any_align(n * 4);
+        return any_align(gs_lsb_wide_temp_bytes(num_items, 8, 4)) + 2 * any_align(n * 8) + 2 * any_align(n * 4) + GS_WS_SLACK;
     const bool pairs = val_bytes != 0 || kb == 4;    // 32-bit keys come here only for odd value sizes
-    return any_align(gs_lsb_temp_bytes(num_items, pairs)) + 2 * any_align(n * 4) + (pairs ? 2 * any_align(n * 4) : 0);
+    return any_align(gs_lsb_temp_bytes(num_items, pairs)) + 2 * any_align(n * 4) + (pairs ? 2 * any_align(n * 4) : 0) + GS_WS_SLACK;
 }
 
 int gs_lsb_sort_any(void *d_temp, size_t temp_bytes, const void *d_keys_in, void *d_keys_out, const void *d_vals_in,
@@ -168,7 +168,7 @@ int gs_lsb_sort_any(void *d_temp, size_t temp_bytes, const void *d_keys_in, void
     hipStream_t s = (hipStream_t)stream;
     const uint64_t n = num_items;
     const dim3 g = any_grid(n), b(256);
-    char *c = (char *)d_temp;
+    char *c = gs_ws_base(d_temp);   // the sort's workspace, then the sort keys and indices
 
     if (kb == 8) {
         const size_t sort_ws = any_align(gs_lsb_wide_temp_bytes(n, 8, 4));
@@ -177,7 +177,7 @@ int gs_lsb_sort_any(void *d_temp, size_t temp_bytes, const void *d_keys_in, void
         hipLaunchKernelGGL(any_prepare64_kernel, g, b, 0, s, (const uint64_t *)d_keys_in, sk[0], ix[0], n);
         void *k2[2] = {sk[0], sk[1]}, *v2[2] = {ix[0], ix[1]};
         int sel = 0;
-        const int e = gs_lsb_sort_wide(d_temp, sort_ws, k2, v2, &sel, n, 8, 4, begin_bit, end_bit, descending, key_type, s);
+        const int e = gs_lsb_sort_wide(c, sort_ws, k2, v2, &sel, n, 8, 4, begin_bit, end_bit, descending, key_type, s);
         if (e) return e;
         launch_gather<8>(val_bytes, ix[sel], d_keys_in, d_keys_out, d_vals_in, d_vals_out, n, s);
         return (int)hipGetLastError();
@@ -196,7 +196,7 @@ int gs_lsb_sort_any(void *d_temp, size_t temp_bytes, const void *d_keys_in, void
     else hipLaunchKernelGGL(any_prepare_kernel<4>, g, b, 0, s, d_keys_in, sk[0], ix[0], n, key_type);
     int sel = 0;
     // the sort keys are twiddled already: plain unsigned keys from here on; descending = the complement inside the sort
-    const int e = gs_lsb_sort_u32(d_temp, sort_ws, sk, pairs ? ix : nullptr, &sel, n, begin_bit, end_bit, descending, GS_KEY_U32, s);
+    const int e = gs_lsb_sort_u32(c, sort_ws, sk, pairs ? ix : nullptr, &sel, n, begin_bit, end_bit, descending, GS_KEY_U32, s);
     if (e) return e;
     if (!pairs) {
         if (kb == 1) hipLaunchKernelGGL(any_narrow_kernel<1>, g, b, 0, s, (const uint32_t *)sk[sel], d_keys_out, n, key_type);

@@ -26,6 +26,17 @@ struct gs_profile {
 // this call's own errors are reported.
 #define GS_CLEAR_STALE_ERROR() ((void)hipGetLastError())
 
+// The workspace contract (include/gpusort.h): d_temp may have any alignment.  Every public *_temp_bytes adds GS_WS_SLACK
+// once, and every public function that takes d_temp carves its layout from gs_ws_base(d_temp), d_temp rounded up to
+// GS_WS_ALIGN bytes (cub's AliasTemporaries does the same).  A function that hands part of its workspace to another public
+// one passes an aligned sub-workspace sized by that function's public query.
+constexpr size_t GS_WS_ALIGN = 256;
+constexpr size_t GS_WS_SLACK = GS_WS_ALIGN;   // (not 255: the queries stay multiples of 256)
+static inline char *gs_ws_base(void *d_temp)
+{
+    return (char *)(((uintptr_t)d_temp + (GS_WS_ALIGN - 1)) & ~(uintptr_t)(GS_WS_ALIGN - 1));
+}
+
 namespace gs {
 extern thread_local gs_profile *tl_profile;
 

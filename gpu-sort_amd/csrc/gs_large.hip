@@ -250,10 +250,12 @@ static int large_range(const LargeCtx &c, uint64_t off, uint64_t m, int cur, int
     return e;
 }
 
-static int large_run(LargeCtx &c, void *d_temp, uint64_t num_items, size_t pass_bytes)
+// `ws`: the caller's workspace rounded up (gs_ws_base); the pass's workspace, then the finishes' one (sized by the public
+// query of gs_msb_finish_temp_bytes / gs_msb_wide_temp_bytes, so it starts 256-byte aligned too)
+static int large_run(LargeCtx &c, char *ws, uint64_t num_items, size_t pass_bytes)
 {
-    c.pass_ws = (char *)d_temp;
-    c.fin_ws = (char *)d_temp + align256(pass_bytes);
+    c.pass_ws = ws;
+    c.fin_ws = ws + align256(pass_bytes);
     int e = large_range(c, 0, num_items, 0, 8 * c.kb - 8, c.key_type);
     if (e) return e;
     if ((e = (int)hipGetLastError())) return e;
@@ -300,7 +302,7 @@ extern "C" {
 size_t gs_msb_large_temp_bytes(uint64_t num_items, int has_values)
 {
     const uint64_t L = large_limit();
-    return align256(large_pass_bytes(num_items, L, false)) + gs_msb_finish_temp_bytes(L, has_values, 1);
+    return align256(large_pass_bytes(num_items, L, false)) + gs_msb_finish_temp_bytes(L, has_values, 1) + GS_WS_SLACK;
 }
 
 int gs_msb_sort_large_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys, uint32_t *d_vals, uint64_t num_items,
@@ -323,7 +325,9 @@ int gs_msb_sort_large_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys, uin
     if (int ce = large_capture_check(s)) return ce;
 
     const uint64_t L = large_limit();
-    if (num_items <= L)   // one group: the plain MSB sort (its workspace fits in the finish's, both sized for L keys)
+    // one group: the plain MSB sort on the caller's workspace, which it rounds up the same way (its query fits in the finish's,
+    // both sized for L keys)
+    if (num_items <= L)
         return gs_msb_sort_u32(d_temp, temp_bytes, d_keys, d_vals, num_items, d_keys_alt, d_vals_alt, nullptr, nullptr, key_type,
                                stream, synchronize);
 
@@ -337,13 +341,13 @@ int gs_msb_sort_large_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys, uin
     c.fin_bytes = gs_msb_finish_temp_bytes(L, pairs, 1);
     c.s = s;
     c.synchronize = synchronize;
-    return large_run(c, d_temp, num_items, large_pass_bytes(num_items, L, false));
+    return large_run(c, gs_ws_base(d_temp), num_items, large_pass_bytes(num_items, L, false));
 }
 
 size_t gs_msb_large_wide_temp_bytes(uint64_t num_items, int key_bytes, int val_bytes)
 {
     const uint64_t L = large_limit();
-    return align256(large_pass_bytes(num_items, L, true)) + gs_msb_wide_temp_bytes(L, key_bytes, val_bytes);
+    return align256(large_pass_bytes(num_items, L, true)) + gs_msb_wide_temp_bytes(L, key_bytes, val_bytes) + GS_WS_SLACK;
 }
 
 int gs_msb_sort_large_wide(void *d_temp, size_t temp_bytes, void *d_keys, void *d_vals, uint64_t num_items, void *d_keys_alt,
@@ -371,7 +375,7 @@ int gs_msb_sort_large_wide(void *d_temp, size_t temp_bytes, void *d_keys, void *
         int e = gs_msb_sort_wide(d_temp, temp_bytes, d_keys, d_vals, num_items, d_keys_alt, d_vals_alt, key_bytes, val_bytes, nullptr,
                                  nullptr, key_type, stream, 0);
         if (e) return e;
-        return synchronize ? msb_wide_overflow(d_temp, num_items, key_bytes, val_bytes, s) : 0;
+        return synchronize ? msb_wide_overflow(gs_ws_base(d_temp), num_items, key_bytes, val_bytes, s) : 0;
     }
 
     LargeCtx c;
@@ -384,7 +388,7 @@ int gs_msb_sort_large_wide(void *d_temp, size_t temp_bytes, void *d_keys, void *
     c.fin_bytes = gs_msb_wide_temp_bytes(L, key_bytes, val_bytes);
     c.s = s;
     c.synchronize = synchronize;
-    return large_run(c, d_temp, num_items, large_pass_bytes(num_items, L, true));
+    return large_run(c, gs_ws_base(d_temp), num_items, large_pass_bytes(num_items, L, true));
 }
 
 }  // extern "C"

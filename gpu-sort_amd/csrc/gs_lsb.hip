@@ -1287,7 +1287,7 @@ int gs_exp_phases(uint32_t *host_out, uint32_t blocks)
 
 size_t gs_lsb_temp_bytes(uint64_t num_items, int /*has_values*/)
 {
-    return lsb_temp_bytes(num_items);
+    return lsb_temp_bytes(num_items) + GS_WS_SLACK;
 }
 
 void gs_lsb_geometry(uint64_t num_items, int /*has_values*/, uint32_t *grid, uint32_t *tile, uint32_t *tiles_per_chunk)
@@ -1306,7 +1306,7 @@ int gs_lsb_upsweep_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_i
     if (num_items == 0) return hipSuccess;
     PassParams p = lsb_make_params(num_items, shift, bits);
     lsb_twiddle_masks(key_type_in, descending, true, true, p);
-    const LsbWorkspace ws = lsb_carve(d_temp, num_items);
+    const LsbWorkspace ws = lsb_carve(gs_ws_base(d_temp), num_items);
     return lsb_upsweep(d_keys_in, ws.spine, ws.prefix16, p, (hipStream_t)stream);
 }
 
@@ -1316,7 +1316,7 @@ int gs_lsb_scan_spine(void *d_temp, size_t temp_bytes, uint64_t num_items, void 
     if (num_items >= (1ull << 32)) return hipErrorInvalidValue;
     if (!d_temp || temp_bytes < gs_lsb_temp_bytes(num_items, 0)) return hipErrorInvalidValue;
     if (num_items == 0) return hipSuccess;
-    const LsbWorkspace ws = lsb_carve(d_temp, num_items);
+    const LsbWorkspace ws = lsb_carve(gs_ws_base(d_temp), num_items);
     return lsb_scan(ws.spine, ws.totals, lsb_grid(num_items), (hipStream_t)stream);
 }
 
@@ -1335,7 +1335,7 @@ int gs_lsb_downsweep_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys
     lsb_twiddle_masks(key_type_out, descending, false, true, out);
     p.f32_in = in.f32_in; p.xor_in = in.xor_in;
     p.f32_out = out.f32_out; p.xor_out = out.xor_out;
-    const LsbWorkspace ws = lsb_carve(d_temp, num_items);
+    const LsbWorkspace ws = lsb_carve(gs_ws_base(d_temp), num_items);
     return lsb_downsweep(d_keys_in, d_keys_out, d_vals_in, d_vals_out, ws.spine, ws.prefix16, ws.totals, p,
                          (hipStream_t)stream);
 }
@@ -1344,7 +1344,7 @@ int gs_lsb_workspace_layout(void *d_temp, uint64_t num_items, uint32_t **d_spine
                             uint16_t **d_prefix16)
 {
     GS_CLEAR_STALE_ERROR();
-    const LsbWorkspace ws = lsb_carve(d_temp, num_items);
+    const LsbWorkspace ws = lsb_carve(gs_ws_base(d_temp), num_items);
     if (d_spine) *d_spine = ws.spine;
     if (d_totals) *d_totals = ws.totals;
     if (d_prefix16) *d_prefix16 = ws.prefix16;
@@ -1357,7 +1357,7 @@ int gs_lsb_pipe_status(void *d_temp, uint64_t num_items, uint32_t *h_status, voi
     if (!d_temp || !h_status || num_items >= (1ull << 32)) return hipErrorInvalidValue;
     *h_status = 0;
     if (!pipe_size_ok(num_items)) return hipSuccess;   // such arrays never take pipelined passes
-    const LsbWorkspace ws = lsb_carve(d_temp, num_items);
+    const LsbWorkspace ws = lsb_carve(gs_ws_base(d_temp), num_items);
     hipError_t e = hipMemcpyAsync(h_status, ws.error_word, sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     return (int)e;
@@ -1381,14 +1381,14 @@ int gs_lsb_sort_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys[2], uint32
         const int passes = (end_bit - begin_bit + RADIX_BITS - 1) / RADIX_BITS, fin = sel ^ (passes & 1);
         PassParams tw{};
         lsb_twiddle_masks(key_type, descending, true, true, tw);
-        const int e = small_stable_sort(d_temp, temp_bytes, d_keys[sel], d_keys[fin], d_vals ? d_vals[sel] : nullptr,
-                                        d_vals ? d_vals[fin] : nullptr, (uint32_t)num_items, begin_bit, end_bit, tw.f32_in,
-                                        tw.xor_in, tw.f32_out, tw.xor_out, (hipStream_t)stream);
+        const int e = small_stable_sort(gs_ws_base(d_temp), lsb_temp_bytes(num_items), d_keys[sel], d_keys[fin],
+                                        d_vals ? d_vals[sel] : nullptr, d_vals ? d_vals[fin] : nullptr, (uint32_t)num_items, begin_bit,
+                                        end_bit, tw.f32_in, tw.xor_in, tw.f32_out, tw.xor_out, (hipStream_t)stream);
         if (e) return e;
         *selector = fin;
         return hipSuccess;
     }
-    const LsbWorkspace ws = lsb_carve(d_temp, num_items);
+    const LsbWorkspace ws = lsb_carve(gs_ws_base(d_temp), num_items);
     const int e = lsb_run_passes(ws, num_items, begin_bit, end_bit, descending, key_type, d_vals != nullptr,
                                  (hipStream_t)stream,
                                  [&](int, int, const uint32_t *&kin, uint32_t *&kout, const uint32_t *&vin, uint32_t *&vout) {
@@ -1407,7 +1407,7 @@ int gs_lsb_sort_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys[2], uint32
 size_t gs_lsb_copy_temp_bytes(uint64_t num_items, int has_values)
 {
     const size_t buf = align256((size_t)num_items * sizeof(uint32_t));
-    return align256(lsb_temp_bytes(num_items)) + buf * (has_values ? 2 : 1);
+    return align256(lsb_temp_bytes(num_items)) + buf * (has_values ? 2 : 1) + GS_WS_SLACK;
 }
 
 int gs_lsb_sort_copy_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, uint32_t *d_keys_out,
@@ -1433,12 +1433,12 @@ int gs_lsb_sort_copy_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys
     if (num_items <= small_sort_capacity(pairs)) {   // one workgroup, straight from IN to OUT
         PassParams tw{};
         lsb_twiddle_masks(key_type, descending, true, true, tw);
-        return small_stable_sort(d_temp, temp_bytes, d_keys_in, d_keys_out, d_vals_in, d_vals_out, (uint32_t)num_items, begin_bit,
-                                 end_bit, tw.f32_in, tw.xor_in, tw.f32_out, tw.xor_out, s);
+        return small_stable_sort(gs_ws_base(d_temp), lsb_temp_bytes(num_items), d_keys_in, d_keys_out, d_vals_in, d_vals_out,
+                                 (uint32_t)num_items, begin_bit, end_bit, tw.f32_in, tw.xor_in, tw.f32_out, tw.xor_out, s);
     }
-    const LsbWorkspace ws = lsb_carve(d_temp, num_items);
+    const LsbWorkspace ws = lsb_carve(gs_ws_base(d_temp), num_items);
     const size_t buf = align256((size_t)num_items * sizeof(uint32_t));
-    uint32_t *tk = (uint32_t *)((char *)d_temp + align256(lsb_temp_bytes(num_items)));
+    uint32_t *tk = (uint32_t *)(gs_ws_base(d_temp) + align256(lsb_temp_bytes(num_items)));
     uint32_t *tv = (uint32_t *)((char *)tk + buf);
     return lsb_run_passes(ws, num_items, begin_bit, end_bit, descending, key_type, pairs, s,
                           [&](int pass, int num_passes, const uint32_t *&kin, uint32_t *&kout, const uint32_t *&vin,

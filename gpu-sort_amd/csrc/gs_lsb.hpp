@@ -130,8 +130,9 @@ int wide_slice_scatter(const void *kin, void *kout, const void *vin, void *vout,
                        int key_type, const uint32_t *spine, const uint16_t *prefix16, const uint64_t *dbase, hipStream_t s);
 // gs_msb.hip: the wide MSB levels for the large sort (gs_large.hip).  msb_wide_finish sorts a group of m < 2^31 elements that
 // lies in src (partitioned on the byte at `shift`, every byte above it equal; h_counts[256] its bucket sizes) and reports in
-// *in_src whether the result landed in src (1) or in oth (0); the workspace is gs_msb_wide_temp_bytes(m) bytes.  A
-// synchronous finish checks the overflow word of its lists.  msb_wide_overflow checks the word gs_msb_sort_wide left.
+// *in_src whether the result landed in src (1) or in oth (0); the workspace is gs_msb_wide_temp_bytes(m) bytes, 256-byte aligned.
+// A synchronous finish checks the overflow word of its lists.  msb_wide_overflow checks the word gs_msb_sort_wide left (at
+// gs_ws_base of its d_temp).
 int msb_wide_finish(void *d_temp, void *src_k, void *src_v, void *oth_k, void *oth_v, uint64_t m, int key_bytes, int val_bytes,
                     const uint64_t *h_counts, int shift, int key_type, hipStream_t s, int synchronize, int *in_src);
 int msb_wide_overflow(void *d_temp, uint64_t n, int key_bytes, int val_bytes, hipStream_t s);

@@ -3049,7 +3049,7 @@ extern "C" {
 
 size_t gs_msb_temp_bytes(uint64_t num_items, int has_values)
 {
-    return align256(lsb_temp_bytes(num_items)) + msb_ws_bytes(num_items, has_values != 0);
+    return align256(lsb_temp_bytes(num_items)) + msb_ws_bytes(num_items, has_values != 0) + GS_WS_SLACK;
 }
 
 // A synchronous sort ends by reading the sort's overflow word (MsbLevel::overflow): a clamped device-side append means a
@@ -3081,8 +3081,9 @@ static int msb_sort_impl(void *d_temp, size_t temp_bytes, uint32_t *d_keys, uint
     hipStream_t s = (hipStream_t)stream;
     const uint32_t n = (uint32_t)num_items;
     const int nclass = msb_num_classes(pairs);
-    const MsbWs ws = msb_carve((char *)d_temp + align256(lsb_temp_bytes(num_items)), num_items, pairs);
-    const LsbWorkspace lw = lsb_carve(d_temp, num_items);
+    char *const base = gs_ws_base(d_temp);
+    const MsbWs ws = msb_carve(base + align256(lsb_temp_bytes(num_items)), num_items, pairs);
+    const LsbWorkspace lw = lsb_carve(base, num_items);
 
     // key twiddles: the first reader maps in, every final writer maps out
     PassParams tw{};
@@ -3170,7 +3171,7 @@ int gs_msb_census(void *d_temp, uint64_t num_items, int has_values, gs_msb_level
 {
     GS_CLEAR_STALE_ERROR();
     if (!d_temp || !out || num_items >= (1ull << 32)) return hipErrorInvalidValue;
-    const MsbWs ws = msb_carve((char *)d_temp + align256(lsb_temp_bytes(num_items)), num_items, has_values != 0);
+    const MsbWs ws = msb_carve(gs_ws_base(d_temp) + align256(lsb_temp_bytes(num_items)), num_items, has_values != 0);
     MsbLevel lv[4];
     std::vector<MsbCensusSlot> slots((size_t)4 * MSB_CLASSIFY_GRID);
     hipError_t e = hipMemcpyAsync(lv, ws.level, sizeof(lv), hipMemcpyDeviceToHost, (hipStream_t)stream);
@@ -3209,7 +3210,7 @@ int gs_msb_read_lists(void *d_temp, uint64_t num_items, int has_values, int leve
     GS_CLEAR_STALE_ERROR();
     if (!d_temp || level < 0 || level > 2 || num_items >= (1ull << 32)) return hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-    const MsbWs ws = msb_carve((char *)d_temp + align256(lsb_temp_bytes(num_items)), num_items, has_values != 0);
+    const MsbWs ws = msb_carve(gs_ws_base(d_temp) + align256(lsb_temp_bytes(num_items)), num_items, has_values != 0);
     MsbLevel lv[4];
     hipError_t e = hipMemcpyAsync(lv, ws.level, sizeof(lv), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -3245,7 +3246,7 @@ int gs_msb_read_lists(void *d_temp, uint64_t num_items, int has_values, int leve
 
 size_t gs_segmented_temp_bytes_impl(uint64_t num_items, int has_values, uint32_t num_segments)
 {
-    return msb_ws_bytes(num_items, has_values != 0, 0, num_segments);
+    return msb_ws_bytes(num_items, has_values != 0, 0, num_segments) + GS_WS_SLACK;
 }
 
 // ---- the MSB path cut at the exchange point of the multi-GPU sort (north_star:
@@ -3266,8 +3267,8 @@ int gs_msb_first_pass_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_key
     hipStream_t s = (hipStream_t)stream;
     if (num_items == 0) return (int)zero_async(d_bucket_counts, RADIX * sizeof(uint64_t), s);
     if ((d_vals_in == nullptr) != (d_vals_out == nullptr) || !d_keys_in || !d_keys_out) return hipErrorInvalidValue;
-    if (!d_temp || temp_bytes < lsb_temp_bytes(num_items)) return hipErrorInvalidValue;
-    const LsbWorkspace lw = lsb_carve(d_temp, num_items);
+    if (!d_temp || temp_bytes < gs_lsb_temp_bytes(num_items, d_vals_in != nullptr)) return hipErrorInvalidValue;
+    const LsbWorkspace lw = lsb_carve(gs_ws_base(d_temp), num_items);
     PassParams p0 = lsb_make_params(num_items, 24, 8);
     lsb_twiddle_masks(key_type, 0, true, false, p0);          // keys leave in their order-preserving u32 form
     int e;
@@ -3282,7 +3283,7 @@ int gs_msb_first_pass_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_key
 size_t gs_msb_finish_temp_bytes(uint64_t num_items, int has_values, int num_src)
 {
     const uint32_t extra = (uint32_t)(num_src > 0 ? num_src : 0) * RADIX;
-    return align256(lsb_temp_bytes(num_items)) + msb_ws_bytes(num_items, has_values != 0, extra);
+    return align256(lsb_temp_bytes(num_items)) + msb_ws_bytes(num_items, has_values != 0, extra) + GS_WS_SLACK;
 }
 
 int gs_msb_finish_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys, uint32_t *d_vals, uint32_t *d_keys_out,
@@ -3302,7 +3303,7 @@ int gs_msb_finish_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys, uint32_
     if (!d_temp || temp_bytes < gs_msb_finish_temp_bytes(num_items, pairs, num_src)) return hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t extra = (uint32_t)num_src * RADIX;
-    const MsbWs ws = msb_carve((char *)d_temp + align256(lsb_temp_bytes(num_items)), num_items, pairs, extra);
+    const MsbWs ws = msb_carve(gs_ws_base(d_temp) + align256(lsb_temp_bytes(num_items)), num_items, pairs, extra);
 
     // host side of what the level-0 classification does on one GPU: bucket list + pieces of level 1.  The tables
     // live on the heap until a host callback behind the copies frees them, so the call never blocks the host: a
@@ -3383,7 +3384,7 @@ int gs_segmented_sort_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys[2], 
     if (!d_temp || temp_bytes < gs_segmented_temp_bytes(num_items, pairs, num_segments)) return hipErrorInvalidValue;
     if (!d_keys[0] || !d_keys[1] || (pairs && (!d_vals[0] || !d_vals[1]))) return hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-    const MsbWs ws = msb_carve(d_temp, num_items, pairs, 0, num_segments);
+    const MsbWs ws = msb_carve(gs_ws_base(d_temp), num_items, pairs, 0, num_segments);
     const int nclass = msb_num_classes(pairs);
     const int num_bits = end_bit - begin_bit, passes = (num_bits + RADIX_BITS - 1) / RADIX_BITS;
     const int sel = *selector, fin = sel ^ (passes & 1);                         // one flip per pass, like gs_lsb_sort_u32
@@ -3487,15 +3488,17 @@ int gs_shard_partition_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_ke
         return hipErrorInvalidValue;
     if (num_items >= (1ull << 32)) return hipErrorInvalidValue;
     if (key_type < GS_KEY_U32 || key_type > GS_KEY_F32) return hipErrorInvalidValue;
+    const bool pairs = d_vals_in != nullptr;
+    if (num_items != 0) {   // (checked before d_counts is zeroed: a refused call writes nothing)
+        if ((d_vals_in == nullptr) != (d_vals_out == nullptr) || !d_keys_in || !d_keys_out) return hipErrorInvalidValue;
+        if (!d_temp || temp_bytes < gs_msb_temp_bytes(num_items, pairs)) return hipErrorInvalidValue;
+    }
     hipStream_t s = (hipStream_t)stream;
     hipError_t e0 = zero_async(d_counts, sizeof(uint64_t) * num_ranks, s);
     if (e0 != hipSuccess) return (int)e0;
     if (num_items == 0) return hipSuccess;
-    if ((d_vals_in == nullptr) != (d_vals_out == nullptr) || !d_keys_in || !d_keys_out) return hipErrorInvalidValue;
-    const bool pairs = d_vals_in != nullptr;
-    if (!d_temp || temp_bytes < gs_msb_temp_bytes(num_items, pairs)) return hipErrorInvalidValue;
     const uint32_t n = (uint32_t)num_items;
-    const MsbWs ws = msb_carve((char *)d_temp + align256(lsb_temp_bytes(num_items)), num_items, pairs);
+    const MsbWs ws = msb_carve(gs_ws_base(d_temp) + align256(lsb_temp_bytes(num_items)), num_items, pairs);
     PassParams tw{};
     lsb_twiddle_masks(key_type, 0, true, true, tw);
     const DigitSel dsel{0, d_dest_of_bin, 32 - bits, tw.f32_in, tw.xor_in, 8, 0};
@@ -3520,7 +3523,7 @@ int gs_shard_partition_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_ke
 
 size_t gs_segmented_wide_temp_bytes(uint64_t num_items, int /*key_bytes*/, int val_bytes, uint32_t num_segments)
 {
-    return msb_ws_bytes(num_items, val_bytes != 0, 0, num_segments, MW_CAP);
+    return msb_ws_bytes(num_items, val_bytes != 0, 0, num_segments, MW_CAP) + GS_WS_SLACK;
 }
 
 int gs_segmented_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys[2], void *d_vals[2], int *selector, uint64_t num_items,
@@ -3542,7 +3545,7 @@ int gs_segmented_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys[2], voi
     if (!d_temp || temp_bytes < gs_segmented_wide_temp_bytes(num_items, key_bytes, val_bytes, num_segments)) return hipErrorInvalidValue;
     if (!d_keys[0] || !d_keys[1] || (d_vals && (!d_vals[0] || !d_vals[1]))) return hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-#define GS_SW(K, V) return seg_wide_sort<K, V>(d_temp, d_keys, d_vals, selector, num_items, num_segments, d_begin_offsets, d_end_offsets, \
+#define GS_SW(K, V) return seg_wide_sort<K, V>(gs_ws_base(d_temp), d_keys, d_vals, selector, num_items, num_segments, d_begin_offsets, d_end_offsets, \
                                                 begin_bit, end_bit, descending, key_type, s)
     if (k64) {
         if (val_bytes == 0) GS_SW(uint64_t, MwNoVal);
@@ -3555,7 +3558,7 @@ int gs_segmented_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys[2], voi
 
 size_t gs_msb_wide_temp_bytes(uint64_t num_items, int key_bytes, int val_bytes)
 {
-    return mw_lsb_bytes(num_items, key_bytes, val_bytes) + msb_ws_bytes(num_items, val_bytes != 0, 0, 0, MW_CAP);
+    return mw_lsb_bytes(num_items, key_bytes, val_bytes) + msb_ws_bytes(num_items, val_bytes != 0, 0, 0, MW_CAP) + GS_WS_SLACK;
 }
 
 int gs_msb_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys, void *d_vals, uint64_t num_items, void *d_keys_alt,
@@ -3577,7 +3580,7 @@ int gs_msb_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys, void *d_vals
     if (!d_temp || temp_bytes < gs_msb_wide_temp_bytes(num_items, key_bytes, val_bytes)) return hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
     int e;
-#define GS_MW(K, V) e = msb_wide_sort<K, V>(d_temp, (K *)d_keys, (V *)d_vals, num_items, (K *)d_keys_alt, (V *)d_vals_alt, key_type, s)
+#define GS_MW(K, V) e = msb_wide_sort<K, V>(gs_ws_base(d_temp), (K *)d_keys, (V *)d_vals, num_items, (K *)d_keys_alt, (V *)d_vals_alt, key_type, s)
     if (k64) {
         if (val_bytes == 0) GS_MW(uint64_t, MwNoVal);
         else if (val_bytes == 4) GS_MW(uint64_t, uint32_t);

@@ -247,7 +247,7 @@ extern "C" {
 
 size_t gs_lsb_wide_temp_bytes(uint64_t num_items, int /*key_bytes*/, int /*val_bytes*/)
 {
-    return w_spine_bytes(num_items) + w_totals_bytes() + w_prefix_bytes(num_items);
+    return w_spine_bytes(num_items) + w_totals_bytes() + w_prefix_bytes(num_items) + GS_WS_SLACK;
 }
 
 int gs_lsb_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys[2], void *d_vals[2], int *selector, uint64_t num_items,
@@ -267,7 +267,7 @@ int gs_lsb_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys[2], void *d_v
     if (!d_temp || temp_bytes < gs_lsb_wide_temp_bytes(num_items, key_bytes, val_bytes)) return hipErrorInvalidValue;
     if (!d_keys[0] || !d_keys[1] || (d_vals && (!d_vals[0] || !d_vals[1]))) return hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-#define GS_WIDE(K, V) return wide_sort<K, V>(d_temp, d_keys, d_vals, selector, num_items, begin_bit, end_bit, descending, key_type, s)
+#define GS_WIDE(K, V) return wide_sort<K, V>(gs_ws_base(d_temp), d_keys, d_vals, selector, num_items, begin_bit, end_bit, descending, key_type, s)
     if (k64) {
         if (val_bytes == 0) GS_WIDE(uint64_t, NoVal);
         if (val_bytes == 4) GS_WIDE(uint64_t, uint32_t);

@@ -10,6 +10,7 @@
 
 #include "gpusort.h"
 #include "gpusort_rccl.h"
+#include "../csrc/gs_host.hpp"   // the workspace rule of every public entry point: gs_ws_base, GS_WS_SLACK
 
 namespace {
 constexpr int RADIX = 256;
@@ -78,7 +79,8 @@ void gs_sharded_exchange_plan(const uint64_t *counts, const uint8_t *dest, int r
 size_t gs_msb_sharded_temp_bytes(uint64_t num_items, uint64_t capacity, int has_values, int world)
 {
     const size_t a = gs_lsb_temp_bytes(num_items, has_values), b = gs_msb_finish_temp_bytes(capacity, has_values, world);
-    return align256(a > b ? a : b) + align256((size_t)RADIX * sizeof(uint64_t)) + align256((size_t)world * RADIX * sizeof(uint64_t));
+    return align256(a > b ? a : b) + align256((size_t)RADIX * sizeof(uint64_t)) + align256((size_t)world * RADIX * sizeof(uint64_t)) +
+           GS_WS_SLACK;
 }
 
 // One grouped exchange round.  Whatever happens between ncclGroupStart and ncclGroupEnd, the group is CLOSED before
@@ -118,14 +120,16 @@ int gs_msb_sort_u32_sharded(void *d_temp, size_t temp_bytes, const uint32_t *d_k
     if (pairs && (!d_grouped_vals || !d_recv_vals || !d_vals_out)) return hipErrorInvalidValue;
     ncclComm_t comm = (ncclComm_t)nccl_comm;
     hipStream_t s = (hipStream_t)stream;
+    // the sort's workspace (first pass, then finish) at the rounded base, the bucket sizes behind it
+    char *const base = gs_ws_base(d_temp);
     const size_t sort_ws = align256(std::max(gs_lsb_temp_bytes(num_items, pairs), gs_msb_finish_temp_bytes(capacity, pairs, world)));
-    uint64_t *d_counts = (uint64_t *)((char *)d_temp + sort_ws);
+    uint64_t *d_counts = (uint64_t *)(base + sort_ws);
     uint64_t *d_all = (uint64_t *)((char *)d_counts + align256((size_t)RADIX * sizeof(uint64_t)));
 
     // 1. first digit pass: the shard grouped by top byte + the 256 bucket sizes.  A LOCAL failure up to the size
     // exchange still takes part in it (with zero sizes and a flag), so that the peers are not left waiting in the
     // all-gather: every rank learns that a rank failed and all return.
-    int e = gs_msb_first_pass_u32(d_temp, sort_ws, d_keys_in, d_grouped_keys, d_vals_in, d_grouped_vals, num_items, key_type, d_counts, s);
+    int e = gs_msb_first_pass_u32(base, sort_ws, d_keys_in, d_grouped_keys, d_vals_in, d_grouped_vals, num_items, key_type, d_counts, s);
     const int local_fail = e;
     if (local_fail) {
         std::vector<uint64_t> poison(RADIX, ~0ull);      // no real bucket holds 2^64 - 1 keys
@@ -164,7 +168,7 @@ int gs_msb_sort_u32_sharded(void *d_temp, size_t temp_bytes, const uint32_t *d_k
     }
     // 5. the rest of the MSB sort on what arrived (pieces picked up where they lie)
     if (m == 0) return 0;
-    return gs_msb_finish_u32(d_temp, sort_ws, d_recv_keys, pairs ? d_recv_vals : nullptr, d_keys_out, pairs ? d_vals_out : nullptr, m,
+    return gs_msb_finish_u32(base, sort_ws, d_recv_keys, pairs ? d_recv_vals : nullptr, d_keys_out, pairs ? d_vals_out : nullptr, m,
                              pieces.data(), world, key_type, s, 0);
 }
 

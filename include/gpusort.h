@@ -67,7 +67,17 @@ const char *gs_error_string(int err);
  * per-tile u16 prefixes: about 1.6 % of the key bytes).
  * Replaces the d_temp_storage==NULL size query
  * (dispatch_radix_sort.cuh:1094-1110).  has_values is accepted for symmetry;
- * like CUB with is_overwrite_okay the value path needs no extra scratch.    */
+ * like CUB with is_overwrite_okay the value path needs no extra scratch.
+ *
+ * Alignment, for every entry point of this header: d_temp may have ANY
+ * alignment.  The workspace is carved from d_temp rounded up to 256 bytes,
+ * and every *_temp_bytes query includes the 256 bytes of slack that rounding
+ * may take (cub's AliasTemporaries, util_device.cuh:68-96), so exactly the
+ * queried size is enough at any address.  Data arrays (keys, values, their
+ * alternates and outputs, segment offsets, bucket counts) need the natural
+ * alignment of their element; the 16-byte values of gs_lsb_sort_any need 16
+ * bytes.  A call writes only inside the arrays and the workspace it was
+ * given, and a refused call (hipErrorInvalidValue) writes nothing.          */
 size_t gs_lsb_temp_bytes(uint64_t num_items, int has_values);
 
 /* d_keys[2] / d_vals[2] are the two halves of a DoubleBuffer
