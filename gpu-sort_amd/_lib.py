@@ -51,6 +51,8 @@ SIGNATURES = {
     "gs_msb_sort_large_u32": (i32, [vp, sz, vp, vp, u64, vp, vp, i32, vp, i32]),
     "gs_msb_large_wide_temp_bytes": (sz, [u64, i32, i32]),
     "gs_msb_sort_large_wide": (i32, [vp, sz, vp, vp, u64, vp, vp, i32, i32, i32, vp, i32]),
+    "gs_lsb_large_temp_bytes": (sz, [u64, i32, i32]),
+    "gs_lsb_sort_large": (i32, [vp, sz, pp, pp, C.POINTER(i32), u64, i32, i32, i32, i32, i32, i32, vp]),
     "gs_msb_census": (i32, [vp, u64, i32, vp, vp]),
     "gs_msb_capacities": (None, [u64, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "gs_msb_classify_upto": (i32, [vp, sz, vp, vp, u64, i32, i32, vp]),
@@ -70,6 +72,7 @@ SIGNATURES = {
     "gs_check_pairs_enumerated_u32": (i32, [vp, vp, vp, u64, vp, vp]),
     "gs_check_sorted_u64": (i32, [vp, u64, i32, vp, vp]),
     "gs_check_pairs_enumerated_wide": (i32, [vp, vp, vp, u64, i32, vp, vp]),
+    "gs_check_sorted_stable": (i32, [vp, vp, u64, i32, i32, i32, i32, i32, vp, vp]),
     "gs_profile_create": (vp, []),
     "gs_profile_destroy": (None, [vp]),
     "gs_profile_begin": (None, [vp]),

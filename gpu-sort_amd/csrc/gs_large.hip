@@ -14,6 +14,9 @@
 // gs_msb_sort_large_wide is the same planner for the wide element types: the pass is the wide
 // LSB pass per slice (wide_slice_count / wide_slice_scatter: wide_downsweep64_kernel), keys keep their representation,
 // and groups are finished by msb_wide_finish (the wide MSB levels, started from the group's counts).
+// gs_lsb_sort_large is the stable LSB sort over the same pass: one 64-bit pass per digit of
+// [begin_bit, end_bit), ping-ponging between the DoubleBuffer halves, keys twiddled on the first pass and restored on the
+// last (lsb_run_passes' rule).  Its offsets are computed on the device, so the sort only enqueues work and can be captured.
 #include "gs_device.hpp"
 #include "gs_lsb.hpp"
 #include <cstdlib>
@@ -24,8 +27,9 @@ constexpr uint64_t LARGE_GROUP = 1ull << 31;   // keys per finish and per slice 
 constexpr uint64_t LARGE_MAX = 1ull << 40;     // num_items limit of the entry point
 constexpr uint32_t LARGE_MIN_TEST_LIMIT = 256;
 
-// Test hook (tests/test_msb_large_gpu.py): GS_MSB_LARGE_TEST_LIMIT=k lowers the group size and the slice size to k keys,
-// so that small arrays take multi-slice passes, multi-group finishes and splits.  Read on every call; never set in production.
+// Test hook (tests/test_msb_large_gpu.py, tests/test_lsb_large_gpu.py): GS_MSB_LARGE_TEST_LIMIT=k lowers the group size and the
+// slice size to k keys, so that small arrays take multi-slice passes, multi-group finishes and splits (and, in gs_lsb_sort_large,
+// arrays of more than k elements the 64-bit passes).  Read on every call; never set in production.
 static uint64_t large_limit()
 {
     if (const char *e = getenv("GS_MSB_LARGE_TEST_LIMIT")) {
@@ -125,15 +129,14 @@ struct LargeCtx {
     int synchronize;
 };
 
-// The 64-bit pass: stable partition of m elements on the byte at `shift`, kin -> kout, with key_type's twiddle applied on
-// read.  The u32 path keeps its keys twiddled (GS_KEY_U32: none); the wide path writes them back in their own representation.
-// The bucket sizes are copied to h_counts (the call waits for them).
-static int large_pass(const LargeCtx &c, const char *kin, char *kout, const char *vin, char *vout, uint64_t m, int shift, int key_type,
-                      uint64_t *h_counts)
+// The 64-bit pass: stable partition of m elements on the digit d (d.bits wide at d.shift), kin -> kout, with d's twiddle
+// (LargeDigit), through the workspace w carved for m.  When h_counts is given, the 256 bucket sizes are copied to it and the
+// call waits for them; otherwise the pass only enqueues work.
+static int large_pass(const LargeCtx &c, const LargePassWs &w, const char *kin, char *kout, const char *vin, char *vout, uint64_t m,
+                      const LargeDigit &d, uint64_t *h_counts)
 {
     const uint64_t S = c.L;
     const hipStream_t s = c.s;
-    const LargePassWs w = large_pass_carve(c.pass_ws, m, S, c.wide);
     const uint64_t ns = large_slices(m, S);
     int e;
     for (uint64_t i = 0; i < ns; ++i) {
@@ -141,11 +144,11 @@ static int large_pass(const LargeCtx &c, const char *kin, char *kout, const char
         uint32_t *spine = (uint32_t *)(w.slice_ws + i * w.per_slice);
         uint16_t *prefix16 = (uint16_t *)(w.slice_ws + i * w.per_slice + w.spine_bytes);
         if (c.wide) {
-            if ((e = wide_slice_count(kin + off * c.kb, len, c.kb, shift, key_type, spine, prefix16, w.totals + i * RADIX, s))) return e;
+            if ((e = wide_slice_count(kin + off * c.kb, len, c.kb, d, spine, prefix16, w.totals + i * RADIX, s))) return e;
             continue;
         }
-        PassParams p = lsb_make_params(len, shift, 8);
-        lsb_twiddle_masks(key_type, 0, true, false, p);
+        PassParams p = lsb_make_params(len, d.shift, d.bits);
+        lsb_twiddle_masks(d.key_type, d.descending, d.first, d.last, p);
         if ((e = lsb_upsweep((const uint32_t *)kin + off, spine, prefix16, p, s))) return e;
         if ((e = lsb_scan(spine, w.totals + i * RADIX, p.grid, s))) return e;
     }
@@ -159,17 +162,18 @@ static int large_pass(const LargeCtx &c, const char *kin, char *kout, const char
         const uint32_t *spine = (const uint32_t *)(w.slice_ws + i * w.per_slice);
         const uint16_t *prefix16 = (const uint16_t *)(w.slice_ws + i * w.per_slice + w.spine_bytes);
         if (c.wide) {
-            if ((e = wide_slice_scatter(kin + off * c.kb, kout, vin ? vin + off * c.vb : nullptr, vout, len, c.kb, c.vb, shift, key_type,
-                                        spine, prefix16, w.dbase + i * RADIX, s)))
+            if ((e = wide_slice_scatter(kin + off * c.kb, kout, vin ? vin + off * c.vb : nullptr, vout, len, c.kb, c.vb, d, spine,
+                                        prefix16, w.dbase + i * RADIX, s)))
                 return e;
             continue;
         }
-        PassParams p = lsb_make_params(len, shift, 8);
-        lsb_twiddle_masks(key_type, 0, true, false, p);
+        PassParams p = lsb_make_params(len, d.shift, d.bits);
+        lsb_twiddle_masks(d.key_type, d.descending, d.first, d.last, p);
         if ((e = lsb_downsweep64((const uint32_t *)kin + off, (uint32_t *)kout, vin ? (const uint32_t *)vin + off : nullptr,
                                  (uint32_t *)vout, spine, prefix16, w.totals + i * RADIX, w.dbase + i * RADIX, p, s)))
             return e;
     }
+    if (!h_counts) return hipSuccess;
     hipError_t he = hipMemcpyAsync(h_counts, w.counts, RADIX * sizeof(uint64_t), hipMemcpyDeviceToHost, s);
     if (he == hipSuccess) he = hipStreamSynchronize(s);
     return (int)he;
@@ -208,8 +212,11 @@ static int large_range(const LargeCtx &c, uint64_t off, uint64_t m, int cur, int
 {
     uint64_t counts[RADIX];
     const int nb = cur ^ 1;
-    int e = large_pass(c, c.k[cur] + off * c.kb, c.k[nb] + off * c.kb, c.vb ? c.v[cur] + off * c.vb : nullptr,
-                       c.vb ? c.v[nb] + off * c.vb : nullptr, m, shift, key_type_in, counts);
+    // the u32 path keeps its keys twiddled until the range is sorted (GS_KEY_U32 below the first pass: none); the wide path
+    // writes them back in their own representation
+    const LargeDigit d{shift, RADIX_BITS, key_type_in, 0, true, c.wide};
+    int e = large_pass(c, large_pass_carve(c.pass_ws, m, c.L, c.wide), c.k[cur] + off * c.kb, c.k[nb] + off * c.kb,
+                       c.vb ? c.v[cur] + off * c.vb : nullptr, c.vb ? c.v[nb] + off * c.vb : nullptr, m, d, counts);
     if (e) return e;
     if (shift == 0) {
         // every byte is ordered: the range is sorted, each bucket one value.  Wide keys are in their own representation;
@@ -291,6 +298,36 @@ static bool wide_types_ok(int key_bytes, int val_bytes, int key_type)
 {
     if (key_bytes == 8) return (val_bytes == 0 || val_bytes == 4 || val_bytes == 8) && key_type >= GS_KEY_U64 && key_type <= GS_KEY_F64;
     return key_bytes == 4 && val_bytes == 8 && key_type >= GS_KEY_U32 && key_type <= GS_KEY_F32;
+}
+
+// ---- gs_lsb_sort_large: the stable LSB sort above 2^32 elements, the 64-bit pass once per digit.
+// The element types of gs_lsb_sort_wide: 32- or 64-bit keys with no, 32-bit or 64-bit values.
+static bool lsb_large_types_ok(int key_bytes, int val_bytes, int key_type)
+{
+    if (val_bytes != 0 && val_bytes != 4 && val_bytes != 8) return false;
+    if (key_bytes == 8) return key_type >= GS_KEY_U64 && key_type <= GS_KEY_F64;
+    return key_bytes == 4 && key_type >= GS_KEY_U32 && key_type <= GS_KEY_F32;
+}
+// (u32, none | u32) take gs_lsb.hip's kernels (and gs_lsb_sort_u32 for one slice), the others the wide set (gs_lsb_sort_wide)
+static inline bool lsb_large_wide(int key_bytes, int val_bytes) { return key_bytes == 8 || val_bytes == 8; }
+
+// one 64-bit pass per digit of [begin_bit, end_bit), d_keys[sel] -> d_keys[sel ^ 1] (c.k / c.v hold the DoubleBuffer halves),
+// all through the one workspace w; the bucket sizes stay on the device, so the host never waits
+static int lsb_large_passes(const LargeCtx &c, const LargePassWs &w, int *selector, uint64_t n, int begin_bit, int end_bit, int descending)
+{
+    const int num_passes = (end_bit - begin_bit + RADIX_BITS - 1) / RADIX_BITS;
+    int sel = *selector;
+    for (int pass = 0; pass < num_passes; ++pass) {
+        const int shift = begin_bit + pass * RADIX_BITS;
+        const LargeDigit d{shift, end_bit - shift < RADIX_BITS ? end_bit - shift : RADIX_BITS, c.key_type, descending, pass == 0,
+                           pass == num_passes - 1};
+        if (int e = large_pass(c, w, c.k[sel], c.k[sel ^ 1], c.vb ? c.v[sel] : nullptr, c.vb ? c.v[sel ^ 1] : nullptr, n, d, nullptr))
+            return e;
+        sel ^= 1;
+    }
+    if (int e = (int)hipGetLastError()) return e;
+    *selector = sel;
+    return hipSuccess;
 }
 
 }  // namespace gs
@@ -389,6 +426,60 @@ int gs_msb_sort_large_wide(void *d_temp, size_t temp_bytes, void *d_keys, void *
     c.s = s;
     c.synchronize = synchronize;
     return large_run(c, gs_ws_base(d_temp), num_items, large_pass_bytes(num_items, L, true));
+}
+
+// the 64-bit pass's workspace, or the delegate's for arrays of one slice, whichever is larger (both grow with n)
+size_t gs_lsb_large_temp_bytes(uint64_t num_items, int key_bytes, int val_bytes)
+{
+    const uint64_t L = large_limit();
+    const bool wide = lsb_large_wide(key_bytes, val_bytes);
+    const uint64_t m = num_items < L ? num_items : L;
+    const size_t pass = align256(large_pass_bytes(num_items, L, wide)) + GS_WS_SLACK;
+    const size_t one = wide ? gs_lsb_wide_temp_bytes(m, key_bytes, val_bytes) : gs_lsb_temp_bytes(m, val_bytes != 0);
+    return pass > one ? pass : one;
+}
+
+int gs_lsb_sort_large(void *d_temp, size_t temp_bytes, void *d_keys[2], void *d_vals[2], int *selector, uint64_t num_items,
+                      int key_bytes, int val_bytes, int begin_bit, int end_bit, int descending, int key_type, void *stream)
+{
+    // argument checks touch no device, and all of them come before anything is enqueued
+    if (!selector || (*selector != 0 && *selector != 1) || !d_keys) return hipErrorInvalidValue;
+    if (!lsb_large_types_ok(key_bytes, val_bytes, key_type)) return hipErrorInvalidValue;
+    if ((val_bytes != 0) != (d_vals != nullptr)) return hipErrorInvalidValue;
+    if (begin_bit < 0 || end_bit > 8 * key_bytes || begin_bit > end_bit) return hipErrorInvalidValue;
+    if (num_items >= LARGE_MAX) return hipErrorInvalidValue;
+    if (num_items == 0 || begin_bit == end_bit) return hipSuccess;
+    if (!d_temp || temp_bytes < gs_lsb_large_temp_bytes(num_items, key_bytes, val_bytes)) return hipErrorInvalidValue;
+    if (!d_keys[0] || !d_keys[1] || (d_vals && (!d_vals[0] || !d_vals[1]))) return hipErrorInvalidValue;
+    const bool pairs = d_vals != nullptr;
+    {
+        const void *arr[4] = {d_keys[0], d_keys[1], pairs ? d_vals[0] : nullptr, pairs ? d_vals[1] : nullptr};
+        const size_t kb = num_items * (size_t)key_bytes, vb = num_items * (size_t)val_bytes, bytes[4] = {kb, kb, vb, vb};
+        if (any_overlap(arr, bytes)) return hipErrorInvalidValue;
+    }
+    GS_CLEAR_STALE_ERROR();
+    const bool wide = lsb_large_wide(key_bytes, val_bytes);
+    const uint64_t L = large_limit();
+    if (num_items <= L) {   // one slice: the plain LSB sort on the same arguments (a stable sort's result is unique)
+        if (wide)
+            return gs_lsb_sort_wide(d_temp, temp_bytes, d_keys, d_vals, selector, num_items, key_bytes, val_bytes, begin_bit, end_bit,
+                                    descending, key_type, stream);
+        uint32_t *k2[2] = {(uint32_t *)d_keys[0], (uint32_t *)d_keys[1]};
+        uint32_t *v2[2] = {pairs ? (uint32_t *)d_vals[0] : nullptr, pairs ? (uint32_t *)d_vals[1] : nullptr};
+        return gs_lsb_sort_u32(d_temp, temp_bytes, k2, pairs ? v2 : nullptr, selector, num_items, begin_bit, end_bit, descending,
+                               key_type, stream);
+    }
+
+    LargeCtx c{};
+    c.k[0] = (char *)d_keys[0]; c.k[1] = (char *)d_keys[1];
+    c.v[0] = pairs ? (char *)d_vals[0] : nullptr; c.v[1] = pairs ? (char *)d_vals[1] : nullptr;
+    c.kb = key_bytes; c.vb = val_bytes;
+    c.wide = wide;
+    c.key_type = key_type;
+    c.L = L;
+    c.pass_ws = gs_ws_base(d_temp);
+    c.s = (hipStream_t)stream;
+    return lsb_large_passes(c, large_pass_carve(c.pass_ws, num_items, L, wide), selector, num_items, begin_bit, end_bit, descending);
 }
 
 }  // extern "C"

@@ -120,14 +120,23 @@ int lsb_downsweep64(const uint32_t *kin, uint32_t *kout, const uint32_t *vin, ui
 
 // gs_wide.hip: digit totals of the last wide pass inside its workspace
 const uint32_t *wide_totals_ptr(void *d_temp, uint64_t n);
+// The digit of one 64-bit pass (gs_large.hip) and the key twiddle around it: digit = (key >> shift) & ((1 << bits) - 1) of
+// the key mapped by key_type's order-preserving twiddle (complemented when descending), which is applied on read when `first`
+// and undone on write when `last` (lsb_twiddle_masks' rule).  Keys between a first and a last pass stay twiddled.
+struct LargeDigit {
+    int shift, bits;
+    int key_type, descending;
+    bool first, last;
+};
+
 // gs_wide.hip: one slice (len < 2^31 elements) of the 64-bit pass over the wide element types (gs_large.hip).  The count
 // runs the wide upsweep and the spine scan (digit totals of the slice into totals[256]); the scatter writes the slice
-// through dbase[256], the absolute u64 start of its run of each digit in kout / vout.  Keys keep their representation.
+// through dbase[256], the absolute u64 start of its run of each digit in kout / vout.
 void wide_slice_bytes(uint64_t S, size_t &spine, size_t &prefix);
-int wide_slice_count(const void *kin, uint64_t len, int key_bytes, int shift, int key_type, uint32_t *spine, uint16_t *prefix16,
+int wide_slice_count(const void *kin, uint64_t len, int key_bytes, const LargeDigit &d, uint32_t *spine, uint16_t *prefix16,
                      uint32_t *totals, hipStream_t s);
-int wide_slice_scatter(const void *kin, void *kout, const void *vin, void *vout, uint64_t len, int key_bytes, int val_bytes, int shift,
-                       int key_type, const uint32_t *spine, const uint16_t *prefix16, const uint64_t *dbase, hipStream_t s);
+int wide_slice_scatter(const void *kin, void *kout, const void *vin, void *vout, uint64_t len, int key_bytes, int val_bytes,
+                       const LargeDigit &d, const uint32_t *spine, const uint16_t *prefix16, const uint64_t *dbase, hipStream_t s);
 // gs_msb.hip: the wide MSB levels for the large sort (gs_large.hip).  msb_wide_finish sorts a group of m < 2^31 elements that
 // lies in src (partitioned on the byte at `shift`, every byte above it equal; h_counts[256] its bucket sizes) and reports in
 // *in_src whether the result landed in src (1) or in oth (0); the workspace is gs_msb_wide_temp_bytes(m) bytes, 256-byte aligned.

@@ -149,6 +149,30 @@ __global__ __launch_bounds__(256) void check_pairs_enum_wide_kernel(const void *
     }
 }
 
+// result[0] += adjacent positions out of the order of a stable sort on the digit (key >> shift) & mask of the key type's
+// order-preserving map (f: float map; x: sign flip and descending complement), and, with rowids, adjacent equal sort keys
+// whose row ids do not strictly increase (32- or 64-bit keys: key_bytes)
+__global__ __launch_bounds__(256) void check_sorted_stable_kernel(const void *__restrict__ keys, const uint64_t *__restrict__ rowids,
+                                                                  uint64_t n, int key_bytes, int f, uint64_t x, int shift, uint64_t mask,
+                                                                  unsigned long long *__restrict__ result)
+{
+    const uint64_t sign = key_bytes == 8 ? 0x8000000000000000ull : 0x80000000ull, all = key_bytes == 8 ? ~0ull : 0xffffffffull;
+    auto sort_key = [&](uint64_t i) {
+        uint64_t u = key_bytes == 8 ? ((const uint64_t *)keys)[i] : ((const uint32_t *)keys)[i];
+        if (f) u ^= (u & sign) ? all : sign;
+        return ((u ^ x) >> shift) & mask;
+    };
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long bad = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i + 1 < n; i += stride) {
+        const uint64_t a = sort_key(i), b = sort_key(i + 1);
+        if (a > b) ++bad;
+        else if (a == b && rowids && rowids[i] >= rowids[i + 1]) ++bad;
+    }
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, WAVE);
+    if (lane_id() == 0 && bad) atomicAdd(&result[0], bad);
+}
+
 static inline uint32_t stream_grid(uint64_t n)
 {
     const uint64_t b = (n + 255) / 256;
@@ -319,6 +343,29 @@ int gs_check_pairs_enumerated_wide(const void *d_keys_in, const void *d_keys_sor
     if (num_items == 0) return hipSuccess;
     hipLaunchKernelGGL(check_pairs_enum_wide_kernel, dim3(stream_grid(num_items)), dim3(256), 0, s, d_keys_in, d_keys_sorted, d_vals,
                        num_items, key_bytes, (unsigned long long *)d_result);
+    return (int)hipGetLastError();
+}
+
+int gs_check_sorted_stable(const void *d_keys_sorted, const uint64_t *d_rowids, uint64_t num_items, int key_bytes, int key_type,
+                           int begin_bit, int end_bit, int descending, uint64_t *d_result, void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (key_bytes == 8 ? (key_type < GS_KEY_U64 || key_type > GS_KEY_F64)
+                       : (key_bytes != 4 || key_type < GS_KEY_U32 || key_type > GS_KEY_F32))
+        return hipErrorInvalidValue;
+    if (begin_bit < 0 || end_bit > 8 * key_bytes || begin_bit > end_bit) return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = zero_async(d_result, sizeof(uint64_t), s);
+    if (e != hipSuccess) return (int)e;
+    if (num_items < 2) return hipSuccess;
+    const int f = (key_type == GS_KEY_F32 || key_type == GS_KEY_F64) ? 1 : 0;
+    const uint64_t all = key_bytes == 8 ? ~0ull : 0xffffffffull;
+    const uint64_t sign = (key_type == GS_KEY_I32 || key_type == GS_KEY_I64) ? (all ^ (all >> 1)) : 0ull;
+    const uint64_t x = sign ^ (descending ? all : 0ull);
+    const int bits = end_bit - begin_bit;
+    const uint64_t mask = bits == 64 ? ~0ull : (1ull << bits) - 1ull;
+    hipLaunchKernelGGL(check_sorted_stable_kernel, dim3(stream_grid(num_items)), dim3(256), 0, s, d_keys_sorted, d_rowids, num_items,
+                       key_bytes, f, x, begin_bit, mask, (unsigned long long *)d_result);
     return (int)hipGetLastError();
 }
 

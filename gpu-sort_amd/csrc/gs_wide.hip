@@ -189,38 +189,44 @@ static int wide_sort(void *d_temp, void *d_keys[2], void *d_vals[2], int *select
     return hipSuccess;
 }
 
-// ---- the 64-bit pass over the wide element types (gs_large.hip), one slice of < 2^31 elements at a time.  The key type's
-// twiddle only finds the digit: keys are written back in the caller's representation, as the wide MSB levels keep them.
+// ---- the 64-bit pass over the wide element types (gs_large.hip), one slice of < 2^31 elements at a time, on the digit
+// d.bits wide at d.shift.  The key type's twiddle (and the descending complement) is applied on read when d.first and undone on
+// write when d.last, the rule of wide_sort's passes; the MSB large sort sets both, so its keys keep the caller's representation.
 void wide_slice_bytes(uint64_t S, size_t &spine, size_t &prefix)
 {
     spine = w_spine_bytes(S);
     prefix = w_prefix_bytes(S);
 }
 
-static WideParams wide_slice_params(uint64_t len, int shift, int key_bytes, int key_type)
+static WideParams wide_slice_params(uint64_t len, int key_bytes, const LargeDigit &d)
 {
     WideParams p{};
     p.n = len; p.num_tiles = w_tiles(len); p.grid = w_grid(len);
-    p.shift = (uint32_t)shift; p.bits = RADIX_BITS; p.mask = RADIX - 1u;
-    p.f_in = p.f_out = (key_type == GS_KEY_F32 || key_type == GS_KEY_F64) ? 1 : 0;
-    p.xor_in = p.xor_out = (key_type == GS_KEY_I32 || key_type == GS_KEY_I64) ? (key_bytes == 8 ? 0x8000000000000000ull : 0x80000000ull) : 0ull;
+    p.shift = (uint32_t)d.shift; p.bits = (uint32_t)d.bits; p.mask = (1u << d.bits) - 1u;
+    const int f = (d.key_type == GS_KEY_F32 || d.key_type == GS_KEY_F64) ? 1 : 0;
+    const uint64_t sign = (d.key_type == GS_KEY_I32 || d.key_type == GS_KEY_I64) ? (key_bytes == 8 ? 0x8000000000000000ull : 0x80000000ull) : 0ull;
+    const uint64_t x = sign ^ (d.descending ? ~0ull : 0ull);
+    p.f_in = d.first ? f : 0;
+    p.f_out = d.last ? f : 0;
+    p.xor_in = d.first ? x : 0ull;
+    p.xor_out = d.last ? x : 0ull;
     return p;
 }
 
-int wide_slice_count(const void *kin, uint64_t len, int key_bytes, int shift, int key_type, uint32_t *spine, uint16_t *prefix16,
+int wide_slice_count(const void *kin, uint64_t len, int key_bytes, const LargeDigit &d, uint32_t *spine, uint16_t *prefix16,
                      uint32_t *totals, hipStream_t s)
 {
-    const WideParams p = wide_slice_params(len, shift, key_bytes, key_type);
+    const WideParams p = wide_slice_params(len, key_bytes, d);
     { KernelTimer kt(GS_K_LSB_UPSWEEP, s);
       if (key_bytes == 8) hipLaunchKernelGGL(wide_upsweep_kernel<uint64_t>, dim3(p.grid), dim3(W_THREADS), 0, s, (const uint64_t *)kin, spine, prefix16, p);
       else hipLaunchKernelGGL(wide_upsweep_kernel<uint32_t>, dim3(p.grid), dim3(W_THREADS), 0, s, (const uint32_t *)kin, spine, prefix16, p); }
     return lsb_scan(spine, totals, p.grid, s);
 }
 
-int wide_slice_scatter(const void *kin, void *kout, const void *vin, void *vout, uint64_t len, int key_bytes, int val_bytes, int shift,
-                       int key_type, const uint32_t *spine, const uint16_t *prefix16, const uint64_t *dbase, hipStream_t s)
+int wide_slice_scatter(const void *kin, void *kout, const void *vin, void *vout, uint64_t len, int key_bytes, int val_bytes,
+                       const LargeDigit &d, const uint32_t *spine, const uint16_t *prefix16, const uint64_t *dbase, hipStream_t s)
 {
-    const WideParams p = wide_slice_params(len, shift, key_bytes, key_type);
+    const WideParams p = wide_slice_params(len, key_bytes, d);
     KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
 #define GS_W64(K, V) hipLaunchKernelGGL((wide_downsweep64_kernel<K, V>), dim3(p.num_tiles), dim3(W_THREADS), 0, s, (const K *)kin, (K *)kout, \
                                         (const V *)vin, (V *)vout, spine, prefix16, dbase, p)

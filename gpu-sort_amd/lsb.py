@@ -227,6 +227,70 @@ class DeviceRadixSort:
                                      end_bit, True, stream, key_type)
 
 
+class DeviceRadixSortLarge:
+    """The stable sort of 2^32 elements and more (gs_lsb_sort_large, num_items < 2^40): the four DoubleBuffer methods of
+    DeviceRadixSort for 32- or 64-bit keys with no, 32-bit or 64-bit values, the key type following the dtype as in
+    DeviceRadixSort._sort_wide.  Stable, on bits [begin_bit, end_bit); the selector flips once per 8-bit pass; the call
+    only enqueues work on the stream and may be captured into a graph.  d_temp_storage=None returns the workspace size."""
+
+    @staticmethod
+    def _sort(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items, begin_bit, end_bit, descending, stream,
+              key_type):
+        kb = d_keys.d_buffers[0].element_size()
+        vb = d_values.d_buffers[0].element_size() if d_values is not None else 0
+        need = lib.gs_lsb_large_temp_bytes(num_items, kb, vb)
+        if d_temp_storage is None:
+            return need
+        if end_bit is None:
+            end_bit = 8 * kb
+        if key_type is None:
+            key_type = _KEY_TYPES.get(d_keys.d_buffers[0].dtype, _lib.GS_KEY_U64 if kb == 8 else _lib.GS_KEY_U32)
+        for b in d_keys.d_buffers:
+            _check_buf(b, num_items, "d_keys", kb)
+        keys = (C.c_void_p * 2)(d_keys.d_buffers[0].data_ptr(), d_keys.d_buffers[1].data_ptr())
+        vals = None
+        if vb:
+            for b in d_values.d_buffers:
+                _check_buf(b, num_items, "d_values", vb)
+            if d_values.selector != d_keys.selector:
+                raise ValueError("d_keys and d_values selectors differ")
+            vals = (C.c_void_p * 2)(d_values.d_buffers[0].data_ptr(), d_values.d_buffers[1].data_ptr())
+        sel = C.c_int(d_keys.selector)
+        err = lib.gs_lsb_sort_large(C.c_void_p(d_temp_storage.data_ptr()),
+                                    min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                    keys, vals, C.byref(sel), num_items, kb, vb, begin_bit, end_bit, int(descending), key_type,
+                                    _stream_ptr(stream))
+        check(err, "gs_lsb_sort_large")
+        d_keys.selector = sel.value
+        if vb:
+            d_values.selector = sel.value
+        return need
+
+    @staticmethod
+    def SortKeys(d_temp_storage, temp_storage_bytes, d_keys, num_items, begin_bit=0, end_bit=None, stream=None,
+                 key_type=None):
+        return DeviceRadixSortLarge._sort(d_temp_storage, temp_storage_bytes, d_keys, None, num_items, begin_bit, end_bit,
+                                          False, stream, key_type)
+
+    @staticmethod
+    def SortKeysDescending(d_temp_storage, temp_storage_bytes, d_keys, num_items, begin_bit=0, end_bit=None,
+                           stream=None, key_type=None):
+        return DeviceRadixSortLarge._sort(d_temp_storage, temp_storage_bytes, d_keys, None, num_items, begin_bit, end_bit,
+                                          True, stream, key_type)
+
+    @staticmethod
+    def SortPairs(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items, begin_bit=0, end_bit=None,
+                  stream=None, key_type=None):
+        return DeviceRadixSortLarge._sort(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items, begin_bit,
+                                          end_bit, False, stream, key_type)
+
+    @staticmethod
+    def SortPairsDescending(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items, begin_bit=0,
+                            end_bit=None, stream=None, key_type=None):
+        return DeviceRadixSortLarge._sort(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items, begin_bit,
+                                          end_bit, True, stream, key_type)
+
+
 class DeviceSegmentedRadixSort:
     """cub::DeviceSegmentedRadixSort (lsb/cub/cub/device/device_segmented_radix_sort.cuh), DoubleBuffer form:
     segment i is [d_begin_offsets[i], d_end_offsets[i]) (int32 device tensors; one offsets tensor of

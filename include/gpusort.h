@@ -20,9 +20,9 @@
  *   - counts are 64-bit in the signature; the current kernels index with
  *     32-bit offsets, so num_items must be < 2^32 (the reference caps at
  *     int / unsigned, device_radix_sort.cuh:599,606, gpu_radix_sort.h:526).
- *     The exceptions are gs_msb_sort_large_u32 and gs_msb_sort_large_wide
- *     (num_items < 2^40), the branch the reference left commented out
- *     (gpu_radix_sort.h:526-529).
+ *     The exceptions are gs_msb_sort_large_u32, gs_msb_sort_large_wide
+ *     and the stable gs_lsb_sort_large (num_items < 2^40), the branch the
+ *     reference left commented out (gpu_radix_sort.h:526-529).
  */
 #ifndef GPUSORT_H_
 #define GPUSORT_H_
@@ -228,6 +228,24 @@ int    gs_msb_sort_large_wide(void *d_temp, size_t temp_bytes, void *d_keys, voi
                               void *d_keys_alt, void *d_vals_alt, int key_bytes, int val_bytes, int key_type,
                               void *stream, int synchronize);
 
+/* The stable LSB sort for num_items of 2^32 and more (up to 2^40): gs_lsb_sort_wide's contract above 2^32.  Keys of
+ * key_bytes = 4 (GS_KEY_U32 / I32 / F32) or 8 (GS_KEY_U64 / I64 / F64), values of val_bytes = 0 (d_vals NULL), 4 or 8;
+ * stable, ascending or descending, on key bits [begin_bit, end_bit).  DoubleBuffer: both halves may be overwritten and
+ * *selector flips once per 8-bit pass, ceil((end_bit - begin_bit) / 8) times.  The call only enqueues work on `stream`
+ * (no host read-back: the 64-bit offsets are computed on the device), so it may be captured into a HIP graph.  One pass
+ * per digit: per slice of 2^31 elements the LSB upsweep and spine scan, u64 digit starts over all slices, then the
+ * downsweep of every slice through them.  Arrays of up to one slice take gs_lsb_sort_u32 ((4, 0),
+ * (4, 4)) or gs_lsb_sort_wide with the same arguments, which give the same result.  num_items == 0 or begin_bit ==
+ * end_bit is a no-op: it returns 0, needs no workspace and leaves *selector alone.  Errors (hipErrorInvalidValue, checked
+ * before anything is enqueued, nothing written): a NULL or too-small workspace, a bad bit range, a bad combination of
+ * key_bytes / val_bytes / key_type, a missing buffer half, values without val_bytes (or val_bytes without values),
+ * overlapping arrays (at their element sizes) or num_items >= 2^40.  gs_lsb_large_temp_bytes is a pure host function:
+ * about 2 % of the key bytes for 32-bit keys.                                                                           */
+size_t gs_lsb_large_temp_bytes(uint64_t num_items, int key_bytes, int val_bytes);
+int    gs_lsb_sort_large(void *d_temp, size_t temp_bytes, void *d_keys[2], void *d_vals[2], int *selector,
+                         uint64_t num_items, int key_bytes, int val_bytes, int begin_bit, int end_bit,
+                         int descending, int key_type, void *stream);
+
 /* Census of the last gs_msb_sort_u32 that used d_temp (read back after synchronising `stream`): what every level
  * partitioned and what it handed to local sorts.  SURVEY.md 8d: the MSB path's algorithmic bytes are data-dependent --
  * "the harness must log the per-pass census and compute bytes from it": level 0 moves every key once (12 B/key), a level
@@ -363,6 +381,13 @@ int gs_check_sorted_u64(const uint64_t *d_keys, uint64_t num_items, int key_type
  * d_keys_in[d_vals[i]] != d_keys_sorted[i] (bitwise), [1] = sum of d_vals mod 2^64.                                   */
 int gs_check_pairs_enumerated_wide(const void *d_keys_in, const void *d_keys_sorted, const uint64_t *d_vals,
                                    uint64_t num_items, int key_bytes, uint64_t *d_result, void *stream);
+/* The result of a stable sort (gs_lsb_sort_large): d_result[0] = number of adjacent positions out of the sort's order on
+ * bits [begin_bit, end_bit) of the key type's order-preserving map (reversed when descending), plus, when d_rowids is not
+ * NULL, the number of adjacent equal sort keys whose row ids do not strictly increase.  32- or 64-bit keys (key_bytes with
+ * a matching key_type); u64 indices.  With gs_check_pairs_enumerated_wide on the same output (every row id points at a
+ * bitwise-equal input key) it proves the output is THE stable sort of the input.                                      */
+int gs_check_sorted_stable(const void *d_keys_sorted, const uint64_t *d_rowids, uint64_t num_items, int key_bytes,
+                           int key_type, int begin_bit, int end_bit, int descending, uint64_t *d_result, void *stream);
 
 /* ------------------------------------------------------ kernel timing hook --
  * Optional per-kernel device timing with hipEvents recorded on the SAME stream

@@ -202,6 +202,70 @@ struct DeviceRadixSort {
     }
 };
 
+// The stable sort of 2^32 elements and more (gs_lsb_sort_large, num_items < 2^40): DeviceRadixSort's DoubleBuffer overloads
+// with a uint64_t count, for 32- or 64-bit keys with no, 32-bit or 64-bit values.  A struct of its own rather than uint64_t
+// overloads of DeviceRadixSort, so that existing callers who pass a size_t keep the overload they had.
+struct DeviceRadixSortLarge {
+    template <typename KeyT, typename ValueT>
+    static hipError_t Dispatch(void *d_temp_storage, size_t &temp_storage_bytes, DoubleBuffer<KeyT> &d_keys,
+                               DoubleBuffer<ValueT> *d_values, uint64_t num_items, int begin_bit, int end_bit, bool descending,
+                               hipStream_t stream)
+    {
+        constexpr int KB = (int)sizeof(KeyT), VB = std::is_same<ValueT, NullType>::value ? 0 : (int)sizeof(ValueT);
+        static_assert(KB == 4 || KB == 8, "32- or 64-bit keys");
+        static_assert(VB == 0 || VB == 4 || VB == 8, "32- or 64-bit values");
+        const int vb = d_values ? VB : 0;
+        const size_t need = gs_lsb_large_temp_bytes(num_items, KB, vb);
+        if (d_temp_storage == nullptr) {
+            temp_storage_bytes = need;
+            return hipSuccess;
+        }
+        void *keys[2] = {d_keys.d_buffers[0], d_keys.d_buffers[1]};
+        void *vals[2] = {nullptr, nullptr};
+        if (d_values) { vals[0] = d_values->d_buffers[0]; vals[1] = d_values->d_buffers[1]; }
+        int sel = d_keys.selector;
+        const int err = gs_lsb_sort_large(d_temp_storage, temp_storage_bytes, keys, d_values ? vals : nullptr, &sel, num_items, KB, vb,
+                                          begin_bit, end_bit, descending ? 1 : 0, KeyTraits<KeyT>::type, stream);
+        if (err == 0) {
+            d_keys.selector = sel;
+            if (d_values) d_values->selector = sel;
+        }
+        return static_cast<hipError_t>(err);
+    }
+    template <typename KeyT>
+    static hipError_t SortKeys(void *d_temp_storage, size_t &temp_storage_bytes, DoubleBuffer<KeyT> &d_keys, uint64_t num_items,
+                               int begin_bit = 0, int end_bit = sizeof(KeyT) * 8, hipStream_t stream = 0,
+                               bool /*debug_synchronous*/ = false)
+    {
+        return Dispatch<KeyT, NullType>(d_temp_storage, temp_storage_bytes, d_keys, nullptr, num_items, begin_bit, end_bit, false,
+                                        stream);
+    }
+    template <typename KeyT>
+    static hipError_t SortKeysDescending(void *d_temp_storage, size_t &temp_storage_bytes, DoubleBuffer<KeyT> &d_keys,
+                                         uint64_t num_items, int begin_bit = 0, int end_bit = sizeof(KeyT) * 8, hipStream_t stream = 0,
+                                         bool /*debug_synchronous*/ = false)
+    {
+        return Dispatch<KeyT, NullType>(d_temp_storage, temp_storage_bytes, d_keys, nullptr, num_items, begin_bit, end_bit, true,
+                                        stream);
+    }
+    template <typename KeyT, typename ValueT>
+    static hipError_t SortPairs(void *d_temp_storage, size_t &temp_storage_bytes, DoubleBuffer<KeyT> &d_keys,
+                                DoubleBuffer<ValueT> &d_values, uint64_t num_items, int begin_bit = 0, int end_bit = sizeof(KeyT) * 8,
+                                hipStream_t stream = 0, bool /*debug_synchronous*/ = false)
+    {
+        return Dispatch<KeyT, ValueT>(d_temp_storage, temp_storage_bytes, d_keys, &d_values, num_items, begin_bit, end_bit, false,
+                                      stream);
+    }
+    template <typename KeyT, typename ValueT>
+    static hipError_t SortPairsDescending(void *d_temp_storage, size_t &temp_storage_bytes, DoubleBuffer<KeyT> &d_keys,
+                                          DoubleBuffer<ValueT> &d_values, uint64_t num_items, int begin_bit = 0,
+                                          int end_bit = sizeof(KeyT) * 8, hipStream_t stream = 0, bool /*debug_synchronous*/ = false)
+    {
+        return Dispatch<KeyT, ValueT>(d_temp_storage, temp_storage_bytes, d_keys, &d_values, num_items, begin_bit, end_bit, true,
+                                      stream);
+    }
+};
+
 // cub::DeviceSegmentedRadixSort, DoubleBuffer overloads (lsb/cub/cub/device/device_segmented_radix_sort.cuh:
 // 266-289, 450-473, 607-629, 779-801): 32- or 64-bit keys, 32- or 64-bit values, int offsets.
 struct DeviceSegmentedRadixSort {
