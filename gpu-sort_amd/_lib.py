@@ -37,6 +37,9 @@ SIGNATURES = {
     "gs_lsb_sort_wide": (i32, [vp, sz, pp, pp, C.POINTER(i32), u64, i32, i32, i32, i32, i32, i32, vp]),
     "gs_lsb_any_temp_bytes": (sz, [u64, i32, i32]),
     "gs_lsb_sort_any": (i32, [vp, sz, vp, vp, vp, vp, u64, i32, i32, i32, i32, i32, vp]),
+    "gs_lsb_narrow_temp_bytes": (sz, [u64, i32, i32]),
+    "gs_lsb_sort_narrow": (i32, [vp, sz, vp, vp, vp, vp, u64, i32, i32, i32, i32, i32, vp]),
+    "gs_lsb_narrow_tile": (C.c_uint32, [i32, i32]),
     "gs_lsb_geometry": (None, [u64, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "gs_lsb_workspace_layout": (i32, [vp, u64, pp, pp, pp]),
     "gs_lsb_pipe_status": (i32, [vp, u64, C.POINTER(C.c_uint32), vp]),

@@ -1,0 +1,503 @@
+// gs_narrow.hip -- the LSB sort of 8- and 16-bit keys (bool / char / signed char / unsigned char / short / unsigned short)
+// with no values or values of 1, 2, 4, 8 or 16 bytes, on kernels of its own: keys and values stay at their own width in HBM
+// and in LDS.  gs_lsb_sort_any (gs_any.hip) widens such keys to (u32 sort key, u32 index) pairs, sorts those and gathers;
+// this file is the native route for the same plain-pointer contract.
+//   (a) the digit pass: a stable 8-bit pass of upsweep, spine scan (gs_lsb.hip's) and downsweep, the decomposition of
+//       gs_wide.hip with K = 1 or 2 bytes.  One pass serves 8-bit keys, two serve 16-bit keys (in -> workspace -> out);
+//       a bit range of 8 bits or fewer is one pass whatever the key's width.
+//       - The tile is sized by its bytes in LDS and its registers: 512 threads x 16 / 8 / 4 elements for values of <= 4 / 8 / 16
+//         bytes (8192, 4096, 2048 elements): the one staging buffer (keys, then values) is 8 to 32 KiB, and 16 elements per
+//         thread keep the downsweep at 4 waves per SIMD (32 per thread took 184-226 VGPRs: 2 waves per SIMD).
+//       - Keys, and 1- and 2-byte values, are read from HBM as aligned 16-byte chunks into LDS (a u8 array may start at any
+//         byte and a u16 array at any even one: the chunks are read from the aligned address below, and only chunks that
+//         hold an element of the array are touched), and each lane takes its elements from there: element i of lane l of
+//         wave w is element w * 64 * KPT + i * 64 + l of the tile, the wave-striped order the ballot ranking needs.
+//       - The spine has one column per TILE ([256][tiles] u32, 1 KiB per tile) instead of the wide pass's chunks of 8 tiles
+//         with u16 in-chunk prefixes: a third more workspace, one array less.
+//       - Keys are never rewritten: the sign flip and the descending complement are an xor on the way to the digit.
+//   (b) 8-bit keys, keys only, all 8 bits (the default SortKeys call): a 256-bin histogram and a fill of the output with
+//       runs; nothing is scattered.  Descending and signed keys only change the order the bins are walked in.
+// 16-bit keys, keys only, take two passes of (a): the 65536-bin fill is not built.
+#include "gs_device.hpp"
+#include "gs_lsb.hpp"
+
+namespace gs {
+
+constexpr int N_THREADS = 512;
+constexpr int N_WAVES = N_THREADS / WAVE;
+constexpr uint32_t N_SHARED_TILES = 2048;   // up to this many tiles, an upsweep block counts one tile with all its waves
+
+constexpr int narrow_kpt(int vb) { return vb <= 4 ? 16 : vb == 8 ? 8 : 4; }
+constexpr int narrow_tile(int vb) { return N_THREADS * narrow_kpt(vb); }
+
+template <int B> struct NElem;
+template <> struct NElem<1> { typedef uint8_t type; };
+template <> struct NElem<2> { typedef uint16_t type; };
+template <> struct NElem<4> { typedef uint32_t type; };
+template <> struct NElem<8> { typedef uint64_t type; };
+template <> struct NElem<16> { typedef uint4 type; };
+
+struct NarrowParams {
+    uint64_t n;
+    uint32_t num_tiles;
+    uint32_t shift, mask;   // digit = ((key ^ xr) >> shift) & mask
+    uint32_t xr;            // sign flip of the key's own width, complement when descending
+};
+
+__device__ __forceinline__ uint32_t n_digit(uint32_t k, const NarrowParams &p) { return ((k ^ p.xr) >> p.shift) & p.mask; }
+
+// ---------------------------------------------------------------- upsweep --
+// A block counts tpb tiles (8: one wave per tile; 1: the 8 waves share one tile, for arrays of few tiles, where 8 tiles
+// per block would leave most of the chip idle): a wave reads 16-byte chunks that hold its share of the tile and counts the
+// digits of the elements that belong to it in a wave-private LDS histogram.
+template <int KB, int TILE>
+__global__ __launch_bounds__(N_THREADS) void narrow_upsweep_kernel(const void *__restrict__ keys, uint32_t *__restrict__ spine,
+                                                                   NarrowParams p, uint32_t tpb)
+{
+    __shared__ uint32_t hist[N_WAVES][RADIX];
+    const int tid = threadIdx.x, w = wave_id(), lane = lane_id();
+    uint32_t *my = hist[w];
+#pragma unroll
+    for (int i = lane; i < RADIX; i += WAVE) my[i] = 0;
+    const uint32_t wpt = (uint32_t)N_WAVES / tpb;                 // waves per tile
+    const uint32_t tile = blockIdx.x * tpb + (uint32_t)w / wpt;
+    if (tile < p.num_tiles) {
+        const uint64_t tile_base = (uint64_t)tile * TILE;
+        const uint32_t valid = (p.n - tile_base < (uint64_t)TILE) ? (uint32_t)(p.n - tile_base) : (uint32_t)TILE;
+        const uint32_t a = (uint32_t)((uintptr_t)keys & 15u);
+        const uint4 *A = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(keys) - a) + tile_base * KB / 16;
+        const uint32_t end_byte = a + valid * KB;                 // the tile's elements are bytes [a, end_byte) from A
+        const uint32_t nch = (end_byte + 15u) / 16u;
+        constexpr int GB = 4;
+#pragma unroll 1
+        for (uint32_t j = ((uint32_t)w % wpt) * (GB * WAVE); j < nch; j += wpt * (GB * WAVE)) {
+            uint4 v[GB];
+#pragma unroll
+            for (int u = 0; u < GB; ++u) {
+                const uint32_t c = j + u * WAVE + lane;
+                v[u] = A[c < nch ? c : nch - 1u];
+            }
+#pragma unroll
+            for (int u = 0; u < GB; ++u) {
+                const uint32_t c = j + u * WAVE + lane;
+                if (c >= nch) continue;
+                const uint32_t b0 = c * 16u;
+                const uint32_t x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+                if (b0 >= a && b0 + 16u <= end_byte) {
+#pragma unroll
+                    for (int q = 0; q < 16 / KB; ++q) {
+                        const uint32_t k = (x[q * KB / 4] >> (8 * (q * KB % 4))) & (KB == 1 ? 0xffu : 0xffffu);
+                        hist_add(my, n_digit(k, p));
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 16 / KB; ++q) {
+                        const uint32_t k = (x[q * KB / 4] >> (8 * (q * KB % 4))) & (KB == 1 ? 0xffu : 0xffffu);
+                        const uint32_t b = b0 + q * KB;
+                        if (b >= a && b < end_byte) hist_add(my, n_digit(k, p));
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < RADIX) {
+        for (uint32_t j = 0; j < tpb; ++j) {
+            const uint32_t t = blockIdx.x * tpb + j;
+            uint32_t sum = 0;
+            for (uint32_t u = 0; u < wpt; ++u) sum += hist[j * wpt + u][tid];
+            if (t < p.num_tiles) spine[(size_t)tid * p.num_tiles + t] = sum;
+        }
+    }
+}
+
+// -------------------------------------------------------------- downsweep --
+// the aligned 16-byte chunks that hold `bytes` bytes starting `a` (< 16) bytes into chunk 0 of A, copied to raw
+template <int MAX_CHUNKS>
+__device__ __forceinline__ void n_stage_in(const uint4 *__restrict__ A, uint32_t nch, unsigned char *raw)
+{
+    constexpr int IT = (MAX_CHUNKS + N_THREADS - 1) / N_THREADS;
+    uint4 v[IT];
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const uint32_t c = (uint32_t)threadIdx.x + it * N_THREADS;
+        v[it] = A[c < nch ? c : nch - 1u];          // unconditional loads from clamped chunks
+    }
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const uint32_t c = (uint32_t)threadIdx.x + it * N_THREADS;
+        if (c < nch) reinterpret_cast<uint4 *>(raw)[c] = v[it];
+    }
+}
+
+template <int KB, int VB>
+__global__ __launch_bounds__(N_THREADS) void narrow_downsweep_kernel(const void *__restrict__ keys_in, void *__restrict__ keys_out,
+                                                                     const void *__restrict__ vals_in, void *__restrict__ vals_out,
+                                                                     const uint32_t *__restrict__ spine,
+                                                                     const uint32_t *__restrict__ totals, NarrowParams p)
+{
+    typedef typename NElem<KB>::type K;
+    constexpr int KPT = narrow_kpt(VB), TILE = narrow_tile(VB);
+    constexpr int ELEM = KB > VB ? KB : VB;
+    __shared__ uint32_t whist[N_WAVES][RADIX];
+    __shared__ uint32_t gbase[RADIX];
+    __shared__ __attribute__((aligned(16))) unsigned char stage_raw[TILE * ELEM + 16];   // (+ 16: the chunk a misaligned tile spills into)
+
+    const int lane = lane_id(), w = wave_id();
+    const uint32_t t = tile_of_item(blockIdx.x, p.num_tiles);   // XCD-contiguous slices: neighbouring runs meet in one L2
+    const uint64_t tile_base = (uint64_t)t * TILE;
+    const uint32_t valid = (p.n - tile_base < (uint64_t)TILE) ? (uint32_t)(p.n - tile_base) : (uint32_t)TILE;
+    uint32_t *my = whist[w];
+    const uint32_t wbase = (uint32_t)w * (WAVE * KPT) + lane;
+
+    // the tile's keys: aligned chunks -> LDS
+    const uint32_t ka = (uint32_t)((uintptr_t)keys_in & 15u);
+    n_stage_in<TILE * KB / 16 + 1>(reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(keys_in) - ka) + tile_base * KB / 16,
+                                   (ka + valid * KB + 15u) / 16u, stage_raw);
+
+    // wave 0, lane l: global start of digits 4l..4l+3 for this tile
+    uint32_t g0[4] = {0, 0, 0, 0};
+    if (w == 0) {
+        const uint4 tot = reinterpret_cast<const uint4 *>(totals)[lane];
+        const uint32_t lane_sum = tot.x + tot.y + tot.z + tot.w;
+        const uint32_t ex = wave_inclusive_scan(lane_sum) - lane_sum;
+        const uint32_t *sp = spine + (size_t)(4 * lane) * p.num_tiles + t;
+        g0[0] = ex + sp[0];
+        g0[1] = ex + tot.x + sp[p.num_tiles];
+        g0[2] = ex + tot.x + tot.y + sp[2 * (size_t)p.num_tiles];
+        g0[3] = ex + tot.x + tot.y + tot.z + sp[3 * (size_t)p.num_tiles];
+    }
+#pragma unroll
+    for (int i = lane; i < RADIX; i += WAVE) my[i] = 0;
+    __syncthreads();
+
+    uint32_t key[KPT];
+    uint32_t pos[KPT];
+    const uint32_t pad = ~p.xr;                 // digit p.mask, the largest: ranked last, behind every element of the tile
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+        const uint32_t idx = wbase + i * WAVE;
+        const uint32_t k = *reinterpret_cast<const K *>(stage_raw + ka + (idx < valid ? idx : 0u) * KB);
+        key[i] = (idx < valid) ? k : pad;
+    }
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+        const uint32_t d = n_digit(key[i], p);
+        uint32_t plo, phi;
+        match_digit(d, plo, phi);
+        const uint32_t lower = count_lower(plo, phi);
+        pos[i] = my[d] + lower;
+        if (lower == 0)
+            __hip_atomic_fetch_add(&my[d], (uint32_t)(__popc(plo) + __popc(phi)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) asm volatile("" : "+v"(pos[i]));
+    __syncthreads();                            // every key is in registers: the raw chunks may be overwritten
+    if (w == 0) {
+        uint32_t run[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < N_WAVES; ++j) {
+            const uint4 x = reinterpret_cast<const uint4 *>(whist[j])[lane];
+            run[0] += x.x; run[1] += x.y; run[2] += x.z; run[3] += x.w;
+        }
+        const uint32_t lane_sum = run[0] + run[1] + run[2] + run[3];
+        uint4 e4;
+        e4.x = wave_inclusive_scan(lane_sum) - lane_sum;
+        e4.y = e4.x + run[0];
+        e4.z = e4.y + run[1];
+        e4.w = e4.z + run[2];
+        reinterpret_cast<uint4 *>(gbase)[lane] = make_uint4(g0[0] - e4.x, g0[1] - e4.y, g0[2] - e4.z, g0[3] - e4.w);
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int j = 0; j < N_WAVES; ++j) {
+            const uint4 x = reinterpret_cast<const uint4 *>(whist[j])[lane];
+            reinterpret_cast<uint4 *>(whist[j])[lane] = e4;
+            e4.x += x.x; e4.y += x.y; e4.z += x.z; e4.w += x.w;
+        }
+    }
+    __syncthreads();
+    K *stage_k = reinterpret_cast<K *>(stage_raw);
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+        pos[i] += my[n_digit(key[i], p)];
+        stage_k[pos[i]] = (K)key[i];
+    }
+    __syncthreads();
+    uint32_t dst[KPT];
+    K *kout = reinterpret_cast<K *>(keys_out);
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+        const uint32_t slot = (uint32_t)w * (WAVE * KPT) + i * WAVE + lane;   // wave-contiguous
+        const K k = stage_k[slot];
+        dst[i] = gbase[n_digit(k, p)] + slot;
+        if (slot < valid) kout[dst[i]] = k;
+    }
+    if constexpr (VB != 0) {
+        typedef typename NElem<VB>::type V;
+        V *stage_v = reinterpret_cast<V *>(stage_raw);
+        V val[KPT];
+        __syncthreads();                        // everyone is done reading the keys
+        if constexpr (VB <= 2) {                // narrow values come the way the keys did
+            const uint32_t va = (uint32_t)((uintptr_t)vals_in & 15u);
+            n_stage_in<TILE * VB / 16 + 1>(reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(vals_in) - va) + tile_base * VB / 16,
+                                           (va + valid * VB + 15u) / 16u, stage_raw);
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < KPT; ++i) {
+                const uint32_t idx = wbase + i * WAVE;
+                val[i] = *reinterpret_cast<const V *>(stage_raw + va + (idx < valid ? idx : 0u) * VB);
+            }
+            __syncthreads();
+        } else {
+            const V *vin = reinterpret_cast<const V *>(vals_in) + tile_base;
+#pragma unroll
+            for (int i = 0; i < KPT; ++i) {
+                const uint32_t idx = wbase + i * WAVE;
+                val[i] = vin[idx < valid ? idx : valid - 1u];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) stage_v[pos[i]] = val[i];
+        __syncthreads();
+        V *vout = reinterpret_cast<V *>(vals_out);
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+            const uint32_t slot = (uint32_t)w * (WAVE * KPT) + i * WAVE + lane;
+            if (slot < valid) vout[dst[i]] = stage_v[slot];
+        }
+    }
+}
+
+// ------------------------------------------- 8-bit keys only: count, fill --
+constexpr int NF_THREADS = 256;
+constexpr int NF_WAVES = NF_THREADS / WAVE;
+constexpr uint32_t NF_MAX_BLOCKS = 2048;
+
+// counts[v] += number of keys with the byte value v (no twiddle: the fill walks the bins in the order asked for)
+__global__ __launch_bounds__(NF_THREADS) void narrow_count8_kernel(const void *__restrict__ keys, uint32_t *__restrict__ counts, uint64_t n)
+{
+    __shared__ uint32_t hist[NF_WAVES][RADIX];
+    const int w = wave_id(), lane = lane_id();
+    uint32_t *my = hist[w];
+#pragma unroll
+    for (int i = lane; i < RADIX; i += WAVE) my[i] = 0;
+    const uint32_t a = (uint32_t)((uintptr_t)keys & 15u);
+    const uint4 *A = reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(keys) - a);
+    const uint64_t end_byte = a + n;                       // the keys are bytes [a, end_byte) from A
+    const uint64_t nch = (end_byte + 15u) / 16u;
+    const uint64_t stride = (uint64_t)gridDim.x * NF_THREADS;
+    for (uint64_t c = (uint64_t)blockIdx.x * NF_THREADS + threadIdx.x; c < nch; c += stride) {
+        const uint4 v = A[c];
+        const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+        const uint64_t b0 = c * 16u;
+        if (b0 >= a && b0 + 16u <= end_byte) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) hist_add(my, (x[q / 4] >> (8 * (q % 4))) & 0xffu);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if (b0 + q >= a && b0 + q < end_byte) hist_add(my, (x[q / 4] >> (8 * (q % 4))) & 0xffu);
+        }
+    }
+    __syncthreads();
+    const uint32_t d = threadIdx.x;
+    const uint32_t sum = hist[0][d] + hist[1][d] + hist[2][d] + hist[3][d];
+    if (sum) atomicAdd(&counts[d], sum);
+}
+
+// out[i] = the key of rank i: bin j of the walk holds the byte value v(j) = (descending ? 255 - j : j) ^ sign
+__global__ __launch_bounds__(NF_THREADS) void narrow_fill8_kernel(void *__restrict__ keys_out, const uint32_t *__restrict__ counts, uint64_t n,
+                                                                  uint32_t sign, int descending)
+{
+    __shared__ uint32_t scratch[8];
+    __shared__ uint32_t ends[RADIX];            // ends[j]: number of keys in bins 0..j (n < 2^32)
+    const uint32_t j0 = threadIdx.x;
+    const uint32_t cnt = counts[((descending ? 255u - j0 : j0) ^ sign) & 0xffu];
+    ends[j0] = block_exclusive_scan_256(cnt, scratch, nullptr) + cnt;
+    __syncthreads();
+    const uint32_t a = (uint32_t)((uintptr_t)keys_out & 15u);
+    unsigned char *A = reinterpret_cast<unsigned char *>(keys_out) - a;
+    const uint64_t end_byte = a + n;
+    const uint64_t nch = (end_byte + 15u) / 16u;
+    const uint64_t stride = (uint64_t)gridDim.x * NF_THREADS;
+    for (uint64_t c = (uint64_t)blockIdx.x * NF_THREADS + threadIdx.x; c < nch; c += stride) {
+        const uint64_t b0 = c * 16u;
+        const uint64_t lo = b0 < a ? a : b0, hi = b0 + 16u < end_byte ? b0 + 16u : end_byte;   // bytes [lo, hi) of this chunk are keys
+        const uint32_t e = (uint32_t)(lo - a);             // rank of the first of them
+        uint32_t j = 0;                                     // smallest j with ends[j] > e
+#pragma unroll
+        for (uint32_t s = 128; s > 0; s >>= 1)
+            if (ends[j + s - 1] <= e) j += s;
+        const uint32_t v = ((descending ? 255u - j : j) ^ sign) & 0xffu;
+        if (hi - lo == 16u && ends[j] - e >= 16u) {         // a whole chunk inside one run
+            const uint32_t v4 = v * 0x01010101u;
+            *reinterpret_cast<uint4 *>(A + b0) = make_uint4(v4, v4, v4, v4);
+        } else if (hi - lo == 16u) {
+            uint32_t x[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                while (ends[j] <= e + q) ++j;
+                x[q / 4] |= (((descending ? 255u - j : j) ^ sign) & 0xffu) << (8 * (q % 4));
+            }
+            *reinterpret_cast<uint4 *>(A + b0) = make_uint4(x[0], x[1], x[2], x[3]);
+        } else {                                            // the array's first or last chunk: byte stores
+            for (uint64_t b = lo; b < hi; ++b) {
+                while (ends[j] <= (uint32_t)(b - a)) ++j;
+                A[b] = (unsigned char)((descending ? 255u - j : j) ^ sign);
+            }
+        }
+    }
+}
+
+// begin_bit == end_bit: the output is the input
+__global__ __launch_bounds__(256) void narrow_copy_kernel(const unsigned char *__restrict__ in, unsigned char *__restrict__ out, uint64_t bytes)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < bytes; i += stride) out[i] = in[i];
+}
+
+// ------------------------------------------------------------------- host --
+static inline size_t n_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline int n_key_bytes(int key_type)
+{
+    switch (key_type) {
+    case GS_KEY_U8: case GS_KEY_I8: return 1;
+    case GS_KEY_U16: case GS_KEY_I16: return 2;
+    default: return 0;
+    }
+}
+static inline bool n_val_ok(int vb) { return vb == 0 || vb == 1 || vb == 2 || vb == 4 || vb == 8 || vb == 16; }
+static inline uint32_t n_tiles(uint64_t n, int vb)
+{
+    const uint64_t T = (uint64_t)narrow_tile(vb);
+    const uint64_t t = (n + T - 1) / T;
+    return (uint32_t)(t ? t : 1);
+}
+static inline size_t n_spine_bytes(uint64_t n, int vb) { return n_align256((size_t)RADIX * n_tiles(n, vb) * 4); }
+static inline size_t n_totals_bytes() { return n_align256(RADIX * 4); }
+
+template <int KB, int VB>
+static int narrow_pass(const void *kin, void *kout, const void *vin, void *vout, uint32_t *spine, uint32_t *totals,
+                       const NarrowParams &p, hipStream_t s)
+{
+    constexpr int TILE = narrow_tile(VB);
+    const uint32_t tpb = p.num_tiles > N_SHARED_TILES ? (uint32_t)N_WAVES : 1u;
+    { KernelTimer kt(GS_K_LSB_UPSWEEP, s);
+      hipLaunchKernelGGL((narrow_upsweep_kernel<KB, TILE>), dim3((p.num_tiles + tpb - 1) / tpb), dim3(N_THREADS), 0, s, kin, spine, p, tpb); }
+    const int e = lsb_scan(spine, totals, p.num_tiles, s);
+    if (e) return e;
+    { KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
+      hipLaunchKernelGGL((narrow_downsweep_kernel<KB, VB>), dim3(p.num_tiles), dim3(N_THREADS), 0, s, kin, kout, vin, vout,
+                         (const uint32_t *)spine, (const uint32_t *)totals, p); }
+    return (int)hipGetLastError();
+}
+
+static int narrow_pass_dispatch(int kb, int vb, const void *kin, void *kout, const void *vin, void *vout, uint32_t *spine,
+                                uint32_t *totals, const NarrowParams &p, hipStream_t s)
+{
+#define GS_N(KB_, VB_) return narrow_pass<KB_, VB_>(kin, kout, vin, vout, spine, totals, p, s)
+#define GS_NV(KB_) switch (vb) { case 0: GS_N(KB_, 0); case 1: GS_N(KB_, 1); case 2: GS_N(KB_, 2); case 4: GS_N(KB_, 4); \
+                                 case 8: GS_N(KB_, 8); default: GS_N(KB_, 16); }
+    if (kb == 1) GS_NV(1)
+    GS_NV(2)
+#undef GS_NV
+#undef GS_N
+}
+
+static inline dim3 n_stream_grid(uint64_t items, uint32_t per_block)
+{
+    const uint64_t b = (items + per_block - 1) / per_block;
+    return dim3((unsigned)(b < 1 ? 1 : (b > NF_MAX_BLOCKS ? NF_MAX_BLOCKS : b)));
+}
+
+}  // namespace gs
+
+using namespace gs;
+
+extern "C" {
+
+uint32_t gs_lsb_narrow_tile(int key_type, int val_bytes)
+{
+    if (n_key_bytes(key_type) == 0 || !n_val_ok(val_bytes)) return 0;
+    return (uint32_t)narrow_tile(val_bytes);
+}
+
+size_t gs_lsb_narrow_temp_bytes(uint64_t num_items, int key_type, int val_bytes)
+{
+    const int kb = n_key_bytes(key_type);
+    if (kb == 0 || !n_val_ok(val_bytes) || num_items >= (1ull << 32)) return 0;
+    size_t b = n_spine_bytes(num_items, val_bytes) + n_totals_bytes() + GS_WS_SLACK;
+    if (kb == 2) b += n_align256((size_t)num_items * 2) + n_align256((size_t)num_items * (size_t)val_bytes);
+    return b;
+}
+
+int gs_lsb_sort_narrow(void *d_temp, size_t temp_bytes, const void *d_keys_in, void *d_keys_out, const void *d_vals_in,
+                       void *d_vals_out, uint64_t num_items, int key_type, int val_bytes, int begin_bit, int end_bit,
+                       int descending, void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    const int kb = n_key_bytes(key_type);
+    if (kb == 0 || !n_val_ok(val_bytes)) return hipErrorInvalidValue;
+    if (begin_bit < 0 || end_bit > 8 * kb || begin_bit > end_bit) return hipErrorInvalidValue;
+    if (num_items >= (1ull << 32)) return hipErrorInvalidValue;
+    if (num_items == 0) return hipSuccess;              // (empty arrays may come with null pointers)
+    if ((val_bytes != 0) != (d_vals_in != nullptr) || (val_bytes != 0) != (d_vals_out != nullptr)) return hipErrorInvalidValue;
+    if (!d_keys_in || !d_keys_out || d_keys_in == d_keys_out || (val_bytes && d_vals_in == d_vals_out)) return hipErrorInvalidValue;
+    if (((uintptr_t)d_keys_in | (uintptr_t)d_keys_out) & (uintptr_t)(kb - 1)) return hipErrorInvalidValue;
+    if (val_bytes && (((uintptr_t)d_vals_in | (uintptr_t)d_vals_out) & (uintptr_t)(val_bytes - 1))) return hipErrorInvalidValue;
+    if (!d_temp || temp_bytes < gs_lsb_narrow_temp_bytes(num_items, key_type, val_bytes)) return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t n = num_items;
+    char *c = gs_ws_base(d_temp);   // spine, totals, then (16-bit keys) the intermediate keys and values
+    uint32_t *spine = (uint32_t *)c;
+    uint32_t *totals = (uint32_t *)(c + n_spine_bytes(n, val_bytes));
+    const uint32_t sign = (key_type == GS_KEY_I8) ? 0x80u : (key_type == GS_KEY_I16) ? 0x8000u : 0u;
+
+    if (begin_bit == end_bit) {
+        hipLaunchKernelGGL(narrow_copy_kernel, n_stream_grid(n * kb, 256 * 16), dim3(256), 0, s, (const unsigned char *)d_keys_in,
+                           (unsigned char *)d_keys_out, n * (uint64_t)kb);
+        if (val_bytes)
+            hipLaunchKernelGGL(narrow_copy_kernel, n_stream_grid(n * val_bytes, 256 * 16), dim3(256), 0, s,
+                               (const unsigned char *)d_vals_in, (unsigned char *)d_vals_out, n * (uint64_t)val_bytes);
+        return (int)hipGetLastError();
+    }
+    if (kb == 1 && val_bytes == 0 && begin_bit == 0 && end_bit == 8) {   // (b): count and fill
+        hipError_t ze = zero_async(totals, RADIX * 4, s);
+        if (ze != hipSuccess) return (int)ze;
+        // one chunk per thread up to 256 blocks, then more chunks per thread (every block ends with 256 global atomics on
+        // the same 256 counters: 2^24 keys took 0.056 ms with 2048 blocks and 0.034 ms with 512), up to 2048 blocks
+        const uint64_t chunks = (n + 15) / 16 + 1;
+        const dim3 g = chunks <= 256ull * NF_THREADS * 8 ? n_stream_grid(chunks < 256ull * NF_THREADS ? chunks : 256ull * NF_THREADS, NF_THREADS)
+                                                         : n_stream_grid(chunks, NF_THREADS * 8);
+        { KernelTimer kt(GS_K_LSB_UPSWEEP, s);
+          hipLaunchKernelGGL(narrow_count8_kernel, g, dim3(NF_THREADS), 0, s, d_keys_in, totals, n); }
+        { KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
+          hipLaunchKernelGGL(narrow_fill8_kernel, g, dim3(NF_THREADS), 0, s, d_keys_out, (const uint32_t *)totals, n, sign, descending ? 1 : 0); }
+        return (int)hipGetLastError();
+    }
+
+    const int num_passes = (end_bit - begin_bit + RADIX_BITS - 1) / RADIX_BITS;   // 1 or 2
+    void *tk = nullptr, *tv = nullptr;
+    if (kb == 2) {
+        tk = c + n_spine_bytes(n, val_bytes) + n_totals_bytes();
+        tv = (char *)tk + n_align256((size_t)n * 2);
+    }
+    for (int pass = 0; pass < num_passes; ++pass) {
+        NarrowParams p{};
+        p.n = n; p.num_tiles = n_tiles(n, val_bytes);
+        p.shift = (uint32_t)(begin_bit + pass * RADIX_BITS);
+        const int bits = (end_bit - (int)p.shift < RADIX_BITS) ? end_bit - (int)p.shift : RADIX_BITS;
+        p.mask = (1u << bits) - 1u;
+        p.xr = sign ^ (descending ? 0xffffffffu : 0u);
+        const bool first = pass == 0, last = pass == num_passes - 1;
+        const void *kin = first ? d_keys_in : tk;
+        const void *vin = first ? d_vals_in : tv;
+        void *kout = last ? d_keys_out : tk;
+        void *vout = last ? d_vals_out : tv;
+        const int e = narrow_pass_dispatch(kb, val_bytes, kin, kout, val_bytes ? vin : nullptr, val_bytes ? vout : nullptr, spine, totals, p, s);
+        if (e) return e;
+    }
+    return hipSuccess;
+}
+
+}  // extern "C"

@@ -102,14 +102,17 @@ class DeviceRadixSort:
     def _sort_any(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items, begin_bit, end_bit, descending,
                   stream, key_type, kb, vb):
         """8- and 16-bit keys (torch.bool / uint8 / int8 / int16 [/ uint16]) and values of any size (1- and 2-byte
-        elements, or rows of a 2-D tensor: 16-byte records like the reference's TestFoo): gs_lsb_sort_any.  It is the
+        elements, or rows of a 2-D tensor: 16-byte records like the reference's TestFoo): gs_lsb_sort_narrow (native
+        kernels) for 8- and 16-bit keys with values of 0 / 1 / 2 / 4 / 8 / 16 bytes, gs_lsb_sort_any for the rest.  Both are the
         plain-pointer form underneath (input untouched, result in the other buffer), so the sorted data ALWAYS ends in
         the alternate buffer and the selector flips once -- a DoubleBuffer contract as good as any other."""
         if key_type is None:
             key_type = _KEY_TYPES.get(d_keys.d_buffers[0].dtype)
             if key_type is None:
                 raise TypeError(f"no key category for dtype {d_keys.d_buffers[0].dtype}: pass key_type")
-        need = lib.gs_lsb_any_temp_bytes(num_items, key_type, vb)
+        # 8- and 16-bit keys with a value size gs_narrow.hip serves: the native kernels (same contract, same result)
+        narrow = kb < 4 and lib.gs_lsb_narrow_tile(key_type, vb) != 0
+        need = (lib.gs_lsb_narrow_temp_bytes if narrow else lib.gs_lsb_any_temp_bytes)(num_items, key_type, vb)
         if d_temp_storage is None:
             return need
         if end_bit is None:
@@ -122,13 +125,14 @@ class DeviceRadixSort:
             if d_values.selector != d_keys.selector:
                 raise ValueError("d_keys and d_values selectors differ")
         sel = d_keys.selector
-        err = lib.gs_lsb_sort_any(C.c_void_p(d_temp_storage.data_ptr()),
-                                  min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
-                                  d_keys.d_buffers[sel].data_ptr(), d_keys.d_buffers[sel ^ 1].data_ptr(),
-                                  d_values.d_buffers[sel].data_ptr() if vb else None,
-                                  d_values.d_buffers[sel ^ 1].data_ptr() if vb else None, num_items, key_type, vb,
-                                  begin_bit, end_bit, int(descending), _stream_ptr(stream))
-        check(err, "gs_lsb_sort_any")
+        fn, name = (lib.gs_lsb_sort_narrow, "gs_lsb_sort_narrow") if narrow else (lib.gs_lsb_sort_any, "gs_lsb_sort_any")
+        err = fn(C.c_void_p(d_temp_storage.data_ptr()),
+                 min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                 d_keys.d_buffers[sel].data_ptr(), d_keys.d_buffers[sel ^ 1].data_ptr(),
+                 d_values.d_buffers[sel].data_ptr() if vb else None,
+                 d_values.d_buffers[sel ^ 1].data_ptr() if vb else None, num_items, key_type, vb,
+                 begin_bit, end_bit, int(descending), _stream_ptr(stream))
+        check(err, name)
         d_keys.selector = sel ^ 1
         if vb:
             d_values.selector = sel ^ 1

@@ -46,7 +46,7 @@ enum gs_key_type {
     GS_KEY_U64 = 3,   /* 64-bit keys: gs_lsb_sort_wide only        */
     GS_KEY_I64 = 4,
     GS_KEY_F64 = 5,
-    GS_KEY_U8 = 6,    /* 8- and 16-bit keys: gs_lsb_sort_any only   */
+    GS_KEY_U8 = 6,    /* 8- and 16-bit keys: gs_lsb_sort_narrow/any */
     GS_KEY_I8 = 7,    /* (bool / unsigned char: U8; char / signed   */
     GS_KEY_U16 = 8,   /*  char: I8; unsigned short / short)         */
     GS_KEY_I16 = 9
@@ -75,8 +75,8 @@ const char *gs_error_string(int err);
  * may take (cub's AliasTemporaries, util_device.cuh:68-96), so exactly the
  * queried size is enough at any address.  Data arrays (keys, values, their
  * alternates and outputs, segment offsets, bucket counts) need the natural
- * alignment of their element; the 16-byte values of gs_lsb_sort_any need 16
- * bytes.  A call writes only inside the arrays and the workspace it was
+ * alignment of their element; the 16-byte values of gs_lsb_sort_any and
+ * gs_lsb_sort_narrow need 16 bytes.  A call writes only inside the arrays and the workspace it was
  * given, and a refused call (hipErrorInvalidValue) writes nothing.          */
 size_t gs_lsb_temp_bytes(uint64_t num_items, int has_values);
 
@@ -155,6 +155,29 @@ size_t gs_lsb_any_temp_bytes(uint64_t num_items, int key_type, int val_bytes);
 int gs_lsb_sort_any(void *d_temp, size_t temp_bytes, const void *d_keys_in, void *d_keys_out,
                     const void *d_vals_in, void *d_vals_out, uint64_t num_items, int key_type, int val_bytes,
                     int begin_bit, int end_bit, int descending, void *stream);
+
+/* 8- and 16-bit keys on kernels of their own (gs_narrow.hip): key_type GS_KEY_U8 / GS_KEY_I8 / GS_KEY_U16 / GS_KEY_I16 with
+ * val_bytes 0, 1, 2, 4, 8 or 16.  The contract is gs_lsb_sort_any's, so a caller can move from one to the other: plain
+ * pointers, the inputs are never written, the outputs must not alias the inputs, stable, ascending or descending, on the bits
+ * [begin_bit, end_bit) of the key's own width (begin_bit == end_bit copies input to output in input order), num_items < 2^32
+ * (0 succeeds with null pointers), only enqueues work on `stream` (no host synchronisation, allocation or read-back; calls
+ * may follow each other on one stream with one workspace).  Every other key type or value size is refused with
+ * hipErrorInvalidValue and its size query returns 0: those stay with gs_lsb_sort_any.  Keys and values move at their own
+ * width: one 8-bit digit pass for 8-bit keys, two for 16-bit keys (only the passes that hold bits of the range run), and a
+ * 256-bin histogram and fill, without a scatter, for 8-bit keys alone over all 8 bits.  The alignment paragraph above holds:
+ * a u8 array may start at any byte address, a u16 array at any even one, values at a multiple of their size.
+ * Workspace, with T = gs_lsb_narrow_tile(key_type, val_bytes) elements per tile (8192 for values of <= 4 bytes, 4096 /
+ * 2048 for 8 / 16 bytes) and every term rounded up to 256 bytes:
+ *   256 * 4 * max(1, ceil(num_items / T))  the spine, one u32 per digit and tile
+ * + 256 * 4                                 the digit totals (the histogram of the fill path)
+ * + 16-bit keys only: 2 * num_items + val_bytes * num_items   the intermediate keys and values of the pass in -> temp -> out
+ * + 256 bytes of alignment slack.                                                                                       */
+size_t gs_lsb_narrow_temp_bytes(uint64_t num_items, int key_type, int val_bytes);
+int gs_lsb_sort_narrow(void *d_temp, size_t temp_bytes, const void *d_keys_in, void *d_keys_out,
+                       const void *d_vals_in, void *d_vals_out, uint64_t num_items, int key_type, int val_bytes,
+                       int begin_bit, int end_bit, int descending, void *stream);
+/* elements per tile of the digit pass for this key type and value size (0: not served); tests sweep sizes around it */
+uint32_t gs_lsb_narrow_tile(int key_type, int val_bytes);
 
 /* ------------------------------------------------------------------ MSB --
  * Unstable most-significant-digit hybrid radix sort, ascending.

@@ -71,14 +71,18 @@ struct DeviceRadixSort {
             // 8- and 16-bit keys, values of any other size (1, 2, 16, ... bytes: TestBackend<KeyT, KeyT>, TestFoo): gs_lsb_sort_any.
             // It is the plain-pointer form underneath, so the result always lands in the ALTERNATE buffer and the
             // selector flips once.
+            // 8- and 16-bit keys with values of 0 / 1 / 2 / 4 / 8 / 16 bytes go to the native kernels of gs_lsb_sort_narrow (the
+            // same contract and the same result).
             const int vb = d_values ? VB : 0;
-            const size_t need_a = gs_lsb_any_temp_bytes((uint64_t)num_items, KeyTraits<KeyT>::type, vb);
+            constexpr bool NARROW = sizeof(KeyT) < 4 && (VB == 0 || VB == 1 || VB == 2 || VB == 4 || VB == 8 || VB == 16);
+            const size_t need_a = NARROW ? gs_lsb_narrow_temp_bytes((uint64_t)num_items, KeyTraits<KeyT>::type, vb)
+                                         : gs_lsb_any_temp_bytes((uint64_t)num_items, KeyTraits<KeyT>::type, vb);
             if (d_temp_storage == nullptr) {
                 temp_storage_bytes = need_a;
                 return hipSuccess;
             }
             const int sel_a = d_keys.selector;
-            const int err_a = gs_lsb_sort_any(d_temp_storage, temp_storage_bytes, d_keys.d_buffers[sel_a], d_keys.d_buffers[sel_a ^ 1],
+            const int err_a = (NARROW ? gs_lsb_sort_narrow : gs_lsb_sort_any)(d_temp_storage, temp_storage_bytes, d_keys.d_buffers[sel_a], d_keys.d_buffers[sel_a ^ 1],
                                               d_values ? (const void *)d_values->d_buffers[sel_a] : nullptr,
                                               d_values ? (void *)d_values->d_buffers[sel_a ^ 1] : nullptr, (uint64_t)num_items,
                                               KeyTraits<KeyT>::type, vb, begin_bit, end_bit, descending ? 1 : 0, stream);

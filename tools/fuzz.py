@@ -249,6 +249,59 @@ def any_case(it):
         fail("any values (stability)", **case)
 
 
+def narrow_case(it):
+    """gs_lsb_sort_narrow through the C ABI: 8- / 16-bit keys with values of 0 / 1 / 2 / 4 / 8 / 16 bytes, keys and values at a
+    random element offset inside their allocations, against torch's stable sort of the keys' order-preserving images"""
+    n = min(max(0, pick_n()), 2_000_000)
+    kt = str(rng.choice(["u8", "i8", "i16", "u16", "bool"]))
+    bits = {"u8": 8, "i8": 8, "bool": 8, "i16": 16, "u16": 16}[kt]
+    gtype = {"u8": gs.GS_KEY_U8, "bool": gs.GS_KEY_U8, "i8": gs.GS_KEY_I8, "i16": gs.GS_KEY_I16, "u16": gs.GS_KEY_U16}[kt]
+    vb = int(rng.choice([0, 1, 2, 4, 8, 16]))
+    koff = int(rng.integers(0, 16))
+    g = torch.Generator(device=dev); g.manual_seed(int(rng.integers(0, 2**31)))
+    raw = torch.randint(0, 1 << 31, (max(n, 1),), device=dev, generator=g, dtype=torch.int64)[:n]
+    if rng.random() < 0.4:
+        raw = raw & torch.randint(0, 1 << 31, (max(n, 1),), device=dev, generator=g, dtype=torch.int64)[:n]
+    if rng.random() < 0.15:
+        raw = torch.full_like(raw, int(rng.integers(0, 1 << 16)))          # all keys equal
+    img = raw & ((1 << bits) - 1)
+    if kt == "bool":
+        img = img & 1
+    tdt = torch.uint8 if bits == 8 else torch.int16
+    wrap = torch.where(img >= (1 << (bits - 1)), img - (1 << bits), img) if bits > 8 else img
+    kbuf = torch.zeros(n + koff, dtype=tdt, device=dev)
+    kbuf[koff:] = wrap.to(tdt)
+    keys = kbuf[koff:]
+    kout = torch.zeros(n + koff, dtype=tdt, device=dev)[koff:]
+    order_img = img ^ (1 << (bits - 1)) if kt in ("i8", "i16") else img
+    desc = bool(rng.random() < 0.4)
+    begin, end = (0, bits) if rng.random() < 0.5 else (lambda b: (b, int(rng.integers(b, bits + 1))))(int(rng.integers(0, bits)))
+    width = end - begin
+    d = (order_img >> begin) & ((1 << width) - 1) if width > 0 else torch.zeros_like(order_img)
+    if desc and width > 0:
+        d = ((1 << width) - 1) - d
+    perm = torch.sort(d, stable=True)[1]
+    vals = vout = None
+    if vb:
+        voff = int(rng.integers(0, 16)) if vb <= 2 else 1
+        vbuf = torch.randint(0, 256, ((n + voff) * vb,), device=dev, generator=g).to(torch.uint8)
+        vals = vbuf[voff * vb:].view(n, vb)
+        vout = torch.zeros((n + voff) * vb, dtype=torch.uint8, device=dev)[voff * vb:].view(n, vb)
+    case = dict(it=it, algo="narrow", n=n, kt=kt, vb=vb, desc=desc, begin=begin, end=end, koff=koff, seed=seed)
+    nb = gs.lib.gs_lsb_narrow_temp_bytes(n, gtype, vb)
+    temp = torch.empty(nb, dtype=torch.uint8, device=dev)
+    err = gs.lib.gs_lsb_sort_narrow(temp.data_ptr(), nb, keys.data_ptr(), kout.data_ptr(), vals.data_ptr() if vb else None,
+                                    vout.data_ptr() if vb else None, n, gtype, vb, begin, end, int(desc), None)
+    if err:
+        fail("narrow error %d" % err, **case)
+    if n == 0:
+        return
+    if not torch.equal(kout, keys[perm]):
+        fail("narrow keys", **case)
+    if vb and not torch.equal(vout, vals[perm]):
+        fail("narrow values (stability)", **case)
+
+
 def shard_case(it):
     """The multi-GPU pipeline's kernels with every rank emulated in this process: gs_msb_first_pass_u32 on W random
     shards, the host's split / group maps, then for one random rank the receive buffer it would get (group-major,
@@ -318,7 +371,11 @@ def shard_case(it):
 KINDS = ["uniform", "and1", "and3", "and6", "and10", "few", "const", "ones_heavy", "sorted", "reverse", "low_bytes", "hot", "zipf", "clustered"]
 counts = {}
 for it in range(iters):
-    algo = str(rng.choice(["lsb", "lsb", "msb", "msb", "seg", "wide", "any"]))
+    algo = str(rng.choice(["lsb", "lsb", "msb", "msb", "seg", "wide", "any", "narrow"]))
+    if algo == "narrow":
+        counts[algo] = counts.get(algo, 0) + 1
+        narrow_case(it)
+        continue
     if algo == "any":
         counts[algo] = counts.get(algo, 0) + 1
         any_case(it)
