@@ -2289,76 +2289,8 @@ __global__ __launch_bounds__(256) void seg_wave_sort_kernel(MsbWs ws, const uint
                                                             const uint32_t *__restrict__ src_v, uint32_t *__restrict__ dst_v, int f32_in,
                                                             uint32_t xor_in, int f32_out, uint32_t xor_out)
 {
-    constexpr int LIST = WKPT == 4 ? 0 : WKPT == 8 ? 1 : 2, CAP = WKPT * WAVE;
-    __shared__ __attribute__((aligned(16))) uint32_t hist[4][RADIX];
-    __shared__ uint32_t stage_k[4][CAP];
-    __shared__ uint32_t stage_v[HAS_VALUES ? 4 : 1][HAS_VALUES ? CAP : 1];
-    const int w = wave_id(), lane = lane_id();
-    uint32_t ntasks = ws.level[2].task_count[LIST];
-    if (ntasks > ws.max_tasks) ntasks = ws.max_tasks;
-    uint32_t *my = hist[w];
-    auto fence = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
-    for (uint32_t t = blockIdx.x * 4u + (uint32_t)w; t < ntasks; t += gridDim.x * 4u) {
-        const MsbTask Tv = ws.tasks[LIST][ws.max_tasks - 1u - t];
-        const uint32_t off = __builtin_amdgcn_readfirstlane(Tv.offset), size = __builtin_amdgcn_readfirstlane(Tv.size);
-        const uint32_t B = __builtin_amdgcn_readfirstlane(Tv.sort_bits), shift0 = __builtin_amdgcn_readfirstlane(Tv.pad);
-        uint32_t key[WKPT], val[HAS_VALUES ? WKPT : 1], pos[WKPT];
-        const uint32_t last = size - 1u;
-#pragma unroll
-        for (int i = 0; i < WKPT; ++i) {
-            const uint32_t idx = (uint32_t)(i * WAVE + lane), at = off + (idx < last ? idx : last);
-            key[i] = src_k[at];
-            if (HAS_VALUES) val[i] = src_v[at];
-        }
-#pragma unroll
-        for (int i = 0; i < WKPT; ++i) {
-            const uint32_t k = twiddle_in(key[i], f32_in, xor_in);
-            key[i] = ((uint32_t)(i * WAVE + lane) < size) ? k : 0xffffffffu;   // pads: last in position, largest in every digit
-        }
-        for (uint32_t done = 0; done < B; done += RADIX_BITS) {
-            const uint32_t bw = B - done < (uint32_t)RADIX_BITS ? B - done : (uint32_t)RADIX_BITS, sh = shift0 + done;
-            reinterpret_cast<uint4 *>(my)[lane] = make_uint4(0u, 0u, 0u, 0u);
-            fence();
-#pragma unroll
-            for (int i = 0; i < WKPT; ++i) {
-                const uint32_t d = __builtin_amdgcn_ubfe(key[i], sh, bw);
-                uint32_t lo, hi;
-                match_digit(d, lo, hi);
-                const uint32_t lower = count_lower(lo, hi);
-                pos[i] = my[d] + lower;
-                if (lower == 0) my[d] += (uint32_t)(__popc(lo) + __popc(hi));   // one lane per digit: no two writers of a word
-                fence();
-            }
-            {   // exclusive scan of the 256 counters, 4 per lane
-                const uint4 c = reinterpret_cast<const uint4 *>(my)[lane];
-                const uint32_t sum = c.x + c.y + c.z + c.w;
-                const uint32_t ex = wave_inclusive_scan(sum) - sum;
-                reinterpret_cast<uint4 *>(my)[lane] = make_uint4(ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z);
-            }
-            fence();
-#pragma unroll
-            for (int i = 0; i < WKPT; ++i) {
-                const uint32_t at = pos[i] + my[__builtin_amdgcn_ubfe(key[i], sh, bw)];
-                stage_k[w][at] = key[i];
-                if (HAS_VALUES) stage_v[w][at] = val[i];
-            }
-            fence();
-#pragma unroll
-            for (int i = 0; i < WKPT; ++i) {
-                key[i] = stage_k[w][i * WAVE + lane];
-                if (HAS_VALUES) val[i] = stage_v[w][i * WAVE + lane];
-            }
-            fence();
-        }
-#pragma unroll
-        for (int i = 0; i < WKPT; ++i) {
-            const uint32_t idx = (uint32_t)(i * WAVE + lane);
-            if (idx < size) {
-                dst_k[off + idx] = twiddle_out(key[i], f32_out, xor_out);
-                if (HAS_VALUES) dst_v[off + idx] = val[i];
-            }
-        }
-    }
+    typedef uint32_t K;
+#include "gs_seg_wave_body.inc"
 }
 
 // Segments of up to 64 elements: a wave sorts FOUR of them at a time, one per round of its four elements per lane -- every
@@ -2370,81 +2302,26 @@ __global__ __launch_bounds__(256) void seg_wave4_sort_kernel(MsbWs ws, const uin
                                                              const uint32_t *__restrict__ src_v, uint32_t *__restrict__ dst_v, int f32_in,
                                                              uint32_t xor_in, int f32_out, uint32_t xor_out)
 {
-    constexpr int NS = 4;                                          // segments per wave and step
-    __shared__ __attribute__((aligned(16))) uint32_t hist[4][NS][RADIX];
-    __shared__ uint32_t stage_k[4][NS * WAVE];
-    __shared__ uint32_t stage_v[HAS_VALUES ? 4 : 1][HAS_VALUES ? NS * WAVE : 1];
-    const int w = wave_id(), lane = lane_id();
-    uint32_t ntasks = ws.level[2].task_count[3];
-    if (ntasks > ws.max_tasks) ntasks = ws.max_tasks;
-    auto fence = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
-    for (uint32_t t0 = (blockIdx.x * 4u + (uint32_t)w) * NS; t0 < ntasks; t0 += gridDim.x * 4u * NS) {
-        uint32_t off[NS], size[NS], key[NS], val[HAS_VALUES ? NS : 1], pos[NS];
-        uint32_t B = 0, shift0 = 0;
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            off[i] = 0; size[i] = 0;
-            if (t0 + i < ntasks) {                                 // wave-uniform
-                const MsbTask Tv = ws.tasks[3][ws.max_tasks - 1u - (t0 + i)];
-                off[i] = __builtin_amdgcn_readfirstlane(Tv.offset); size[i] = __builtin_amdgcn_readfirstlane(Tv.size);
-                B = __builtin_amdgcn_readfirstlane(Tv.sort_bits); shift0 = __builtin_amdgcn_readfirstlane(Tv.pad);   // the same for every segment of a call
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            key[i] = 0xffffffffu;
-            if (HAS_VALUES) val[i] = 0;
-            if ((uint32_t)lane < size[i]) {
-                key[i] = twiddle_in(src_k[off[i] + lane], f32_in, xor_in);
-                if (HAS_VALUES) val[i] = src_v[off[i] + lane];
-            } else {
-                key[i] = 0xffffffffu;                              // pads: behind the segment's elements, largest in every digit
-            }
-        }
-        for (uint32_t done = 0; done < B; done += RADIX_BITS) {
-            const uint32_t bw = B - done < (uint32_t)RADIX_BITS ? B - done : (uint32_t)RADIX_BITS, sh = shift0 + done;
-#pragma unroll
-            for (int i = 0; i < NS; ++i) reinterpret_cast<uint4 *>(hist[w][i])[lane] = make_uint4(0u, 0u, 0u, 0u);
-            fence();
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const uint32_t d = __builtin_amdgcn_ubfe(key[i], sh, bw);
-                uint32_t lo, hi;
-                match_digit(d, lo, hi);
-                pos[i] = count_lower(lo, hi);
-                if (pos[i] == 0) hist[w][i][d] = (uint32_t)(__popc(lo) + __popc(hi));
-            }
-            fence();
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {   // exclusive scan of segment i's 256 counters, 4 per lane
-                const uint4 c = reinterpret_cast<const uint4 *>(hist[w][i])[lane];
-                const uint32_t sum = c.x + c.y + c.z + c.w;
-                const uint32_t ex = wave_inclusive_scan(sum) - sum;
-                reinterpret_cast<uint4 *>(hist[w][i])[lane] = make_uint4(ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z);
-            }
-            fence();
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                const uint32_t at = (uint32_t)(i * WAVE) + pos[i] + hist[w][i][__builtin_amdgcn_ubfe(key[i], sh, bw)];
-                stage_k[w][at] = key[i];
-                if (HAS_VALUES) stage_v[w][at] = val[i];
-            }
-            fence();
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                key[i] = stage_k[w][i * WAVE + lane];
-                if (HAS_VALUES) val[i] = stage_v[w][i * WAVE + lane];
-            }
-            fence();
-        }
-#pragma unroll
-        for (int i = 0; i < NS; ++i) {
-            if ((uint32_t)lane < size[i]) {
-                dst_k[off[i] + lane] = twiddle_out(key[i], f32_out, xor_out);
-                if (HAS_VALUES) dst_v[off[i] + lane] = val[i];
-            }
-        }
-    }
+    typedef uint32_t K;
+#include "gs_seg_wave4_body.inc"
+}
+
+// The same two kernels for 8- and 16-bit keys (gs_segmented_sort_narrow): K is the element type in memory, the keys live in
+// registers as u32 as above; only the loads and the stores differ.  A store is one element wide, so no byte outside the
+// segment is written.
+template <bool HAS_VALUES, int WKPT, typename K>
+__global__ __launch_bounds__(256) void seg_wave_sort_narrow_kernel(MsbWs ws, const K *__restrict__ src_k, K *__restrict__ dst_k,
+                                                                   const uint32_t *__restrict__ src_v, uint32_t *__restrict__ dst_v, int f32_in,
+                                                                   uint32_t xor_in, int f32_out, uint32_t xor_out)
+{
+#include "gs_seg_wave_body.inc"
+}
+template <bool HAS_VALUES, typename K>
+__global__ __launch_bounds__(256) void seg_wave4_sort_narrow_kernel(MsbWs ws, const K *__restrict__ src_k, K *__restrict__ dst_k,
+                                                                    const uint32_t *__restrict__ src_v, uint32_t *__restrict__ dst_v, int f32_in,
+                                                                    uint32_t xor_in, int f32_out, uint32_t xor_out)
+{
+#include "gs_seg_wave4_body.inc"
 }
 
 // ================================================================ wide MSB ==
@@ -3041,6 +2918,8 @@ static int seg_wide_sort(void *d_temp, void *d_keys[2], void *d_vals[2], int *se
     return (int)hipGetLastError();
 }
 
+#include "gs_seg_narrow.inc"
+
 }  // namespace gs
 
 using namespace gs;
@@ -3554,6 +3433,59 @@ int gs_segmented_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys[2], voi
     }
     GS_SW(uint32_t, uint64_t);
 #undef GS_SW
+}
+
+static inline int sn_key_bytes(int key_type)
+{
+    switch (key_type) {
+    case GS_KEY_U8: case GS_KEY_I8: return 1;
+    case GS_KEY_U16: case GS_KEY_I16: return 2;
+    default: return 0;
+    }
+}
+static inline bool sn_served(int key_type, int val_bytes)
+{
+    return sn_key_bytes(key_type) != 0 && (val_bytes == 0 || val_bytes == 4 || val_bytes == 8);
+}
+
+uint32_t gs_segmented_narrow_cap(int key_type, int val_bytes) { return sn_served(key_type, val_bytes) ? SN_CAP : 0u; }
+
+size_t gs_segmented_narrow_temp_bytes(uint64_t num_items, int key_type, int val_bytes, uint32_t num_segments)
+{
+    if (!sn_served(key_type, val_bytes) || num_items >= (1ull << 31)) return 0;
+    return msb_ws_bytes(num_items, val_bytes != 0, 0, num_segments, SN_CAP) + GS_WS_SLACK;
+}
+
+int gs_segmented_sort_narrow(void *d_temp, size_t temp_bytes, void *d_keys[2], void *d_vals[2], int *selector, uint64_t num_items,
+                             uint32_t num_segments, const int32_t *d_begin_offsets, const int32_t *d_end_offsets, int key_type,
+                             int val_bytes, int begin_bit, int end_bit, int descending, void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (!selector || (*selector != 0 && *selector != 1)) return hipErrorInvalidValue;
+    if (!sn_served(key_type, val_bytes)) return hipErrorInvalidValue;
+    const int kb = sn_key_bytes(key_type);
+    if (begin_bit < 0 || end_bit > 8 * kb || begin_bit > end_bit) return hipErrorInvalidValue;
+    if (num_items >= (1ull << 31)) return hipErrorInvalidValue;                  // int offsets
+    if (num_items == 0 || num_segments == 0 || begin_bit == end_bit) return hipSuccess;   // (nothing to do: null buffers are fine)
+    if (!d_keys || (val_bytes != 0) != (d_vals != nullptr)) return hipErrorInvalidValue;
+    if (!d_begin_offsets || !d_end_offsets) return hipErrorInvalidValue;
+    if (!d_temp || temp_bytes < gs_segmented_narrow_temp_bytes(num_items, key_type, val_bytes, num_segments)) return hipErrorInvalidValue;
+    if (!d_keys[0] || !d_keys[1] || (d_vals && (!d_vals[0] || !d_vals[1]))) return hipErrorInvalidValue;
+    if (((uintptr_t)d_keys[0] | (uintptr_t)d_keys[1]) & (uintptr_t)(kb - 1)) return hipErrorInvalidValue;
+    if (d_vals && (((uintptr_t)d_vals[0] | (uintptr_t)d_vals[1]) & (uintptr_t)(val_bytes - 1))) return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t sign = key_type == GS_KEY_I8 ? 0x80u : key_type == GS_KEY_I16 ? 0x8000u : 0u;
+#define GS_SN(KB, V) return seg_narrow_sort<KB, V>(gs_ws_base(d_temp), d_keys, d_vals, selector, num_items, num_segments, d_begin_offsets, \
+                                                   d_end_offsets, begin_bit, end_bit, descending, sign, s)
+    if (kb == 1) {
+        if (val_bytes == 0) GS_SN(1, MwNoVal);
+        if (val_bytes == 4) GS_SN(1, uint32_t);
+        GS_SN(1, uint64_t);
+    }
+    if (val_bytes == 0) GS_SN(2, MwNoVal);
+    if (val_bytes == 4) GS_SN(2, uint32_t);
+    GS_SN(2, uint64_t);
+#undef GS_SN
 }
 
 size_t gs_msb_wide_temp_bytes(uint64_t num_items, int key_bytes, int val_bytes)

@@ -204,6 +204,19 @@ int main(int argc, char **argv)
     bad += test_segmented<unsigned long long>(n, 1, true, "u64");
     bad += test_segmented<unsigned long long>(n, 37, false, "u64");
     bad += test_segmented<long long>(n, 5000, true, "i64");
+    // 8- and 16-bit keys: gs_segmented_sort_narrow
+    bad += test_segmented<unsigned char>(n, 1, false, "u8");
+    bad += test_segmented<unsigned char>(n, 37, true, "u8");
+    bad += test_segmented<unsigned char>(n, 5000, false, "u8");
+    bad += test_segmented<signed char>(n, 1, true, "i8");
+    bad += test_segmented<signed char>(n, 37, false, "i8");
+    bad += test_segmented<signed char>(n, 5000, true, "i8");
+    bad += test_segmented<unsigned short>(n, 1, false, "u16");
+    bad += test_segmented<unsigned short>(n, 37, true, "u16");
+    bad += test_segmented<unsigned short>(n, 5000, false, "u16");
+    bad += test_segmented<short>(n, 1, true, "i16");
+    bad += test_segmented<short>(n, 37, false, "i16");
+    bad += test_segmented<short>(n, 5000, true, "i16");
     printf("%s\n", bad ? "SOME CASES FAILED" : "ALL CORRECT");
     return bad ? 1 : 0;
 }

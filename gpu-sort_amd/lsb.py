@@ -306,6 +306,10 @@ class DeviceSegmentedRadixSort:
         has_values = d_values is not None
         kb = d_keys.d_buffers[0].element_size()
         vb = d_values.d_buffers[0].element_size() if has_values else 0
+        if kb < 4:                           # 8- and 16-bit keys: gs_segmented_sort_narrow
+            return DeviceSegmentedRadixSort._sort_narrow(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items,
+                                                         num_segments, d_begin_offsets, d_end_offsets, begin_bit, end_bit,
+                                                         descending, stream, key_type, kb, vb)
         wide = kb == 8 or vb == 8            # the wide element types: gs_segmented_sort_wide
         need = (lib.gs_segmented_wide_temp_bytes(num_items, kb, vb, num_segments) if wide
                 else lib.gs_segmented_temp_bytes(num_items, int(has_values), num_segments))
@@ -346,6 +350,52 @@ class DeviceSegmentedRadixSort:
         check(err, "gs_segmented_sort_u32")
         d_keys.selector = sel.value
         if has_values:
+            d_values.selector = sel.value
+        return need
+
+    @staticmethod
+    def _sort_narrow(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items, num_segments, d_begin_offsets,
+                     d_end_offsets, begin_bit, end_bit, descending, stream, key_type, kb, vb):
+        """8- and 16-bit keys (torch.bool / uint8 / int8 / int16 [/ uint16]) with no, 4-byte or 8-byte values:
+        gs_segmented_sort_narrow.  The selector flips once per 8-bit pass of the bit range.  Floating-point keys of these widths
+        (float16, bfloat16, 8-bit floats) have no key category and are refused, with or without an explicit key_type: a U16 / I16
+        key_type would sort them by bit pattern, which is not their order."""
+        if d_keys.d_buffers[0].dtype.is_floating_point:
+            raise TypeError(f"segmented sort: no key category for dtype {d_keys.d_buffers[0].dtype} (half-precision keys are not served)")
+        if key_type is None:
+            key_type = _KEY_TYPES.get(d_keys.d_buffers[0].dtype)
+            if key_type is None:
+                raise TypeError(f"no key category for dtype {d_keys.d_buffers[0].dtype}: pass key_type")
+        if lib.gs_segmented_narrow_cap(key_type, vb) == 0:
+            raise ValueError(f"segmented sort of {kb}-byte keys (key_type {key_type}): values of {vb} bytes are not served "
+                             "(none, 4 or 8 bytes are)")
+        need = lib.gs_segmented_narrow_temp_bytes(num_items, key_type, vb, num_segments)
+        if d_temp_storage is None:
+            return need
+        if end_bit is None:
+            end_bit = 8 * kb
+        for b in d_keys.d_buffers:
+            _check_buf(b, num_items, "d_keys", kb)
+        for o in (d_begin_offsets, d_end_offsets):
+            if not isinstance(o, torch.Tensor) or o.dtype != torch.int32 or not o.is_cuda or o.numel() < num_segments:
+                raise ValueError("segment offsets: expected int32 device tensors of >= num_segments entries")
+        keys = (C.c_void_p * 2)(d_keys.d_buffers[0].data_ptr(), d_keys.d_buffers[1].data_ptr())
+        vals = None
+        if vb:
+            for b in d_values.d_buffers:
+                _check_buf(b, num_items, "d_values", vb)
+            if d_values.selector != d_keys.selector:
+                raise ValueError("d_keys and d_values selectors differ")
+            vals = (C.c_void_p * 2)(d_values.d_buffers[0].data_ptr(), d_values.d_buffers[1].data_ptr())
+        sel = C.c_int(d_keys.selector)
+        err = lib.gs_segmented_sort_narrow(C.c_void_p(d_temp_storage.data_ptr()),
+                                           min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                           keys, vals, C.byref(sel), num_items, num_segments,
+                                           C.c_void_p(d_begin_offsets.data_ptr()), C.c_void_p(d_end_offsets.data_ptr()),
+                                           key_type, vb, begin_bit, end_bit, int(descending), _stream_ptr(stream))
+        check(err, "gs_segmented_sort_narrow")
+        d_keys.selector = sel.value
+        if vb:
             d_values.selector = sel.value
         return need
 

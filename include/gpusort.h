@@ -337,6 +337,39 @@ int gs_segmented_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys[2], voi
                            const int32_t *d_end_offsets, int key_bytes, int val_bytes, int begin_bit, int end_bit,
                            int descending, int key_type, void *stream);
 
+/* The same for 8- and 16-bit keys on kernels of their own (gs_seg_narrow.inc): key_type GS_KEY_U8 / GS_KEY_I8 / GS_KEY_U16 /
+ * GS_KEY_I16 with val_bytes 0 (d_vals == NULL), 4 or 8.  Every other key type or value size is refused with
+ * hipErrorInvalidValue, and both queries below return 0 for it (the convention of gs_lsb_narrow_temp_bytes).
+ * Stable, ascending or descending, on bits [begin_bit, end_bit) of the key's order-preserving image at its own width
+ * (end_bit <= 8 or <= 16).  DoubleBuffer semantics as gs_segmented_sort_u32: both halves may be overwritten inside segments,
+ * and *selector flips once per 8-bit pass, ceil((end_bit - begin_bit) / 8) times -- once for 8-bit keys; for 16-bit keys over
+ * all bits it ends where it started.  Positions outside every segment are not written, in either half of either array: every
+ * store is one element wide, so no byte next to a segment is touched.  Segments must not overlap; empty segments and
+ * end < begin are ignored; offsets outside [0, num_items] are clamped on the device.  The alignment paragraph above holds: a u8
+ * array may start at any byte address, a u16 array at any even one, values at a multiple of their size, d_temp anywhere.
+ * num_items == 0, num_segments == 0 or begin_bit == end_bit returns 0, writes nothing, needs no workspace and leaves
+ * *selector alone.  num_items < 2^31 (int offsets).  The call only enqueues work on `stream` (no host synchronisation,
+ * allocation or read-back); calls may follow each other on one stream with one workspace.  Refused with
+ * hipErrorInvalidValue before anything is enqueued or written: a NULL or too-small workspace, a selector other than 0 or 1,
+ * a missing buffer half, values without val_bytes or val_bytes without values, a bad bit range, num_items >= 2^31, NULL
+ * offsets, a misaligned array.
+ * Segments of up to gs_segmented_narrow_cap elements (8192) cost one read and one write; the larger ones are partitioned
+ * together, one 8-bit digit per pass, in tiles of gs_lsb_narrow_tile(key_type, val_bytes) elements.
+ * Workspace (a pure host function of its arguments, a multiple of 256): the list workspace of gs_segmented_sort_wide's
+ * geometry -- with B = num_items / 8192 + 257 buckets, T = 8 * ((num_items / 4096 + B + num_items / 2^20 + 2) / 8 + 2) tile
+ * records and K = 2 * num_items / 3000 + 3 * B + 512 + num_segments task records per class, every term rounded up to 256
+ * bytes: 10 level records of 64 bytes, 2 * 16 B bucket records, 16 T tile records, 1024 B cursors, 128 T spine, 512 T
+ * in-chunk prefixes, 4 * 16 K task records, 32 B heavy-hitter records (unused here), 10 * 4096 * 32 census bytes -- plus
+ * 256 bytes of alignment slack.  No element is ever copied into the workspace.                                          */
+size_t gs_segmented_narrow_temp_bytes(uint64_t num_items, int key_type, int val_bytes, uint32_t num_segments);
+int gs_segmented_sort_narrow(void *d_temp, size_t temp_bytes, void *d_keys[2], void *d_vals[2], int *selector,
+                             uint64_t num_items, uint32_t num_segments, const int32_t *d_begin_offsets,
+                             const int32_t *d_end_offsets, int key_type, int val_bytes, int begin_bit, int end_bit,
+                             int descending, void *stream);
+/* the largest segment, in elements, that one workgroup sorts for this key type and value size (0: not served); tests sweep
+ * sizes around it */
+uint32_t gs_segmented_narrow_cap(int key_type, int val_bytes);
+
 /* The MSB path cut at the exchange point (north_star: "a single RCCL all-to-all after the
  * first digit pass"): gs_msb_first_pass_u32 is the top-byte partition on its own -- keys (and
  * values) leave grouped by top byte in d_*_out, in their order-preserving u32 form, and

@@ -271,7 +271,7 @@ struct DeviceRadixSortLarge {
 };
 
 // cub::DeviceSegmentedRadixSort, DoubleBuffer overloads (lsb/cub/cub/device/device_segmented_radix_sort.cuh:
-// 266-289, 450-473, 607-629, 779-801): 32- or 64-bit keys, 32- or 64-bit values, int offsets.
+// 266-289, 450-473, 607-629, 779-801): 8-, 16-, 32- or 64-bit keys, 32- or 64-bit values, int offsets.
 struct DeviceSegmentedRadixSort {
     template <typename KeyT, typename ValueT>
     static hipError_t Dispatch(void *d_temp_storage, size_t &temp_storage_bytes, DoubleBuffer<KeyT> &d_keys,
@@ -280,19 +280,28 @@ struct DeviceSegmentedRadixSort {
     {
         constexpr bool keys_only = std::is_same<ValueT, NullType>::value;
         constexpr int KB = (int)sizeof(KeyT), VB = keys_only ? 0 : (int)sizeof(ValueT);
-        static_assert(KB == 4 || KB == 8, "32- or 64-bit keys");
+        static_assert(KB == 1 || KB == 2 || KB == 4 || KB == 8, "8-, 16-, 32- or 64-bit keys");
         static_assert(VB == 0 || VB == 4 || VB == 8, "32- or 64-bit values");
-        constexpr bool wide = KB == 8 || VB == 8;
+        constexpr bool narrow = KB < 4;                   // gs_segmented_sort_narrow
+        constexpr bool wide = !narrow && (KB == 8 || VB == 8);
         const int vb = d_values ? VB : 0;
-        const size_t need = wide ? gs_segmented_wide_temp_bytes((uint64_t)num_items, KB, vb, (uint32_t)num_segments)
-                                 : gs_segmented_temp_bytes((uint64_t)num_items, d_values != nullptr, (uint32_t)num_segments);
+        const size_t need = narrow ? gs_segmented_narrow_temp_bytes((uint64_t)num_items, KeyTraits<KeyT>::type, vb, (uint32_t)num_segments)
+                            : wide ? gs_segmented_wide_temp_bytes((uint64_t)num_items, KB, vb, (uint32_t)num_segments)
+                                   : gs_segmented_temp_bytes((uint64_t)num_items, d_values != nullptr, (uint32_t)num_segments);
         if (d_temp_storage == nullptr) {
             temp_storage_bytes = need;
             return hipSuccess;
         }
         int sel = d_keys.selector;
         int err;
-        if constexpr (wide) {
+        if constexpr (narrow) {
+            void *keys[2] = {d_keys.d_buffers[0], d_keys.d_buffers[1]};
+            void *vals[2] = {nullptr, nullptr};
+            if (d_values) { vals[0] = d_values->d_buffers[0]; vals[1] = d_values->d_buffers[1]; }
+            err = gs_segmented_sort_narrow(d_temp_storage, temp_storage_bytes, keys, d_values ? vals : nullptr, &sel, (uint64_t)num_items,
+                                           (uint32_t)num_segments, d_begin_offsets, d_end_offsets, KeyTraits<KeyT>::type, vb, begin_bit,
+                                           end_bit, descending ? 1 : 0, stream);
+        } else if constexpr (wide) {
             void *keys[2] = {d_keys.d_buffers[0], d_keys.d_buffers[1]};
             void *vals[2] = {nullptr, nullptr};
             if (d_values) { vals[0] = d_values->d_buffers[0]; vals[1] = d_values->d_buffers[1]; }

@@ -33,6 +33,12 @@ def _kernels(build_dir, tmp, tag):
                 code[cur] = []
             elif cur and line.strip():
                 code[cur].append(re.sub(r"//.*$", "", line).rstrip())
+        # "..." is llvm-objdump's elision of a run of zero bytes.  As the LAST line of a function it is the padding between the
+        # function's final instruction and the next symbol, which moves with the link order and is not code: only there is it
+        # dropped.  A run of zeros anywhere inside a function is kept and compared.
+        for k in code:
+            while code[k] and code[k][-1].strip() == "...":
+                code[k].pop()
         notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", base + ".co"], text=True)
         for block in notes.split("  - .agpr_count")[1:]:
             name = re.search(r"\.name:\s+(\S+)", block)
