@@ -36,7 +36,11 @@ def _check(oracle, keys_u64, key_type, out_k, vals=None, out_v=None):
         # values may be permuted inside runs of equal keys only
         ev = vals[ranks]
         start = np.flatnonzero(np.concatenate(([True], exp[1:] != exp[:-1])))
-        run_id = np.repeat(np.arange(start.size), np.diff(np.concatenate((start, [exp.size]))))
+        length = np.diff(np.concatenate((start, [exp.size])))
+        run_id = np.repeat(np.arange(start.size), length)
+        multi = np.repeat(length > 1, length)             # a run of one key holds exactly its value; the others are sorted run by run
+        assert np.array_equal(ev[~multi], out_v[~multi])
+        ev, out_v, run_id = ev[multi], out_v[multi], run_id[multi]
         a = np.lexsort((ev, run_id))
         b = np.lexsort((out_v, run_id))
         assert np.array_equal(ev[a], out_v[b])
@@ -132,3 +136,31 @@ def test_wide_and_of_draws_levels(gs, oracle, cuda, n, kt, pairs):
         if pairs:
             out_v = seq.sorted_values.cpu().numpy()
             assert np.array_equal(keys[out_v], out_k) and np.array_equal(np.sort(out_v), vals), f"level {level}"
+
+
+@pytest.mark.parametrize("combo", ["u64", "u64_u32", "u64_u64", "u32_u64"])
+def test_wide_large_buckets_at_odd_offsets(gs, oracle, cuda, combo):
+    """The wide counterpart of tests/test_msb_gpu.py::test_large_buckets_at_odd_offsets: buckets of 256 tiles (of 4096 elements) or
+    more whose offset is no multiple of 64 elements get a short first tile (ws_first_tile, gs_msb.hip).  Three top bytes hold
+    1 200 001 / 1 100 003 / 1 150 005 elements, so the second and third level-1 bucket start at offsets = 1 and 36 (mod 64) and carry
+    two ragged tiles each."""
+    from gpu_sort_amd.msb import rdxsrt_unstable_sort_wide
+    rng = np.random.default_rng(12)
+    sizes = [1_200_001, 1_100_003, 1_150_005]
+    tops = [0x11, 0x5A, 0xC3]
+    assert all(m >= 256 * 4096 for m in sizes) and sizes[0] % 64 == 1 and (sizes[0] + sizes[1]) % 64 == 36
+    k32 = combo == "u32_u64"
+    low = 24 if k32 else 56
+    keys = np.concatenate([(np.uint64(t) << np.uint64(low)) | rng.integers(0, 1 << low, m, dtype=np.uint64) for t, m in zip(tops, sizes)])
+    rng.shuffle(keys)
+    n = keys.size
+    dk = torch.from_numpy((keys.astype(np.uint32).view(np.int32) if k32 else keys.view(np.int64)).copy()).to(cuda)
+    vdt = {"u64": None, "u64_u32": np.int32, "u64_u64": np.int64, "u32_u64": np.int64}[combo]
+    vals = np.arange(n, dtype=vdt) if vdt else None
+    dv = torch.from_numpy(vals.copy()).to(cuda) if vdt else None
+    seq, _ = rdxsrt_unstable_sort_wide(dk, dv, n, torch.empty_like(dk), torch.empty_like(dv) if vdt else None,
+                                       key_type=gs.GS_KEY_U32 if k32 else GS_KEY_U64)
+    out_k = seq.sorted_keys.cpu().numpy()
+    out_k = out_k.view(np.uint32).astype(np.uint64) if k32 else out_k.view(np.uint64)
+    assert np.array_equal(out_k, np.sort(keys))                       # (unsigned keys: the order map is the identity)
+    _check(oracle, keys, GS_KEY_U64, out_k, vals, seq.sorted_values.cpu().numpy() if vdt else None)
