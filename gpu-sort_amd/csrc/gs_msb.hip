@@ -3526,6 +3526,53 @@ int gs_msb_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys, void *d_vals
     return e;
 }
 
+// gs_msb_census for the workspace of gs_msb_sort_wide (carved as msb_wide_overflow does): host-side read-back only
+int gs_msb_wide_census(void *d_temp, uint64_t num_items, int key_bytes, int val_bytes, gs_msb_level_census out[8], void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (!d_temp || !out || num_items >= (1ull << 32)) return hipErrorInvalidValue;
+    if (key_bytes != 4 && key_bytes != 8) return hipErrorInvalidValue;
+    if (val_bytes != 0 && val_bytes != 4 && val_bytes != 8) return hipErrorInvalidValue;
+    if (key_bytes == 4 && val_bytes != 8) return hipErrorInvalidValue;
+    constexpr int NL = 8;
+    if (num_items == 0) {                               // the sort touched nothing
+        for (int L = 0; L < NL; ++L) out[L] = gs_msb_level_census{};
+        return hipSuccess;
+    }
+    const MsbWs ws = msb_carve(gs_ws_base(d_temp) + mw_lsb_bytes(num_items, key_bytes, val_bytes), num_items, val_bytes != 0, 0, 0, MW_CAP,
+                               (uint32_t)(8 * key_bytes));
+    hipStream_t s = (hipStream_t)stream;
+    MsbLevel lv[NL];
+    std::vector<MsbCensusSlot> slots((size_t)key_bytes * MSB_CLASSIFY_GRID);
+    hipError_t e = hipMemcpyAsync(lv, ws.level, (size_t)key_bytes * sizeof(MsbLevel), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(slots.data(), ws.census, slots.size() * sizeof(MsbCensusSlot), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return (int)e;
+    unsigned long long next_keys[NL] = {}, task_keys[NL] = {};
+    for (int L = 0; L < key_bytes; ++L) {
+        const uint32_t nbk = lv[L].census_blocks < MSB_CLASSIFY_GRID ? lv[L].census_blocks : MSB_CLASSIFY_GRID;
+        for (uint32_t i = 0; i < nbk; ++i) {
+            const MsbCensusSlot &q = slots[(size_t)L * MSB_CLASSIFY_GRID + i];
+            next_keys[L] += q.next_keys; task_keys[L] += q.task_keys;
+        }
+    }
+    for (int L = 0; L < NL; ++L) {
+        gs_msb_level_census c{};
+        if (L < key_bytes) {
+            c.buckets = lv[L].packed >> 32;
+            c.tiles = (uint32_t)lv[L].packed;
+            c.keys = L == 0 ? lv[0].keys : next_keys[L - 1];
+            c.task_keys = task_keys[L];
+            c.tasks[0] = lv[L].task_count[0];
+            c.tasks[1] = lv[L].task_count[1];
+            c.flagged = lv[L].flagged;
+            c.overflow = lv[0].overflow;
+        }
+        out[L] = c;
+    }
+    return hipSuccess;
+}
+
 }  // extern "C"
 
 namespace gs {

@@ -107,13 +107,25 @@ class _LevelCensus(C.Structure):
                 ("overflow", C.c_uint32)]
 
 
+def _census_dicts(out):
+    return [{"buckets": int(c.buckets), "tiles": int(c.tiles), "keys": int(c.keys), "pivot_buckets": int(c.pivot_buckets),
+             "pivot_keys": int(c.pivot_keys), "task_keys": int(c.task_keys), "tasks": [int(x) for x in c.tasks],
+             "flagged": int(c.flagged), "overflow": int(c.overflow)} for c in out]
+
+
 def msb_census(dm, key_count, has_values=False):
     """Per-level census of the last rdxsrt_unstable_sort that used the workspace tensor `dm`: a list of 4 dicts."""
     out = (_LevelCensus * 4)()
     check(lib.gs_msb_census(dm.data_ptr(), key_count, int(has_values), C.cast(out, C.c_void_p), None), "gs_msb_census")
-    return [{"buckets": int(c.buckets), "tiles": int(c.tiles), "keys": int(c.keys), "pivot_buckets": int(c.pivot_buckets),
-             "pivot_keys": int(c.pivot_keys), "task_keys": int(c.task_keys), "tasks": [int(x) for x in c.tasks],
-             "flagged": int(c.flagged), "overflow": int(c.overflow)} for c in out]
+    return _census_dicts(out)
+
+
+def msb_wide_census(dm, key_count, key_bytes, val_bytes):
+    """Per-level census of the last rdxsrt_unstable_sort_wide that used the workspace tensor `dm` (gs_msb_wide_census): a list of
+    8 dicts like msb_census's, all zeros from level `key_bytes` on."""
+    out = (_LevelCensus * 8)()
+    check(lib.gs_msb_wide_census(dm.data_ptr(), key_count, key_bytes, val_bytes, C.cast(out, C.c_void_p), None), "gs_msb_wide_census")
+    return _census_dicts(out)
 
 
 def msb_algorithmic_bytes(census, key_count, has_values=False):

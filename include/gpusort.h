@@ -289,6 +289,17 @@ typedef struct gs_msb_level_census {
                               /* gs_msb_sort_u32 returns hipErrorUnknown in that case.                      */
 } gs_msb_level_census;
 int gs_msb_census(void *d_temp, uint64_t num_items, int has_values, gs_msb_level_census out[4], void *stream);
+/* The same for the last gs_msb_sort_wide that used d_temp with these num_items, key_bytes and val_bytes (read back after
+ * synchronising `stream`; no kernel runs).  A key of key_bytes bytes has key_bytes byte levels: out[L] for L < key_bytes
+ * holds `buckets` and `tiles` (tiles of 4096 elements) partitioned at level L, `keys` in them (level 0: num_items), the
+ * local-sort `tasks[0]` (<= 2048 elements) and `tasks[1]` (<= 8192) that level L's classification emitted, their
+ * `task_keys`, and `flagged` / `overflow` as in gs_msb_census.  The wide sort has no heavy-hitter path and two size
+ * classes: pivot_buckets, pivot_keys, tasks[2] and tasks[3] are 0.  The last level emits no tasks (its scatter finishes
+ * every key it gets) and levels the data never reached are all zeros, as are the records of levels >= key_bytes.
+ * An array of <= 8192 elements is one task and no classification runs: out[0] has buckets 1, tiles 1 or 2, keys
+ * num_items and one task in its class, but task_keys 0.  num_items == 0: all zeros.  Errors: hipErrorInvalidValue for a
+ * NULL d_temp or out, num_items >= 2^32 or a key_bytes / val_bytes combination gs_msb_sort_wide refuses.              */
+int gs_msb_wide_census(void *d_temp, uint64_t num_items, int key_bytes, int val_bytes, gs_msb_level_census out[8], void *stream);
 /* Capacities of the workspace's device-side lists for num_items (records): buckets a level may hold, local-sort tasks per
  * size class, tile records.  The sizing argument (gs_msb.hip, msb_max_*): a level's buckets are > the largest local sort
  * each; a task is >= 3000 keys or followed by something that did not merge with it (<= 2n / 3000, + 256 per bucket's
