@@ -56,6 +56,8 @@ SIGNATURES = {
     "gs_msb_sort_large_wide": (i32, [vp, sz, vp, vp, u64, vp, vp, i32, i32, i32, vp, i32]),
     "gs_lsb_large_temp_bytes": (sz, [u64, i32, i32]),
     "gs_lsb_sort_large": (i32, [vp, sz, pp, pp, C.POINTER(i32), u64, i32, i32, i32, i32, i32, i32, vp]),
+    "gs_lsb_narrow_large_temp_bytes": (sz, [u64, i32, i32]),
+    "gs_lsb_sort_narrow_large": (i32, [vp, sz, vp, vp, vp, vp, u64, i32, i32, i32, i32, i32, vp]),
     "gs_msb_census": (i32, [vp, u64, i32, vp, vp]),
     "gs_msb_wide_census": (i32, [vp, u64, i32, i32, vp, vp]),
     "gs_msb_capacities": (None, [u64, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -17,6 +17,9 @@
 // gs_lsb_sort_large is the stable LSB sort over the same pass: one 64-bit pass per digit of
 // [begin_bit, end_bit), ping-ponging between the DoubleBuffer halves, keys twiddled on the first pass and restored on the
 // last (lsb_run_passes' rule).  Its offsets are computed on the device, so the sort only enqueues work and can be captured.
+// gs_lsb_sort_narrow_large is gs_lsb_sort_narrow's plain-pointer contract over the same pass for 8- and 16-bit
+// keys: per slice the narrow upsweep and downsweep (narrow_slice_count / narrow_slice_scatter: narrow_downsweep64_kernel), one or
+// two passes, in -> (workspace ->) out; 8-bit keys alone take a histogram with 64-bit counts and a fill (narrow_fill_large).
 #include "gs_device.hpp"
 #include "gs_lsb.hpp"
 #include <cstdlib>
@@ -27,9 +30,10 @@ constexpr uint64_t LARGE_GROUP = 1ull << 31;   // keys per finish and per slice 
 constexpr uint64_t LARGE_MAX = 1ull << 40;     // num_items limit of the entry point
 constexpr uint32_t LARGE_MIN_TEST_LIMIT = 256;
 
-// Test hook (tests/test_msb_large_gpu.py, tests/test_lsb_large_gpu.py): GS_MSB_LARGE_TEST_LIMIT=k lowers the group size and the
-// slice size to k keys, so that small arrays take multi-slice passes, multi-group finishes and splits (and, in gs_lsb_sort_large,
-// arrays of more than k elements the 64-bit passes).  Read on every call; never set in production.
+// Test hook (tests/test_msb_large_gpu.py, tests/test_lsb_large_gpu.py, tests/test_narrow_large_gpu.py): GS_MSB_LARGE_TEST_LIMIT=k
+// lowers the group size and the slice size to k keys, so that small arrays take multi-slice passes, multi-group finishes and splits
+// (and, in gs_lsb_sort_large and gs_lsb_sort_narrow_large, arrays of more than k elements the 64-bit passes).  Read on every call;
+// never set in production.
 static uint64_t large_limit()
 {
     if (const char *e = getenv("GS_MSB_LARGE_TEST_LIMIT")) {
@@ -330,6 +334,65 @@ static int lsb_large_passes(const LargeCtx &c, const LargePassWs &w, int *select
     return hipSuccess;
 }
 
+// ---- gs_lsb_sort_narrow_large: 8- and 16-bit keys above 2^32 elements, gs_lsb_sort_narrow's
+// plain-pointer contract over the 64-bit pass.  The workspace: per slice a spine sized for a full slice, the slices' digit
+// totals [slices][256] u32, the digit starts [slices][256] u64, the counts [256] u64 (the histogram of the fill path), then
+// for 16-bit keys the intermediate keys and values of the pass in -> workspace -> out.
+struct NarrowLargeWs {
+    char *spines;
+    size_t spine_bytes;      // of one slice
+    uint32_t *totals;
+    uint64_t *dbase;
+    uint64_t *counts;
+    char *tk, *tv;           // 16-bit keys only
+};
+static size_t narrow_large_pass_bytes(uint64_t n, uint64_t S, int kb, int vb)
+{
+    const uint64_t ns = large_slices(n, S);
+    size_t b = (size_t)ns * narrow_slice_spine_bytes(S, vb) + align256((size_t)ns * RADIX * sizeof(uint32_t)) +
+               align256((size_t)ns * RADIX * sizeof(uint64_t)) + align256(RADIX * sizeof(uint64_t));
+    if (kb == 2) b += align256((size_t)n * 2) + align256((size_t)n * (size_t)vb);
+    return b;
+}
+static NarrowLargeWs narrow_large_carve(char *c, uint64_t n, uint64_t S, int vb)
+{
+    NarrowLargeWs w;
+    const uint64_t ns = large_slices(n, S);
+    w.spine_bytes = narrow_slice_spine_bytes(S, vb);
+    w.spines = c; c += (size_t)ns * w.spine_bytes;
+    w.totals = (uint32_t *)c; c += align256((size_t)ns * RADIX * sizeof(uint32_t));
+    w.dbase = (uint64_t *)c; c += align256((size_t)ns * RADIX * sizeof(uint64_t));
+    w.counts = (uint64_t *)c; c += align256(RADIX * sizeof(uint64_t));
+    w.tk = c;
+    w.tv = c + align256((size_t)n * 2);
+    return w;
+}
+
+// one stable 8-bit pass over n elements in slices of S: kin -> kout through 64-bit digit starts (large_pass for the narrow types)
+static int narrow_large_pass(const NarrowLargeWs &w, const char *kin, char *kout, const char *vin, char *vout, uint64_t n, uint64_t S,
+                             int kb, int vb, const LargeDigit &d, hipStream_t s)
+{
+    const uint64_t ns = large_slices(n, S);
+    int e;
+    for (uint64_t i = 0; i < ns; ++i) {
+        const uint64_t off = i * S, len = n - off < S ? n - off : S;
+        if ((e = narrow_slice_count(kin + off * kb, len, vb, d, (uint32_t *)(w.spines + i * w.spine_bytes), w.totals + i * RADIX, s)))
+            return e;
+    }
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(large_offsets_kernel, dim3(1), dim3(RADIX), 0, s, (const uint32_t *)w.totals, (uint32_t)ns,
+                           (unsigned long long *)w.dbase, (unsigned long long *)w.counts);
+    }
+    for (uint64_t i = 0; i < ns; ++i) {
+        const uint64_t off = i * S, len = n - off < S ? n - off : S;
+        if ((e = narrow_slice_scatter(kin + off * kb, kout, vin ? vin + off * vb : nullptr, vout, len, vb, d,
+                                      (const uint32_t *)(w.spines + i * w.spine_bytes), w.dbase + i * RADIX, s)))
+            return e;
+    }
+    return hipSuccess;
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -480,6 +543,67 @@ int gs_lsb_sort_large(void *d_temp, size_t temp_bytes, void *d_keys[2], void *d_
     c.pass_ws = gs_ws_base(d_temp);
     c.s = (hipStream_t)stream;
     return lsb_large_passes(c, large_pass_carve(c.pass_ws, num_items, L, wide), selector, num_items, begin_bit, end_bit, descending);
+}
+
+// the 64-bit pass's workspace, or gs_lsb_sort_narrow's for arrays of one slice, whichever is larger (both grow with n)
+size_t gs_lsb_narrow_large_temp_bytes(uint64_t num_items, int key_type, int val_bytes)
+{
+    const int kb = narrow_key_bytes(key_type);
+    if (kb == 0 || gs_lsb_narrow_tile(key_type, val_bytes) == 0 || num_items >= LARGE_MAX) return 0;
+    const uint64_t L = large_limit();
+    const size_t pass = narrow_large_pass_bytes(num_items, L, kb, val_bytes) + GS_WS_SLACK;
+    const size_t one = gs_lsb_narrow_temp_bytes(num_items < L ? num_items : L, key_type, val_bytes);
+    return pass > one ? pass : one;
+}
+
+int gs_lsb_sort_narrow_large(void *d_temp, size_t temp_bytes, const void *d_keys_in, void *d_keys_out, const void *d_vals_in,
+                             void *d_vals_out, uint64_t num_items, int key_type, int val_bytes, int begin_bit, int end_bit,
+                             int descending, void *stream)
+{
+    // argument checks touch no device, and all of them come before anything is enqueued
+    const int kb = narrow_key_bytes(key_type);
+    if (kb == 0 || gs_lsb_narrow_tile(key_type, val_bytes) == 0) return hipErrorInvalidValue;
+    if (begin_bit < 0 || end_bit > 8 * kb || begin_bit > end_bit) return hipErrorInvalidValue;
+    if (num_items >= LARGE_MAX) return hipErrorInvalidValue;
+    if (num_items == 0) return hipSuccess;              // (empty arrays may come with null pointers)
+    if ((val_bytes != 0) != (d_vals_in != nullptr) || (val_bytes != 0) != (d_vals_out != nullptr)) return hipErrorInvalidValue;
+    if (!d_keys_in || !d_keys_out) return hipErrorInvalidValue;
+    if (((uintptr_t)d_keys_in | (uintptr_t)d_keys_out) & (uintptr_t)(kb - 1)) return hipErrorInvalidValue;
+    if (val_bytes && (((uintptr_t)d_vals_in | (uintptr_t)d_vals_out) & (uintptr_t)(val_bytes - 1))) return hipErrorInvalidValue;
+    {
+        const void *arr[4] = {d_keys_in, d_keys_out, d_vals_in, d_vals_out};
+        const size_t kbytes = num_items * (size_t)kb, vbytes = num_items * (size_t)val_bytes, bytes[4] = {kbytes, kbytes, vbytes, vbytes};
+        if (any_overlap(arr, bytes)) return hipErrorInvalidValue;
+    }
+    if (!d_temp || temp_bytes < gs_lsb_narrow_large_temp_bytes(num_items, key_type, val_bytes)) return hipErrorInvalidValue;
+    const uint64_t L = large_limit();
+    if (num_items <= L)     // one slice: the plain narrow sort on the same arguments (a stable sort's result is unique)
+        return gs_lsb_sort_narrow(d_temp, temp_bytes, d_keys_in, d_keys_out, d_vals_in, d_vals_out, num_items, key_type, val_bytes,
+                                  begin_bit, end_bit, descending, stream);
+    GS_CLEAR_STALE_ERROR();
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t n = num_items;
+    const NarrowLargeWs w = narrow_large_carve(gs_ws_base(d_temp), n, L, val_bytes);
+
+    if (begin_bit == end_bit) {
+        if (int e = narrow_copy_bytes(d_keys_in, d_keys_out, n * (uint64_t)kb, s)) return e;
+        return val_bytes ? narrow_copy_bytes(d_vals_in, d_vals_out, n * (uint64_t)val_bytes, s) : 0;
+    }
+    if (kb == 1 && val_bytes == 0 && begin_bit == 0 && end_bit == 8)   // count and fill: nothing is scattered, no slices
+        return narrow_fill_large(d_keys_in, d_keys_out, n, key_type, descending, w.counts, s);
+
+    const int num_passes = (end_bit - begin_bit + RADIX_BITS - 1) / RADIX_BITS;   // 1 or 2: in -> (workspace ->) out
+    for (int pass = 0; pass < num_passes; ++pass) {
+        const int shift = begin_bit + pass * RADIX_BITS;
+        const bool first = pass == 0, last = pass == num_passes - 1;
+        const LargeDigit d{shift, end_bit - shift < RADIX_BITS ? end_bit - shift : RADIX_BITS, key_type, descending, first, last};
+        const char *kin = first ? (const char *)d_keys_in : w.tk;
+        const char *vin = !val_bytes ? nullptr : first ? (const char *)d_vals_in : w.tv;
+        char *kout = last ? (char *)d_keys_out : w.tk;
+        char *vout = !val_bytes ? nullptr : last ? (char *)d_vals_out : w.tv;
+        if (int e = narrow_large_pass(w, kin, kout, vin, vout, n, L, kb, val_bytes, d, s)) return e;
+    }
+    return (int)hipGetLastError();
 }
 
 }  // extern "C"

@@ -137,6 +137,18 @@ int wide_slice_count(const void *kin, uint64_t len, int key_bytes, const LargeDi
                      uint32_t *totals, hipStream_t s);
 int wide_slice_scatter(const void *kin, void *kout, const void *vin, void *vout, uint64_t len, int key_bytes, int val_bytes,
                        const LargeDigit &d, const uint32_t *spine, const uint16_t *prefix16, const uint64_t *dbase, hipStream_t s);
+// gs_narrow.hip: one slice (len < 2^31 elements) of the 64-bit pass over 8- and 16-bit keys (gs_large.hip), the narrow
+// counterparts of wide_slice_*: the spine of a slice is narrow_slice_spine_bytes(S, val_bytes) bytes (one u32 per digit and
+// tile, no prefix16), d.key_type is the narrow key type (its width is narrow_key_bytes, 0 for every other type) and keys are
+// never rewritten (d.first / d.last are ignored).  narrow_fill_large sorts 8-bit keys alone over all 8 bits by a histogram
+// with u64 counters (counts[256]) and a fill, for n < 2^40; narrow_copy_bytes is the copy of begin_bit == end_bit.
+int narrow_key_bytes(int key_type);
+size_t narrow_slice_spine_bytes(uint64_t S, int val_bytes);
+int narrow_slice_count(const void *kin, uint64_t len, int val_bytes, const LargeDigit &d, uint32_t *spine, uint32_t *totals, hipStream_t s);
+int narrow_slice_scatter(const void *kin, void *kout, const void *vin, void *vout, uint64_t len, int val_bytes, const LargeDigit &d,
+                         const uint32_t *spine, const uint64_t *dbase, hipStream_t s);
+int narrow_fill_large(const void *kin, void *kout, uint64_t n, int key_type, int descending, uint64_t *counts, hipStream_t s);
+int narrow_copy_bytes(const void *in, void *out, uint64_t bytes, hipStream_t s);
 // gs_msb.hip: the wide MSB levels for the large sort (gs_large.hip).  msb_wide_finish sorts a group of m < 2^31 elements that
 // lies in src (partitioned on the byte at `shift`, every byte above it equal; h_counts[256] its bucket sizes) and reports in
 // *in_src whether the result landed in src (1) or in oth (0); the workspace is gs_msb_wide_temp_bytes(m) bytes, 256-byte aligned.

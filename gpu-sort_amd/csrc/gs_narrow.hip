@@ -18,6 +18,8 @@
 //   (b) 8-bit keys, keys only, all 8 bits (the default SortKeys call): a 256-bin histogram and a fill of the output with
 //       runs; nothing is scattered.  Descending and signed keys only change the order the bins are walked in.
 // 16-bit keys, keys only, take two passes of (a): the 65536-bin fill is not built.
+//   (c) above 2^32 elements (gs_lsb_sort_narrow_large, host loop in gs_large.hip): the slice functions at the end of this file run
+//       (a) on slices of 2^31 elements with u64 digit starts (narrow_downsweep64_kernel) and (b) with u64 counts.
 #include "gs_device.hpp"
 #include "gs_lsb.hpp"
 
@@ -130,6 +132,11 @@ __device__ __forceinline__ void n_stage_in(const uint4 *__restrict__ A, uint32_t
     }
 }
 
+// OFF64 = false (narrow_downsweep_kernel): the tile of a whole array (n < 2^32): the digit starts are the exclusive scan of
+// totals[256].  OFF64 = true (narrow_downsweep64_kernel): the tile belongs to one slice (< 2^31 elements) of a larger array
+// (gs_large.hip's 64-bit pass): keys_in / vals_in point at the slice, keys_out / vals_out at the whole output, spine is the
+// slice's own and dbase[d] the absolute u64 start of the slice's run of digit d, so gbase (1 KiB more LDS) and the
+// destination indices are u64.  The body is gs_narrow_tile.inc.
 template <int KB, int VB>
 __global__ __launch_bounds__(N_THREADS) void narrow_downsweep_kernel(const void *__restrict__ keys_in, void *__restrict__ keys_out,
                                                                      const void *__restrict__ vals_in, void *__restrict__ vals_out,
@@ -142,130 +149,28 @@ __global__ __launch_bounds__(N_THREADS) void narrow_downsweep_kernel(const void 
     __shared__ uint32_t whist[N_WAVES][RADIX];
     __shared__ uint32_t gbase[RADIX];
     __shared__ __attribute__((aligned(16))) unsigned char stage_raw[TILE * ELEM + 16];   // (+ 16: the chunk a misaligned tile spills into)
+    constexpr bool OFF64 = false;
+    typedef uint32_t Off;
+    const uint64_t *dbase = nullptr;
+#include "gs_narrow_tile.inc"
+}
 
-    const int lane = lane_id(), w = wave_id();
-    const uint32_t t = tile_of_item(blockIdx.x, p.num_tiles);   // XCD-contiguous slices: neighbouring runs meet in one L2
-    const uint64_t tile_base = (uint64_t)t * TILE;
-    const uint32_t valid = (p.n - tile_base < (uint64_t)TILE) ? (uint32_t)(p.n - tile_base) : (uint32_t)TILE;
-    uint32_t *my = whist[w];
-    const uint32_t wbase = (uint32_t)w * (WAVE * KPT) + lane;
-
-    // the tile's keys: aligned chunks -> LDS
-    const uint32_t ka = (uint32_t)((uintptr_t)keys_in & 15u);
-    n_stage_in<TILE * KB / 16 + 1>(reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(keys_in) - ka) + tile_base * KB / 16,
-                                   (ka + valid * KB + 15u) / 16u, stage_raw);
-
-    // wave 0, lane l: global start of digits 4l..4l+3 for this tile
-    uint32_t g0[4] = {0, 0, 0, 0};
-    if (w == 0) {
-        const uint4 tot = reinterpret_cast<const uint4 *>(totals)[lane];
-        const uint32_t lane_sum = tot.x + tot.y + tot.z + tot.w;
-        const uint32_t ex = wave_inclusive_scan(lane_sum) - lane_sum;
-        const uint32_t *sp = spine + (size_t)(4 * lane) * p.num_tiles + t;
-        g0[0] = ex + sp[0];
-        g0[1] = ex + tot.x + sp[p.num_tiles];
-        g0[2] = ex + tot.x + tot.y + sp[2 * (size_t)p.num_tiles];
-        g0[3] = ex + tot.x + tot.y + tot.z + sp[3 * (size_t)p.num_tiles];
-    }
-#pragma unroll
-    for (int i = lane; i < RADIX; i += WAVE) my[i] = 0;
-    __syncthreads();
-
-    uint32_t key[KPT];
-    uint32_t pos[KPT];
-    const uint32_t pad = ~p.xr;                 // digit p.mask, the largest: ranked last, behind every element of the tile
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) {
-        const uint32_t idx = wbase + i * WAVE;
-        const uint32_t k = *reinterpret_cast<const K *>(stage_raw + ka + (idx < valid ? idx : 0u) * KB);
-        key[i] = (idx < valid) ? k : pad;
-    }
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) {
-        const uint32_t d = n_digit(key[i], p);
-        uint32_t plo, phi;
-        match_digit(d, plo, phi);
-        const uint32_t lower = count_lower(plo, phi);
-        pos[i] = my[d] + lower;
-        if (lower == 0)
-            __hip_atomic_fetch_add(&my[d], (uint32_t)(__popc(plo) + __popc(phi)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    }
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) asm volatile("" : "+v"(pos[i]));
-    __syncthreads();                            // every key is in registers: the raw chunks may be overwritten
-    if (w == 0) {
-        uint32_t run[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < N_WAVES; ++j) {
-            const uint4 x = reinterpret_cast<const uint4 *>(whist[j])[lane];
-            run[0] += x.x; run[1] += x.y; run[2] += x.z; run[3] += x.w;
-        }
-        const uint32_t lane_sum = run[0] + run[1] + run[2] + run[3];
-        uint4 e4;
-        e4.x = wave_inclusive_scan(lane_sum) - lane_sum;
-        e4.y = e4.x + run[0];
-        e4.z = e4.y + run[1];
-        e4.w = e4.z + run[2];
-        reinterpret_cast<uint4 *>(gbase)[lane] = make_uint4(g0[0] - e4.x, g0[1] - e4.y, g0[2] - e4.z, g0[3] - e4.w);
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int j = 0; j < N_WAVES; ++j) {
-            const uint4 x = reinterpret_cast<const uint4 *>(whist[j])[lane];
-            reinterpret_cast<uint4 *>(whist[j])[lane] = e4;
-            e4.x += x.x; e4.y += x.y; e4.z += x.z; e4.w += x.w;
-        }
-    }
-    __syncthreads();
-    K *stage_k = reinterpret_cast<K *>(stage_raw);
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) {
-        pos[i] += my[n_digit(key[i], p)];
-        stage_k[pos[i]] = (K)key[i];
-    }
-    __syncthreads();
-    uint32_t dst[KPT];
-    K *kout = reinterpret_cast<K *>(keys_out);
-#pragma unroll
-    for (int i = 0; i < KPT; ++i) {
-        const uint32_t slot = (uint32_t)w * (WAVE * KPT) + i * WAVE + lane;   // wave-contiguous
-        const K k = stage_k[slot];
-        dst[i] = gbase[n_digit(k, p)] + slot;
-        if (slot < valid) kout[dst[i]] = k;
-    }
-    if constexpr (VB != 0) {
-        typedef typename NElem<VB>::type V;
-        V *stage_v = reinterpret_cast<V *>(stage_raw);
-        V val[KPT];
-        __syncthreads();                        // everyone is done reading the keys
-        if constexpr (VB <= 2) {                // narrow values come the way the keys did
-            const uint32_t va = (uint32_t)((uintptr_t)vals_in & 15u);
-            n_stage_in<TILE * VB / 16 + 1>(reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(vals_in) - va) + tile_base * VB / 16,
-                                           (va + valid * VB + 15u) / 16u, stage_raw);
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < KPT; ++i) {
-                const uint32_t idx = wbase + i * WAVE;
-                val[i] = *reinterpret_cast<const V *>(stage_raw + va + (idx < valid ? idx : 0u) * VB);
-            }
-            __syncthreads();
-        } else {
-            const V *vin = reinterpret_cast<const V *>(vals_in) + tile_base;
-#pragma unroll
-            for (int i = 0; i < KPT; ++i) {
-                const uint32_t idx = wbase + i * WAVE;
-                val[i] = vin[idx < valid ? idx : valid - 1u];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < KPT; ++i) stage_v[pos[i]] = val[i];
-        __syncthreads();
-        V *vout = reinterpret_cast<V *>(vals_out);
-#pragma unroll
-        for (int i = 0; i < KPT; ++i) {
-            const uint32_t slot = (uint32_t)w * (WAVE * KPT) + i * WAVE + lane;
-            if (slot < valid) vout[dst[i]] = stage_v[slot];
-        }
-    }
+template <int KB, int VB>
+__global__ __launch_bounds__(N_THREADS) void narrow_downsweep64_kernel(const void *__restrict__ keys_in, void *__restrict__ keys_out,
+                                                                       const void *__restrict__ vals_in, void *__restrict__ vals_out,
+                                                                       const uint32_t *__restrict__ spine,
+                                                                       const uint64_t *__restrict__ dbase, NarrowParams p)
+{
+    typedef typename NElem<KB>::type K;
+    constexpr int KPT = narrow_kpt(VB), TILE = narrow_tile(VB);
+    constexpr int ELEM = KB > VB ? KB : VB;
+    __shared__ uint32_t whist[N_WAVES][RADIX];
+    __shared__ uint64_t gbase[RADIX];
+    __shared__ __attribute__((aligned(16))) unsigned char stage_raw[TILE * ELEM + 16];
+    constexpr bool OFF64 = true;
+    typedef uint64_t Off;
+    const uint32_t *totals = nullptr;
+#include "gs_narrow_tile.inc"
 }
 
 // ------------------------------------------- 8-bit keys only: count, fill --
@@ -273,8 +178,13 @@ constexpr int NF_THREADS = 256;
 constexpr int NF_WAVES = NF_THREADS / WAVE;
 constexpr uint32_t NF_MAX_BLOCKS = 2048;
 
-// counts[v] += number of keys with the byte value v (no twiddle: the fill walks the bins in the order asked for)
-__global__ __launch_bounds__(NF_THREADS) void narrow_count8_kernel(const void *__restrict__ keys, uint32_t *__restrict__ counts, uint64_t n)
+// counts[v] += number of keys with the byte value v (no twiddle: the fill walks the bins in the order asked for).
+// C = uint64_t (narrow_count8_large_kernel, n < 2^40): only the global counters are 64-bit.  A block's partial sums stay
+// u32: the grid-stride loop gives a block at most ceil(chunks / gridDim.x) rounds of NF_THREADS chunks of 16 keys, and above
+// 2^32 keys the grid is NF_MAX_BLOCKS = 2048 blocks (n_count_grid), so a block sees fewer than 2^40 / 2048 + 16 * NF_THREADS
+// = 2^29 + 4096 keys in all, and the sum of its four wave histograms cannot wrap.
+template <typename C>
+__device__ __forceinline__ void narrow_count8_body(const void *__restrict__ keys, C *__restrict__ counts, uint64_t n)
 {
     __shared__ uint32_t hist[NF_WAVES][RADIX];
     const int w = wave_id(), lane = lane_id();
@@ -302,7 +212,21 @@ __global__ __launch_bounds__(NF_THREADS) void narrow_count8_kernel(const void *_
     __syncthreads();
     const uint32_t d = threadIdx.x;
     const uint32_t sum = hist[0][d] + hist[1][d] + hist[2][d] + hist[3][d];
-    if (sum) atomicAdd(&counts[d], sum);
+    if constexpr (sizeof(C) == 8) {
+        if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(&counts[d]), (unsigned long long)sum);
+    } else {
+        if (sum) atomicAdd(&counts[d], sum);
+    }
+}
+
+__global__ __launch_bounds__(NF_THREADS) void narrow_count8_kernel(const void *__restrict__ keys, uint32_t *__restrict__ counts, uint64_t n)
+{
+    narrow_count8_body<uint32_t>(keys, counts, n);
+}
+
+__global__ __launch_bounds__(NF_THREADS) void narrow_count8_large_kernel(const void *__restrict__ keys, uint64_t *__restrict__ counts, uint64_t n)
+{
+    narrow_count8_body<uint64_t>(keys, counts, n);
 }
 
 // out[i] = the key of rank i: bin j of the walk holds the byte value v(j) = (descending ? 255 - j : j) ^ sign
@@ -343,6 +267,55 @@ __global__ __launch_bounds__(NF_THREADS) void narrow_fill8_kernel(void *__restri
         } else {                                            // the array's first or last chunk: byte stores
             for (uint64_t b = lo; b < hi; ++b) {
                 while (ends[j] <= (uint32_t)(b - a)) ++j;
+                A[b] = (unsigned char)((descending ? 255u - j : j) ^ sign);
+            }
+        }
+    }
+}
+
+// the same for n < 2^40 (gs_lsb_sort_narrow_large): the counts, ends[], the rank e and the search are 64-bit
+__global__ __launch_bounds__(NF_THREADS) void narrow_fill8_large_kernel(void *__restrict__ keys_out, const uint64_t *__restrict__ counts, uint64_t n,
+                                                                        uint32_t sign, int descending)
+{
+    __shared__ uint64_t ends[RADIX];            // ends[j]: number of keys in bins 0..j
+    const uint32_t j0 = threadIdx.x;
+    const uint64_t cnt = counts[((descending ? 255u - j0 : j0) ^ sign) & 0xffu];
+    ends[j0] = cnt;                             // inclusive scan in place, once per block
+    __syncthreads();
+    for (uint32_t off = 1; off < RADIX; off <<= 1) {
+        const uint64_t v = j0 >= off ? ends[j0 - off] : 0ull;
+        __syncthreads();
+        ends[j0] += v;
+        __syncthreads();
+    }
+    const uint32_t a = (uint32_t)((uintptr_t)keys_out & 15u);
+    unsigned char *A = reinterpret_cast<unsigned char *>(keys_out) - a;
+    const uint64_t end_byte = a + n;
+    const uint64_t nch = (end_byte + 15u) / 16u;
+    const uint64_t stride = (uint64_t)gridDim.x * NF_THREADS;
+    for (uint64_t c = (uint64_t)blockIdx.x * NF_THREADS + threadIdx.x; c < nch; c += stride) {
+        const uint64_t b0 = c * 16u;
+        const uint64_t lo = b0 < a ? a : b0, hi = b0 + 16u < end_byte ? b0 + 16u : end_byte;   // bytes [lo, hi) of this chunk are keys
+        const uint64_t e = lo - a;                         // rank of the first of them
+        uint32_t j = 0;                                     // smallest j with ends[j] > e
+#pragma unroll
+        for (uint32_t s = 128; s > 0; s >>= 1)
+            if (ends[j + s - 1] <= e) j += s;
+        const uint32_t v = ((descending ? 255u - j : j) ^ sign) & 0xffu;
+        if (hi - lo == 16u && ends[j] - e >= 16u) {         // a whole chunk inside one run
+            const uint32_t v4 = v * 0x01010101u;
+            *reinterpret_cast<uint4 *>(A + b0) = make_uint4(v4, v4, v4, v4);
+        } else if (hi - lo == 16u) {
+            uint32_t x[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                while (ends[j] <= e + q) ++j;
+                x[q / 4] |= (((descending ? 255u - j : j) ^ sign) & 0xffu) << (8 * (q % 4));
+            }
+            *reinterpret_cast<uint4 *>(A + b0) = make_uint4(x[0], x[1], x[2], x[3]);
+        } else {                                            // the array's first or last chunk: byte stores
+            for (uint64_t b = lo; b < hi; ++b) {
+                while (ends[j] <= b - a) ++j;
                 A[b] = (unsigned char)((descending ? 255u - j : j) ^ sign);
             }
         }
@@ -410,6 +383,97 @@ static inline dim3 n_stream_grid(uint64_t items, uint32_t per_block)
     return dim3((unsigned)(b < 1 ? 1 : (b > NF_MAX_BLOCKS ? NF_MAX_BLOCKS : b)));
 }
 
+// the grid of the count and the fill over n keys: one chunk per thread up to 256 blocks, then more chunks per thread (every
+// block ends with 256 global atomics on the same 256 counters: 2^24 keys took 0.056 ms with 2048 blocks and 0.034 ms with
+// 512), up to 2048 blocks
+static inline dim3 n_count_grid(uint64_t n)
+{
+    const uint64_t chunks = (n + 15) / 16 + 1;
+    return chunks <= 256ull * NF_THREADS * 8 ? n_stream_grid(chunks < 256ull * NF_THREADS ? chunks : 256ull * NF_THREADS, NF_THREADS)
+                                             : n_stream_grid(chunks, NF_THREADS * 8);
+}
+
+// ---- the 64-bit pass over 8- and 16-bit keys (gs_large.hip: gs_lsb_sort_narrow_large), one slice of < 2^31 elements at a
+// time, on the digit d.bits wide at d.shift of the key mapped by d.key_type's sign flip (complemented when d.descending).
+// Keys are never rewritten, so d.first / d.last play no part.  The count runs the upsweep and the spine scan (digit totals of
+// the slice into totals[256]); the scatter writes the slice through dbase[256], the absolute u64 start of its run of each
+// digit in kout / vout.  The slice pointers may have any alignment the element size allows.
+int narrow_key_bytes(int key_type) { return n_key_bytes(key_type); }
+size_t narrow_slice_spine_bytes(uint64_t S, int val_bytes) { return n_spine_bytes(S, val_bytes); }
+
+static NarrowParams narrow_slice_params(uint64_t len, int val_bytes, const LargeDigit &d)
+{
+    NarrowParams p{};
+    p.n = len; p.num_tiles = n_tiles(len, val_bytes);
+    p.shift = (uint32_t)d.shift;
+    p.mask = (1u << d.bits) - 1u;
+    const uint32_t sign = (d.key_type == GS_KEY_I8) ? 0x80u : (d.key_type == GS_KEY_I16) ? 0x8000u : 0u;
+    p.xr = sign ^ (d.descending ? 0xffffffffu : 0u);
+    return p;
+}
+
+int narrow_slice_count(const void *kin, uint64_t len, int val_bytes, const LargeDigit &d, uint32_t *spine, uint32_t *totals, hipStream_t s)
+{
+    const NarrowParams p = narrow_slice_params(len, val_bytes, d);
+    const uint32_t tpb = p.num_tiles > N_SHARED_TILES ? (uint32_t)N_WAVES : 1u;
+    const dim3 grid((p.num_tiles + tpb - 1) / tpb), block(N_THREADS);
+    { KernelTimer kt(GS_K_LSB_UPSWEEP, s);
+#define GS_NU(KB_, VB_) hipLaunchKernelGGL((narrow_upsweep_kernel<KB_, narrow_tile(VB_)>), grid, block, 0, s, kin, spine, p, tpb)
+      if (n_key_bytes(d.key_type) == 1) { if (val_bytes <= 4) GS_NU(1, 4); else if (val_bytes == 8) GS_NU(1, 8); else GS_NU(1, 16); }
+      else { if (val_bytes <= 4) GS_NU(2, 4); else if (val_bytes == 8) GS_NU(2, 8); else GS_NU(2, 16); }
+#undef GS_NU
+    }
+    return lsb_scan(spine, totals, p.num_tiles, s);
+}
+
+template <int KB>
+static void narrow_scatter64(int vb, const void *kin, void *kout, const void *vin, void *vout, const uint32_t *spine,
+                             const uint64_t *dbase, const NarrowParams &p, hipStream_t s)
+{
+#define GS_N64(VB_) hipLaunchKernelGGL((narrow_downsweep64_kernel<KB, VB_>), dim3(p.num_tiles), dim3(N_THREADS), 0, s, kin, kout, vin, vout, \
+                                       spine, dbase, p)
+    switch (vb) {
+    case 0: GS_N64(0); break;
+    case 1: GS_N64(1); break;
+    case 2: GS_N64(2); break;
+    case 4: GS_N64(4); break;
+    case 8: GS_N64(8); break;
+    default: GS_N64(16); break;
+    }
+#undef GS_N64
+}
+
+int narrow_slice_scatter(const void *kin, void *kout, const void *vin, void *vout, uint64_t len, int val_bytes, const LargeDigit &d,
+                         const uint32_t *spine, const uint64_t *dbase, hipStream_t s)
+{
+    const NarrowParams p = narrow_slice_params(len, val_bytes, d);
+    KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
+    if (n_key_bytes(d.key_type) == 1) narrow_scatter64<1>(val_bytes, kin, kout, vin, vout, spine, dbase, p, s);
+    else narrow_scatter64<2>(val_bytes, kin, kout, vin, vout, spine, dbase, p, s);
+    return (int)hipGetLastError();
+}
+
+// 8-bit keys alone over all 8 bits, n < 2^40: the histogram with u64 counters (counts[256], zeroed here) and the fill
+int narrow_fill_large(const void *kin, void *kout, uint64_t n, int key_type, int descending, uint64_t *counts, hipStream_t s)
+{
+    hipError_t ze = zero_async(counts, RADIX * sizeof(uint64_t), s);
+    if (ze != hipSuccess) return (int)ze;
+    const dim3 g = n_count_grid(n);
+    { KernelTimer kt(GS_K_LSB_UPSWEEP, s);
+      hipLaunchKernelGGL(narrow_count8_large_kernel, g, dim3(NF_THREADS), 0, s, kin, counts, n); }
+    { KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
+      hipLaunchKernelGGL(narrow_fill8_large_kernel, g, dim3(NF_THREADS), 0, s, kout, (const uint64_t *)counts, n,
+                         key_type == GS_KEY_I8 ? 0x80u : 0u, descending ? 1 : 0); }
+    return (int)hipGetLastError();
+}
+
+// begin_bit == end_bit: the output is the input (bytes of either array)
+int narrow_copy_bytes(const void *in, void *out, uint64_t bytes, hipStream_t s)
+{
+    hipLaunchKernelGGL(narrow_copy_kernel, n_stream_grid(bytes, 256 * 16), dim3(256), 0, s, (const unsigned char *)in, (unsigned char *)out, bytes);
+    return (int)hipGetLastError();
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -464,11 +528,7 @@ int gs_lsb_sort_narrow(void *d_temp, size_t temp_bytes, const void *d_keys_in, v
     if (kb == 1 && val_bytes == 0 && begin_bit == 0 && end_bit == 8) {   // (b): count and fill
         hipError_t ze = zero_async(totals, RADIX * 4, s);
         if (ze != hipSuccess) return (int)ze;
-        // one chunk per thread up to 256 blocks, then more chunks per thread (every block ends with 256 global atomics on
-        // the same 256 counters: 2^24 keys took 0.056 ms with 2048 blocks and 0.034 ms with 512), up to 2048 blocks
-        const uint64_t chunks = (n + 15) / 16 + 1;
-        const dim3 g = chunks <= 256ull * NF_THREADS * 8 ? n_stream_grid(chunks < 256ull * NF_THREADS ? chunks : 256ull * NF_THREADS, NF_THREADS)
-                                                         : n_stream_grid(chunks, NF_THREADS * 8);
+        const dim3 g = n_count_grid(n);
         { KernelTimer kt(GS_K_LSB_UPSWEEP, s);
           hipLaunchKernelGGL(narrow_count8_kernel, g, dim3(NF_THREADS), 0, s, d_keys_in, totals, n); }
         { KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);

@@ -235,12 +235,18 @@ class DeviceRadixSortLarge:
     """The stable sort of 2^32 elements and more (gs_lsb_sort_large, num_items < 2^40): the four DoubleBuffer methods of
     DeviceRadixSort for 32- or 64-bit keys with no, 32-bit or 64-bit values, the key type following the dtype as in
     DeviceRadixSort._sort_wide.  Stable, on bits [begin_bit, end_bit); the selector flips once per 8-bit pass; the call
-    only enqueues work on the stream and may be captured into a graph.  d_temp_storage=None returns the workspace size."""
+    only enqueues work on the stream and may be captured into a graph.  d_temp_storage=None returns the workspace size.
+    Keys of 8 and 16 bits (torch.bool / uint8 / int8 / int16 [/ uint16]) go to gs_lsb_sort_narrow_large with the convention
+    of DeviceRadixSort._sort_any: values are elements or rows of 1 / 2 / 4 / 8 / 16 bytes, the result ALWAYS ends in the
+    alternate buffer and the selector flips once."""
 
     @staticmethod
     def _sort(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items, begin_bit, end_bit, descending, stream,
               key_type):
         kb = d_keys.d_buffers[0].element_size()
+        if kb < 4:
+            return DeviceRadixSortLarge._sort_narrow(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items, begin_bit,
+                                                     end_bit, descending, stream, key_type, kb)
         vb = d_values.d_buffers[0].element_size() if d_values is not None else 0
         need = lib.gs_lsb_large_temp_bytes(num_items, kb, vb)
         if d_temp_storage is None:
@@ -268,6 +274,49 @@ class DeviceRadixSortLarge:
         d_keys.selector = sel.value
         if vb:
             d_values.selector = sel.value
+        return need
+
+    @staticmethod
+    def _sort_narrow(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items, begin_bit, end_bit, descending, stream,
+                     key_type, kb):
+        """8- and 16-bit keys: gs_lsb_sort_narrow_large, plain pointers underneath (input untouched, result in the other buffer)."""
+        vb = 0
+        if d_values is not None:    # a value is one element of a 1-D tensor or one row of a 2-D one
+            v0 = d_values.d_buffers[0]
+            row = 1
+            for d in v0.shape[1:]:
+                row *= d
+            vb = v0.element_size() * row
+        if key_type is None:
+            key_type = _KEY_TYPES.get(d_keys.d_buffers[0].dtype)
+            if key_type is None:
+                raise TypeError(f"no key category for dtype {d_keys.d_buffers[0].dtype}: pass key_type")
+        if lib.gs_lsb_narrow_tile(key_type, vb) == 0:
+            raise ValueError(f"large sort of {kb}-byte keys (key_type {key_type}): values of {vb} bytes are not served "
+                             "(none, 1, 2, 4, 8 or 16 bytes are)")
+        need = lib.gs_lsb_narrow_large_temp_bytes(num_items, key_type, vb)
+        if d_temp_storage is None:
+            return need
+        if end_bit is None:
+            end_bit = 8 * kb
+        for b in d_keys.d_buffers:
+            _check_buf(b, num_items, "d_keys", kb)
+        if vb:
+            for b in d_values.d_buffers:
+                _check_buf(b, num_items * (vb // b.element_size()), "d_values", b.element_size())
+            if d_values.selector != d_keys.selector:
+                raise ValueError("d_keys and d_values selectors differ")
+        sel = d_keys.selector
+        err = lib.gs_lsb_sort_narrow_large(C.c_void_p(d_temp_storage.data_ptr()),
+                                           min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                           d_keys.d_buffers[sel].data_ptr(), d_keys.d_buffers[sel ^ 1].data_ptr(),
+                                           d_values.d_buffers[sel].data_ptr() if vb else None,
+                                           d_values.d_buffers[sel ^ 1].data_ptr() if vb else None, num_items, key_type, vb,
+                                           begin_bit, end_bit, int(descending), _stream_ptr(stream))
+        check(err, "gs_lsb_sort_narrow_large")
+        d_keys.selector = sel ^ 1
+        if vb:
+            d_values.selector = sel ^ 1
         return need
 
     @staticmethod

@@ -269,6 +269,35 @@ int    gs_lsb_sort_large(void *d_temp, size_t temp_bytes, void *d_keys[2], void 
                          uint64_t num_items, int key_bytes, int val_bytes, int begin_bit, int end_bit,
                          int descending, int key_type, void *stream);
 
+/* gs_lsb_sort_narrow for num_items of 2^32 and more (up to 2^40): 8- and 16-bit keys (GS_KEY_U8 / I8 / U16 / I16) with
+ * values of 0, 1, 2, 4, 8 or 16 bytes -- e.g. a dictionary-coded column of more than 2^32 rows with u64 row ids.  The
+ * argument list and the contract are gs_lsb_sort_narrow's: plain pointers, the inputs are never written, stable, ascending or
+ * descending, on the bits [begin_bit, end_bit) of the key's own width (begin_bit == end_bit copies input to output),
+ * num_items == 0 succeeds with null pointers, a u8 array may start at any byte address, a u16 array at any even one, values
+ * at a multiple of their size, d_temp anywhere.  The call only enqueues work on `stream` (no host read-back, allocation or
+ * synchronisation), so it may be captured into a HIP graph, and calls may follow each other on one stream with one
+ * workspace.  One 64-bit pass per 8-bit digit of the range: per slice of 2^31 elements the narrow
+ * upsweep and spine scan, u64 digit starts over all slices, then the downsweep of every slice through them; 16-bit keys over
+ * more than 8 bits take two passes, in -> workspace -> out.  8-bit keys alone over all 8 bits take a histogram with 64-bit
+ * counts and a fill.  Arrays of up to one slice take gs_lsb_sort_narrow with the same arguments, which gives the same result.
+ * Errors (hipErrorInvalidValue, checked before anything is enqueued, nothing written): every other key type or value size
+ * (the size query returns 0 for those and for num_items >= 2^40), num_items >= 2^40, a bad bit range, a NULL or too-small
+ * workspace, values without val_bytes (or val_bytes without values), a misaligned array, input and output arrays that share
+ * a byte (at their element sizes).
+ * Workspace: a pure host function of its arguments, a multiple of 256.  With S = 2^31 elements per slice, slices =
+ * max(1, ceil(num_items / S)), T = gs_lsb_narrow_tile(key_type, val_bytes) and every term rounded up to 256 bytes:
+ *   slices * 256 * 4 * ceil(S / T)          per slice, a spine sized for a full slice
+ * + slices * 256 * 4                        the slices' digit totals
+ * + slices * 256 * 8                        the slices' u64 digit starts
+ * + 256 * 8                                 the u64 counts (the histogram of the fill path)
+ * + 16-bit keys only: 2 * num_items + val_bytes * num_items   the intermediate keys and values of the pass in -> temp -> out
+ * + 256 bytes of alignment slack;
+ * or gs_lsb_narrow_temp_bytes(min(num_items, S), ...) where that is larger (arrays of up to one slice).                   */
+size_t gs_lsb_narrow_large_temp_bytes(uint64_t num_items, int key_type, int val_bytes);
+int    gs_lsb_sort_narrow_large(void *d_temp, size_t temp_bytes, const void *d_keys_in, void *d_keys_out,
+                                const void *d_vals_in, void *d_vals_out, uint64_t num_items, int key_type,
+                                int val_bytes, int begin_bit, int end_bit, int descending, void *stream);
+
 /* Census of the last gs_msb_sort_u32 that used d_temp (read back after synchronising `stream`): what every level
  * partitioned and what it handed to local sorts.  SURVEY.md 8d: the MSB path's algorithmic bytes are data-dependent --
  * "the harness must log the per-pass census and compute bytes from it": level 0 moves every key once (12 B/key), a level

@@ -207,7 +207,8 @@ struct DeviceRadixSort {
 };
 
 // The stable sort of 2^32 elements and more (gs_lsb_sort_large, num_items < 2^40): DeviceRadixSort's DoubleBuffer overloads
-// with a uint64_t count, for 32- or 64-bit keys with no, 32-bit or 64-bit values.  A struct of its own rather than uint64_t
+// with a uint64_t count, for 32- or 64-bit keys with no, 32-bit or 64-bit values, and (gs_lsb_sort_narrow_large) 8- and 16-bit
+// keys with no values or values of 1, 2, 4, 8 or 16 bytes, whose result lands in the alternate buffer.  A struct of its own rather than uint64_t
 // overloads of DeviceRadixSort, so that existing callers who pass a size_t keep the overload they had.
 struct DeviceRadixSortLarge {
     template <typename KeyT, typename ValueT>
@@ -216,9 +217,29 @@ struct DeviceRadixSortLarge {
                                hipStream_t stream)
     {
         constexpr int KB = (int)sizeof(KeyT), VB = std::is_same<ValueT, NullType>::value ? 0 : (int)sizeof(ValueT);
-        static_assert(KB == 4 || KB == 8, "32- or 64-bit keys");
-        static_assert(VB == 0 || VB == 4 || VB == 8, "32- or 64-bit values");
+        static_assert(KB == 1 || KB == 2 || KB == 4 || KB == 8, "8-, 16-, 32- or 64-bit keys");
         const int vb = d_values ? VB : 0;
+        if constexpr (KB < 4) {
+            // 8- and 16-bit keys: gs_lsb_sort_narrow_large, with DeviceRadixSort's convention for these types: the plain-pointer
+            // form underneath, so the result always lands in the ALTERNATE buffer and the selector flips once
+            static_assert(VB == 0 || VB == 1 || VB == 2 || VB == 4 || VB == 8 || VB == 16, "values of 1, 2, 4, 8 or 16 bytes");
+            const size_t need_n = gs_lsb_narrow_large_temp_bytes(num_items, KeyTraits<KeyT>::type, vb);
+            if (d_temp_storage == nullptr) {
+                temp_storage_bytes = need_n;
+                return hipSuccess;
+            }
+            const int sel_n = d_keys.selector;
+            const int err_n = gs_lsb_sort_narrow_large(d_temp_storage, temp_storage_bytes, d_keys.d_buffers[sel_n], d_keys.d_buffers[sel_n ^ 1],
+                                                       d_values ? (const void *)d_values->d_buffers[sel_n] : nullptr,
+                                                       d_values ? (void *)d_values->d_buffers[sel_n ^ 1] : nullptr, num_items,
+                                                       KeyTraits<KeyT>::type, vb, begin_bit, end_bit, descending ? 1 : 0, stream);
+            if (err_n == 0 && num_items > 0) {
+                d_keys.selector = sel_n ^ 1;
+                if (d_values) d_values->selector = sel_n ^ 1;
+            }
+            return static_cast<hipError_t>(err_n);
+        }
+        static_assert(KB < 4 || VB == 0 || VB == 4 || VB == 8, "32- or 64-bit values");
         const size_t need = gs_lsb_large_temp_bytes(num_items, KB, vb);
         if (d_temp_storage == nullptr) {
             temp_storage_bytes = need;
