@@ -22,207 +22,18 @@
 //             and stores of different blocks overlap.  Measured on MI355X:
 //             2.05 ms per pass at 2^30 keys, against 3.2 ms for persistent
 //             blocks that each own a long run of tiles and march in lockstep.
+//
+// The device code of the upsweep and of one downsweep tile lives in gs_lsb_upsweep.inc / gs_lsb_downsweep.inc: the
+// keys-only plan (gs_lsb_plan.hip) builds its pass slots from the same functions.
 #include "gs_device.hpp"
 #include "gs_lsb.hpp"
-#ifndef GS_EXP_SLEEP_MODE
-#define GS_EXP_SLEEP_MODE 0
-#endif
-#ifndef GS_EXP_SLEEP_MIN_TILES
-#define GS_EXP_SLEEP_MIN_TILES 49152u
-#endif
-#ifndef GS_EXP_SLEEP_PAIRS
-#define GS_EXP_SLEEP_PAIRS 0
-#endif
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
 namespace gs {
 
-// ---------------------------------------------------------------- upsweep --
-#ifndef UPSWEEP_BATCH
-#define UPSWEEP_BATCH 64   // dword loads in flight per lane (a tile is 128 per lane).  In-process A/B at 2^30 keys (round 3, tools/ab_inproc.py):
-                           // 16 -> 0.751 ms, 32 -> 0.709-0.721, 64 -> 0.685-0.694, 128 -> 0.707 ms per launch (64: 150 VGPRs, one workgroup per CU)
-#endif
-#ifndef UPSWEEP_SUB
-#define UPSWEEP_SUB 4      // histogram copies per wave (power of two)
-#endif
-// relaxed agent-scope accesses = `sc1` loads / write-through stores: what workgroups of one launch may exchange
-// without fences (cdna_hip_programming.md Guideline 16, forms R1 / R2; compiler-visible, so hipcc counts their waits)
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint64_t ld_agent(const uint64_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(uint64_t *p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// NEXT: the wave also counts the digit of the FOLLOWING pass (one plain histogram copy per wave) and the block adds
-// its sums to `next_totals` -- the pipelined pass needs the digit totals before its first tile is scattered.
-// PIPE: the block is one role of lsb_pipe_pass_kernel: key loads with the default cache policy (they must stay in the
-// Infinity Cache for the downsweep role; the streaming hint would keep them out), results published write-through.
-template <bool NEXT, bool PIPE>
-struct UpsweepSmem {
-    // every wave counts into UPSWEEP_SUB copies of its histogram (lane & 3 picks one; rows padded by one word so
-    // equal digits of different copies sit in different banks): under skew the lanes that share a hot digit
-    // spread over four banks instead of queueing on one (Zipf keys: 1.40 -> ~1.0 ms at level 1 of the MSB sort)
-    uint32_t hist[LSB_WAVES][UPSWEEP_SUB][RADIX + 1];
-    uint32_t hist2[NEXT ? LSB_WAVES : 1][NEXT ? RADIX : 1];
-    alignas(8) uint16_t pre[PIPE ? LSB_WAVES : 1][PIPE ? RADIX : 4];   // prefix16 rows on their way to 8-byte stores
-    alignas(8) uint32_t tot[PIPE ? RADIX : 2];
-};
-
-// Plain dword loads in batches beat 16-byte loads here (0.81 vs 0.84 ms at 2^30) and need no alignment.
-// PLAIN: the keys need no transform on the way in (u32 ascending, and every pass after the first: keys travel
-// twiddled between passes), so the full-tile path below is load, v_bfe, address, ds_add and nothing else.
-template <bool NEXT, bool PIPE, bool PLAIN = false>
-__device__ __forceinline__ void upsweep_chunk(UpsweepSmem<NEXT, PIPE> &sm, const uint32_t *__restrict__ keys, uint32_t chunk,
-                                              uint32_t *__restrict__ spine, uint16_t *__restrict__ prefix16,
-                                              uint32_t *__restrict__ cc, uint32_t *__restrict__ next_totals, const PassParams &p,
-                                              const PipeParams &q)
-{
-    const int tid = threadIdx.x, w = wave_id(), lane = lane_id();
-    uint32_t *my = sm.hist[w][lane & (UPSWEEP_SUB - 1)];
-    for (int i = lane; i < UPSWEEP_SUB * (RADIX + 1); i += WAVE) (&sm.hist[w][0][0])[i] = 0;
-    if (NEXT)
-        for (int i = lane; i < RADIX; i += WAVE) sm.hist2[w][i] = 0;
-
-    const uint32_t tile = chunk * LSB_CHUNK + (uint32_t)w;
-    if (tile < p.num_tiles) {
-        const uint64_t lo = (uint64_t)tile * LSB_TILE;
-        const uint32_t len = (p.n - lo < (uint64_t)LSB_TILE) ? (uint32_t)(p.n - lo) : (uint32_t)LSB_TILE;
-        const uint32_t *src = keys + lo;
-        auto count = [&](uint32_t raw) {
-            const uint32_t k = twiddle_in(raw, p.f32_in, p.xor_in);
-            hist_add(my, __builtin_amdgcn_ubfe(k, p.shift, p.bits));        // wave-private ds_add_u32
-            if (NEXT) hist_add(sm.hist2[w], __builtin_amdgcn_ubfe(k, q.next_shift, q.next_bits));
-        };
-        constexpr int GB = UPSWEEP_BATCH;
-        if (!NEXT && !PIPE && len == (uint32_t)LSB_TILE) {
-            // full tile (all but the array's last one): no clamps, no guards, and the test for a digit shared by the
-            // whole wave (a hot bucket, constant high bytes: 64 lanes would queue on 4 counters) is made on two keys
-            // of the batch instead of on each -- 15 -> 4 vector instructions per key
-            uint32_t wbits = p.bits;
-            asm volatile("" : "+v"(wbits));   // v_bfe_u32 takes one scalar operand (the shift)
-            auto digit_of = [&](uint32_t raw) {
-                return __builtin_amdgcn_ubfe(PLAIN ? raw : twiddle_in(raw, p.f32_in, p.xor_in), p.shift, wbits);
-            };
-#pragma unroll 1
-            for (uint32_t j = 0; j < (uint32_t)LSB_TILE; j += GB * WAVE) {
-                const uint32_t *at = src + j + lane;
-                uint32_t v[GB];
-#pragma unroll
-                for (int u = 0; u < GB; ++u) v[u] = __builtin_nontemporal_load(at + u * WAVE);
-                const uint32_t da = digit_of(v[0]), db = digit_of(v[GB / 2]);
-                const bool hot = __builtin_amdgcn_ballot_w64(da == __builtin_amdgcn_readfirstlane(da)) == ~0ull ||
-                                 __builtin_amdgcn_ballot_w64(db == __builtin_amdgcn_readfirstlane(db)) == ~0ull;
-                if (hot) {
-#pragma unroll
-                    for (int u = 0; u < GB; ++u) hist_add(my, digit_of(v[u]));
-                } else {
-#pragma unroll
-                    for (int u = 0; u < GB; ++u) atomicAdd(&my[digit_of(v[u])], 1u);
-                }
-            }
-        } else {
-        // batches of dword loads from clamped indices: one code path for partial and misaligned tiles
-        // (a loop of one guarded load per trip would pay one HBM round trip per 64 keys)
-        const uint32_t last = len - 1u;
-#pragma unroll 1
-        for (uint32_t j = 0; j < len; j += GB * WAVE) {
-            uint32_t v[GB];
-#pragma unroll
-            for (int u = 0; u < GB; ++u) {
-                const uint32_t idx = j + u * WAVE + lane;
-                const uint32_t *at = &src[idx < last ? idx : last];
-                v[u] = PIPE ? *at : __builtin_nontemporal_load(at);   // streaming hint: 0.80 -> 0.76 ms
-            }
-#pragma unroll
-            for (int u = 0; u < GB; ++u)
-                if (j + u * WAVE + lane < len) count(v[u]);
-        }
-        }
-    }
-    __syncthreads();
-#if defined(GS_EXP_UPS) && GS_EXP_UPS == 4
-    if (!PIPE && !NEXT && (chunk & 7u) != 0u) return;     // timing experiment: only one workgroup in eight writes its results
-#endif
-#if defined(GS_EXP_UPS) && GS_EXP_UPS >= 1 && GS_EXP_UPS <= 3
-    // timing experiments only (results land in the wrong layout): 1 = the chunk's prefix16 rows as ONE 16-byte store per
-    // digit thread (4 KiB per workgroup in four wave instructions instead of 32), 2 = also the spine as one 1 KiB row per
-    // chunk, 3 = no result stores at all
-    if (!PIPE && !NEXT && tid < RADIX) {
-        uint32_t run = 0, pk[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < LSB_WAVES; ++j) {
-            pk[j >> 1] |= (run & 0xffffu) << (16 * (j & 1));
-            uint32_t c = 0;
-#pragma unroll
-            for (int u = 0; u < UPSWEEP_SUB; ++u) c += sm.hist[j][u][tid];
-            run += c;
-        }
-#if GS_EXP_UPS < 3
-        reinterpret_cast<uint4 *>(prefix16 + (size_t)chunk * LSB_CHUNK * RADIX)[tid] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-#if GS_EXP_UPS == 2
-        spine[(size_t)chunk * RADIX + tid] = run;
-#else
-        spine[(uint32_t)tid * p.grid + chunk] = run;
-#endif
-#else
-        if (run == 0xffffffffu) spine[0] = pk[0] + pk[1] + pk[2] + pk[3];
-#endif
-        return;
-    }
-#endif
-    if (tid < RADIX) {
-        uint32_t run = 0;
-#pragma unroll
-        for (int j = 0; j < LSB_WAVES; ++j) {
-            const uint32_t t = chunk * LSB_CHUNK + (uint32_t)j;
-            if (PIPE) sm.pre[j][tid] = (uint16_t)run;
-            else if (t < p.num_tiles) prefix16[(size_t)t * RADIX + tid] = (uint16_t)run;
-            uint32_t c = 0;
-#pragma unroll
-            for (int u = 0; u < UPSWEEP_SUB; ++u) c += sm.hist[j][u][tid];
-            run += c;
-        }
-        if (PIPE) sm.tot[tid] = run | (q.tag << 28);       // run <= 65536
-        else spine[(uint32_t)tid * p.grid + chunk] = run;
-        if (NEXT) {
-            uint32_t s2 = 0;
-#pragma unroll
-            for (int j = 0; j < LSB_WAVES; ++j) s2 += sm.hist2[j][tid];
-            if (s2) atomicAdd(&next_totals[tid], s2);
-        }
-    }
-    if (PIPE) {
-        // publish: the chunk's prefix16 rows (wave w = tile w, 8 bytes per lane), drained by every storing wave,
-        // then -- behind the workgroup's barrier -- the tagged count words the scanner role polls
-        __syncthreads();
-        uint32_t tid2 = threadIdx.x;
-        asm volatile("" : "+v"(tid2));   // recomputed from scratch: otherwise `tile` lives (and spills) across the counting loop
-        const uint32_t tile2 = chunk * LSB_CHUNK + (tid2 >> 6);
-        if (tile2 < p.num_tiles)
-            st_agent(reinterpret_cast<uint64_t *>(prefix16 + (size_t)tile2 * RADIX) + lane,
-                     reinterpret_cast<const uint64_t *>(sm.pre[tile2 - chunk * LSB_CHUNK])[lane]);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid < RADIX / 2)
-            st_agent(reinterpret_cast<uint64_t *>(cc + (size_t)chunk * RADIX) + tid, reinterpret_cast<const uint64_t *>(sm.tot)[tid]);
-    }
-}
-
-#ifndef GS_EXP_UPS_WPE
-#define GS_EXP_UPS_WPE 1
-#endif
-template <bool NEXT, bool PLAIN = false>
-__global__ __launch_bounds__(LSB_THREADS, GS_EXP_UPS_WPE) void lsb_upsweep_kernel(const uint32_t *__restrict__ keys,
-                                                                  uint32_t *__restrict__ spine,
-                                                                  uint16_t *__restrict__ prefix16,
-                                                                  uint32_t *__restrict__ next_totals, PassParams p, PipeParams q)
-{
-    // blocks are dispatched round-robin over the 8 XCDs; the blocks of one XCD take CONSECUTIVE chunks, so the 16 chunk
-    // totals that share a 64-byte line of a spine row are merged in one L2 instead of leaving eight L2s as partial
-    // lines (0.736 -> 0.708 ms per launch at 2^30 keys)
-    __shared__ UpsweepSmem<NEXT, false> sm;
-    upsweep_chunk<NEXT, false, PLAIN>(sm, keys, chunk_of_block(blockIdx.x, p.grid), spine, prefix16, nullptr, next_totals, p, q);
-}
+#include "gs_lsb_upsweep.inc"
 
 // ---- small arrays (up to LSB_SMALL_TILES tiles): with one wave per tile a handful of waves would each
 // walk 8192 keys in four dependent batches (15 us however small the array).  Here a whole workgroup counts
@@ -319,445 +130,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void lsb_scan_kernel(uint32_t *__rest
     if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
 
-// -------------------------------------------------------------- downsweep --
-// Stable scatter, one tile at a time:
-//   1. wave-striped coalesced load (key i of lane l of wave w sits at
-//      tile + w*1024 + i*64 + l, so position order = (w, i, l)); HBM latency
-//      is covered by the other blocks resident on the CU;
-//   2. rank inside the wave: the set of lanes holding the same digit (ballot
-//      match) gives the rank inside the group by popcount of the lower lanes;
-//      the wave's running count of the digit (wave-private LDS histogram) gives
-//      the rank of the group.  Every lane reads the count, the first lane of the
-//      group then adds the group size with a no-return LDS atomic; LDS executes
-//      one wave's operations in order, so round i+1 sees round i's add without a
-//      wait.  The match set comes either from 8 VALU ballots (match_digit) or
-//      from LDS: each lane ORs its lane bit into the wave's mask entry of its
-//      digit, reads the entry back and clears its bit again.  Both are exact;
-//      `valu_rounds` splits the 16 rounds between the two pipes;
-//   3. the 8 wave histograms become tile-absolute bases per (wave, digit) (4 digits
-//      per lane, b128 LDS accesses, DPP scan), by wave 0 alone (keys only, 3
-//      blocks/CU) or redundantly by every wave for its own row, which removes a
-//      barrier and the serial section (pairs, 2 blocks/CU); wave 0 publishes, per
-//      digit, the tile's global base = digit start + scanned chunk count + prefix16;
-//   4. keys (and values) go to LDS at their tile rank and are read back in rank
-//      order: consecutive lanes hit consecutive addresses inside a digit run.
-// Two (pairs) or three (keys only) block barriers per tile.
-// OFF64: the 64-bit pass (lsb_downsweep64): gbase holds absolute u64 element offsets instead of u32 ones.
-template <bool HAS_VALUES, bool OFF64 = false>
-struct DownsweepSmem {
-    uint32_t whist[LSB_WAVES][RADIX];                     // wave-private digit counters, then bases (byte offsets)
-#ifdef GS_EXP_ALLWAVE_KEYS
-    uint16_t wbase[LSB_WAVES][RADIX];
-#else
-    uint16_t wbase[HAS_VALUES ? LSB_WAVES : 1][RADIX];    // pairs: tile-absolute base of (wave, digit), < 8192
-#endif
-    std::conditional_t<OFF64, uint64_t, uint32_t> gbase[RADIX];   // global offset of digit run - tile-local start
-    uint32_t stage[LSB_TILE * (HAS_VALUES ? 2 : 1)];      // tile in rank order; pairs interleaved {key,val}
-    uint32_t dead;                                        // pipelined pass only: wave 0's wait gave up -> the tile stores nothing
-};
-
-#ifdef GS_EXP_PHASES
-// experiment builds only (tools/phase_exp.py): shader-clock length of every phase of wave 0
-__device__ uint32_t gs_phase_buf[131072 * 16];   // [block][phase], n <= 2^30
-#define GS_PHASE(k)                                                                          \
-    do {                                                                                     \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();                        \
-        if (tid == 0 && t < 131072u) gs_phase_buf[t * 16 + (k)] = (uint32_t)(now_ - tprev_); \
-        tprev_ = now_;                                                                       \
-    } while (0)
-#define GS_PHASE_WAIT(what) asm volatile("s_waitcnt " what ::: "memory")
-#else
-#define GS_PHASE(k) do { } while (0)
-#define GS_PHASE_WAIT(what) do { } while (0)
-#endif
-
-// The kernel is VALU-bound on MI355X (about 900 vector instructions per wave and tile, 57 % of
-// them the ballot match; measured with tools/phase_exp.py and an ISA count), so the template
-// parameters exist to keep instructions out of the hot variants:
-// TAIL = false: one of the array's FULL tiles.
-// TAIL = true: one block handles the last, partial tile (guarded loads); being
-// last in key order, its keys of digit d sit at the very end of digit d's global
-// range, so it needs only the digit totals.  Splitting it off keeps the guarded
-// path's registers out of the hot kernel.
-// TW: key transform on read / write.  0 = none (u32 ascending, and every middle pass: keys
-// travel twiddled between passes), 1 = xor mask (signed keys, descending), 2 = float + xor.
-// BIG = false: n <= 2^30, so byte offsets into the output fit 32 bits and a store needs no
-// 64-bit address arithmetic.
-// PIPE = true: the tile is one block of lsb_pipe_pass_kernel; its chunk's scanned counts come from the scanner
-// role as {tag, value} granules (`sc`), its in-chunk prefixes from the upsweep role (`prefix16`), both published
-// write-through inside the same launch and read here with agent-scope loads.
-// OFF64 = true: the tile belongs to one slice (< 2^31 keys) of a larger array (lsb_downsweep64_kernel): the spine,
-// prefix16 and totals are the slice's own, and dbase[d] is the absolute u64 output offset of the slice's run of digit
-// d, so the global base of a digit run is dbase[d] + (signed 32-bit in-slice offset) and the stores index with 64 bits.
-constexpr uint32_t PIPE_SPIN_LIMIT = 1u << 18;   // polls (each >= one memory round trip) before a wait gives up
-
-template <bool HAS_VALUES, bool TAIL, int TW, bool BIG, bool PIPE, bool OFF64 = false>
-__device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES, OFF64> &sm, const uint32_t t,
-    const uint32_t *__restrict__ keys_in, uint32_t *__restrict__ keys_out, const uint32_t *__restrict__ vals_in,
-    uint32_t *__restrict__ vals_out, const uint32_t *__restrict__ spine, const uint16_t *__restrict__ prefix16,
-    const uint32_t *__restrict__ totals, const PassParams &p, const uint64_t *__restrict__ sc, uint32_t tag,
-    uint32_t *__restrict__ error_word, const uint32_t tid_ = threadIdx.x, const uint64_t *__restrict__ dbase = nullptr)
-{
-#ifdef GS_EXP_ALLWAVE_KEYS
-    constexpr bool ALLWAVE = true;          // experiment: every wave computes its own bases for keys too (no second barrier)
-#else
-    constexpr bool ALLWAVE = HAS_VALUES;   // see step 3
-#endif
-
-    [[maybe_unused]] const int tid = (int)tid_;
-    const int lane = (int)(tid_ & 63u), w = (int)(tid_ >> 6);
-    const uint32_t full_tiles = p.n / (uint32_t)LSB_TILE;
-    auto tw_in = [&](uint32_t k) { return TW == 0 ? k : twiddle_in(k, TW == 2 ? p.f32_in : 0, p.xor_in); };
-    auto tw_out = [&](uint32_t k) { return TW == 0 ? k : twiddle_out(k, TW == 2 ? p.f32_out : 0, p.xor_out); };
-    // the digit width lives in a vector register: v_bfe_u32 takes one scalar operand (the shift)
-    uint32_t wbits = p.bits;
-    asm volatile("" : "+v"(wbits));
-    auto digit = [&](uint32_t k) { return __builtin_amdgcn_ubfe(k, p.shift, wbits); };
-
-    uint32_t *my = sm.whist[w];
-    const uint16_t *mybase = sm.wbase[w];
-    const uint32_t wbase = (uint32_t)w * (WAVE * LSB_KPT) + lane;
-    const uint32_t tail_valid = p.n - full_tiles * (uint32_t)LSB_TILE;   // used when TAIL
-    (void)full_tiles;
-
-#ifdef GS_EXP_PHASES
-    unsigned long long tprev_ = __builtin_amdgcn_s_memtime();
-    const unsigned long long t0_ = tprev_, r0_ = __builtin_amdgcn_s_memrealtime();
-#endif
-    // keys only: the waves that issue loads and stores get priority over the ones that rank, so the memory
-    // pipes are fed as early as possible (1.87 -> 1.82 ms; with values it costs 7 %, so pairs keep the default)
-#ifdef GS_EXP_SLEEP_START
-    __builtin_amdgcn_s_sleep(GS_EXP_SLEEP_START);
-#endif
-    if (!HAS_VALUES) __builtin_amdgcn_s_setprio(3);
-    const uint64_t tile_base = (uint64_t)t * LSB_TILE;
-    const uint32_t valid = TAIL ? tail_valid : (uint32_t)LSB_TILE;
-
-    // pipelined pass: the chunk's scanned counts are requested first, so they are back before the keys are
-    uint64_t scg[4] = {0, 0, 0, 0};
-    const uint64_t *scrow = nullptr;
-    if (PIPE && w == 0) {
-        scrow = sc + (size_t)(t / LSB_CHUNK) * RADIX + 4 * lane;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) scg[q] = ld_agent(scrow + q);
-    }
-
-    // 1. wave-striped coalesced load
-    uint32_t key[LSB_KPT], val[HAS_VALUES ? LSB_KPT : 1], pos[LSB_KPT];
-    {
-        const uint32_t *kin = keys_in + tile_base;
-        if (!TAIL) {
-#pragma unroll
-            for (int i = 0; i < LSB_KPT; ++i) key[i] = kin[wbase + i * WAVE];
-        } else {
-            // pad with keys whose twiddled form is all ones (largest digit; ranked after
-            // every real key of that digit because they sit at the tail)
-            const uint32_t pad = twiddle_out(0xffffffffu, TW == 2 ? p.f32_in : 0, TW ? p.xor_in : 0u);
-#pragma unroll
-            for (int i = 0; i < LSB_KPT; ++i) {
-                const uint32_t idx = wbase + i * WAVE;
-                key[i] = pad;
-                if (idx < tail_valid) key[i] = kin[idx];
-            }
-        }
-    }
-    GS_PHASE(0);                                   // load issue
-#ifndef GS_EXP_RANK_PRIO
-#define GS_EXP_RANK_PRIO 0
-#endif
-    if (!HAS_VALUES) __builtin_amdgcn_s_setprio(GS_EXP_RANK_PRIO);
-    if (HAS_VALUES) {
-        const uint32_t *vin = vals_in + tile_base;
-#pragma unroll
-        for (int i = 0; i < LSB_KPT; ++i) {
-            const uint32_t idx = wbase + i * WAVE;
-            val[i] = 0;
-            if (!TAIL || idx < valid) val[i] = vin[idx];
-        }
-    }
-    // (after the key loads are in flight) wave 0, lane l: global start of digits 4l..4l+3 (exclusive scan of the totals)
-    // (TAIL: inclusive scan; the tile's own counts are subtracted later)
-    uint32_t dstart[4] = {0, 0, 0, 0};
-    if constexpr (OFF64) {
-        // digit starts are dbase[d] (added in publish_gbase); TAIL: the slice's run of d ends at dbase[d] + totals[d]
-        if (TAIL && w == 0) {
-            const uint4 tot = reinterpret_cast<const uint4 *>(totals)[lane];
-            dstart[0] = tot.x; dstart[1] = tot.y; dstart[2] = tot.z; dstart[3] = tot.w;
-        }
-    } else if (w == 0) {
-        const uint4 tot = reinterpret_cast<const uint4 *>(totals)[lane];
-        const uint32_t lane_sum = tot.x + tot.y + tot.z + tot.w;
-        const uint32_t ex = wave_inclusive_scan(lane_sum) - lane_sum;
-        dstart[0] = ex + (TAIL ? tot.x : 0u);
-        dstart[1] = dstart[0] + (TAIL ? tot.y : tot.x);
-        dstart[2] = dstart[1] + (TAIL ? tot.z : tot.y);
-        dstart[3] = dstart[2] + (TAIL ? tot.w : tot.z);
-    }
-
-    // this tile's global offsets (wave 0): scanned chunk count + count of the chunk's earlier tiles
-    uint32_t tbase[4] = {0, 0, 0, 0};
-    if (!TAIL && !PIPE && w == 0) {
-        const uint32_t *sp = spine + (uint32_t)(4 * lane) * p.grid + t / LSB_CHUNK;
-        const uint2 pf = reinterpret_cast<const uint2 *>(prefix16 + (size_t)t * RADIX)[lane];
-        tbase[0] = sp[0] + (pf.x & 0xffffu);
-        tbase[1] = sp[p.grid] + (pf.x >> 16);
-        tbase[2] = sp[2 * p.grid] + (pf.y & 0xffffu);
-        tbase[3] = sp[3 * p.grid] + (pf.y >> 16);
-    }
-
-    if (PIPE && !TAIL && w == 0) {
-        // every granule carries this pass's tag once the scanner has written it (normally long ago: the upsweep
-        // role runs PIPE_LEAD_CHUNKS ahead); only then may the prefix16 row be read (it was published before the
-        // counts the scanner waited for).  Bounded: a wait that gives up flags the sort instead of hanging the GPU --
-        // and the tile then stores NOTHING: its offsets would come from untagged words (stale values of another pass
-        // can exceed n: an out-of-bounds scatter), so the whole workgroup leaves behind the first barrier.
-        uint32_t spins = 0;
-        bool gave_up = false;
-        for (;;) {
-            const bool ok = (uint32_t)(scg[0] >> 32) == tag && (uint32_t)(scg[1] >> 32) == tag &&
-                            (uint32_t)(scg[2] >> 32) == tag && (uint32_t)(scg[3] >> 32) == tag;
-            if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
-            if (++spins > PIPE_SPIN_LIMIT) {
-                if (lane == 0) atomicOr(error_word, 1u);
-                gave_up = true;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(8);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) scg[q] = ld_agent(scrow + q);
-        }
-        if (lane == 0) sm.dead = gave_up ? 1u : 0u;
-        const uint64_t pf = ld_agent(reinterpret_cast<const uint64_t *>(prefix16 + (size_t)t * RADIX) + lane);
-        tbase[0] = (uint32_t)scg[0] + (uint32_t)(pf & 0xffffu);
-        tbase[1] = (uint32_t)scg[1] + (uint32_t)((pf >> 16) & 0xffffu);
-        tbase[2] = (uint32_t)scg[2] + (uint32_t)((pf >> 32) & 0xffffu);
-        tbase[3] = (uint32_t)scg[3] + (uint32_t)(pf >> 48);
-    }
-
-    // global base of digit run = digit start + tile offset - tile-local start (wave 0, lane l: digits 4l..4l+3)
-    auto publish_gbase = [&](const uint32_t (&ex)[4], const uint32_t (&run)[4]) {
-        uint32_t g[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) g[q] = dstart[q] + tbase[q] - ex[q];
-        if (TAIL) {   // keys of digit d end exactly at the inclusive total of d
-#pragma unroll
-            for (int q = 0; q < 4; ++q) g[q] -= run[q];
-            // padded keys inflate the count of the largest digit only, and they are never stored
-            const uint32_t pads = (uint32_t)LSB_TILE - valid, dmax = p.mask;
-            if (lane == (int)(dmax >> 2)) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if ((dmax & 3u) == (uint32_t)q) g[q] += pads;
-            }
-        }
-        if constexpr (OFF64) {   // in-slice offsets are in (-2^13, 2^31): signed 32-bit
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sm.gbase[4 * lane + q] = dbase[4 * lane + q] + (uint64_t)(int64_t)(int32_t)g[q];
-        } else {
-            if (!BIG) {   // byte offsets (mod 2^32; exact once the slot is added)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) g[q] <<= 2;
-            }
-            reinterpret_cast<uint4 *>(sm.gbase)[lane] = make_uint4(g[0], g[1], g[2], g[3]);
-        }
-    };
-
-    // 2. rank inside the wave (the LDS count of round i is consumed one round later, so
-    //    its latency hides behind the match of round i+1)
-#pragma unroll
-    for (int i = lane; i < RADIX; i += WAVE) my[i] = 0;
-    GS_PHASE_WAIT("vmcnt(0)");
-    GS_PHASE(1);                                   // load wait
-#pragma unroll
-    for (int i = 0; i < LSB_KPT; ++i) key[i] = tw_in(key[i]);
-    {
-        uint32_t d_prev = 0, plo = 0, phi = 0;
-#pragma unroll
-        for (int i = 0; i <= LSB_KPT; ++i) {
-            uint32_t d_cur = 0, clo = 0, chi = 0;
-            if (i < LSB_KPT) {
-                d_cur = digit(key[i]);
-                match_digit(d_cur, clo, chi);
-            }
-            if (i > 0) {
-                const uint32_t lower = count_lower(plo, phi);
-                pos[i - 1] = my[d_prev] + lower;            // LDS read, all lanes
-                if (lower == 0)                             // first lane of the group adds the group size
-                    __hip_atomic_fetch_add(&my[d_prev], (uint32_t)(__popc(plo) + __popc(phi)), __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_WAVEFRONT);
-            }
-            d_prev = d_cur; plo = clo; phi = chi;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < LSB_KPT; ++i) {
-        // finish the adds before the barrier, and make the keys opaque so their LDS
-        // histogram addresses are recomputed after the barrier instead of kept live
-        asm volatile("" : "+v"(pos[i]), "+v"(key[i]));
-    }
-    GS_PHASE_WAIT("lgkmcnt(0)");
-    GS_PHASE(2);                                   // rank
-    __syncthreads();
-    GS_PHASE(3);                                   // barrier 1
-    if (PIPE && !TAIL && sm.dead) return;          // the wait for this tile's offsets gave up: no global store (all waves alike)
-
-    // 3. wave histograms -> tile-absolute base of every (wave, digit) + global base per digit.
-    //    4 digits per lane, b128 LDS accesses, DPP scan of the 256 digit totals.
-    if constexpr (ALLWAVE) {
-        // every wave sums the 8 rows and keeps only its own row's bases (own row of `wbase`), so
-        // there is no serial section and no second barrier: best at 2 blocks/CU (pairs)
-        uint32_t run[4] = {0, 0, 0, 0}, below[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < LSB_WAVES; ++j) {
-            const uint4 x = reinterpret_cast<const uint4 *>(sm.whist[j])[lane];
-            run[0] += x.x; run[1] += x.y; run[2] += x.z; run[3] += x.w;
-            if (j < w) { below[0] += x.x; below[1] += x.y; below[2] += x.z; below[3] += x.w; }
-        }
-        const uint32_t lane_sum = run[0] + run[1] + run[2] + run[3];
-        uint32_t ex[4];
-        ex[0] = wave_inclusive_scan(lane_sum) - lane_sum;
-        ex[1] = ex[0] + run[0];
-        ex[2] = ex[1] + run[1];
-        ex[3] = ex[2] + run[2];
-        reinterpret_cast<uint2 *>(sm.wbase[w])[lane] =
-            make_uint2((ex[0] + below[0]) | ((ex[1] + below[1]) << 16), (ex[2] + below[2]) | ((ex[3] + below[3]) << 16));
-        if (w == 0) publish_gbase(ex, run);
-    } else {
-        // wave 0 alone, two sweeps over the 8 rows (only one row in registers at a time), bases
-        // written back in place as BYTE offsets into `stage`; the other waves wait at the barrier
-        // while the CU's other two blocks run: best at 3 blocks/CU (keys only)
-        if (w == 0) {
-            uint32_t run[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int j = 0; j < LSB_WAVES; ++j) {
-                const uint4 x = reinterpret_cast<const uint4 *>(sm.whist[j])[lane];
-                run[0] += x.x; run[1] += x.y; run[2] += x.z; run[3] += x.w;
-            }
-            const uint32_t lane_sum = run[0] + run[1] + run[2] + run[3];
-            uint32_t ex[4];
-            ex[0] = wave_inclusive_scan(lane_sum) - lane_sum;
-            ex[1] = ex[0] + run[0];
-            ex[2] = ex[1] + run[1];
-            ex[3] = ex[2] + run[2];
-            publish_gbase(ex, run);
-            asm volatile("" ::: "memory");   // re-read the rows instead of keeping 32 registers live
-            uint4 e4 = make_uint4(ex[0] << 2, ex[1] << 2, ex[2] << 2, ex[3] << 2);
-#pragma unroll
-            for (int j = 0; j < LSB_WAVES; ++j) {
-                const uint4 x = reinterpret_cast<const uint4 *>(sm.whist[j])[lane];
-                reinterpret_cast<uint4 *>(sm.whist[j])[lane] = e4;
-                e4.x += x.x << 2; e4.y += x.y << 2; e4.z += x.z << 2; e4.w += x.w << 2;
-            }
-        }
-        __syncthreads();
-    }
-    GS_PHASE(4);                                   // scan + barrier 2
-
-    // 4. tile -> LDS in rank order -> global.  All 16 base reads are issued before the first
-    //    write so the LDS round trip is paid once, not per key.
-    {
-        uint32_t wb[LSB_KPT];
-#pragma unroll
-        for (int i = 0; i < LSB_KPT; ++i) {
-            const uint32_t d = digit(key[i]);
-            wb[i] = ALLWAVE ? (uint32_t)mybase[d] : my[d];
-        }
-#pragma unroll
-        for (int i = 0; i < LSB_KPT; ++i) {
-            if (HAS_VALUES) {
-                reinterpret_cast<uint2 *>(sm.stage)[pos[i] + wb[i]] = make_uint2(key[i], val[i]);
-            } else if (ALLWAVE) {
-                sm.stage[pos[i] + wb[i]] = key[i];
-            } else {
-                const uint32_t at = (pos[i] << 2) + wb[i];       // bytes
-                *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(sm.stage) + at) = key[i];
-            }
-        }
-    }
-    GS_PHASE_WAIT("lgkmcnt(0)");
-    GS_PHASE(5);                                   // LDS scatter
-    __syncthreads();
-    GS_PHASE(6);                                   // barrier 3
-    // Pacing (round 3, in-process A/B on the same buffers, tools/ab_inproc.py): every wave pauses 32 x 64 cycles (~0.9 us) between
-    // barrier 3 and its 16 stores.  What it buys depends on where the driver placed the arrays: on placements where the kernel
-    // runs 1.89-1.94 ms per launch without the pause it runs 1.78-1.79 ms with it; on placements where it runs 1.74 ms without,
-    // the pause costs 0.7-1.5 % (1.755-1.77 ms) -- profiles/r03_ab_pacing.txt has both kinds, from the same box and process
-    // sequence.  So the pause takes 8 % off the slow placements and the spread between placements shrinks from 11 % to 2 %.
-    // Pauses of 8/16/24 recover less of the slow case (1.91/1.88/1.81 ms), 40-64 cost more of the fast one; pausing only the odd
-    // waves (behind a scalar branch) 1.85 ms.  Only from 2^29 keys up: below, the launch is not bound by the memory system
-    // and the pause is latency (2^28 keys: +1 %; 2^22-2^24: +5 %).  Pairs gain nothing from it (3.57-3.62 ms with 16/32, 3.71 with
-    // 64, 3.58-3.60 without).  GS_EXP_SLEEP* override all of it for experiments.
-#ifndef GS_EXP_SLEEP
-#define GS_EXP_SLEEP 32
-#define GS_EXP_SLEEP_MODE_DEFAULT 0
-#else
-#define GS_EXP_SLEEP_MODE_DEFAULT GS_EXP_SLEEP_MODE
-#endif
-    if ((!HAS_VALUES || GS_EXP_SLEEP_PAIRS) && full_tiles >= GS_EXP_SLEEP_MIN_TILES) {
-        // s_sleep is a scalar instruction: it must sit behind a SCALAR branch (a branch on a vector condition only masks lanes
-        // and the wave sleeps all the same), hence the readfirstlane
-        [[maybe_unused]] const int ws = __builtin_amdgcn_readfirstlane(w);
-#if GS_EXP_SLEEP_MODE_DEFAULT == 3
-        if (ws & 1) __builtin_amdgcn_s_sleep(GS_EXP_SLEEP); else __builtin_amdgcn_s_sleep(GS_EXP_SLEEP_B);
-#elif GS_EXP_SLEEP_MODE_DEFAULT == 4
-        if (ws >= 4) __builtin_amdgcn_s_sleep(GS_EXP_SLEEP);
-#elif GS_EXP_SLEEP_MODE_DEFAULT == 1
-        if (ws & 1) __builtin_amdgcn_s_sleep(GS_EXP_SLEEP);
-#elif GS_EXP_SLEEP_MODE_DEFAULT == 0
-        __builtin_amdgcn_s_sleep(GS_EXP_SLEEP);
-#endif
-    }
-#ifndef GS_EXP_STORE_PRIO
-#define GS_EXP_STORE_PRIO 3
-#endif
-    if (!HAS_VALUES) __builtin_amdgcn_s_setprio(GS_EXP_STORE_PRIO);
-#pragma unroll
-    for (int i = 0; i < LSB_KPT; ++i) {
-        // a wave stores 1024 CONSECUTIVE slots (not every 512th 64-slot group): its 16 store instructions walk ~32
-        // neighbouring digit runs in order instead of touching ~48 runs all over the output -- keys 1.92 -> 1.81 ms,
-        // pairs 4.37 -> 4.15 ms per pass on the same box (the output pages are reused by consecutive instructions)
-        const uint32_t slot = (uint32_t)w * (WAVE * LSB_KPT) + i * WAVE + lane;
-        uint32_t k, v = 0;
-        if (HAS_VALUES) {
-            const uint2 kv = reinterpret_cast<const uint2 *>(sm.stage)[slot];
-            k = kv.x; v = kv.y;
-        } else {
-            k = sm.stage[slot];
-        }
-        const auto g = sm.gbase[digit(k)];
-        if (!TAIL || slot < valid) {
-            if constexpr (OFF64) {
-                const uint64_t dst = g + slot;
-                keys_out[dst] = tw_out(k);
-                if (HAS_VALUES) vals_out[dst] = v;
-            } else if (BIG) {
-                const uint32_t dst = g + slot;
-                keys_out[dst] = tw_out(k);
-                if (HAS_VALUES) vals_out[dst] = v;
-            } else {
-                const uint32_t off = g + slot * 4u;             // 32-bit byte offset: scalar base + vector offset
-                *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(keys_out) + off) = tw_out(k);
-                if (HAS_VALUES) *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(vals_out) + off) = v;
-            }
-        }
-    }
-    GS_PHASE(7);                                   // store issue
-#ifdef GS_EXP_DRAIN
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // experiment: the wave stays until its stores are acknowledged
-#endif
-    GS_PHASE_WAIT("vmcnt(0)");
-    GS_PHASE(8);                                   // store drain
-#ifdef GS_EXP_PHASES
-    if (tid == 0 && t < 131072u) {                 // clock calibration: shader clocks vs 100 MHz real time; who and where
-        gs_phase_buf[t * 16 + 9] = (uint32_t)(__builtin_amdgcn_s_memtime() - t0_);
-        gs_phase_buf[t * 16 + 10] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - r0_);
-        gs_phase_buf[t * 16 + 11] = (uint32_t)r0_;
-        gs_phase_buf[t * 16 + 12] = blockIdx.x;
-        gs_phase_buf[t * 16 + 13] = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_ID
-        gs_phase_buf[t * 16 + 14] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // XCC_ID
-    }
-#endif
-}
+#include "gs_lsb_downsweep.inc"
 
 // The arguments the first instructions need (key count, digit position, spine row length, the key pointers) come first
 // and as plain scalars: with -mllvm -amdgpu-kernarg-preload-count they arrive in SGPRs with the wave, so the key loads
@@ -1051,6 +424,7 @@ static inline uint32_t pipe_min_tiles()
     return v;
 }
 
+bool lsb_pipe_enabled() { return pipe_enabled(); }
 static inline bool pipe_size_ok(uint64_t n) { return pipe_enabled() && lsb_num_tiles(n) >= pipe_min_tiles() && n > small_sort_capacity(false); }
 
 // the pipelined passes' block exists only in processes that asked for them (the error word always does)
@@ -1094,9 +468,11 @@ static int lsb_upsweep_next(const uint32_t *keys, uint32_t *spine, uint16_t *pre
     return (int)hipGetLastError();
 }
 
-int lsb_scan(uint32_t *spine, uint32_t *totals, uint32_t grid, hipStream_t s)
+int lsb_scan(uint32_t *spine, uint32_t *totals, uint32_t grid, hipStream_t s) { return lsb_scan_as(spine, totals, grid, s, GS_K_LSB_SCAN); }
+
+int lsb_scan_as(uint32_t *spine, uint32_t *totals, uint32_t grid, hipStream_t s, int timer_id)
 {
-    KernelTimer kt(GS_K_LSB_SCAN, s);
+    KernelTimer kt(timer_id, s);
     hipLaunchKernelGGL(lsb_scan_kernel, dim3(RADIX), dim3(SCAN_THREADS), 0, s, spine, totals, grid);
     return (int)hipGetLastError();
 }
@@ -1287,7 +663,7 @@ int gs_exp_phases(uint32_t *host_out, uint32_t blocks)
 
 size_t gs_lsb_temp_bytes(uint64_t num_items, int /*has_values*/)
 {
-    return lsb_temp_bytes(num_items) + GS_WS_SLACK;
+    return (lsb_plan_has_block(num_items) ? lsb_plan_temp_bytes(num_items) : lsb_temp_bytes(num_items)) + GS_WS_SLACK;
 }
 
 void gs_lsb_geometry(uint64_t num_items, int /*has_values*/, uint32_t *grid, uint32_t *tile, uint32_t *tiles_per_chunk)
@@ -1388,6 +764,8 @@ int gs_lsb_sort_u32(void *d_temp, size_t temp_bytes, uint32_t *d_keys[2], uint32
         *selector = fin;
         return hipSuccess;
     }
+    if (!d_vals && begin_bit == 0 && end_bit == 32 && lsb_plan_applies(num_items))   // the keys-only plan (gs_lsb_plan.hip)
+        return lsb_plan_sort(gs_ws_base(d_temp), d_keys, selector, num_items, descending, key_type, (hipStream_t)stream);
     const LsbWorkspace ws = lsb_carve(gs_ws_base(d_temp), num_items);
     const int e = lsb_run_passes(ws, num_items, begin_bit, end_bit, descending, key_type, d_vals != nullptr,
                                  (hipStream_t)stream,

@@ -111,12 +111,22 @@ PassParams lsb_make_params(uint64_t n, int shift, int bits);
 void lsb_twiddle_masks(int key_type, int descending, bool first, bool last, PassParams &p);
 int lsb_upsweep(const uint32_t *keys, uint32_t *spine, uint16_t *prefix16, const PassParams &p, hipStream_t s);
 int lsb_scan(uint32_t *spine, uint32_t *totals, uint32_t grid, hipStream_t s);
+int lsb_scan_as(uint32_t *spine, uint32_t *totals, uint32_t grid, hipStream_t s, int timer_id);   // timed under another profiling id
 int lsb_downsweep(const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, const uint32_t *spine,
                   const uint16_t *prefix16, const uint32_t *totals, const PassParams &p, hipStream_t s);
 // the downsweep of one slice (p.n < 2^31 keys) of the 64-bit pass (gs_large.hip): spine / prefix16 / totals are the slice's
 // own (lsb_upsweep + lsb_scan on it), dbase[256] the absolute u64 start of the slice's run of each digit in kout / vout
 int lsb_downsweep64(const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, const uint32_t *spine,
                     const uint16_t *prefix16, const uint32_t *totals, const uint64_t *dbase, const PassParams &p, hipStream_t s);
+
+// gs_lsb_plan.hip: the keys-only plan of gs_lsb_sort_u32 (full-width keys without values, sizes inside its window).
+// lsb_plan_has_block: the workspace of n keys carries the plan block (lsb_plan_temp_bytes instead of lsb_temp_bytes);
+// lsb_plan_applies: a keys-only sort of n keys on all 32 bits takes lsb_plan_sort.  `base` is the aligned workspace.
+bool lsb_pipe_enabled();   // GS_LSB_MODE=pipe: such processes have no plan
+bool lsb_plan_has_block(uint64_t n);
+size_t lsb_plan_temp_bytes(uint64_t n);
+bool lsb_plan_applies(uint64_t n);
+int lsb_plan_sort(char *base, uint32_t *d_keys[2], int *selector, uint64_t n, int descending, int key_type, hipStream_t s);
 
 // gs_wide.hip: digit totals of the last wide pass inside its workspace
 const uint32_t *wide_totals_ptr(void *d_temp, uint64_t n);

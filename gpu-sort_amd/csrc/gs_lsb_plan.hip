@@ -1,0 +1,468 @@
+// gs_lsb_plan.hip -- the keys-only plan of gs_lsb_sort_u32: full-width 32-bit keys without values are sorted by two
+// scatter passes and one in-LDS local sort per group of equal top 16 bits, where the data allows it, and by the four
+// passes where it does not -- decided on the device, with one fixed launch sequence.  A translation unit of its own: the
+// pass slots are new instantiations of the upsweep / downsweep code (gs_lsb_upsweep.inc, gs_lsb_downsweep.inc), and the
+// kernels of gs_lsb.hip compile exactly as they did without it.
+#include "gs_device.hpp"
+#include "gs_lsb.hpp"
+#include "gs_msb_tasks.hpp"
+#ifndef GS_PLAN_N_MIN
+#define GS_PLAN_N_MIN (1ull << 28)
+#endif
+#include <cstddef>
+#include <cstdlib>
+#include <cstring>
+#include <type_traits>
+
+namespace gs {
+
+#include "gs_lsb_upsweep.inc"
+
+#include "gs_lsb_downsweep.inc"
+
+// --------------------------------------------------------- keys-only plan --
+// A full-width keys-only sort needs no four stable scatters: equal keys are indistinguishable.  Two stable scatters on the
+// top two bytes leave 65536 groups of equal top 16 bits, each of which one local sort (gs_msb.hip) finishes on its low 16
+// bits in LDS: 24 + 8 B/key through HBM instead of 48.  That only works while every group fits the largest local sort, and
+// the sort may neither wait on the host nor change its launches with the data.  So:
+//   look      one read of the input: the exact histogram of the top 16 bits of the twiddled keys (lsb_plan_look_kernel:
+//             a table of 65536 16-bit counters in LDS per workgroup, partial tables in the alternate key buffer, which is
+//             free until the first scatter; lsb_plan_reduce_kernel sums them; lsb_plan_decide_kernel writes the PlanBlock);
+//   slots     the usual four passes, as kernels that take their digit position from the PlanBlock: shifts 16, 24, skip,
+//             skip when PLANNED, 0, 8, 16, 24 when CLASSIC (a group above the cap).  A skipped slot's blocks return at once;
+//   finish    lsb_plan_tasks_kernel turns the group table into the local sorts' task lists (nothing when CLASSIC), and the
+//             local sorts run in place over worst-case grids: with empty lists their blocks exit.
+// The buffer ping-pong is the four passes' on both routes, so the selector and the result buffer do not depend on the route.
+constexpr uint32_t PLAN_GROUPS = 65536;
+constexpr uint32_t PLAN_WORDS = PLAN_GROUPS / 2;          // 16-bit counters, two to a word: 128 KiB of LDS
+constexpr uint32_t PLAN_PLANNED = 1u, PLAN_CLASSIC = 2u;  // route word (0: no sort has run on this workspace)
+constexpr uint32_t PLAN_SKIP = 0xffffffffu;               // shift of a slot that does nothing
+constexpr int PLAN_LOOK_THREADS = 1024, PLAN_LOOK_WAVES = PLAN_LOOK_THREADS / WAVE, PLAN_LOOK_BATCH = 32;
+constexpr uint32_t PLAN_LOOK_MAX_GRID = MI355X_CUS;       // one resident workgroup per CU
+constexpr uint32_t PLAN_BLOCKS = 128, PLAN_BLOCK_WORDS = PLAN_WORDS / PLAN_BLOCKS, PLAN_BLOCK_GROUPS = PLAN_GROUPS / PLAN_BLOCKS;
+constexpr int PLAN_SORT_BITS = 16;
+constexpr int PLAN_SKEW_LANES = 8;                      // look: lanes of a wave in one group from which a batch counts as skewed
+
+struct PlanBlock {
+    // head: what gs_lsb_plan_status returns
+    uint32_t route, max_group, nonempty, tasks[MSB_NCLASS], total;
+    uint32_t shift[4];                                     // digit position of each pass slot
+    uint32_t pad[4];
+    MsbLevel level[2];                                     // [0]: the finish's task counts; [1]: read by the sample look
+    uint32_t wg_bad[PLAN_LOOK_MAX_GRID];                   // look: the workgroup's table does not add up (a counter wrapped)
+    uint32_t blk_total[PLAN_BLOCKS], blk_max[PLAN_BLOCKS], blk_nonempty[PLAN_BLOCKS];
+    uint32_t blk_class[PLAN_BLOCKS][MSB_NCLASS];           // groups per local-sort class among the block's 512 groups
+    uint32_t blk_class_base[PLAN_BLOCKS][MSB_NCLASS];      // the same, summed over the earlier blocks
+    uint32_t offsets[PLAN_GROUPS + 1];                     // exclusive scan of the group sizes
+};
+static_assert(sizeof(MsbLevel) == 64 && offsetof(PlanBlock, level) == 64, "plan block layout");
+
+__device__ __forceinline__ int plan_class_of(uint32_t size)
+{
+    return size <= msb_class_cap(0) ? 0 : size <= msb_class_cap(1) ? 1 : size <= msb_class_cap(2) ? 2 : 3;
+}
+
+// one count into the packed table; a group shared by the whole wave (constant high bytes) is one add, not 64 queued ones
+__device__ __forceinline__ void plan_add(uint32_t *tab, uint32_t g)
+{
+    const unsigned long long act = __builtin_amdgcn_ballot_w64(true);
+    const uint32_t g0 = __builtin_amdgcn_readfirstlane(g);
+    if (__builtin_amdgcn_ballot_w64(g == g0) == act) {
+        if (count_lower_mask(act) == 0) atomicAdd(&tab[g0 >> 1], (uint32_t)__popcll(act) << ((g0 & 1u) * 16u));
+    } else {
+        atomicAdd(&tab[g >> 1], 1u << ((g & 1u) * 16u));
+    }
+}
+
+// The same for a full wave of keys that looks skewed (see the look kernel): the two most likely shared groups -- that of the
+// first lane, then that of the first lane left over -- are one add each, the other lanes add for themselves.  Lanes that
+// add to the same counter in one instruction are served one after the other: with half of the keys in one group that was
+// 20-35 % of the whole sort.
+__device__ __forceinline__ void plan_add_skew(uint32_t *tab, uint32_t g, int lane)
+{
+    unsigned long long rest = ~0ull;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        if (rest == 0ull) break;
+        const int lead = __builtin_amdgcn_readfirstlane(__builtin_ctzll(rest));
+        const uint32_t g0 = (uint32_t)__builtin_amdgcn_readlane((int)g, lead);
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(g == g0) & rest;
+        if (lane == lead) atomicAdd(&tab[g0 >> 1], (uint32_t)__popcll(m) << ((g0 & 1u) * 16u));
+        rest &= ~m;
+    }
+    if ((rest >> lane) & 1ull) atomicAdd(&tab[g >> 1], 1u << ((g & 1u) * 16u));
+}
+
+// Workgroup b walks the chunks b, b + grid, ... of 16 tiles, one wave per tile, batched dword loads as in the upsweep.
+// A 16-bit counter wraps only when the workgroup saw 65536 keys of one group -- far above the cap -- and then the table no
+// longer sums to the keys counted (a wrap of the low half carries into the high half: -65535; of the high half: -65536):
+// the workgroup reports that, and the plan is CLASSIC.
+__global__ __launch_bounds__(PLAN_LOOK_THREADS) void lsb_plan_look_kernel(const uint32_t *__restrict__ keys, uint32_t *__restrict__ partial,
+                                                                          PlanBlock *__restrict__ plan, uint32_t n, int f32_in, uint32_t xor_in)
+{
+    __shared__ uint32_t tab[PLAN_WORDS];
+    __shared__ uint32_t red[2];
+    const int tid = threadIdx.x, w = wave_id(), lane = lane_id();
+    for (uint32_t i = tid; i < PLAN_WORDS; i += PLAN_LOOK_THREADS) tab[i] = 0;
+    if (tid < 2) red[tid] = 0;
+    __syncthreads();
+    const uint32_t num_tiles = n / (uint32_t)LSB_TILE + (n % (uint32_t)LSB_TILE ? 1u : 0u);
+    auto group_of = [&](uint32_t raw) { return twiddle_in(raw, f32_in, xor_in) >> 16; };
+    uint32_t counted = 0;   // wave-uniform
+    constexpr int GB = PLAN_LOOK_BATCH;
+#pragma unroll 1
+    for (uint32_t tile = blockIdx.x * PLAN_LOOK_WAVES + (uint32_t)w; tile < num_tiles; tile += gridDim.x * PLAN_LOOK_WAVES) {
+        const uint32_t lo = tile * (uint32_t)LSB_TILE;                       // < n < 2^32
+        const uint32_t len = (n - lo < (uint32_t)LSB_TILE) ? n - lo : (uint32_t)LSB_TILE;
+        const uint32_t *src = keys + lo;
+        counted += len;
+        if (len == (uint32_t)LSB_TILE) {
+#pragma unroll 1
+            for (uint32_t j = 0; j < (uint32_t)LSB_TILE; j += GB * WAVE) {
+                const uint32_t *at = src + j + lane;
+                uint32_t v[GB];
+#pragma unroll
+                for (int u = 0; u < GB; ++u) v[u] = __builtin_nontemporal_load(at + u * WAVE);
+                const uint32_t ga = group_of(v[0]), gb = group_of(v[GB / 2]);
+                // how many lanes share the first lane's group, on two keys of the batch: all of them (constant high bytes),
+                // PLAN_SKEW_LANES or more (a few heavy groups), or hardly any (the usual case: one plain add per key)
+                const unsigned long long ma = __builtin_amdgcn_ballot_w64(ga == __builtin_amdgcn_readfirstlane(ga)),
+                                         mb = __builtin_amdgcn_ballot_w64(gb == __builtin_amdgcn_readfirstlane(gb));
+                if (ma == ~0ull || mb == ~0ull) {
+#pragma unroll
+                    for (int u = 0; u < GB; ++u) plan_add(tab, group_of(v[u]));
+                } else if (__popcll(ma) >= PLAN_SKEW_LANES || __popcll(mb) >= PLAN_SKEW_LANES) {
+#pragma unroll
+                    for (int u = 0; u < GB; ++u) plan_add_skew(tab, group_of(v[u]), lane);
+                } else {
+#pragma unroll
+                    for (int u = 0; u < GB; ++u) {
+                        const uint32_t g = group_of(v[u]);
+                        atomicAdd(&tab[g >> 1], 1u << ((g & 1u) * 16u));
+                    }
+                }
+            }
+        } else {
+            // the array's ragged last tile: loads from clamped indices, guarded counts
+            const uint32_t last = len - 1u;
+#pragma unroll 1
+            for (uint32_t j = 0; j < len; j += GB * WAVE) {
+                uint32_t v[GB];
+#pragma unroll
+                for (int u = 0; u < GB; ++u) {
+                    const uint32_t idx = j + u * WAVE + lane;
+                    v[u] = src[idx < last ? idx : last];
+                }
+#pragma unroll
+                for (int u = 0; u < GB; ++u)
+                    if (j + u * WAVE + lane < len) plan_add(tab, group_of(v[u]));
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t sum = 0;
+    uint32_t *out = partial + (size_t)blockIdx.x * PLAN_WORDS;
+    for (uint32_t i = tid; i < PLAN_WORDS; i += PLAN_LOOK_THREADS) {
+        const uint32_t c = tab[i];
+        sum += (c & 0xffffu) + (c >> 16);
+        out[i] = c;
+    }
+    sum = wave_reduce_sum(sum);
+    if (lane == 0) { atomicAdd(&red[0], sum); atomicAdd(&red[1], counted); }
+    __syncthreads();
+    if (tid == 0) plan->wg_bad[blockIdx.x] = red[0] != red[1] ? 1u : 0u;
+}
+
+// Block b sums the partial tables of the groups [512 b, 512 b + 512): sizes -> block-local exclusive scan (into `offsets`),
+// the block's total, largest group, non-empty groups and groups per class.
+__global__ __launch_bounds__(RADIX) void lsb_plan_reduce_kernel(const uint32_t *__restrict__ partial, PlanBlock *__restrict__ plan, uint32_t parts)
+{
+    __shared__ uint32_t scratch[8];
+    __shared__ uint32_t red[2 + MSB_NCLASS];
+    const uint32_t tid = threadIdx.x, wi = blockIdx.x * PLAN_BLOCK_WORDS + tid;
+    if (tid < 2 + MSB_NCLASS) red[tid] = 0;
+    uint32_t c0 = 0, c1 = 0;
+#pragma unroll 8
+    for (uint32_t g = 0; g < parts; ++g) {
+        const uint32_t v = partial[(size_t)g * PLAN_WORDS + wi];
+        c0 += v & 0xffffu;
+        c1 += v >> 16;
+    }
+    uint32_t total = 0;
+    const uint32_t ex = block_exclusive_scan_256(c0 + c1, scratch, &total);   // (its barriers also cover `red`)
+    plan->offsets[2 * wi] = ex;
+    plan->offsets[2 * wi + 1] = ex + c0;
+    atomicMax(&red[0], c0 > c1 ? c0 : c1);
+    if (c0) { atomicAdd(&red[1], 1u); atomicAdd(&red[2 + plan_class_of(c0)], 1u); }
+    if (c1) { atomicAdd(&red[1], 1u); atomicAdd(&red[2 + plan_class_of(c1)], 1u); }
+    __syncthreads();
+    if (tid == 0) {
+        plan->blk_total[blockIdx.x] = total;
+        plan->blk_max[blockIdx.x] = red[0];
+        plan->blk_nonempty[blockIdx.x] = red[1];
+    }
+    if (tid < MSB_NCLASS) plan->blk_class[blockIdx.x][tid] = red[2 + tid];
+}
+
+// Every block scans the 128 block records (a few hundred words) for itself and makes its 512 offsets global; block 0 also
+// writes the decision: PLANNED if and only if no look workgroup reported a wrapped counter, the sizes add up to n and no
+// group exceeds the largest local sort.  The level records of the finish are (re)written here on every sort, so stale
+// lists of an earlier sort on the same workspace never run.
+__global__ __launch_bounds__(RADIX) void lsb_plan_decide_kernel(PlanBlock *__restrict__ plan, uint32_t n, uint32_t parts)
+{
+    __shared__ uint32_t s_base, s_total, s_max, s_nz, s_cls[MSB_NCLASS], s_clsbase[MSB_NCLASS];
+    const uint32_t tid = threadIdx.x, b = blockIdx.x;
+    if (tid == 0) {
+        uint32_t base = 0, total = 0, mx = 0, nz = 0;
+        for (uint32_t i = 0; i < PLAN_BLOCKS; ++i) {
+            if (i == b) base = total;
+            total += plan->blk_total[i];
+            const uint32_t m = plan->blk_max[i];
+            mx = m > mx ? m : mx;
+            nz += plan->blk_nonempty[i];
+        }
+        s_base = base; s_total = total; s_max = mx; s_nz = nz;
+    } else if (tid <= MSB_NCLASS) {
+        const uint32_t c = tid - 1u;
+        uint32_t base = 0, total = 0;
+        for (uint32_t i = 0; i < PLAN_BLOCKS; ++i) {
+            if (i == b) base = total;
+            total += plan->blk_class[i][c];
+        }
+        s_cls[c] = total; s_clsbase[c] = base;
+    }
+    const int any_bad = __syncthreads_or(tid < parts ? (int)plan->wg_bad[tid] : 0);
+    const uint32_t g = b * PLAN_BLOCK_GROUPS + 2u * tid;
+    plan->offsets[g] += s_base;
+    plan->offsets[g + 1] += s_base;
+    if (tid < MSB_NCLASS) plan->blk_class_base[b][tid] = s_clsbase[tid];
+    if (b == 0 && tid == 0) {
+        const bool planned = !any_bad && s_total == n && s_max <= msb_class_cap(MSB_NCLASS - 1);
+        plan->route = planned ? PLAN_PLANNED : PLAN_CLASSIC;
+        plan->max_group = s_max;
+        plan->nonempty = s_nz;
+        plan->total = s_total;
+        MsbLevel l0{}, l1{};
+        for (int c = 0; c < MSB_NCLASS; ++c) {
+            plan->tasks[c] = planned ? s_cls[c] : 0u;
+            l0.task_count[c] = planned ? s_cls[c] : 0u;
+        }
+        l0.keys = n;
+        l1.packed = planned ? (1ull << 32) : 0ull;   // "the level showed skew": the sample look runs, so tasks of few distinct values get their plan
+        plan->level[0] = l0;
+        plan->level[1] = l1;
+        for (int q = 0; q < 4; ++q) plan->shift[q] = planned ? (q < 2 ? 16u + 8u * (uint32_t)q : PLAN_SKIP) : 8u * (uint32_t)q;
+        plan->offsets[PLAN_GROUPS] = n;
+    }
+}
+
+// The finish's task lists: one task per non-empty group, in group order inside each class.  Nothing when CLASSIC.
+struct PlanLists { MsbTask *tasks[MSB_NCLASS]; uint32_t cap[MSB_NCLASS]; };
+__global__ __launch_bounds__(PLAN_BLOCK_GROUPS) void lsb_plan_tasks_kernel(const PlanBlock *__restrict__ plan, PlanLists lists)
+{
+    __shared__ uint32_t wcnt[PLAN_BLOCK_GROUPS / WAVE][MSB_NCLASS];
+    if (plan->route != PLAN_PLANNED) return;
+    const uint32_t tid = threadIdx.x, g = blockIdx.x * PLAN_BLOCK_GROUPS + tid;
+    const int w = wave_id(), lane = lane_id();
+    const uint32_t off = plan->offsets[g], size = plan->offsets[g + 1] - off;
+    const int cls = size ? plan_class_of(size) : -1;
+    uint32_t lower = 0;
+#pragma unroll
+    for (int c = 0; c < MSB_NCLASS; ++c) {
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(cls == c);
+        if (cls == c) lower = count_lower_mask(m);
+        if (lane == 0) wcnt[w][c] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (cls >= 0) {
+        uint32_t idx = plan->blk_class_base[blockIdx.x][cls] + lower;
+        for (int j = 0; j < w; ++j) idx += wcnt[j][cls];
+        if (idx < lists.cap[cls]) lists.tasks[cls][idx] = MsbTask{off, size, (uint32_t)PLAN_SORT_BITS, 0u};
+    }
+}
+
+// The pass slots: lsb_upsweep_kernel / lsb_downsweep_kernel with the digit position read from the plan (one scalar load).
+template <bool PLAIN>
+__global__ __launch_bounds__(LSB_THREADS, GS_EXP_UPS_WPE) void lsb_plan_upsweep_kernel(const uint32_t *__restrict__ keys,
+                                                                       uint32_t *__restrict__ spine, uint16_t *__restrict__ prefix16,
+                                                                       const uint32_t *__restrict__ slot_shift, PassParams p)
+{
+    __shared__ UpsweepSmem<false, false> sm;
+    const uint32_t sh = *slot_shift;
+    if (sh == PLAN_SKIP) return;
+    p.shift = sh;
+    upsweep_chunk<false, false, PLAIN>(sm, keys, chunk_of_block(blockIdx.x, p.grid), spine, prefix16, nullptr, nullptr, p, PipeParams{});
+}
+
+template <bool TAIL, int TW, bool BIG>
+__global__ __launch_bounds__(LSB_THREADS, 6) void lsb_plan_downsweep_kernel(const uint32_t *__restrict__ keys_in, uint32_t *__restrict__ keys_out,
+                                                                            const uint32_t *__restrict__ totals, const uint32_t *__restrict__ spine,
+                                                                            const uint16_t *__restrict__ prefix16,
+                                                                            const uint32_t *__restrict__ slot_shift, PassParams p)
+{
+    __shared__ __attribute__((aligned(16))) DownsweepSmem<false> sm;
+    const uint32_t sh = *slot_shift;
+    if (sh == PLAN_SKIP) return;
+    p.shift = sh;
+    const uint32_t full_tiles = p.n / (uint32_t)LSB_TILE;
+    if (!TAIL && blockIdx.x >= full_tiles) return;
+    const uint32_t t = TAIL ? full_tiles : tile_of_item_wide(blockIdx.x, full_tiles);
+    downsweep_tile<false, TAIL, TW, BIG, false>(sm, t, keys_in, keys_out, nullptr, nullptr, spine, prefix16, totals, p, nullptr, 0u, nullptr);
+}
+
+// ------------------------------------------------------------------- host --
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// GS_LSB_KEYS_PLAN=classic|auto (default auto): classic = the four passes, always.  GS_LSB_PLAN_MIN_ITEMS=<n> (tests only)
+// moves the lower end of the size window, so that small inputs reach the plan.  Both are read once per process.
+static inline bool plan_enabled()
+{
+    static const bool v = [] { const char *e = getenv("GS_LSB_KEYS_PLAN"); return !(e && strcmp(e, "classic") == 0); }();
+    return v;
+}
+// N_MAX: 65536 groups of uniform keys are binomial with mean m = n / 65536 and deviation sqrt(m); the largest of 65536 such
+// groups lies 4 to 5 deviations above the mean, so m + 6 sqrt(m) <= 17408 (m = 16620, sqrt(m) = 129) keeps uniform keys
+// PLANNED with a chance of failure below 1e-4 per sort.  Above it the look would nearly always say CLASSIC.
+constexpr uint64_t PLAN_N_MAX = (uint64_t)PLAN_GROUPS * 16620u;
+constexpr uint64_t PLAN_N_FLOOR = 65536;            // the partial tables need room in the alternate buffer: two look workgroups at least
+constexpr uint64_t PLAN_N_MIN = GS_PLAN_N_MIN;      // 2^28: the smallest measured size from which PLANNED wins by more than 5 % on uniform keys
+static inline uint64_t plan_min_items()
+{
+    static const uint64_t v = [] {
+        const char *e = getenv("GS_LSB_PLAN_MIN_ITEMS");
+        if (!e) return PLAN_N_MIN;
+        const uint64_t x = strtoull(e, nullptr, 10);
+        return x < PLAN_N_FLOOR ? PLAN_N_FLOOR : x;
+    }();
+    return v;
+}
+// sizes whose workspace carries the plan block (every size from the window's lower end up: the query stays monotone)
+static inline bool plan_has_block(uint64_t n) { return !lsb_pipe_enabled() && n >= plan_min_items(); }
+static inline bool plan_size_ok(uint64_t n) { return plan_has_block(n) && n <= PLAN_N_MAX; }
+// the lists' capacities: one task per non-empty group, and a class-c task holds more than cap(c - 1) keys
+static inline uint32_t plan_list_cap(uint64_t n, int c)
+{
+    const uint64_t m = c == 0 ? n : n / ((uint64_t)msb_class_cap(c - 1) + 1u) + 1u;
+    return (uint32_t)(m < PLAN_GROUPS ? m : PLAN_GROUPS);
+}
+static inline size_t plan_lists_bytes(uint64_t n)
+{
+    size_t b = 0;
+    for (int c = 0; c < MSB_NCLASS; ++c) b += (size_t)plan_list_cap(n, c) * sizeof(MsbTask);
+    return b;
+}
+// Layout: the plan block follows the four-pass workspace.  The task lists END where the plan block starts and reach back
+// over the spine / totals / prefix16 / pass-totals region, which is dead by the time they are written (PLANNED: the last
+// real pass is slot 2; the lists are written after slot 4); only arrays too small for that (test sizes) get extra room.
+static inline size_t plan_block_offset(uint64_t n)
+{
+    const size_t a = lsb_temp_bytes(n), b = plan_lists_bytes(n);
+    return align256(a > b ? a : b);
+}
+static inline size_t plan_temp_bytes(uint64_t n) { return plan_block_offset(n) + align256(sizeof(PlanBlock)); }
+
+template <int TW, bool BIG>
+static void launch_plan_downsweep(const uint32_t *kin, uint32_t *kout, const LsbWorkspace &ws, const uint32_t *slot_shift,
+                                  const PassParams &p, hipStream_t s)
+{
+    hipLaunchKernelGGL((lsb_plan_downsweep_kernel<false, TW, BIG>), dim3(p.ds_grid), dim3(LSB_THREADS), 0, s, kin, kout, ws.totals,
+                       ws.spine, ws.prefix16, slot_shift, p);
+}
+
+// one pass slot: upsweep, scan, downsweep (+ the partial last tile); `real`: a slot that scatters on both routes
+static int lsb_plan_slot(const uint32_t *kin, uint32_t *kout, const LsbWorkspace &ws, const uint32_t *slot_shift, const PassParams &p,
+                         bool real, hipStream_t s)
+{
+    {
+        KernelTimer kt(real ? GS_K_LSB_UPSWEEP : GS_K_OTHER, s);
+        if (!p.f32_in && !p.xor_in)
+            hipLaunchKernelGGL(lsb_plan_upsweep_kernel<true>, dim3(p.grid), dim3(LSB_THREADS), 0, s, kin, ws.spine, ws.prefix16, slot_shift, p);
+        else
+            hipLaunchKernelGGL(lsb_plan_upsweep_kernel<false>, dim3(p.grid), dim3(LSB_THREADS), 0, s, kin, ws.spine, ws.prefix16, slot_shift, p);
+    }
+    {   // (on a skipped slot the scan rescans the spine of the slot before: harmless, nothing reads it)
+        if (const int e = lsb_scan_as(ws.spine, ws.totals, p.grid, s, real ? GS_K_LSB_SCAN : GS_K_OTHER)) return e;
+    }
+    {
+        KernelTimer kt(real ? GS_K_LSB_DOWNSWEEP : GS_K_OTHER, s);
+        if (p.n >= (uint32_t)LSB_TILE) {
+            const int tw = (p.f32_in || p.f32_out) ? 2 : ((p.xor_in | p.xor_out) ? 1 : 0);
+            const bool big = p.n > (1u << 30);
+#define GS_PDS(TW_, BIG_) launch_plan_downsweep<TW_, BIG_>(kin, kout, ws, slot_shift, p, s)
+            if (big) { if (tw == 2) GS_PDS(2, true); else if (tw == 1) GS_PDS(1, true); else GS_PDS(0, true); }
+            else { if (tw == 2) GS_PDS(2, false); else if (tw == 1) GS_PDS(1, false); else GS_PDS(0, false); }
+#undef GS_PDS
+        }
+        if (p.n % (uint32_t)LSB_TILE)
+            hipLaunchKernelGGL((lsb_plan_downsweep_kernel<true, 2, true>), dim3(1), dim3(LSB_THREADS), 0, s, kin, kout, ws.totals,
+                               (const uint32_t *)nullptr, (const uint16_t *)nullptr, slot_shift, p);
+    }
+    return (int)hipGetLastError();
+}
+
+int lsb_plan_sort(char *base, uint32_t *d_keys[2], int *selector, uint64_t n, int descending, int key_type, hipStream_t s)
+{
+    const LsbWorkspace ws = lsb_carve(base, n);
+    char *lists_end = base + plan_block_offset(n);
+    PlanBlock *plan = (PlanBlock *)lists_end;
+    PlanLists lists;
+    for (int c = MSB_NCLASS - 1; c >= 0; --c) {
+        lists.cap[c] = plan_list_cap(n, c);
+        lists_end -= (size_t)lists.cap[c] * sizeof(MsbTask);
+        lists.tasks[c] = (MsbTask *)lists_end;
+    }
+    int sel = *selector, e;
+    PassParams tw{};
+    lsb_twiddle_masks(key_type, descending, true, true, tw);
+    // the look: one workgroup per CU at most, each with room for its 128 KiB table in the alternate buffer
+    const uint32_t parts = (uint32_t)(n / PLAN_WORDS < PLAN_LOOK_MAX_GRID ? n / PLAN_WORDS : PLAN_LOOK_MAX_GRID);
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(lsb_plan_look_kernel, dim3(parts), dim3(PLAN_LOOK_THREADS), 0, s, d_keys[sel], d_keys[sel ^ 1], plan, (uint32_t)n,
+                           tw.f32_in, tw.xor_in);
+        hipLaunchKernelGGL(lsb_plan_reduce_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, d_keys[sel ^ 1], plan, parts);
+        hipLaunchKernelGGL(lsb_plan_decide_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, plan, (uint32_t)n, parts);
+    }
+    if ((e = (int)hipGetLastError())) return e;
+    for (int slot = 0; slot < 4; ++slot) {
+        PassParams p = lsb_make_params(n, 0, RADIX_BITS);   // (the shift comes from the plan)
+        lsb_twiddle_masks(key_type, descending, slot == 0, slot == 3, p);
+        if ((e = lsb_plan_slot(d_keys[sel], d_keys[sel ^ 1], ws, &plan->shift[slot], p, slot < 2, s))) return e;
+        sel ^= 1;
+    }
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(lsb_plan_tasks_kernel, dim3(PLAN_BLOCKS), dim3(PLAN_BLOCK_GROUPS), 0, s, plan, lists);
+    }
+    if ((e = (int)hipGetLastError())) return e;
+    if ((e = msb_local_sorts_in_place(plan->level, lists.tasks, PLAN_GROUPS, PLAN_GROUPS, d_keys[sel], PLAN_SORT_BITS, n, tw.f32_out,
+                                      tw.xor_out, s)))
+        return e;
+    *selector = sel;
+    return hipSuccess;
+}
+
+
+bool lsb_plan_has_block(uint64_t n) { return plan_has_block(n); }
+size_t lsb_plan_temp_bytes(uint64_t n) { return plan_temp_bytes(n); }
+bool lsb_plan_applies(uint64_t n) { return plan_enabled() && plan_size_ok(n); }
+
+}  // namespace gs
+
+using namespace gs;
+
+extern "C" {
+
+int gs_lsb_plan_status(void *d_temp, uint64_t num_items, uint32_t out[8], void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (!d_temp || !out || num_items >= (1ull << 32)) return hipErrorInvalidValue;
+    memset(out, 0, 8 * sizeof(uint32_t));
+    if (!plan_enabled() || !plan_size_ok(num_items)) return hipSuccess;   // such sorts never look
+    const PlanBlock *plan = (const PlanBlock *)(gs_ws_base(d_temp) + plan_block_offset(num_items));
+    hipError_t e = hipMemcpyAsync(out, plan, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    return (int)e;
+}
+
+}  // extern "C"

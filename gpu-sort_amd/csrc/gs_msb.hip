@@ -30,6 +30,7 @@
 #include "gs_device.hpp"
 #include <new>
 #include "gs_lsb.hpp"
+#include "gs_msb_tasks.hpp"
 #include <type_traits>
 #include <vector>
 #include <cstdlib>
@@ -40,30 +41,8 @@ constexpr int MSB_THREADS = 512;
 constexpr int MSB_WAVES = MSB_THREADS / WAVE;
 constexpr int MSB_KPT = 16;
 constexpr int MSB_TILE = MSB_THREADS * MSB_KPT;    // 8192 keys per partition tile
-constexpr int MSB_NCLASS = 4;                      // local-sort size classes (reference: 7-9 configs)
 constexpr uint32_t MSB_MERGE = 3000;               // merge adjacent sub-buckets while the sum is below this
 constexpr uint32_t MSB_MAX_GRID = 16384;           // blocks per launch; kernels stride over longer lists
-// local-sort classes: threads x keys per thread = capacity 2048, 4608, 9216, 17408.  The two big
-// classes run 1024 threads so that two workgroups per CU give 32 waves.
-#ifndef GS_LS3_THREADS
-#define GS_LS3_THREADS 1024
-#define GS_LS3_KPT 17
-#endif
-#ifndef GS_LS2_THREADS
-#define GS_LS2_THREADS 512
-#define GS_LS2_KPT 18
-#endif
-#ifndef GS_LS1_THREADS
-#define GS_LS1_THREADS 512
-#define GS_LS1_KPT 9
-#endif
-#ifndef GS_LS0_THREADS
-#define GS_LS0_THREADS 512
-#define GS_LS0_KPT 4
-#endif
-__host__ __device__ constexpr int msb_class_threads(int c) { return c == 0 ? GS_LS0_THREADS : c == 1 ? GS_LS1_THREADS : c == 2 ? GS_LS2_THREADS : GS_LS3_THREADS; }
-__host__ __device__ constexpr int msb_class_kpt(int c) { return c == 0 ? GS_LS0_KPT : c == 1 ? GS_LS1_KPT : c == 2 ? GS_LS2_KPT : GS_LS3_KPT; }
-__host__ __device__ constexpr uint32_t msb_class_cap(int c) { return (uint32_t)(msb_class_kpt(c) * msb_class_threads(c)); }
 // tiles of a range of x keys; x + MSB_TILE - 1 would wrap for ranges within one tile of 2^32
 __host__ __device__ constexpr uint32_t msb_tiles_of(uint32_t x) { return x / (uint32_t)MSB_TILE + (x % (uint32_t)MSB_TILE ? 1u : 0u); }
 // pairs keep {key,value} in LDS: their 17408 class takes 139 KiB, i.e. one 1024-thread workgroup per CU (still 7 ms
@@ -76,20 +55,6 @@ __host__ __device__ constexpr int msb_num_classes(bool has_values) { return has_
 struct MsbBucket { uint32_t offset, size, tile_start, tiles; }; // a bucket still to be partitioned (output offset, keys, its tiles)
 struct MsbPiece { uint32_t lo, size, tile_start, bucket; };     // multi-GPU: a bucket arrives in one piece per source rank
 struct MsbTile { uint32_t lo, valid, bucket, pad; };            // one tile of a level: keys [lo, lo + valid)
-struct MsbTask { uint32_t offset, size, sort_bits, pad; };      // a range to finish with a local sort
-struct MsbLevel {
-    unsigned long long packed;           // hi32: buckets to partition at this level, lo32: their tiles
-    uint32_t task_count[MSB_NCLASS];     // local-sort tasks emitted by this level's classification
-    uint32_t flagged;                    // != 0: the one-pass local sort left tasks to the general kernel (a plain store:
-                                         // thousands of atomics on one word would cost a millisecond)
-    uint32_t overflow;                   // level 0's record only: != 0 once ANY device-side append of the sort was clamped by a list
-                                         // capacity (a bucket, tile or task record dropped: the result is then wrong).  "Never by
-                                         // sizing" (msb_max_*) is an argument; this word is the check.
-    unsigned long long unused1;
-    unsigned long long keys;             // level 0: the array's size (census)
-    unsigned long long unused2;
-    uint32_t census_blocks, pad;         // slots of MsbWs::census this level's classification wrote
-};
 // Census (gs_msb_census: what bench.py prices the MSB sort's algorithmic bytes with).  Every classification block sums what
 // its buckets pass on and leaves ONE record; the reader adds them up.  (Three or four global atomics per bucket on the
 // level's counters were half of the classification's time once a level had thousands of buckets: Zipf 2^30, 0.46 -> 0.25 ms.)
@@ -1979,6 +1944,21 @@ static void launch_local_sorts(const MsbWs &ws, int L, uint32_t bound, const uin
 #undef GS_LS1
 #undef GS_LS1P
 #undef GS_LSDD
+}
+
+// gs_msb_tasks.hpp: the local sorts over lists the caller wrote (the keys-only plan of the LSB sort).  Only the fields the
+// local-sort path reads are filled in: msb_task_sample_kernel and msb_local_sort_kernel use level, tasks, max_tasks and caps.
+int msb_local_sorts_in_place(MsbLevel *level, MsbTask *const tasks[MSB_NCLASS], uint32_t max_tasks, uint32_t bound, uint32_t *keys,
+                             int sort_bits, uint64_t num_items, int f32_out, uint32_t xor_out, hipStream_t s)
+{
+    MsbWs ws{};
+    ws.level = level;
+    for (int c = 0; c < MSB_NCLASS; ++c) { ws.tasks[c] = tasks[c]; ws.caps[c] = msb_class_cap(c); }
+    ws.max_tasks = max_tasks;
+    ws.tile_shift = 13u;
+    ws.key_bits = 32u;
+    launch_local_sorts<false>(ws, 0, bound, keys, keys, nullptr, nullptr, 0, 0u, f32_out, xor_out, s, sort_bits, num_items);
+    return (int)hipGetLastError();
 }
 
 // Levels 1..3 (partition on bytes 2, 1, 0 + the local sorts after each): keys travel between

@@ -85,7 +85,18 @@ size_t gs_lsb_temp_bytes(uint64_t num_items, int has_values);
  * which half holds the result on return.  d_vals == NULL sorts keys only.
  * Both halves may be overwritten.  Sorts on key bits [begin_bit, end_bit).
  * Errors: hipErrorInvalidValue for a NULL/too-small workspace, bad bit range
- * or num_items >= 2^32 (util_device.cuh:90-93 behaviour).                    */
+ * or num_items >= 2^32 (util_device.cuh:90-93 behaviour).
+ *
+ * Keys only on all 32 bits, for num_items inside a size window (DESIGN.md
+ * section 3, "keys-only plan"): the sort first reads the input once and
+ * counts the keys of each of the 65536 values of the top 16 bits.  If every
+ * such group fits the largest in-LDS local sort, two scatter passes (bits
+ * 16-23, 24-31) and one local sort per group replace the four passes; if
+ * not, the four passes run.  The decision is taken on the device: the same
+ * kernels are launched in the same order whatever the data, nothing waits on
+ * the host, the call can be captured in a graph, and the selector and the
+ * result buffer are those of the four passes.  GS_LSB_KEYS_PLAN=classic
+ * (environment, read once per process) switches the plan off.               */
 int gs_lsb_sort_u32(void *d_temp, size_t temp_bytes,
                     uint32_t *d_keys[2], uint32_t *d_vals[2], int *selector,
                     uint64_t num_items, int begin_bit, int end_bit,
@@ -135,6 +146,14 @@ int  gs_lsb_workspace_layout(void *d_temp, uint64_t num_items, uint32_t **d_spin
  * the last sort that used d_temp to *h_status after synchronising `stream` (0 = clean, also for
  * sorts that ran no pipelined pass).  Diagnostic: tests and benches read it.                      */
 int  gs_lsb_pipe_status(void *d_temp, uint64_t num_items, uint32_t *h_status, void *stream);
+/* What the keys-only plan of the last full-width keys-only gs_lsb_sort_u32 on d_temp decided, after
+ * synchronising `stream`: out[0] = route (1 = two scatters + local sorts, 2 = the four passes),
+ * out[1] = keys in the largest group of equal top 16 bits, out[2] = non-empty groups, out[3..6] =
+ * local-sort tasks per size class (zeros on route 2), out[7] = keys counted.  With a group of 65536
+ * keys or more a 16-bit counter of the look may wrap: the route is then 2, and out[1], out[2] and
+ * out[7] are those of the wrapped counters.  All zeros for sizes outside the plan's window and when
+ * the plan is switched off.  Diagnostic: tests read it.                                           */
+int  gs_lsb_plan_status(void *d_temp, uint64_t num_items, uint32_t out[8], void *stream);
 int  gs_lsb_upsweep_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in,
                         uint64_t num_items, int shift, int bits, int descending,
                         int key_type_in, void *stream);
