@@ -27,9 +27,11 @@ namespace gs {
 // the sort may neither wait on the host nor change its launches with the data.  So:
 //   look      one read of the input: the exact histogram of the top 16 bits of the twiddled keys (lsb_plan_look_kernel:
 //             a table of 65536 16-bit counters in LDS per workgroup, partial tables in the alternate key buffer, which is
-//             free until the first scatter; lsb_plan_reduce_kernel sums them; lsb_plan_decide_kernel writes the PlanBlock);
+//             free until the first scatter; lsb_plan_reduce_kernel sums them; lsb_plan_decide_kernel writes the PlanBlock).
+//             The same read counts bits 16-23 per tile and leaves the spine and prefix16 of the first PLANNED scatter;
 //   slots     the usual four passes, as kernels that take their digit position from the PlanBlock: shifts 16, 24, skip,
-//             skip when PLANNED, 0, 8, 16, 24 when CLASSIC (a group above the cap).  A skipped slot's blocks return at once;
+//             skip when PLANNED, 0, 8, 16, 24 when CLASSIC (a group above the cap).  A skipped slot's blocks return at once,
+//             and so do those of slot 1's upsweep when PLANNED: the look has done its work;
 //   finish    lsb_plan_tasks_kernel turns the group table into the local sorts' task lists (nothing when CLASSIC), and the
 //             local sorts run in place over worst-case grids: with empty lists their blocks exit.
 // The buffer ping-pong is the four passes' on both routes, so the selector and the result buffer do not depend on the route.
@@ -37,7 +39,12 @@ constexpr uint32_t PLAN_GROUPS = 65536;
 constexpr uint32_t PLAN_WORDS = PLAN_GROUPS / 2;          // 16-bit counters, two to a word: 128 KiB of LDS
 constexpr uint32_t PLAN_PLANNED = 1u, PLAN_CLASSIC = 2u;  // route word (0: no sort has run on this workspace)
 constexpr uint32_t PLAN_SKIP = 0xffffffffu;               // shift of a slot that does nothing
+// The look's wave-private digit histograms have the 32 KiB of LDS that the table leaves: one copy per wave (the upsweep's
+// four do not fit), 1024 threads = two chunks at a time.  Two packed 16-bit copies per wave were as fast and 512 threads
+// with two copies slower (profiles/fused_look_layouts.json).
 constexpr int PLAN_LOOK_THREADS = 1024, PLAN_LOOK_WAVES = PLAN_LOOK_THREADS / WAVE, PLAN_LOOK_BATCH = 32;
+constexpr uint32_t PLAN_LOOK_HALVES = PLAN_LOOK_WAVES / LSB_CHUNK;   // chunks a look workgroup counts at a time
+static_assert(PLAN_LOOK_WAVES % LSB_CHUNK == 0, "a look workgroup takes whole chunks");
 constexpr uint32_t PLAN_LOOK_MAX_GRID = MI355X_CUS;       // one resident workgroup per CU
 constexpr uint32_t PLAN_BLOCKS = 128, PLAN_BLOCK_WORDS = PLAN_WORDS / PLAN_BLOCKS, PLAN_BLOCK_GROUPS = PLAN_GROUPS / PLAN_BLOCKS;
 constexpr int PLAN_SORT_BITS = 16;
@@ -47,7 +54,7 @@ struct PlanBlock {
     // head: what gs_lsb_plan_status returns
     uint32_t route, max_group, nonempty, tasks[MSB_NCLASS], total;
     uint32_t shift[4];                                     // digit position of each pass slot
-    uint32_t pad[4];
+    uint32_t ups_skip[4];                                  // the slot's upsweep has nothing to do (the look left slot 1's counts)
     MsbLevel level[2];                                     // [0]: the finish's task counts; [1]: read by the sample look
     uint32_t wg_bad[PLAN_LOOK_MAX_GRID];                   // look: the workgroup's table does not add up (a counter wrapped)
     uint32_t blk_total[PLAN_BLOCKS], blk_max[PLAN_BLOCKS], blk_nonempty[PLAN_BLOCKS];
@@ -62,23 +69,29 @@ __device__ __forceinline__ int plan_class_of(uint32_t size)
     return size <= msb_class_cap(0) ? 0 : size <= msb_class_cap(1) ? 1 : size <= msb_class_cap(2) ? 2 : 3;
 }
 
-// one count into the packed table; a group shared by the whole wave (constant high bytes) is one add, not 64 queued ones
-__device__ __forceinline__ void plan_add(uint32_t *tab, uint32_t g)
+// The look counts two things per key: its group (top 16 bits, into the workgroup's packed table) and the digit of the first
+// PLANNED scatter, bits 16-23 = group & 0xff, into a histogram private to the wave (= the tile).  One count of each; a group
+// shared by the whole wave (constant high bytes) is one add to each, not 64 queued ones.
+__device__ __forceinline__ void look_add(uint32_t *tab, uint32_t *my, uint32_t g)
 {
     const unsigned long long act = __builtin_amdgcn_ballot_w64(true);
     const uint32_t g0 = __builtin_amdgcn_readfirstlane(g);
     if (__builtin_amdgcn_ballot_w64(g == g0) == act) {
-        if (count_lower_mask(act) == 0) atomicAdd(&tab[g0 >> 1], (uint32_t)__popcll(act) << ((g0 & 1u) * 16u));
+        if (count_lower_mask(act) == 0) {
+            atomicAdd(&tab[g0 >> 1], (uint32_t)__popcll(act) << ((g0 & 1u) * 16u));
+            atomicAdd(&my[g0 & 0xffu], (uint32_t)__popcll(act));
+        }
     } else {
         atomicAdd(&tab[g >> 1], 1u << ((g & 1u) * 16u));
+        atomicAdd(&my[g & 0xffu], 1u);
     }
 }
 
 // The same for a full wave of keys that looks skewed (see the look kernel): the two most likely shared groups -- that of the
 // first lane, then that of the first lane left over -- are one add each, the other lanes add for themselves.  Lanes that
 // add to the same counter in one instruction are served one after the other: with half of the keys in one group that was
-// 20-35 % of the whole sort.
-__device__ __forceinline__ void plan_add_skew(uint32_t *tab, uint32_t g, int lane)
+// 20-35 % of the whole sort.  Lanes that share a group share its digit.
+__device__ __forceinline__ void look_add_skew(uint32_t *tab, uint32_t *my, uint32_t g, int lane)
 {
     unsigned long long rest = ~0ull;
 #pragma unroll
@@ -87,31 +100,64 @@ __device__ __forceinline__ void plan_add_skew(uint32_t *tab, uint32_t g, int lan
         const int lead = __builtin_amdgcn_readfirstlane(__builtin_ctzll(rest));
         const uint32_t g0 = (uint32_t)__builtin_amdgcn_readlane((int)g, lead);
         const unsigned long long m = __builtin_amdgcn_ballot_w64(g == g0) & rest;
-        if (lane == lead) atomicAdd(&tab[g0 >> 1], (uint32_t)__popcll(m) << ((g0 & 1u) * 16u));
+        if (lane == lead) {
+            atomicAdd(&tab[g0 >> 1], (uint32_t)__popcll(m) << ((g0 & 1u) * 16u));
+            atomicAdd(&my[g0 & 0xffu], (uint32_t)__popcll(m));
+        }
         rest &= ~m;
     }
-    if ((rest >> lane) & 1ull) atomicAdd(&tab[g >> 1], 1u << ((g & 1u) * 16u));
+    if ((rest >> lane) & 1ull) {
+        atomicAdd(&tab[g >> 1], 1u << ((g & 1u) * 16u));
+        atomicAdd(&my[g & 0xffu], 1u);
+    }
 }
 
-// Workgroup b walks the chunks b, b + grid, ... of 16 tiles, one wave per tile, batched dword loads as in the upsweep.
-// A 16-bit counter wraps only when the workgroup saw 65536 keys of one group -- far above the cap -- and then the table no
-// longer sums to the keys counted (a wrap of the low half carries into the high half: -65535; of the high half: -65536):
-// the workgroup reports that, and the plan is CLASSIC.
-__global__ __launch_bounds__(PLAN_LOOK_THREADS) void lsb_plan_look_kernel(const uint32_t *__restrict__ keys, uint32_t *__restrict__ partial,
-                                                                          PlanBlock *__restrict__ plan, uint32_t n, int f32_in, uint32_t xor_in)
+// Look workgroup b -> the position of its first unit of PLAN_LOOK_HALVES chunks: under round-robin dispatch the workgroups
+// of one XCD take consecutive units, so the chunk totals that share a 64-byte line of a spine row meet in one L2 (as
+// chunk_of_block does for the upsweep).  Speed only: any bijection gives the same result.
+__device__ __forceinline__ uint32_t look_slot_of_block(uint32_t b, uint32_t grid)
 {
-    __shared__ uint32_t tab[PLAN_WORDS];
-    __shared__ uint32_t red[2];
+    if (grid % MI355X_XCDS) return b;
+    return (b % MI355X_XCDS) * (grid / MI355X_XCDS) + b / MI355X_XCDS;
+}
+
+// The fused look.  The unit of work is the upsweep's chunk of LSB_CHUNK tiles, one wave per tile; a workgroup of 16 waves
+// takes PLAN_LOOK_HALVES = 2 neighbouring chunks at a time and walks the units slot, slot + grid, ...  Besides the group
+// table it leaves, per chunk, exactly what upsweep_chunk<false, false> writes for shift 16, bits 8 (the first scatter of the
+// PLANNED route): prefix16[tile][d] = keys of digit d in the earlier tiles of the chunk, spine[d][chunk] = the chunk's total.
+// So the slot-1 upsweep has nothing to do when the plan is PLANNED; when CLASSIC it runs at shift 0 and overwrites both.
+// A 16-bit counter of the table wraps only when the workgroup saw 65536 keys of one group -- far above the cap -- and then
+// the table no longer sums to the keys counted (a wrap of the low half carries into the high half: -65535; of the high
+// half: -65536): the workgroup reports that, and the plan is CLASSIC.
+struct LookSmem {
+    uint32_t tab[PLAN_WORDS];
+    uint32_t hist[PLAN_LOOK_WAVES][RADIX + 1];   // (rows padded as in UpsweepSmem)
+    uint32_t red[2];
+};
+static_assert(sizeof(LookSmem) <= 160 * 1024, "the look's LDS");
+
+__global__ __launch_bounds__(PLAN_LOOK_THREADS) void lsb_plan_look_kernel(const uint32_t *__restrict__ keys, uint32_t *__restrict__ partial,
+                                                                          PlanBlock *__restrict__ plan, uint32_t *__restrict__ spine,
+                                                                          uint16_t *__restrict__ prefix16, uint32_t n, uint32_t chunks,
+                                                                          int f32_in, uint32_t xor_in)
+{
+    __shared__ LookSmem sm;
+    uint32_t *tab = sm.tab;
     const int tid = threadIdx.x, w = wave_id(), lane = lane_id();
     for (uint32_t i = tid; i < PLAN_WORDS; i += PLAN_LOOK_THREADS) tab[i] = 0;
-    if (tid < 2) red[tid] = 0;
+    for (uint32_t i = tid; i < sizeof(sm.hist) / sizeof(uint32_t); i += PLAN_LOOK_THREADS) (&sm.hist[0][0])[i] = 0;
+    if (tid < 2) sm.red[tid] = 0;
     __syncthreads();
+    uint32_t *my = sm.hist[w];
     const uint32_t num_tiles = n / (uint32_t)LSB_TILE + (n % (uint32_t)LSB_TILE ? 1u : 0u);
+    const uint32_t units = (chunks + PLAN_LOOK_HALVES - 1u) / PLAN_LOOK_HALVES;
     auto group_of = [&](uint32_t raw) { return twiddle_in(raw, f32_in, xor_in) >> 16; };
     uint32_t counted = 0;   // wave-uniform
     constexpr int GB = PLAN_LOOK_BATCH;
 #pragma unroll 1
-    for (uint32_t tile = blockIdx.x * PLAN_LOOK_WAVES + (uint32_t)w; tile < num_tiles; tile += gridDim.x * PLAN_LOOK_WAVES) {
+    for (uint32_t unit = look_slot_of_block(blockIdx.x, gridDim.x); unit < units; unit += gridDim.x) {
+        const uint32_t tile = unit * (uint32_t)PLAN_LOOK_WAVES + (uint32_t)w;      // wave w: tile w % 8 of the unit's chunk w / 8
+        if (tile < num_tiles) {
         const uint32_t lo = tile * (uint32_t)LSB_TILE;                       // < n < 2^32
         const uint32_t len = (n - lo < (uint32_t)LSB_TILE) ? n - lo : (uint32_t)LSB_TILE;
         const uint32_t *src = keys + lo;
@@ -125,20 +171,21 @@ __global__ __launch_bounds__(PLAN_LOOK_THREADS) void lsb_plan_look_kernel(const 
                 for (int u = 0; u < GB; ++u) v[u] = __builtin_nontemporal_load(at + u * WAVE);
                 const uint32_t ga = group_of(v[0]), gb = group_of(v[GB / 2]);
                 // how many lanes share the first lane's group, on two keys of the batch: all of them (constant high bytes),
-                // PLAN_SKEW_LANES or more (a few heavy groups), or hardly any (the usual case: one plain add per key)
+                // PLAN_SKEW_LANES or more (a few heavy groups), or hardly any (the usual case: two plain adds per key)
                 const unsigned long long ma = __builtin_amdgcn_ballot_w64(ga == __builtin_amdgcn_readfirstlane(ga)),
                                          mb = __builtin_amdgcn_ballot_w64(gb == __builtin_amdgcn_readfirstlane(gb));
                 if (ma == ~0ull || mb == ~0ull) {
 #pragma unroll
-                    for (int u = 0; u < GB; ++u) plan_add(tab, group_of(v[u]));
+                    for (int u = 0; u < GB; ++u) look_add(tab, my, group_of(v[u]));
                 } else if (__popcll(ma) >= PLAN_SKEW_LANES || __popcll(mb) >= PLAN_SKEW_LANES) {
 #pragma unroll
-                    for (int u = 0; u < GB; ++u) plan_add_skew(tab, group_of(v[u]), lane);
+                    for (int u = 0; u < GB; ++u) look_add_skew(tab, my, group_of(v[u]), lane);
                 } else {
 #pragma unroll
                     for (int u = 0; u < GB; ++u) {
                         const uint32_t g = group_of(v[u]);
                         atomicAdd(&tab[g >> 1], 1u << ((g & 1u) * 16u));
+                        atomicAdd(&my[g & 0xffu], 1u);
                     }
                 }
             }
@@ -155,11 +202,27 @@ __global__ __launch_bounds__(PLAN_LOOK_THREADS) void lsb_plan_look_kernel(const 
                 }
 #pragma unroll
                 for (int u = 0; u < GB; ++u)
-                    if (j + u * WAVE + lane < len) plan_add(tab, group_of(v[u]));
+                    if (j + u * WAVE + lane < len) look_add(tab, my, group_of(v[u]));
             }
         }
+        }
+        __syncthreads();
+        // the unit's results, one thread per chunk and digit; the thread clears the counters it has read
+        if (tid < (int)PLAN_LOOK_HALVES * RADIX) {
+            const uint32_t half = (uint32_t)tid / RADIX, d = (uint32_t)tid % RADIX, chunk = unit * PLAN_LOOK_HALVES + half;
+            uint32_t run = 0;
+#pragma unroll
+            for (int j = 0; j < LSB_CHUNK; ++j) {
+                const uint32_t t = chunk * LSB_CHUNK + (uint32_t)j;
+                if (t < num_tiles) prefix16[(size_t)t * RADIX + d] = (uint16_t)run;
+                uint32_t *c = &sm.hist[half * LSB_CHUNK + j][d];
+                run += *c;
+                *c = 0;
+            }
+            if (chunk < chunks) spine[d * chunks + chunk] = run;
+        }
+        __syncthreads();
     }
-    __syncthreads();
     uint32_t sum = 0;
     uint32_t *out = partial + (size_t)blockIdx.x * PLAN_WORDS;
     for (uint32_t i = tid; i < PLAN_WORDS; i += PLAN_LOOK_THREADS) {
@@ -168,9 +231,9 @@ __global__ __launch_bounds__(PLAN_LOOK_THREADS) void lsb_plan_look_kernel(const 
         out[i] = c;
     }
     sum = wave_reduce_sum(sum);
-    if (lane == 0) { atomicAdd(&red[0], sum); atomicAdd(&red[1], counted); }
+    if (lane == 0) { atomicAdd(&sm.red[0], sum); atomicAdd(&sm.red[1], counted); }
     __syncthreads();
-    if (tid == 0) plan->wg_bad[blockIdx.x] = red[0] != red[1] ? 1u : 0u;
+    if (tid == 0) plan->wg_bad[blockIdx.x] = sm.red[0] != sm.red[1] ? 1u : 0u;
 }
 
 // Block b sums the partial tables of the groups [512 b, 512 b + 512): sizes -> block-local exclusive scan (into `offsets`),
@@ -251,7 +314,10 @@ __global__ __launch_bounds__(RADIX) void lsb_plan_decide_kernel(PlanBlock *__res
         l1.packed = planned ? (1ull << 32) : 0ull;   // "the level showed skew": the sample look runs, so tasks of few distinct values get their plan
         plan->level[0] = l0;
         plan->level[1] = l1;
-        for (int q = 0; q < 4; ++q) plan->shift[q] = planned ? (q < 2 ? 16u + 8u * (uint32_t)q : PLAN_SKIP) : 8u * (uint32_t)q;
+        for (int q = 0; q < 4; ++q) {
+            plan->shift[q] = planned ? (q < 2 ? 16u + 8u * (uint32_t)q : PLAN_SKIP) : 8u * (uint32_t)q;
+            plan->ups_skip[q] = planned && q != 1 ? 1u : 0u;   // PLANNED: slot 1 scans and scatters on the look's counts
+        }
         plan->offsets[PLAN_GROUPS] = n;
     }
 }
@@ -282,14 +348,16 @@ __global__ __launch_bounds__(PLAN_BLOCK_GROUPS) void lsb_plan_tasks_kernel(const
 }
 
 // The pass slots: lsb_upsweep_kernel / lsb_downsweep_kernel with the digit position read from the plan (one scalar load).
+// The upsweep also returns when the plan says that the look has already left this slot's spine and prefix16.
 template <bool PLAIN>
 __global__ __launch_bounds__(LSB_THREADS, GS_EXP_UPS_WPE) void lsb_plan_upsweep_kernel(const uint32_t *__restrict__ keys,
                                                                        uint32_t *__restrict__ spine, uint16_t *__restrict__ prefix16,
-                                                                       const uint32_t *__restrict__ slot_shift, PassParams p)
+                                                                       const uint32_t *__restrict__ slot_shift,
+                                                                       const uint32_t *__restrict__ slot_ups_skip, PassParams p)
 {
     __shared__ UpsweepSmem<false, false> sm;
     const uint32_t sh = *slot_shift;
-    if (sh == PLAN_SKIP) return;
+    if (sh == PLAN_SKIP || *slot_ups_skip) return;
     p.shift = sh;
     upsweep_chunk<false, false, PLAIN>(sm, keys, chunk_of_block(blockIdx.x, p.grid), spine, prefix16, nullptr, nullptr, p, PipeParams{});
 }
@@ -369,16 +437,19 @@ static void launch_plan_downsweep(const uint32_t *kin, uint32_t *kout, const Lsb
                        ws.spine, ws.prefix16, slot_shift, p);
 }
 
-// one pass slot: upsweep, scan, downsweep (+ the partial last tile); `real`: a slot that scatters on both routes
-static int lsb_plan_slot(const uint32_t *kin, uint32_t *kout, const LsbWorkspace &ws, const uint32_t *slot_shift, const PassParams &p,
-                         bool real, hipStream_t s)
+// one pass slot: upsweep, scan, downsweep (+ the partial last tile); `real`: a slot that scatters on both routes;
+// `ups_real`: its upsweep counts on both routes too (slot 1's does so only when CLASSIC, which the host does not know)
+static int lsb_plan_slot(const uint32_t *kin, uint32_t *kout, const LsbWorkspace &ws, const uint32_t *slot_shift,
+                         const uint32_t *slot_ups_skip, const PassParams &p, bool real, bool ups_real, hipStream_t s)
 {
     {
-        KernelTimer kt(real ? GS_K_LSB_UPSWEEP : GS_K_OTHER, s);
+        KernelTimer kt(ups_real ? GS_K_LSB_UPSWEEP : GS_K_OTHER, s);
         if (!p.f32_in && !p.xor_in)
-            hipLaunchKernelGGL(lsb_plan_upsweep_kernel<true>, dim3(p.grid), dim3(LSB_THREADS), 0, s, kin, ws.spine, ws.prefix16, slot_shift, p);
+            hipLaunchKernelGGL(lsb_plan_upsweep_kernel<true>, dim3(p.grid), dim3(LSB_THREADS), 0, s, kin, ws.spine, ws.prefix16, slot_shift,
+                               slot_ups_skip, p);
         else
-            hipLaunchKernelGGL(lsb_plan_upsweep_kernel<false>, dim3(p.grid), dim3(LSB_THREADS), 0, s, kin, ws.spine, ws.prefix16, slot_shift, p);
+            hipLaunchKernelGGL(lsb_plan_upsweep_kernel<false>, dim3(p.grid), dim3(LSB_THREADS), 0, s, kin, ws.spine, ws.prefix16, slot_shift,
+                               slot_ups_skip, p);
     }
     {   // (on a skipped slot the scan rescans the spine of the slot before: harmless, nothing reads it)
         if (const int e = lsb_scan_as(ws.spine, ws.totals, p.grid, s, real ? GS_K_LSB_SCAN : GS_K_OTHER)) return e;
@@ -400,6 +471,21 @@ static int lsb_plan_slot(const uint32_t *kin, uint32_t *kout, const LsbWorkspace
     return (int)hipGetLastError();
 }
 
+// the look: one workgroup per CU at most, each with room for its 128 KiB table in the alternate buffer; its spine and
+// prefix16 are those of a pass at shift 16 (lsb_make_params' grid)
+static int lsb_plan_look(const uint32_t *keys, uint32_t *alt, const LsbWorkspace &ws, PlanBlock *plan, uint64_t n, const PassParams &tw,
+                         hipStream_t s)
+{
+    const uint32_t parts = (uint32_t)(n / PLAN_WORDS < PLAN_LOOK_MAX_GRID ? n / PLAN_WORDS : PLAN_LOOK_MAX_GRID);
+    const uint32_t chunks = lsb_make_params(n, 16, RADIX_BITS).grid;
+    KernelTimer kt(GS_K_OTHER, s);
+    hipLaunchKernelGGL(lsb_plan_look_kernel, dim3(parts), dim3(PLAN_LOOK_THREADS), 0, s, keys, alt, plan, ws.spine, ws.prefix16, (uint32_t)n,
+                       chunks, tw.f32_in, tw.xor_in);
+    hipLaunchKernelGGL(lsb_plan_reduce_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, alt, plan, parts);
+    hipLaunchKernelGGL(lsb_plan_decide_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, plan, (uint32_t)n, parts);
+    return (int)hipGetLastError();
+}
+
 int lsb_plan_sort(char *base, uint32_t *d_keys[2], int *selector, uint64_t n, int descending, int key_type, hipStream_t s)
 {
     const LsbWorkspace ws = lsb_carve(base, n);
@@ -414,20 +500,11 @@ int lsb_plan_sort(char *base, uint32_t *d_keys[2], int *selector, uint64_t n, in
     int sel = *selector, e;
     PassParams tw{};
     lsb_twiddle_masks(key_type, descending, true, true, tw);
-    // the look: one workgroup per CU at most, each with room for its 128 KiB table in the alternate buffer
-    const uint32_t parts = (uint32_t)(n / PLAN_WORDS < PLAN_LOOK_MAX_GRID ? n / PLAN_WORDS : PLAN_LOOK_MAX_GRID);
-    {
-        KernelTimer kt(GS_K_OTHER, s);
-        hipLaunchKernelGGL(lsb_plan_look_kernel, dim3(parts), dim3(PLAN_LOOK_THREADS), 0, s, d_keys[sel], d_keys[sel ^ 1], plan, (uint32_t)n,
-                           tw.f32_in, tw.xor_in);
-        hipLaunchKernelGGL(lsb_plan_reduce_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, d_keys[sel ^ 1], plan, parts);
-        hipLaunchKernelGGL(lsb_plan_decide_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, plan, (uint32_t)n, parts);
-    }
-    if ((e = (int)hipGetLastError())) return e;
+    if ((e = lsb_plan_look(d_keys[sel], d_keys[sel ^ 1], ws, plan, n, tw, s))) return e;
     for (int slot = 0; slot < 4; ++slot) {
         PassParams p = lsb_make_params(n, 0, RADIX_BITS);   // (the shift comes from the plan)
         lsb_twiddle_masks(key_type, descending, slot == 0, slot == 3, p);
-        if ((e = lsb_plan_slot(d_keys[sel], d_keys[sel ^ 1], ws, &plan->shift[slot], p, slot < 2, s))) return e;
+        if ((e = lsb_plan_slot(d_keys[sel], d_keys[sel ^ 1], ws, &plan->shift[slot], &plan->ups_skip[slot], p, slot < 2, slot == 1, s))) return e;
         sel ^= 1;
     }
     {
@@ -463,6 +540,30 @@ int gs_lsb_plan_status(void *d_temp, uint64_t num_items, uint32_t out[8], void *
     hipError_t e = hipMemcpyAsync(out, plan, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     return (int)e;
+}
+
+int gs_lsb_plan_look_only(void *d_temp, const void *d_keys, void *d_alt, uint64_t num_items, int key_type, int descending, void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (!d_temp || !d_keys || !d_alt || num_items >= (1ull << 32)) return hipErrorInvalidValue;
+    if (!plan_enabled() || !plan_size_ok(num_items)) return hipErrorInvalidValue;   // such sorts never look
+    char *base = gs_ws_base(d_temp);
+    PassParams tw{};
+    lsb_twiddle_masks(key_type, descending, true, true, tw);
+    return lsb_plan_look((const uint32_t *)d_keys, (uint32_t *)d_alt, lsb_carve(base, num_items), (PlanBlock *)(base + plan_block_offset(num_items)),
+                         num_items, tw, (hipStream_t)stream);
+}
+
+int gs_lsb_plan_layout(uint64_t num_items, uint64_t out[4])
+{
+    if (!out || num_items >= (1ull << 32) || !plan_enabled() || !plan_size_ok(num_items)) return hipErrorInvalidValue;
+    char *base = (char *)(uintptr_t)GS_WS_ALIGN;   // (any aligned address: only the differences are used)
+    const LsbWorkspace ws = lsb_carve(base, num_items);
+    out[0] = (uint64_t)((char *)ws.spine - base);
+    out[1] = (uint64_t)((char *)ws.prefix16 - base);
+    out[2] = plan_block_offset(num_items);
+    out[3] = lsb_make_params(num_items, 16, RADIX_BITS).grid;
+    return hipSuccess;
 }
 
 }  // extern "C"

@@ -154,6 +154,18 @@ int  gs_lsb_pipe_status(void *d_temp, uint64_t num_items, uint32_t *h_status, vo
  * out[7] are those of the wrapped counters.  All zeros for sizes outside the plan's window and when
  * the plan is switched off.  Diagnostic: tests read it.                                           */
 int  gs_lsb_plan_status(void *d_temp, uint64_t num_items, uint32_t out[8], void *stream);
+/* Test hooks of the keys-only plan.  gs_lsb_plan_look_only runs the look alone (the fused look, the
+ * reduction of its tables and the decision) on a workspace of gs_lsb_temp_bytes(num_items) bytes and
+ * returns without sorting: d_keys is read, the first num_items * 4 bytes of d_alt are scratch.  What
+ * it leaves -- the spine and prefix16 of a pass on bits 16-23 and the plan block -- lies at the byte
+ * offsets gs_lsb_plan_layout reports, counted from d_temp rounded up to 256 bytes: out[0] = spine
+ * (u32 [256][grid]), out[1] = prefix16 (u16 [tiles][256]), out[2] = plan block (its first eight words
+ * are gs_lsb_plan_status', the next four the digit positions of the pass slots, the next four the
+ * flags "this slot's upsweep has nothing to do"), out[3] = grid.  Both return hipErrorInvalidValue for
+ * null pointers and for sizes outside the plan's window (or when the plan is switched off).         */
+int  gs_lsb_plan_look_only(void *d_temp, const void *d_keys, void *d_alt, uint64_t num_items,
+                           int key_type, int descending, void *stream);
+int  gs_lsb_plan_layout(uint64_t num_items, uint64_t out[4]);
 int  gs_lsb_upsweep_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in,
                         uint64_t num_items, int shift, int bits, int descending,
                         int key_type_in, void *stream);
