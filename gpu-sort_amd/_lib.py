@@ -20,6 +20,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 GS_KEY_U32, GS_KEY_I32, GS_KEY_F32, GS_KEY_U64, GS_KEY_I64, GS_KEY_F64 = 0, 1, 2, 3, 4, 5
 GS_KEY_U8, GS_KEY_I8, GS_KEY_U16, GS_KEY_I16 = 6, 7, 8, 9
+GS_KEY_F16, GS_KEY_BF16, GS_KEY_F8 = 10, 11, 12
 GS_GEN_UNIFORM, GS_GEN_ZIPF, GS_GEN_ENTROPY_AND, GS_GEN_ENUMERATED = 0, 1, 2, 3
 
 u64, i32, vp, sz = C.c_uint64, C.c_int, C.c_void_p, C.c_size_t

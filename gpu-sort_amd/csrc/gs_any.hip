@@ -19,8 +19,8 @@ static inline size_t any_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int any_key_bytes(int key_type)
 {
     switch (key_type) {
-    case GS_KEY_U8: case GS_KEY_I8: return 1;
-    case GS_KEY_U16: case GS_KEY_I16: return 2;
+    case GS_KEY_U8: case GS_KEY_I8: case GS_KEY_F8: return 1;
+    case GS_KEY_U16: case GS_KEY_I16: case GS_KEY_F16: case GS_KEY_BF16: return 2;
     case GS_KEY_U32: case GS_KEY_I32: case GS_KEY_F32: return 4;
     case GS_KEY_U64: case GS_KEY_I64: case GS_KEY_F64: return 8;
     default: return 0;
@@ -39,6 +39,8 @@ __device__ __forceinline__ uint32_t any_load_sortkey(const void *keys, uint64_t 
     else if (key_type == GS_KEY_I16) k ^= 0x8000u;
     else if (key_type == GS_KEY_I32) k ^= 0x80000000u;
     else if (key_type == GS_KEY_F32) k = twiddle_in(k, 1, 0u);
+    else if (key_type == GS_KEY_F8) k = float_flip<8>(k) ^ 0x80u;          // twiddle_in's float map at the key's own width
+    else if (key_type == GS_KEY_F16 || key_type == GS_KEY_BF16) k = float_flip<16>(k) ^ 0x8000u;
     return k;
 }
 
@@ -73,6 +75,8 @@ __global__ __launch_bounds__(256) void any_narrow_kernel(const uint32_t *__restr
         uint32_t k = sortkeys[i];
         if (key_type == GS_KEY_I8) k ^= 0x80u;
         else if (key_type == GS_KEY_I16) k ^= 0x8000u;
+        else if (key_type == GS_KEY_F8) k = float_flip<8>(k ^ 0x80u);          // (float_flip leaves the sign bit alone: its own inverse)
+        else if (key_type == GS_KEY_F16 || key_type == GS_KEY_BF16) k = float_flip<16>(k ^ 0x8000u);
         if (KB == 1) reinterpret_cast<uint8_t *>(keys_out)[i] = (uint8_t)k;
         else reinterpret_cast<uint16_t *>(keys_out)[i] = (uint16_t)k;
     }

@@ -30,6 +30,16 @@ __device__ __forceinline__ uint32_t twiddle_out(uint32_t k, int f32, uint32_t x)
     return k;
 }
 
+// The float term of the 8- and 16-bit float categories (GS_KEY_F8 / F16 / BF16), at the key's own width W: a set sign bit
+// flips the magnitude bits.  With the sign flip itself in the xor mask -- the one a signed integer of that width takes --
+// this is twiddle_in's f32 map at width W, and it is its own inverse (it leaves the sign bit alone).  W = 0: no float
+// term, the identity, so a kernel shared with the integer types keeps their code.
+template <int W> __device__ __forceinline__ uint32_t float_flip(uint32_t k)
+{
+    if constexpr (W == 0) return k;
+    else return k ^ ((uint32_t)((int32_t)(k << (32 - W)) >> 31) & ((1u << (W - 1)) - 1u));
+}
+
 __device__ __forceinline__ uint32_t count_lower_mask(unsigned long long m)
 {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));

@@ -2270,6 +2270,7 @@ __global__ __launch_bounds__(256) void seg_wave_sort_kernel(MsbWs ws, const uint
                                                             uint32_t xor_in, int f32_out, uint32_t xor_out)
 {
     typedef uint32_t K;
+    constexpr int FW = 0;
 #include "gs_seg_wave_body.inc"
 }
 
@@ -2283,20 +2284,23 @@ __global__ __launch_bounds__(256) void seg_wave4_sort_kernel(MsbWs ws, const uin
                                                              uint32_t xor_in, int f32_out, uint32_t xor_out)
 {
     typedef uint32_t K;
+    constexpr int FW = 0;
 #include "gs_seg_wave4_body.inc"
 }
 
 // The same two kernels for 8- and 16-bit keys (gs_segmented_sort_narrow): K is the element type in memory, the keys live in
 // registers as u32 as above; only the loads and the stores differ.  A store is one element wide, so no byte outside the
-// segment is written.
-template <bool HAS_VALUES, int WKPT, typename K>
+// segment is written.  FW = 8 * sizeof(K) for the float categories (GS_KEY_F8 / F16 / BF16), 0 for the integer ones: the float
+// term goes in front of twiddle_in, whose xor mask carries the sign flip, so the pads (all ones, set after the map) stay the
+// largest image in both directions.
+template <bool HAS_VALUES, int WKPT, typename K, int FW>
 __global__ __launch_bounds__(256) void seg_wave_sort_narrow_kernel(MsbWs ws, const K *__restrict__ src_k, K *__restrict__ dst_k,
                                                                    const uint32_t *__restrict__ src_v, uint32_t *__restrict__ dst_v, int f32_in,
                                                                    uint32_t xor_in, int f32_out, uint32_t xor_out)
 {
 #include "gs_seg_wave_body.inc"
 }
-template <bool HAS_VALUES, typename K>
+template <bool HAS_VALUES, typename K, int FW>
 __global__ __launch_bounds__(256) void seg_wave4_sort_narrow_kernel(MsbWs ws, const K *__restrict__ src_k, K *__restrict__ dst_k,
                                                                     const uint32_t *__restrict__ src_v, uint32_t *__restrict__ dst_v, int f32_in,
                                                                     uint32_t xor_in, int f32_out, uint32_t xor_out)
@@ -3418,8 +3422,8 @@ int gs_segmented_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys[2], voi
 static inline int sn_key_bytes(int key_type)
 {
     switch (key_type) {
-    case GS_KEY_U8: case GS_KEY_I8: return 1;
-    case GS_KEY_U16: case GS_KEY_I16: return 2;
+    case GS_KEY_U8: case GS_KEY_I8: case GS_KEY_F8: return 1;
+    case GS_KEY_U16: case GS_KEY_I16: case GS_KEY_F16: case GS_KEY_BF16: return 2;
     default: return 0;
     }
 }
@@ -3454,9 +3458,12 @@ int gs_segmented_sort_narrow(void *d_temp, size_t temp_bytes, void *d_keys[2], v
     if (((uintptr_t)d_keys[0] | (uintptr_t)d_keys[1]) & (uintptr_t)(kb - 1)) return hipErrorInvalidValue;
     if (d_vals && (((uintptr_t)d_vals[0] | (uintptr_t)d_vals[1]) & (uintptr_t)(val_bytes - 1))) return hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-    const uint32_t sign = key_type == GS_KEY_I8 ? 0x80u : key_type == GS_KEY_I16 ? 0x8000u : 0u;
-#define GS_SN(KB, V) return seg_narrow_sort<KB, V>(gs_ws_base(d_temp), d_keys, d_vals, selector, num_items, num_segments, d_begin_offsets, \
-                                                   d_end_offsets, begin_bit, end_bit, descending, sign, s)
+    const bool fk = key_type == GS_KEY_F8 || key_type == GS_KEY_F16 || key_type == GS_KEY_BF16;   // the sign flip of I8 / I16 plus the float term
+    const uint32_t sign = (key_type == GS_KEY_I8 || key_type == GS_KEY_F8) ? 0x80u : (key_type == GS_KEY_I16 || fk) ? 0x8000u : 0u;
+#define GS_SN(KB, V) do { if (fk) return seg_narrow_sort<KB, V, true>(gs_ws_base(d_temp), d_keys, d_vals, selector, num_items, num_segments, \
+                                                                      d_begin_offsets, d_end_offsets, begin_bit, end_bit, descending, sign, s); \
+                          return seg_narrow_sort<KB, V, false>(gs_ws_base(d_temp), d_keys, d_vals, selector, num_items, num_segments, \
+                                                                       d_begin_offsets, d_end_offsets, begin_bit, end_bit, descending, sign, s); } while (0)
     if (kb == 1) {
         if (val_bytes == 0) GS_SN(1, MwNoVal);
         if (val_bytes == 4) GS_SN(1, uint32_t);

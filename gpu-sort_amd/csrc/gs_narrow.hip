@@ -46,13 +46,20 @@ struct NarrowParams {
     uint32_t xr;            // sign flip of the key's own width, complement when descending
 };
 
-__device__ __forceinline__ uint32_t n_digit(uint32_t k, const NarrowParams &p) { return ((k ^ p.xr) >> p.shift) & p.mask; }
+// FK: the key is a sign-magnitude float of KB bytes (GS_KEY_F8 / F16 / BF16): a set sign bit flips the magnitude bits as well
+// (cub::Traits<float>::TwiddleIn at the key's own width; the sign flip itself is in xr, as for a signed integer).  A template
+// parameter, so that the integer kernels keep the code they had.
+template <int KB, bool FK>
+__device__ __forceinline__ uint32_t n_digit(uint32_t k, const NarrowParams &p)
+{
+    return ((float_flip<FK ? 8 * KB : 0>(k) ^ p.xr) >> p.shift) & p.mask;
+}
 
 // ---------------------------------------------------------------- upsweep --
 // A block counts tpb tiles (8: one wave per tile; 1: the 8 waves share one tile, for arrays of few tiles, where 8 tiles
 // per block would leave most of the chip idle): a wave reads 16-byte chunks that hold its share of the tile and counts the
 // digits of the elements that belong to it in a wave-private LDS histogram.
-template <int KB, int TILE>
+template <int KB, int TILE, bool FK>
 __global__ __launch_bounds__(N_THREADS) void narrow_upsweep_kernel(const void *__restrict__ keys, uint32_t *__restrict__ spine,
                                                                    NarrowParams p, uint32_t tpb)
 {
@@ -89,14 +96,14 @@ __global__ __launch_bounds__(N_THREADS) void narrow_upsweep_kernel(const void *_
 #pragma unroll
                     for (int q = 0; q < 16 / KB; ++q) {
                         const uint32_t k = (x[q * KB / 4] >> (8 * (q * KB % 4))) & (KB == 1 ? 0xffu : 0xffffu);
-                        hist_add(my, n_digit(k, p));
+                        hist_add(my, n_digit<KB, FK>(k, p));
                     }
                 } else {
 #pragma unroll
                     for (int q = 0; q < 16 / KB; ++q) {
                         const uint32_t k = (x[q * KB / 4] >> (8 * (q * KB % 4))) & (KB == 1 ? 0xffu : 0xffffu);
                         const uint32_t b = b0 + q * KB;
-                        if (b >= a && b < end_byte) hist_add(my, n_digit(k, p));
+                        if (b >= a && b < end_byte) hist_add(my, n_digit<KB, FK>(k, p));
                     }
                 }
             }
@@ -137,7 +144,7 @@ __device__ __forceinline__ void n_stage_in(const uint4 *__restrict__ A, uint32_t
 // (gs_large.hip's 64-bit pass): keys_in / vals_in point at the slice, keys_out / vals_out at the whole output, spine is the
 // slice's own and dbase[d] the absolute u64 start of the slice's run of digit d, so gbase (1 KiB more LDS) and the
 // destination indices are u64.  The body is gs_narrow_tile.inc.
-template <int KB, int VB>
+template <int KB, int VB, bool FK>
 __global__ __launch_bounds__(N_THREADS) void narrow_downsweep_kernel(const void *__restrict__ keys_in, void *__restrict__ keys_out,
                                                                      const void *__restrict__ vals_in, void *__restrict__ vals_out,
                                                                      const uint32_t *__restrict__ spine,
@@ -155,7 +162,7 @@ __global__ __launch_bounds__(N_THREADS) void narrow_downsweep_kernel(const void 
 #include "gs_narrow_tile.inc"
 }
 
-template <int KB, int VB>
+template <int KB, int VB, bool FK>
 __global__ __launch_bounds__(N_THREADS) void narrow_downsweep64_kernel(const void *__restrict__ keys_in, void *__restrict__ keys_out,
                                                                        const void *__restrict__ vals_in, void *__restrict__ vals_out,
                                                                        const uint32_t *__restrict__ spine,
@@ -229,14 +236,22 @@ __global__ __launch_bounds__(NF_THREADS) void narrow_count8_large_kernel(const v
     narrow_count8_body<uint64_t>(keys, counts, n);
 }
 
-// out[i] = the key of rank i: bin j of the walk holds the byte value v(j) = (descending ? 255 - j : j) ^ sign
+// bin j of the walk holds the key whose image, complemented when descending, is j: the image is key ^ sign for the integer
+// types (sign = 0x80 for I8) and, for GS_KEY_F8 (sign = 0x80, mag = 0x7f; mag = 0 otherwise), key ^ (key & 0x80 ? 0xff : 0x80)
+__device__ __forceinline__ uint32_t nf_key(uint32_t j, uint32_t sign, uint32_t mag, int descending)
+{
+    const uint32_t u = ((descending ? 255u - j : j) ^ sign) & 0xffu;
+    return u ^ ((0u - (u >> 7)) & mag);
+}
+
+// out[i] = the key of rank i
 __global__ __launch_bounds__(NF_THREADS) void narrow_fill8_kernel(void *__restrict__ keys_out, const uint32_t *__restrict__ counts, uint64_t n,
-                                                                  uint32_t sign, int descending)
+                                                                  uint32_t sign, uint32_t mag, int descending)
 {
     __shared__ uint32_t scratch[8];
     __shared__ uint32_t ends[RADIX];            // ends[j]: number of keys in bins 0..j (n < 2^32)
     const uint32_t j0 = threadIdx.x;
-    const uint32_t cnt = counts[((descending ? 255u - j0 : j0) ^ sign) & 0xffu];
+    const uint32_t cnt = counts[nf_key(j0, sign, mag, descending)];
     ends[j0] = block_exclusive_scan_256(cnt, scratch, nullptr) + cnt;
     __syncthreads();
     const uint32_t a = (uint32_t)((uintptr_t)keys_out & 15u);
@@ -252,7 +267,7 @@ __global__ __launch_bounds__(NF_THREADS) void narrow_fill8_kernel(void *__restri
 #pragma unroll
         for (uint32_t s = 128; s > 0; s >>= 1)
             if (ends[j + s - 1] <= e) j += s;
-        const uint32_t v = ((descending ? 255u - j : j) ^ sign) & 0xffu;
+        const uint32_t v = nf_key(j, sign, mag, descending);
         if (hi - lo == 16u && ends[j] - e >= 16u) {         // a whole chunk inside one run
             const uint32_t v4 = v * 0x01010101u;
             *reinterpret_cast<uint4 *>(A + b0) = make_uint4(v4, v4, v4, v4);
@@ -261,13 +276,13 @@ __global__ __launch_bounds__(NF_THREADS) void narrow_fill8_kernel(void *__restri
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 while (ends[j] <= e + q) ++j;
-                x[q / 4] |= (((descending ? 255u - j : j) ^ sign) & 0xffu) << (8 * (q % 4));
+                x[q / 4] |= nf_key(j, sign, mag, descending) << (8 * (q % 4));
             }
             *reinterpret_cast<uint4 *>(A + b0) = make_uint4(x[0], x[1], x[2], x[3]);
         } else {                                            // the array's first or last chunk: byte stores
             for (uint64_t b = lo; b < hi; ++b) {
                 while (ends[j] <= (uint32_t)(b - a)) ++j;
-                A[b] = (unsigned char)((descending ? 255u - j : j) ^ sign);
+                A[b] = (unsigned char)nf_key(j, sign, mag, descending);
             }
         }
     }
@@ -275,11 +290,11 @@ __global__ __launch_bounds__(NF_THREADS) void narrow_fill8_kernel(void *__restri
 
 // the same for n < 2^40 (gs_lsb_sort_narrow_large): the counts, ends[], the rank e and the search are 64-bit
 __global__ __launch_bounds__(NF_THREADS) void narrow_fill8_large_kernel(void *__restrict__ keys_out, const uint64_t *__restrict__ counts, uint64_t n,
-                                                                        uint32_t sign, int descending)
+                                                                        uint32_t sign, uint32_t mag, int descending)
 {
     __shared__ uint64_t ends[RADIX];            // ends[j]: number of keys in bins 0..j
     const uint32_t j0 = threadIdx.x;
-    const uint64_t cnt = counts[((descending ? 255u - j0 : j0) ^ sign) & 0xffu];
+    const uint64_t cnt = counts[nf_key(j0, sign, mag, descending)];
     ends[j0] = cnt;                             // inclusive scan in place, once per block
     __syncthreads();
     for (uint32_t off = 1; off < RADIX; off <<= 1) {
@@ -301,7 +316,7 @@ __global__ __launch_bounds__(NF_THREADS) void narrow_fill8_large_kernel(void *__
 #pragma unroll
         for (uint32_t s = 128; s > 0; s >>= 1)
             if (ends[j + s - 1] <= e) j += s;
-        const uint32_t v = ((descending ? 255u - j : j) ^ sign) & 0xffu;
+        const uint32_t v = nf_key(j, sign, mag, descending);
         if (hi - lo == 16u && ends[j] - e >= 16u) {         // a whole chunk inside one run
             const uint32_t v4 = v * 0x01010101u;
             *reinterpret_cast<uint4 *>(A + b0) = make_uint4(v4, v4, v4, v4);
@@ -310,13 +325,13 @@ __global__ __launch_bounds__(NF_THREADS) void narrow_fill8_large_kernel(void *__
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 while (ends[j] <= e + q) ++j;
-                x[q / 4] |= (((descending ? 255u - j : j) ^ sign) & 0xffu) << (8 * (q % 4));
+                x[q / 4] |= nf_key(j, sign, mag, descending) << (8 * (q % 4));
             }
             *reinterpret_cast<uint4 *>(A + b0) = make_uint4(x[0], x[1], x[2], x[3]);
         } else {                                            // the array's first or last chunk: byte stores
             for (uint64_t b = lo; b < hi; ++b) {
                 while (ends[j] <= b - a) ++j;
-                A[b] = (unsigned char)((descending ? 255u - j : j) ^ sign);
+                A[b] = (unsigned char)nf_key(j, sign, mag, descending);
             }
         }
     }
@@ -334,9 +349,19 @@ static inline size_t n_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int n_key_bytes(int key_type)
 {
     switch (key_type) {
-    case GS_KEY_U8: case GS_KEY_I8: return 1;
-    case GS_KEY_U16: case GS_KEY_I16: return 2;
+    case GS_KEY_U8: case GS_KEY_I8: case GS_KEY_F8: return 1;
+    case GS_KEY_U16: case GS_KEY_I16: case GS_KEY_F16: case GS_KEY_BF16: return 2;
     default: return 0;
+    }
+}
+static inline bool n_float(int key_type) { return key_type == GS_KEY_F8 || key_type == GS_KEY_F16 || key_type == GS_KEY_BF16; }
+// the sign bit of the signed types, at the key's own width (0 for the unsigned ones)
+static inline uint32_t n_sign(int key_type)
+{
+    switch (key_type) {
+    case GS_KEY_I8: case GS_KEY_F8: return 0x80u;
+    case GS_KEY_I16: case GS_KEY_F16: case GS_KEY_BF16: return 0x8000u;
+    default: return 0u;
     }
 }
 static inline bool n_val_ok(int vb) { return vb == 0 || vb == 1 || vb == 2 || vb == 4 || vb == 8 || vb == 16; }
@@ -349,26 +374,27 @@ static inline uint32_t n_tiles(uint64_t n, int vb)
 static inline size_t n_spine_bytes(uint64_t n, int vb) { return n_align256((size_t)RADIX * n_tiles(n, vb) * 4); }
 static inline size_t n_totals_bytes() { return n_align256(RADIX * 4); }
 
-template <int KB, int VB>
+template <int KB, int VB, bool FK>
 static int narrow_pass(const void *kin, void *kout, const void *vin, void *vout, uint32_t *spine, uint32_t *totals,
                        const NarrowParams &p, hipStream_t s)
 {
     constexpr int TILE = narrow_tile(VB);
     const uint32_t tpb = p.num_tiles > N_SHARED_TILES ? (uint32_t)N_WAVES : 1u;
     { KernelTimer kt(GS_K_LSB_UPSWEEP, s);
-      hipLaunchKernelGGL((narrow_upsweep_kernel<KB, TILE>), dim3((p.num_tiles + tpb - 1) / tpb), dim3(N_THREADS), 0, s, kin, spine, p, tpb); }
+      hipLaunchKernelGGL((narrow_upsweep_kernel<KB, TILE, FK>), dim3((p.num_tiles + tpb - 1) / tpb), dim3(N_THREADS), 0, s, kin, spine, p, tpb); }
     const int e = lsb_scan(spine, totals, p.num_tiles, s);
     if (e) return e;
     { KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
-      hipLaunchKernelGGL((narrow_downsweep_kernel<KB, VB>), dim3(p.num_tiles), dim3(N_THREADS), 0, s, kin, kout, vin, vout,
+      hipLaunchKernelGGL((narrow_downsweep_kernel<KB, VB, FK>), dim3(p.num_tiles), dim3(N_THREADS), 0, s, kin, kout, vin, vout,
                          (const uint32_t *)spine, (const uint32_t *)totals, p); }
     return (int)hipGetLastError();
 }
 
-static int narrow_pass_dispatch(int kb, int vb, const void *kin, void *kout, const void *vin, void *vout, uint32_t *spine,
+static int narrow_pass_dispatch(int kb, int vb, bool fk, const void *kin, void *kout, const void *vin, void *vout, uint32_t *spine,
                                 uint32_t *totals, const NarrowParams &p, hipStream_t s)
 {
-#define GS_N(KB_, VB_) return narrow_pass<KB_, VB_>(kin, kout, vin, vout, spine, totals, p, s)
+#define GS_N(KB_, VB_) do { if (fk) return narrow_pass<KB_, VB_, true>(kin, kout, vin, vout, spine, totals, p, s); \
+                            return narrow_pass<KB_, VB_, false>(kin, kout, vin, vout, spine, totals, p, s); } while (0)
 #define GS_NV(KB_) switch (vb) { case 0: GS_N(KB_, 0); case 1: GS_N(KB_, 1); case 2: GS_N(KB_, 2); case 4: GS_N(KB_, 4); \
                                  case 8: GS_N(KB_, 8); default: GS_N(KB_, 16); }
     if (kb == 1) GS_NV(1)
@@ -407,8 +433,7 @@ static NarrowParams narrow_slice_params(uint64_t len, int val_bytes, const Large
     p.n = len; p.num_tiles = n_tiles(len, val_bytes);
     p.shift = (uint32_t)d.shift;
     p.mask = (1u << d.bits) - 1u;
-    const uint32_t sign = (d.key_type == GS_KEY_I8) ? 0x80u : (d.key_type == GS_KEY_I16) ? 0x8000u : 0u;
-    p.xr = sign ^ (d.descending ? 0xffffffffu : 0u);
+    p.xr = n_sign(d.key_type) ^ (d.descending ? 0xffffffffu : 0u);
     return p;
 }
 
@@ -418,7 +443,8 @@ int narrow_slice_count(const void *kin, uint64_t len, int val_bytes, const Large
     const uint32_t tpb = p.num_tiles > N_SHARED_TILES ? (uint32_t)N_WAVES : 1u;
     const dim3 grid((p.num_tiles + tpb - 1) / tpb), block(N_THREADS);
     { KernelTimer kt(GS_K_LSB_UPSWEEP, s);
-#define GS_NU(KB_, VB_) hipLaunchKernelGGL((narrow_upsweep_kernel<KB_, narrow_tile(VB_)>), grid, block, 0, s, kin, spine, p, tpb)
+#define GS_NU(KB_, VB_) do { if (n_float(d.key_type)) hipLaunchKernelGGL((narrow_upsweep_kernel<KB_, narrow_tile(VB_), true>), grid, block, 0, s, kin, spine, p, tpb); \
+                             else hipLaunchKernelGGL((narrow_upsweep_kernel<KB_, narrow_tile(VB_), false>), grid, block, 0, s, kin, spine, p, tpb); } while (0)
       if (n_key_bytes(d.key_type) == 1) { if (val_bytes <= 4) GS_NU(1, 4); else if (val_bytes == 8) GS_NU(1, 8); else GS_NU(1, 16); }
       else { if (val_bytes <= 4) GS_NU(2, 4); else if (val_bytes == 8) GS_NU(2, 8); else GS_NU(2, 16); }
 #undef GS_NU
@@ -426,11 +452,11 @@ int narrow_slice_count(const void *kin, uint64_t len, int val_bytes, const Large
     return lsb_scan(spine, totals, p.num_tiles, s);
 }
 
-template <int KB>
+template <int KB, bool FK>
 static void narrow_scatter64(int vb, const void *kin, void *kout, const void *vin, void *vout, const uint32_t *spine,
                              const uint64_t *dbase, const NarrowParams &p, hipStream_t s)
 {
-#define GS_N64(VB_) hipLaunchKernelGGL((narrow_downsweep64_kernel<KB, VB_>), dim3(p.num_tiles), dim3(N_THREADS), 0, s, kin, kout, vin, vout, \
+#define GS_N64(VB_) hipLaunchKernelGGL((narrow_downsweep64_kernel<KB, VB_, FK>), dim3(p.num_tiles), dim3(N_THREADS), 0, s, kin, kout, vin, vout, \
                                        spine, dbase, p)
     switch (vb) {
     case 0: GS_N64(0); break;
@@ -448,8 +474,14 @@ int narrow_slice_scatter(const void *kin, void *kout, const void *vin, void *vou
 {
     const NarrowParams p = narrow_slice_params(len, val_bytes, d);
     KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
-    if (n_key_bytes(d.key_type) == 1) narrow_scatter64<1>(val_bytes, kin, kout, vin, vout, spine, dbase, p, s);
-    else narrow_scatter64<2>(val_bytes, kin, kout, vin, vout, spine, dbase, p, s);
+    const bool fk = n_float(d.key_type);
+    if (n_key_bytes(d.key_type) == 1) {
+        if (fk) narrow_scatter64<1, true>(val_bytes, kin, kout, vin, vout, spine, dbase, p, s);
+        else narrow_scatter64<1, false>(val_bytes, kin, kout, vin, vout, spine, dbase, p, s);
+    } else {
+        if (fk) narrow_scatter64<2, true>(val_bytes, kin, kout, vin, vout, spine, dbase, p, s);
+        else narrow_scatter64<2, false>(val_bytes, kin, kout, vin, vout, spine, dbase, p, s);
+    }
     return (int)hipGetLastError();
 }
 
@@ -463,7 +495,7 @@ int narrow_fill_large(const void *kin, void *kout, uint64_t n, int key_type, int
       hipLaunchKernelGGL(narrow_count8_large_kernel, g, dim3(NF_THREADS), 0, s, kin, counts, n); }
     { KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
       hipLaunchKernelGGL(narrow_fill8_large_kernel, g, dim3(NF_THREADS), 0, s, kout, (const uint64_t *)counts, n,
-                         key_type == GS_KEY_I8 ? 0x80u : 0u, descending ? 1 : 0); }
+                         n_sign(key_type), n_float(key_type) ? 0x7fu : 0u, descending ? 1 : 0); }
     return (int)hipGetLastError();
 }
 
@@ -515,7 +547,8 @@ int gs_lsb_sort_narrow(void *d_temp, size_t temp_bytes, const void *d_keys_in, v
     char *c = gs_ws_base(d_temp);   // spine, totals, then (16-bit keys) the intermediate keys and values
     uint32_t *spine = (uint32_t *)c;
     uint32_t *totals = (uint32_t *)(c + n_spine_bytes(n, val_bytes));
-    const uint32_t sign = (key_type == GS_KEY_I8) ? 0x80u : (key_type == GS_KEY_I16) ? 0x8000u : 0u;
+    const uint32_t sign = n_sign(key_type);
+    const bool fk = n_float(key_type);
 
     if (begin_bit == end_bit) {
         hipLaunchKernelGGL(narrow_copy_kernel, n_stream_grid(n * kb, 256 * 16), dim3(256), 0, s, (const unsigned char *)d_keys_in,
@@ -532,7 +565,7 @@ int gs_lsb_sort_narrow(void *d_temp, size_t temp_bytes, const void *d_keys_in, v
         { KernelTimer kt(GS_K_LSB_UPSWEEP, s);
           hipLaunchKernelGGL(narrow_count8_kernel, g, dim3(NF_THREADS), 0, s, d_keys_in, totals, n); }
         { KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
-          hipLaunchKernelGGL(narrow_fill8_kernel, g, dim3(NF_THREADS), 0, s, d_keys_out, (const uint32_t *)totals, n, sign, descending ? 1 : 0); }
+          hipLaunchKernelGGL(narrow_fill8_kernel, g, dim3(NF_THREADS), 0, s, d_keys_out, (const uint32_t *)totals, n, sign, fk ? 0x7fu : 0u, descending ? 1 : 0); }
         return (int)hipGetLastError();
     }
 
@@ -554,7 +587,7 @@ int gs_lsb_sort_narrow(void *d_temp, size_t temp_bytes, const void *d_keys_in, v
         const void *vin = first ? d_vals_in : tv;
         void *kout = last ? d_keys_out : tk;
         void *vout = last ? d_vals_out : tv;
-        const int e = narrow_pass_dispatch(kb, val_bytes, kin, kout, val_bytes ? vin : nullptr, val_bytes ? vout : nullptr, spine, totals, p, s);
+        const int e = narrow_pass_dispatch(kb, val_bytes, fk, kin, kout, val_bytes ? vin : nullptr, val_bytes ? vout : nullptr, spine, totals, p, s);
         if (e) return e;
     }
     return hipSuccess;

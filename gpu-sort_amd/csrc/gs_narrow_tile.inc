@@ -1,6 +1,7 @@
 // The tile body shared by narrow_downsweep_kernel and narrow_downsweep64_kernel in gs_narrow.hip.  It is a fragment rather
 // than a device function so that the first kernel compiles to the code it had before the second one existed (as
 // gs_wide_tile.inc).  The including kernel defines K, Off, OFF64, KPT, TILE, the LDS arrays whist / gbase / stage_raw and
+// FK (n_digit's float term) and
 // both of totals and dbase (the one it does not take as an argument is a null pointer that is never read).
 
     const int lane = lane_id(), w = wave_id();
@@ -39,7 +40,9 @@
 
     uint32_t key[KPT];
     uint32_t pos[KPT];
-    const uint32_t pad = ~p.xr;                 // digit p.mask, the largest: ranked last, behind every element of the tile
+    // digit p.mask, the largest: ranked last, behind every element of the tile (a float key's pad is the preimage of all ones:
+    // a descending ~xr has the sign bit set, and the float term would flip its magnitude bits back to zero)
+    const uint32_t pad = FK ? (~p.xr | (KB == 1 ? 0x7fu : 0x7fffu)) : ~p.xr;
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
         const uint32_t idx = wbase + i * WAVE;
@@ -48,7 +51,7 @@
     }
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
-        const uint32_t d = n_digit(key[i], p);
+        const uint32_t d = n_digit<KB, FK>(key[i], p);
         uint32_t plo, phi;
         match_digit(d, plo, phi);
         const uint32_t lower = count_lower(plo, phi);
@@ -90,7 +93,7 @@
     K *stage_k = reinterpret_cast<K *>(stage_raw);
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
-        pos[i] += my[n_digit(key[i], p)];
+        pos[i] += my[n_digit<KB, FK>(key[i], p)];
         stage_k[pos[i]] = (K)key[i];
     }
     __syncthreads();
@@ -100,7 +103,7 @@
     for (int i = 0; i < KPT; ++i) {
         const uint32_t slot = (uint32_t)w * (WAVE * KPT) + i * WAVE + lane;   // wave-contiguous
         const K k = stage_k[slot];
-        dst[i] = gbase[n_digit(k, p)] + slot;
+        dst[i] = gbase[n_digit<KB, FK>(k, p)] + slot;
         if (slot < valid) kout[dst[i]] = k;
     }
     if constexpr (VB != 0) {

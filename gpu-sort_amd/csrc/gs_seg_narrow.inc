@@ -10,7 +10,10 @@
 //     taken from the aligned address below its first byte, and only chunks that hold one of its bytes are read -- and each
 //     lane takes its elements from there in wave-striped order (element i of lane l of wave w is w * 64 * KPT + i * 64 + l);
 //   - keys stay in the caller's representation: the sign flip of the key's own width and the descending complement are one
-//     xor on the way to the digit.  A pad is ~xr: the largest digit in every pass, ranked last because it comes last;
+//     xor on the way to the digit; the float categories (FK) add float_flip at the key's width in front of it.  A pad is the
+//     preimage of the all-ones image, the largest digit in every pass, ranked last because it comes last: ~xr for the
+//     integer types; for a float key ~xr with the magnitude bits set (0x7fff / 0x7f ascending, 0xffff / 0xff descending:
+//     a descending ~xr alone, 0x8000, has the sign set and the image 0x8000);
 //   - every store is one element wide and goes to a position inside the segment, so no byte outside a segment is written
 //     and no dword is shared between two workgroups' stores.
 constexpr int SN_THREADS = 512, SN_WAVES = SN_THREADS / WAVE;
@@ -22,7 +25,12 @@ template <int B> struct SnKey;
 template <> struct SnKey<1> { typedef uint8_t type; };
 template <> struct SnKey<2> { typedef uint16_t type; };
 
-__device__ __forceinline__ uint32_t sn_digit(uint32_t k, uint32_t xr, uint32_t shift, uint32_t mask) { return ((k ^ xr) >> shift) & mask; }
+template <int KB, bool FK>
+__device__ __forceinline__ uint32_t sn_digit(uint32_t k, uint32_t xr, uint32_t shift, uint32_t mask)
+{
+    return ((float_flip<FK ? 8 * KB : 0>(k) ^ xr) >> shift) & mask;
+}
+template <int KB, bool FK> __device__ __forceinline__ uint32_t sn_pad(uint32_t xr) { return FK ? (~xr | (KB == 1 ? 0x7fu : 0x7fffu)) : ~xr; }
 
 // the aligned 16-byte chunks that hold elements [first, first + count) of `base` (count >= 1), copied to raw; returns the
 // offset of element `first` in raw (< 16)
@@ -50,7 +58,7 @@ __device__ __forceinline__ uint32_t sn_stage_in(const void *__restrict__ base, u
 
 // digit counts of the level's tiles: one wave per tile, MSB_WAVES tiles per block and step (mw_upsweep_kernel's layout of
 // the spine and the in-chunk prefixes), the keys read as aligned chunks (narrow_upsweep_kernel)
-template <int KB>
+template <int KB, bool FK>
 __global__ __launch_bounds__(SN_THREADS) void sn_upsweep_kernel(MsbWs ws, int L, const void *__restrict__ src, uint32_t shift,
                                                                 uint32_t mask, uint32_t xr)
 {
@@ -89,14 +97,14 @@ __global__ __launch_bounds__(SN_THREADS) void sn_upsweep_kernel(MsbWs ws, int L,
 #pragma unroll
                         for (int q = 0; q < 16 / KB; ++q) {
                             const uint32_t k = (x[q * KB / 4] >> (8 * (q * KB % 4))) & (KB == 1 ? 0xffu : 0xffffu);
-                            hist_add(my, sn_digit(k, xr, shift, mask));
+                            hist_add(my, sn_digit<KB, FK>(k, xr, shift, mask));
                         }
                     } else {
 #pragma unroll
                         for (int q = 0; q < 16 / KB; ++q) {
                             const uint32_t k = (x[q * KB / 4] >> (8 * (q * KB % 4))) & (KB == 1 ? 0xffu : 0xffffu);
                             const uint32_t b = b0 + q * KB;
-                            if (b >= a && b < end_byte) hist_add(my, sn_digit(k, xr, shift, mask));
+                            if (b >= a && b < end_byte) hist_add(my, sn_digit<KB, FK>(k, xr, shift, mask));
                         }
                     }
                 }
@@ -118,7 +126,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_upsweep_kernel(MsbWs ws, int L,
 
 // one level tile: stable counting-sort scatter on the digit at `shift` (mw_scatter_kernel's bases from cursors, spine and
 // prefix16; narrow_downsweep_kernel's staging, ranking and per-element stores).  Pads rank last and are not stored.
-template <int KB, typename V>
+template <int KB, typename V, bool FK>
 __global__ __launch_bounds__(SN_THREADS) void sn_scatter_kernel(MsbWs ws, int L, const void *__restrict__ src_k, void *__restrict__ dst_k,
                                                                 const V *__restrict__ src_v, V *__restrict__ dst_v, uint32_t shift,
                                                                 uint32_t mask, uint32_t xr)
@@ -155,14 +163,14 @@ __global__ __launch_bounds__(SN_THREADS) void sn_scatter_kernel(MsbWs ws, int L,
     __syncthreads();
 
     uint32_t key[KPT], pos[KPT];
-    const uint32_t pad = ~xr;                   // digit `mask`, the largest: ranked last, behind every element of the tile
+    const uint32_t pad = sn_pad<KB, FK>(xr);    // digit `mask`, the largest: ranked last, behind every element of the tile
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
         const uint32_t idx = wbase + i * WAVE;
         const uint32_t k = *reinterpret_cast<const K *>(stage_raw + ka + (idx < valid ? idx : 0u) * KB);
         key[i] = (idx < valid) ? k : pad;
     }
-    mw_rank<KPT>(my, pos, [&](int i) { return sn_digit(key[i], xr, shift, mask); });
+    mw_rank<KPT>(my, pos, [&](int i) { return sn_digit<KB, FK>(key[i], xr, shift, mask); });
     __syncthreads();                            // every key is in registers: the raw chunks may be overwritten
     if (w == 0) {
         uint32_t ex[4];
@@ -173,7 +181,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_scatter_kernel(MsbWs ws, int L,
     K *stage_k = reinterpret_cast<K *>(stage_raw);
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
-        pos[i] += my[sn_digit(key[i], xr, shift, mask)];
+        pos[i] += my[sn_digit<KB, FK>(key[i], xr, shift, mask)];
         stage_k[pos[i]] = (K)key[i];
     }
     __syncthreads();
@@ -183,7 +191,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_scatter_kernel(MsbWs ws, int L,
     for (int i = 0; i < KPT; ++i) {
         const uint32_t slot = wbase + i * WAVE;          // wave-contiguous slots
         const K k = stage_k[slot];
-        dst[i] = gbase[sn_digit(k, xr, shift, mask)] + slot;
+        dst[i] = gbase[sn_digit<KB, FK>(k, xr, shift, mask)] + slot;
         if (slot < valid) kout[dst[i]] = k;
     }
     if constexpr (HAS_VALUES) {
@@ -211,7 +219,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_scatter_kernel(MsbWs ws, int L,
 // sorted by stable LSD passes of 8 bits over the task's `sort_bits` bits from bit `pad` (one pass for 8-bit keys, two for 16-bit
 // keys, fewer for a narrower bit range), keys and values exchanged through one LDS buffer after every pass, and written once.
 // Everything is in registers before the first store, so source and destination may be the same array.
-template <int KB, typename V, int KPT>
+template <int KB, typename V, int KPT, bool FK>
 __global__ __launch_bounds__(SN_THREADS) void sn_local_sort_kernel(MsbWs ws, int L, int cls, const void *__restrict__ src_k,
                                                                    void *__restrict__ dst_k, const V *__restrict__ src_v,
                                                                    V *__restrict__ dst_v, uint32_t xr)
@@ -229,7 +237,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_local_sort_kernel(MsbWs ws, int
     const int lane = lane_id(), w = wave_id();
     uint32_t *my = whist[w];
     const uint32_t wbase = (uint32_t)w * (WAVE * KPT) + lane;
-    const uint32_t pad = ~xr;
+    const uint32_t pad = sn_pad<KB, FK>(xr);
     for (uint32_t t = blockIdx.x; t < ntasks; t += gridDim.x) {
         const MsbTask T = ws.tasks[cls][t];
         const uint32_t size = T.size < (uint32_t)CAP ? T.size : (uint32_t)CAP;
@@ -257,13 +265,13 @@ __global__ __launch_bounds__(SN_THREADS) void sn_local_sort_kernel(MsbWs ws, int
             const uint32_t shift = T.pad + done, dm = (T.sort_bits - done < 8u) ? ((1u << (T.sort_bits - done)) - 1u) : 0xffu;
 #pragma unroll
             for (int i = lane; i < RADIX; i += WAVE) my[i] = 0;
-            mw_rank<KPT>(my, pos, [&](int i) { return sn_digit(key[i], xr, shift, dm); });
+            mw_rank<KPT>(my, pos, [&](int i) { return sn_digit<KB, FK>(key[i], xr, shift, dm); });
             __syncthreads();
             if (w == 0) { uint32_t ex[4]; mw_scan_rows<SN_WAVES>(whist, ex); }
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < KPT; ++i) {
-                pos[i] += my[sn_digit(key[i], xr, shift, dm)];
+                pos[i] += my[sn_digit<KB, FK>(key[i], xr, shift, dm)];
                 stage_k[pos[i]] = (K)key[i];
             }
             __syncthreads();
@@ -291,14 +299,14 @@ __global__ __launch_bounds__(SN_THREADS) void sn_local_sort_kernel(MsbWs ws, int
     }
 }
 
-template <int KB, typename V>
+template <int KB, typename V, bool FK>
 static int seg_narrow_sort(void *d_temp, void *d_keys[2], void *d_vals[2], int *selector, uint64_t num_items, uint32_t num_segments,
                            const int32_t *d_begin_offsets, const int32_t *d_end_offsets, int begin_bit, int end_bit, int descending,
                            uint32_t sign, hipStream_t s)
 {
     typedef typename SnKey<KB>::type K;
     constexpr bool pairs = !std::is_same<V, MwNoVal>::value;
-    constexpr int VB = pairs ? (int)sizeof(V) : 0, nclass = 2, TILE = SN_THREADS * sn_kpt(VB);
+    constexpr int VB = pairs ? (int)sizeof(V) : 0, nclass = 2, TILE = SN_THREADS * sn_kpt(VB), FW = FK ? 8 * KB : 0;
     // the lists are carved for tiles of 4096 elements (tile_shift 12), which bounds the tiles of 8192 the narrower values use:
     // msb_carve derives the list capacities from the tile size, never from the tile_shift field, which only expand and
     // classify read on the device -- so the larger tile is set on the carved struct, and a carve that ever came back with
@@ -325,16 +333,16 @@ static int seg_narrow_sort(void *d_temp, void *d_keys[2], void *d_vals[2], int *
           uint32_t *vfin = pairs ? (uint32_t *)d_vals[fin] : nullptr;
           const uint32_t wg = (num_segments + 3u) / 4u, wg4 = (num_segments + 15u) / 16u;
           const dim3 grid(wg < MSB_MAX_GRID ? wg : MSB_MAX_GRID), grid4(wg4 < MSB_MAX_GRID ? wg4 : MSB_MAX_GRID);
-          hipLaunchKernelGGL((seg_wave_sort_narrow_kernel<pairs, 4, K>), grid, dim3(256), 0, s, ws, ksel, kfin, vsel, vfin, 0, xr, 0, xr);
-          hipLaunchKernelGGL((seg_wave_sort_narrow_kernel<pairs, 8, K>), grid, dim3(256), 0, s, ws, ksel, kfin, vsel, vfin, 0, xr, 0, xr);
-          hipLaunchKernelGGL((seg_wave_sort_narrow_kernel<pairs, 16, K>), grid, dim3(256), 0, s, ws, ksel, kfin, vsel, vfin, 0, xr, 0, xr);
-          hipLaunchKernelGGL((seg_wave4_sort_narrow_kernel<pairs, K>), grid4, dim3(256), 0, s, ws, ksel, kfin, vsel, vfin, 0, xr, 0, xr);
+          hipLaunchKernelGGL((seg_wave_sort_narrow_kernel<pairs, 4, K, FW>), grid, dim3(256), 0, s, ws, ksel, kfin, vsel, vfin, 0, xr, 0, xr);
+          hipLaunchKernelGGL((seg_wave_sort_narrow_kernel<pairs, 8, K, FW>), grid, dim3(256), 0, s, ws, ksel, kfin, vsel, vfin, 0, xr, 0, xr);
+          hipLaunchKernelGGL((seg_wave_sort_narrow_kernel<pairs, 16, K, FW>), grid, dim3(256), 0, s, ws, ksel, kfin, vsel, vfin, 0, xr, 0, xr);
+          hipLaunchKernelGGL((seg_wave4_sort_narrow_kernel<pairs, K, FW>), grid4, dim3(256), 0, s, ws, ksel, kfin, vsel, vfin, 0, xr, 0, xr);
       }
       const uint32_t g = ws.max_tasks < MSB_MAX_GRID ? ws.max_tasks : MSB_MAX_GRID;
       const V *vsel = pairs ? (const V *)d_vals[sel] : nullptr;
       V *vfin = pairs ? (V *)d_vals[fin] : nullptr;
-      hipLaunchKernelGGL((sn_local_sort_kernel<KB, V, 4>), dim3(g), dim3(SN_THREADS), 0, s, ws, 1, 0, (const void *)ksel, (void *)kfin, vsel, vfin, xr);
-      hipLaunchKernelGGL((sn_local_sort_kernel<KB, V, 16>), dim3(g), dim3(SN_THREADS), 0, s, ws, 1, 1, (const void *)ksel, (void *)kfin, vsel, vfin, xr); }
+      hipLaunchKernelGGL((sn_local_sort_kernel<KB, V, 4, FK>), dim3(g), dim3(SN_THREADS), 0, s, ws, 1, 0, (const void *)ksel, (void *)kfin, vsel, vfin, xr);
+      hipLaunchKernelGGL((sn_local_sort_kernel<KB, V, 16, FK>), dim3(g), dim3(SN_THREADS), 0, s, ws, 1, 1, (const void *)ksel, (void *)kfin, vsel, vfin, xr); }
     // large segments: `passes` stable partitions of the same bucket list, 8 bits at a time from begin_bit
     const uint32_t max_b = ws.max_buckets;
     const uint32_t tiles_ub = (uint32_t)(num_items / TILE) + max_b;
@@ -350,14 +358,14 @@ static int seg_narrow_sort(void *d_temp, void *d_keys[2], void *d_vals[2], int *
         V *dv = pairs ? (V *)d_vals[sel ^ ((p + 1) & 1)] : nullptr;
         { KernelTimer kt(GS_K_MSB_HISTOGRAM, s);
           const uint32_t hg_ub = tiles_ub / SN_WAVES + 1;
-          hipLaunchKernelGGL((sn_upsweep_kernel<KB>), dim3(hg_ub < MSB_MAX_GRID ? hg_ub : MSB_MAX_GRID), dim3(SN_THREADS), 0, s, ws, 1, sk,
+          hipLaunchKernelGGL((sn_upsweep_kernel<KB, FK>), dim3(hg_ub < MSB_MAX_GRID ? hg_ub : MSB_MAX_GRID), dim3(SN_THREADS), 0, s, ws, 1, sk,
                              shift, mask, xr);
           hipLaunchKernelGGL(msb_scan_kernel, dim3(RADIX), dim3(1024), 0, s, ws, 1); }
         { KernelTimer kt(GS_K_MSB_CLASSIFY, s);
           hipLaunchKernelGGL((msb_classify_kernel<true, false>), dim3(max_b < 4096u ? max_b : 4096u), dim3(256), 0, s, ws, 1,
                              (const uint32_t *)nullptr, nclass); }
         { KernelTimer kt(GS_K_MSB_PARTITION, s);
-          hipLaunchKernelGGL((sn_scatter_kernel<KB, V>), dim3(tiles_ub), dim3(SN_THREADS), 0, s, ws, 1, sk, dk, sv, dv, shift, mask, xr); }
+          hipLaunchKernelGGL((sn_scatter_kernel<KB, V, FK>), dim3(tiles_ub), dim3(SN_THREADS), 0, s, ws, 1, sk, dk, sv, dv, shift, mask, xr); }
     }
     *selector = fin;
     return (int)hipGetLastError();

@@ -1,5 +1,5 @@
 // gs_seg_wave4_body.inc -- the body of seg_wave4_sort_kernel (gs_msb.hip): one wave sorts four segments of up to 64 elements.
-// A fragment for the same reason as gs_seg_wave_body.inc; the including kernel declares K, HAS_VALUES and the same parameters.
+// A fragment for the same reason as gs_seg_wave_body.inc; the including kernel declares K, HAS_VALUES, FW and the same parameters.
     constexpr int NS = 4;                                          // segments per wave and step
     __shared__ __attribute__((aligned(16))) uint32_t hist[4][NS][RADIX];
     __shared__ uint32_t stage_k[4][NS * WAVE];
@@ -25,7 +25,7 @@
             key[i] = 0xffffffffu;
             if (HAS_VALUES) val[i] = 0;
             if ((uint32_t)lane < size[i]) {
-                key[i] = twiddle_in(src_k[off[i] + lane], f32_in, xor_in);
+                key[i] = twiddle_in(float_flip<FW>(src_k[off[i] + lane]), f32_in, xor_in);
                 if (HAS_VALUES) val[i] = src_v[off[i] + lane];
             } else {
                 key[i] = 0xffffffffu;                              // pads: behind the segment's elements, largest in every digit
@@ -70,7 +70,7 @@
 #pragma unroll
         for (int i = 0; i < NS; ++i) {
             if ((uint32_t)lane < size[i]) {
-                dst_k[off[i] + lane] = (K)twiddle_out(key[i], f32_out, xor_out);
+                dst_k[off[i] + lane] = (K)float_flip<FW>(twiddle_out(key[i], f32_out, xor_out));
                 if (HAS_VALUES) dst_v[off[i] + lane] = val[i];
             }
         }

@@ -1,7 +1,7 @@
 // gs_seg_wave_body.inc -- the body of seg_wave_sort_kernel (gs_msb.hip): one wave sorts a segment of up to WKPT * 64 elements.
 // A fragment, like gs_wide_tile.inc, so that the u32 kernel compiles to exactly the code it had before the key type became a
 // parameter.  The including kernel declares K (the element type of src_k / dst_k; keys live in registers as u32), HAS_VALUES,
-// WKPT and the parameters ws, src_k, dst_k, src_v, dst_v, f32_in, xor_in, f32_out, xor_out.
+// WKPT, FW (the width of a narrow float key for float_flip, 0 for every other key: the identity) and the parameters ws, src_k, dst_k, src_v, dst_v, f32_in, xor_in, f32_out, xor_out.
     constexpr int LIST = WKPT == 4 ? 0 : WKPT == 8 ? 1 : 2, CAP = WKPT * WAVE;
     __shared__ __attribute__((aligned(16))) uint32_t hist[4][RADIX];
     __shared__ uint32_t stage_k[4][CAP];
@@ -25,7 +25,7 @@
         }
 #pragma unroll
         for (int i = 0; i < WKPT; ++i) {
-            const uint32_t k = twiddle_in(key[i], f32_in, xor_in);
+            const uint32_t k = twiddle_in(float_flip<FW>(key[i]), f32_in, xor_in);
             key[i] = ((uint32_t)(i * WAVE + lane) < size) ? k : 0xffffffffu;   // pads: last in position, largest in every digit
         }
         for (uint32_t done = 0; done < B; done += RADIX_BITS) {
@@ -67,7 +67,7 @@
         for (int i = 0; i < WKPT; ++i) {
             const uint32_t idx = (uint32_t)(i * WAVE + lane);
             if (idx < size) {
-                dst_k[off + idx] = (K)twiddle_out(key[i], f32_out, xor_out);
+                dst_k[off + idx] = (K)float_flip<FW>(twiddle_out(key[i], f32_out, xor_out));
                 if (HAS_VALUES) dst_v[off + idx] = val[i];
             }
         }

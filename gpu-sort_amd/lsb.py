@@ -21,6 +21,13 @@ if hasattr(torch, "uint32"):
     _KEY_TYPES[torch.uint32] = _lib.GS_KEY_U32
 if hasattr(torch, "uint64"):
     _KEY_TYPES[torch.uint64] = _lib.GS_KEY_U64
+# the 8- and 16-bit float categories (order: negative NaNs, -inf ... -0.0, +0.0 ... +inf, positive NaNs -- not torch.sort's)
+_KEY_TYPES.update({torch.float16: _lib.GS_KEY_F16, torch.bfloat16: _lib.GS_KEY_BF16})
+for _name in ("float8_e4m3fn", "float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz"):
+    if hasattr(torch, _name):
+        _KEY_TYPES[getattr(torch, _name)] = _lib.GS_KEY_F8
+_FLOAT_NARROW = {_lib.GS_KEY_F16: 2, _lib.GS_KEY_BF16: 2, _lib.GS_KEY_F8: 1}     # key_type -> key bytes
+_FLOAT_NARROW_NAMES = {_lib.GS_KEY_F16: "GS_KEY_F16", _lib.GS_KEY_BF16: "GS_KEY_BF16", _lib.GS_KEY_F8: "GS_KEY_F8"}
 
 
 def _stream_ptr(stream):
@@ -101,7 +108,8 @@ class DeviceRadixSort:
     @staticmethod
     def _sort_any(d_temp_storage, temp_storage_bytes, d_keys, d_values, num_items, begin_bit, end_bit, descending,
                   stream, key_type, kb, vb):
-        """8- and 16-bit keys (torch.bool / uint8 / int8 / int16 [/ uint16]) and values of any size (1- and 2-byte
+        """8- and 16-bit keys (torch.bool / uint8 / int8 / int16 [/ uint16], float16 / bfloat16 and the float8 dtypes in the
+        order of GS_KEY_F16 / BF16 / F8) and values of any size (1- and 2-byte
         elements, or rows of a 2-D tensor: 16-byte records like the reference's TestFoo): gs_lsb_sort_narrow (native
         kernels) for 8- and 16-bit keys with values of 0 / 1 / 2 / 4 / 8 / 16 bytes, gs_lsb_sort_any for the rest.  Both are the
         plain-pointer form underneath (input untouched, result in the other buffer), so the sorted data ALWAYS ends in
@@ -236,7 +244,7 @@ class DeviceRadixSortLarge:
     DeviceRadixSort for 32- or 64-bit keys with no, 32-bit or 64-bit values, the key type following the dtype as in
     DeviceRadixSort._sort_wide.  Stable, on bits [begin_bit, end_bit); the selector flips once per 8-bit pass; the call
     only enqueues work on the stream and may be captured into a graph.  d_temp_storage=None returns the workspace size.
-    Keys of 8 and 16 bits (torch.bool / uint8 / int8 / int16 [/ uint16]) go to gs_lsb_sort_narrow_large with the convention
+    Keys of 8 and 16 bits (torch.bool / uint8 / int8 / int16 [/ uint16], float16 / bfloat16 / float8) go to gs_lsb_sort_narrow_large with the convention
     of DeviceRadixSort._sort_any: values are elements or rows of 1 / 2 / 4 / 8 / 16 bytes, the result ALWAYS ends in the
     alternate buffer and the selector flips once."""
 
@@ -407,10 +415,21 @@ class DeviceSegmentedRadixSort:
                      d_end_offsets, begin_bit, end_bit, descending, stream, key_type, kb, vb):
         """8- and 16-bit keys (torch.bool / uint8 / int8 / int16 [/ uint16]) with no, 4-byte or 8-byte values:
         gs_segmented_sort_narrow.  The selector flips once per 8-bit pass of the bit range.  Floating-point keys of these widths
-        (float16, bfloat16, 8-bit floats) have no key category and are refused, with or without an explicit key_type: a U16 / I16
-        key_type would sort them by bit pattern, which is not their order."""
-        if d_keys.d_buffers[0].dtype.is_floating_point:
-            raise TypeError(f"segmented sort: no key category for dtype {d_keys.d_buffers[0].dtype} (half-precision keys are not served)")
+        (float16, bfloat16, 8-bit floats) are served only when the caller passes the matching float key_type explicitly
+        (GS_KEY_F16 / GS_KEY_BF16 for 2-byte dtypes, GS_KEY_F8 for 1-byte ones); without one, or with U16 / I16 (which would sort
+        them by bit pattern, not their order), they are refused with a TypeError that names the key_type to pass, and so is a
+        float key_type of another width.  Unlike DeviceRadixSort, the dtype alone does not select the category here: that
+        asymmetry comes from tests/test_segmented_narrow_cpu.py::test_half_precision_keys_are_refused, which pins the refusal
+        without a key_type; a later change that revisits that test can lift it."""
+        dt = d_keys.d_buffers[0].dtype
+        if dt.is_floating_point:
+            want = _KEY_TYPES.get(dt)
+            if key_type not in _FLOAT_NARROW:
+                raise TypeError(f"segmented sort: no key category for dtype {dt} is chosen by default or by an integer key_type: "
+                                f"pass key_type={_FLOAT_NARROW_NAMES.get(want, 'GS_KEY_F16 / GS_KEY_BF16 / GS_KEY_F8')}")
+            if _FLOAT_NARROW[key_type] != kb:
+                raise TypeError(f"segmented sort: {_FLOAT_NARROW_NAMES[key_type]} is a {_FLOAT_NARROW[key_type]}-byte key category, "
+                                f"dtype {dt} has {kb}-byte elements")
         if key_type is None:
             key_type = _KEY_TYPES.get(d_keys.d_buffers[0].dtype)
             if key_type is None:

@@ -49,8 +49,16 @@ enum gs_key_type {
     GS_KEY_U8 = 6,    /* 8- and 16-bit keys: gs_lsb_sort_narrow/any */
     GS_KEY_I8 = 7,    /* (bool / unsigned char: U8; char / signed   */
     GS_KEY_U16 = 8,   /*  char: I8; unsigned short / short)         */
-    GS_KEY_I16 = 9
+    GS_KEY_I16 = 9,
+    GS_KEY_F16 = 10,  /* IEEE half, and                            */
+    GS_KEY_BF16 = 11, /* bfloat16: the same kernels, another name  */
+    GS_KEY_F8 = 12    /* every 8-bit sign-magnitude float: e4m3fn, e5m2 and their fnuz forms */
 };
+/* GS_KEY_F16 / BF16 / F8 (gs_lsb_sort_narrow, _narrow_large, _any and gs_segmented_sort_narrow) use GS_KEY_F32's map at the
+ * key's own width W (16, 16, 8): image(k) = k ^ (sign bit of k set ? all W ones : the sign bit only); bit ranges
+ * [begin_bit, end_bit) apply to that image.  The order is the one of GS_KEY_F32 / F64: negative NaNs first, ordered by their
+ * bits, then -inf ... -0.0, +0.0 ... +inf, then positive NaNs, ordered by their bits.  This is not torch.sort's order ("all
+ * NaNs last, -0 equal to +0").  Outputs hold the caller's bit patterns, NaN payloads included: keys are never rewritten. */
 
 int         gs_version(void);
 const char *gs_error_string(int err);
@@ -187,7 +195,8 @@ int gs_lsb_sort_any(void *d_temp, size_t temp_bytes, const void *d_keys_in, void
                     const void *d_vals_in, void *d_vals_out, uint64_t num_items, int key_type, int val_bytes,
                     int begin_bit, int end_bit, int descending, void *stream);
 
-/* 8- and 16-bit keys on kernels of their own (gs_narrow.hip): key_type GS_KEY_U8 / GS_KEY_I8 / GS_KEY_U16 / GS_KEY_I16 with
+/* 8- and 16-bit keys on kernels of their own (gs_narrow.hip): key_type GS_KEY_U8 / GS_KEY_I8 / GS_KEY_U16 / GS_KEY_I16, or
+ * the float categories GS_KEY_F16 / GS_KEY_BF16 (16 bits) / GS_KEY_F8 (8 bits) in the order stated at the enum, with
  * val_bytes 0, 1, 2, 4, 8 or 16.  The contract is gs_lsb_sort_any's, so a caller can move from one to the other: plain
  * pointers, the inputs are never written, the outputs must not alias the inputs, stable, ascending or descending, on the bits
  * [begin_bit, end_bit) of the key's own width (begin_bit == end_bit copies input to output in input order), num_items < 2^32
@@ -300,7 +309,8 @@ int    gs_lsb_sort_large(void *d_temp, size_t temp_bytes, void *d_keys[2], void 
                          uint64_t num_items, int key_bytes, int val_bytes, int begin_bit, int end_bit,
                          int descending, int key_type, void *stream);
 
-/* gs_lsb_sort_narrow for num_items of 2^32 and more (up to 2^40): 8- and 16-bit keys (GS_KEY_U8 / I8 / U16 / I16) with
+/* gs_lsb_sort_narrow for num_items of 2^32 and more (up to 2^40): 8- and 16-bit keys (GS_KEY_U8 / I8 / U16 / I16 and
+ * the float categories GS_KEY_F16 / BF16 / F8, which size and behave as U16 / U16 / U8 but for the order) with
  * values of 0, 1, 2, 4, 8 or 16 bytes -- e.g. a dictionary-coded column of more than 2^32 rows with u64 row ids.  The
  * argument list and the contract are gs_lsb_sort_narrow's: plain pointers, the inputs are never written, stable, ascending or
  * descending, on the bits [begin_bit, end_bit) of the key's own width (begin_bit == end_bit copies input to output),
@@ -409,7 +419,9 @@ int gs_segmented_sort_wide(void *d_temp, size_t temp_bytes, void *d_keys[2], voi
                            int descending, int key_type, void *stream);
 
 /* The same for 8- and 16-bit keys on kernels of their own (gs_seg_narrow.inc): key_type GS_KEY_U8 / GS_KEY_I8 / GS_KEY_U16 /
- * GS_KEY_I16 with val_bytes 0 (d_vals == NULL), 4 or 8.  Every other key type or value size is refused with
+ * GS_KEY_I16, or the float categories GS_KEY_F16 / GS_KEY_BF16 / GS_KEY_F8 in the order stated at the enum (a short tile is
+ * padded with the preimage of the all-ones image, 0x7fff / 0x7f ascending and 0xffff / 0xff descending), with val_bytes 0
+ * (d_vals == NULL), 4 or 8.  Every other key type or value size is refused with
  * hipErrorInvalidValue, and both queries below return 0 for it (the convention of gs_lsb_narrow_temp_bytes).
  * Stable, ascending or descending, on bits [begin_bit, end_bit) of the key's order-preserving image at its own width
  * (end_bit <= 8 or <= 16).  DoubleBuffer semantics as gs_segmented_sort_u32: both halves may be overwritten inside segments,

@@ -11,7 +11,8 @@
 //   rdxsrt_unstable_sort_keys / _pairs            <- msb/src/sort/gpu_radix_sort.h:511,544
 //   RDXSRT_SortedSequence<K,V>                    <- msb/src/sort/gpu_radix_sort.h:31-34
 //
-// Supported key types: unsigned int, int, float (the graded configurations are u32) and,
+// Supported key types: unsigned int, int, float (the graded configurations are u32), the 8- and 16-bit
+// integer types, _Float16 / __half / __hip_bfloat16 and,
 // through the DoubleBuffer overloads, unsigned long long, long long, double; value type:
 // any 4- or 8-byte trivially copyable type or NullType.  The plain-pointer (copy)
 // overloads are 32-bit only.  rdxsrt_unstable_sort with 64-bit keys or values goes through the
@@ -58,6 +59,16 @@ template <> struct KeyTraits<signed char> { static constexpr int type = GS_KEY_I
 template <> struct KeyTraits<char> { static constexpr int type = (char)-1 < 0 ? GS_KEY_I8 : GS_KEY_U8; };
 template <> struct KeyTraits<unsigned short> { static constexpr int type = GS_KEY_U16; };
 template <> struct KeyTraits<short> { static constexpr int type = GS_KEY_I16; };
+// 16-bit float keys (GS_KEY_F16 / GS_KEY_BF16: negative NaNs, -inf ... -0.0, +0.0 ... +inf, positive NaNs).  _Float16 is a
+// compiler type; __half and __hip_bfloat16 are served where the including file has brought in <hip/hip_fp16.h> /
+// <hip/hip_bf16.h> before this header, so the shim itself does not depend on them.
+template <> struct KeyTraits<_Float16> { static constexpr int type = GS_KEY_F16; };
+#ifdef HIP_INCLUDE_HIP_HIP_FP16_H
+template <> struct KeyTraits<__half> { static constexpr int type = GS_KEY_F16; };
+#endif
+#ifdef HIP_INCLUDE_HIP_HIP_BF16_H
+template <> struct KeyTraits<__hip_bfloat16> { static constexpr int type = GS_KEY_BF16; };
+#endif
 
 struct DeviceRadixSort {
     template <typename KeyT, typename ValueT>
