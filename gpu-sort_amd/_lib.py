@@ -62,6 +62,9 @@ SIGNATURES = {
     "gs_lsb_sort_large": (i32, [vp, sz, pp, pp, C.POINTER(i32), u64, i32, i32, i32, i32, i32, i32, vp]),
     "gs_lsb_narrow_large_temp_bytes": (sz, [u64, i32, i32]),
     "gs_lsb_sort_narrow_large": (i32, [vp, sz, vp, vp, vp, vp, u64, i32, i32, i32, i32, i32, vp]),
+    "gs_topk_temp_bytes": (sz, [u64, u64, i32]),
+    "gs_topk_u32": (i32, [vp, sz, vp, vp, vp, vp, u64, u64, i32, i32, vp]),
+    "gs_topk_status": (i32, [vp, u64, u64, i32, C.POINTER(C.c_uint32), vp]),
     "gs_msb_census": (i32, [vp, u64, i32, vp, vp]),
     "gs_msb_wide_census": (i32, [vp, u64, i32, i32, vp, vp]),
     "gs_msb_capacities": (None, [u64, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

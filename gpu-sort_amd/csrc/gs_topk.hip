@@ -1,0 +1,527 @@
+// gs_topk.hip -- gs_topk_u32: the first k elements of the stable LSB sort, by radix select.
+//
+// The result is defined by the sort: S = gs_lsb_sort_copy_u32(..., 0, 32, descending, key_type) of the same input, and the
+// call leaves S[0..k) in the outputs.  Instead of sorting n elements it finds the image of S[k-1] digit by digit, most
+// significant byte first, and sorts only the k elements that belong to the result:
+//
+//   round one   lsb_upsweep at shift 24 + lsb_scan: per-digit totals, per-chunk prefixes (spine) and per-tile prefix16 of
+//               the top byte of the image (complemented when descending); topk_pick0 finds the digit d0 that holds the
+//               k-th element and opens the state block
+//   filter      second read of the input, one workgroup per tile: elements whose top byte sorts before d0 are certainly
+//               selected and go, in input order, to the staging area; those with top byte d0 go, in input order, to the
+//               candidate list (route 1: the list holds them all).  Positions come from the tables of round one.
+//   rounds 2-4  filtered histogram of the next byte + pick, over the candidate list (route 1) or over the input itself
+//               with the prefix filter (route 2: more elements share the top byte than the list holds).  Source and count
+//               are read from the state block, so both routes are the same launches; workgroups past the count return.
+//   select      count / scan / scatter over the same source: every element of the bucket sorting before the k-th image,
+//               then the first `take` elements equal to it, appended to the staging area in input order
+//   finish      the library's own stable sort of the k staged (key, index) pairs into the outputs, and in pairs mode the
+//               gather vals_out[i] = vals_in[idx[i]]
+//
+// Equal keys always land in ONE group of the staging area (before d0 / before the k-th image / equal to it) and every
+// group is filled in input order, so the stable finish reproduces S bit for bit.  No kernel waits on another workgroup
+// and no atomic decides a position: the only global atomics are the integer adds of the workgroups' histograms.
+// Arrays that fit one workgroup (route 3) are sorted whole into the workspace and the first k copied out.
+#include "gs_device.hpp"
+#include "gs_lsb.hpp"
+
+namespace gs {
+
+constexpr int TK_THREADS = LSB_THREADS;          // 8 waves
+constexpr int TK_WAVES = TK_THREADS / WAVE;
+constexpr int TK_KPT = LSB_KPT;                  // 16 elements per thread: a tile is LSB_TILE
+constexpr uint32_t TK_MIN_CAND = 65536;          // smallest candidate list; also holds route 3's copies (2 * 32768)
+static_assert(TK_THREADS * TK_KPT == LSB_TILE, "the filter walks the tiles of the LSB upsweep");
+
+// state block (u32 words): 0..7 are gs_topk_status' words
+enum { TK_ROUTE = 0, TK_KTH = 1, TK_LESS = 2, TK_TAKE = 3, TK_TOP = 4, TK_STAGED0 = 8, TK_D0 = 9, TK_SRC_COUNT = 10, TK_WORDS = 64 };
+
+struct TopkWs {
+    uint32_t *state, *hist;          // [64], [3][256]
+    char *scratch;                   // 512 bytes for small_stable_sort
+    uint32_t *spine, *totals;
+    uint16_t *prefix16;
+    uint32_t *tilecnt;               // [tiles][2]: {before the k-th image, equal to it} per source tile, scanned in place
+    uint32_t *cand_keys, *cand_idx;
+    uint32_t *stage_keys, *stage_idx;
+    uint32_t *idx_sorted;
+    char *sort_ws;
+    size_t sort_ws_bytes;
+};
+
+static inline size_t tk_align(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline uint64_t tk_tiles(uint64_t n) { const uint64_t t = (n + LSB_TILE - 1) / LSB_TILE; return t ? t : 1; }
+static inline uint64_t tk_grid(uint64_t n) { return (tk_tiles(n) + LSB_CHUNK - 1) / LSB_CHUNK; }
+static inline uint64_t tk_cand_cap(uint64_t n) { return n / 32 > TK_MIN_CAND ? n / 32 : TK_MIN_CAND; }
+
+static size_t tk_carve(char *base, uint64_t n, uint64_t k, bool hv, TopkWs *ws)
+{
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *p = (char *)((uintptr_t)base + off); off += tk_align(bytes); return p; };   // (base may be null: the size query)
+    char *head = take(4096);
+    char *spine = take((size_t)RADIX * 4 * tk_grid(n));
+    char *totals = take(RADIX * 4);
+    char *prefix16 = take((size_t)RADIX * 2 * tk_tiles(n));
+    char *tilecnt = take((size_t)8 * tk_tiles(n));
+    char *ck = take((size_t)4 * tk_cand_cap(n));
+    char *ci = hv ? take((size_t)4 * tk_cand_cap(n)) : nullptr;
+    char *sk = take((size_t)4 * k);
+    char *si = hv ? take((size_t)4 * k) : nullptr;
+    char *is = hv ? take((size_t)4 * k) : nullptr;
+    const size_t sort_bytes = gs_lsb_copy_temp_bytes(k, hv ? 1 : 0);
+    char *sw = take(sort_bytes);
+    if (ws) {
+        ws->state = (uint32_t *)head; ws->hist = (uint32_t *)(head + 256); ws->scratch = head + 256 + 3 * RADIX * 4;
+        ws->spine = (uint32_t *)spine; ws->totals = (uint32_t *)totals; ws->prefix16 = (uint16_t *)prefix16;
+        ws->tilecnt = (uint32_t *)tilecnt; ws->cand_keys = (uint32_t *)ck; ws->cand_idx = (uint32_t *)ci;
+        ws->stage_keys = (uint32_t *)sk; ws->stage_idx = (uint32_t *)si; ws->idx_sorted = (uint32_t *)is;
+        ws->sort_ws = sw; ws->sort_ws_bytes = sort_bytes;
+    }
+    return off;
+}
+
+// ---------------------------------------------------------------- round one: pick --
+// One workgroup: the digit d0 whose run of S holds position k - 1.  Opens the state block and clears the histograms of
+// rounds two to four.
+__global__ __launch_bounds__(RADIX) void topk_pick0_kernel(const uint32_t *__restrict__ totals, uint32_t *__restrict__ state,
+                                                           uint32_t *__restrict__ hist, uint32_t n, uint32_t k, uint32_t cap)
+{
+    __shared__ uint32_t scratch[8];
+    const uint32_t t = threadIdx.x, c = totals[t];
+    const uint32_t ex = block_exclusive_scan_256(c, scratch, nullptr);
+    for (uint32_t i = t; i < 3u * RADIX; i += RADIX) hist[i] = 0;
+    if (t >= 5 && t < TK_WORDS && t != TK_STAGED0 && t != TK_D0 && t != TK_SRC_COUNT) state[t] = 0;
+    if (ex < k && k - ex <= c) {
+        const bool fits = c <= cap;
+        state[TK_ROUTE] = fits ? 1u : 2u;
+        state[TK_KTH] = t << 24;
+        state[TK_LESS] = ex;
+        state[TK_TAKE] = k - ex;
+        state[TK_TOP] = c;
+        state[TK_STAGED0] = ex;
+        state[TK_D0] = t;
+        state[TK_SRC_COUNT] = fits ? c : n;
+    }
+}
+
+// Rounds two to four: the digit at `shift` that holds the k-th element among those matching the prefix so far.
+__global__ __launch_bounds__(RADIX) void topk_pick_kernel(const uint32_t *__restrict__ hist, uint32_t *__restrict__ state, uint32_t shift)
+{
+    __shared__ uint32_t scratch[8];
+    const uint32_t t = threadIdx.x, c = hist[t];
+    const uint32_t krem = state[TK_TAKE], less = state[TK_LESS], kth = state[TK_KTH];
+    const uint32_t ex = block_exclusive_scan_256(c, scratch, nullptr);   // (its barriers order the reads above before the writes below)
+    if (ex < krem && krem - ex <= c) {
+        state[TK_KTH] = kth | (t << shift);
+        state[TK_LESS] = less + ex;
+        state[TK_TAKE] = krem - ex;
+    }
+}
+
+// ------------------------------------------------- ordered two-group compaction --
+// One workgroup, one tile of `src` starting at element lo: wave w owns elements [w * 1024, (w + 1) * 1024) of the tile
+// and reads them in 16 coalesced rows, so (wave, row, lane) is the input order.  cls(raw key) says 0 = drop, 1 = group A,
+// 2 = group B.  Element number r of a group inside the tile goes to position base + r of that group's arrays, when
+// below lim (group B's limit cuts the tie run; the others only fence the arrays).  IDX: also write the element's index --
+// src_idx[i], or i itself when src_idx is null.
+template <bool IDX, typename Cls>
+__device__ __forceinline__ void compact_tile(const uint32_t *__restrict__ src, const uint32_t *__restrict__ src_idx, uint32_t lo,
+                                             uint32_t count, Cls cls, uint32_t baseA, uint32_t limA, uint32_t *__restrict__ ak,
+                                             uint32_t *__restrict__ ai, uint32_t baseB, uint32_t limB, uint32_t *__restrict__ bk,
+                                             uint32_t *__restrict__ bi, uint32_t (*wcnt)[TK_WAVES])
+{
+    const uint32_t w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t first = lo + w * (uint32_t)(WAVE * TK_KPT) + lane;
+    uint32_t raw[TK_KPT], c[TK_KPT];
+#pragma unroll
+    for (int u = 0; u < TK_KPT; ++u) {
+        const uint32_t i = first + (uint32_t)u * WAVE;
+        raw[u] = (i < count && i >= lo) ? __builtin_nontemporal_load(src + i) : 0u;
+    }
+    uint32_t nA = 0, nB = 0;
+#pragma unroll
+    for (int u = 0; u < TK_KPT; ++u) {
+        const uint32_t i = first + (uint32_t)u * WAVE;
+        c[u] = (i < count && i >= lo) ? cls(raw[u]) : 0u;
+        nA += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(c[u] == 1u));
+        nB += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(c[u] == 2u));
+    }
+    if (lane == 0) { wcnt[0][w] = nA; wcnt[1][w] = nB; }
+    __syncthreads();
+    uint32_t tot = 0;
+    for (uint32_t j = 0; j < (uint32_t)TK_WAVES; ++j) {
+        const uint32_t a = wcnt[0][j], b = wcnt[1][j];
+        tot += a + b;
+        if (j < w) { baseA += a; baseB += b; }
+    }
+    if (tot == 0) return;   // nothing of either group in this tile (workgroup-uniform)
+#pragma unroll
+    for (int u = 0; u < TK_KPT; ++u) {
+        const uint32_t i = first + (uint32_t)u * WAVE;
+        asm volatile("" : "+v"(c[u]));   // ballot again: 32 masks kept from the counting loop would not fit the SGPRs
+        const unsigned long long mA = __builtin_amdgcn_ballot_w64(c[u] == 1u), mB = __builtin_amdgcn_ballot_w64(c[u] == 2u);
+        if (c[u] == 1u) {
+            const uint32_t pos = baseA + count_lower(mA);
+            if (pos < limA) {
+                ak[pos] = raw[u];
+                if (IDX) ai[pos] = src_idx ? src_idx[i] : i;
+            }
+        } else if (c[u] == 2u) {
+            const uint32_t pos = baseB + count_lower(mB);
+            if (pos < limB) {
+                bk[pos] = raw[u];
+                if (IDX) bi[pos] = src_idx ? src_idx[i] : i;
+            }
+        }
+        baseA += (uint32_t)__popcll(mA);
+        baseB += (uint32_t)__popcll(mB);
+    }
+}
+
+// --------------------------------------------------------------------- filter --
+// Second read of the input, one workgroup per tile of the upsweep.  Group A: top byte before d0 -> staging area, at the
+// number of such elements in front of the tile (sum over the digits below d0 of spine + prefix16).  Group B (route 1
+// only): top byte d0 -> candidate list, at spine[d0] + prefix16[d0].
+template <bool IDX>
+__global__ __launch_bounds__(TK_THREADS) void topk_filter_kernel(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ spine,
+                                                                 const uint16_t *__restrict__ prefix16, const uint32_t *__restrict__ state,
+                                                                 uint32_t *__restrict__ stage_keys, uint32_t *__restrict__ stage_idx,
+                                                                 uint32_t *__restrict__ cand_keys, uint32_t *__restrict__ cand_idx, uint32_t n,
+                                                                 uint32_t grid, uint32_t k, uint32_t cap, int f32, uint32_t x)
+{
+    __shared__ uint32_t wcnt[2][TK_WAVES];
+    __shared__ uint32_t wsum[TK_WAVES];
+    __shared__ uint32_t cbase;
+    const uint32_t tile = blockIdx.x, chunk = tile / (uint32_t)LSB_CHUNK, tid = threadIdx.x;
+    const uint32_t d0 = state[TK_D0], route = state[TK_ROUTE];
+    uint32_t below = 0;
+    if (tid <= d0) {   // d0 < 256: only the digits that count are read
+        const uint32_t v = spine[(size_t)tid * grid + chunk] + prefix16[(size_t)tile * RADIX + tid];
+        if (tid < d0) below = v;
+        if (tid == d0) cbase = v;
+    }
+    below = wave_reduce_sum(below);
+    if (lane_id() == 0) wsum[wave_id()] = below;
+    __syncthreads();
+    uint32_t baseA = 0;
+    for (int j = 0; j < RADIX / WAVE; ++j) baseA += wsum[j];
+    const uint32_t baseB = cbase;
+    auto cls = [&](uint32_t raw) -> uint32_t {
+        const uint32_t tb = twiddle_in(raw, f32, x) >> 24;
+        return tb < d0 ? 1u : (tb == d0 && route == 1u) ? 2u : 0u;
+    };
+    compact_tile<IDX>(keys, nullptr, tile * (uint32_t)LSB_TILE, n, cls, baseA, k, stage_keys, stage_idx, baseB, cap, cand_keys, cand_idx, wcnt);
+}
+
+// ------------------------------------------------------ rounds two to four: count --
+// Histogram of the byte at `shift` over the source elements whose bytes above it equal the prefix found so far.  LDS
+// histogram per workgroup, then one integer add per non-empty bin.
+__global__ __launch_bounds__(TK_THREADS) void topk_hist_kernel(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ cand_keys,
+                                                               const uint32_t *__restrict__ state, uint32_t *__restrict__ hist,
+                                                               uint32_t shift, int f32, uint32_t x)
+{
+    __shared__ uint32_t h[RADIX];
+    const uint32_t count = state[TK_SRC_COUNT];
+    const uint64_t lo64 = (uint64_t)blockIdx.x * LSB_TILE;
+    if (lo64 >= count) return;
+    const uint32_t lo = (uint32_t)lo64, tid = threadIdx.x;
+    const uint32_t *src = state[TK_ROUTE] == 1u ? cand_keys : keys;
+    const uint32_t prefix = state[TK_KTH], mask = 0xffffff00u << shift;
+    if (tid < (uint32_t)RADIX) h[tid] = 0;
+    __syncthreads();
+    uint32_t raw[TK_KPT];
+#pragma unroll
+    for (int u = 0; u < TK_KPT; ++u) {
+        const uint32_t i = lo + (uint32_t)u * TK_THREADS + tid;
+        raw[u] = (i < count && i >= lo) ? __builtin_nontemporal_load(src + i) : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < TK_KPT; ++u) {
+        const uint32_t i = lo + (uint32_t)u * TK_THREADS + tid;
+        const uint32_t img = twiddle_in(raw[u], f32, x);
+        if (i < count && i >= lo && ((img ^ prefix) & mask) == 0u) hist_add(h, (img >> shift) & 255u);
+    }
+    __syncthreads();
+    if (tid < (uint32_t)RADIX && h[tid]) atomicAdd(&hist[tid], h[tid]);
+}
+
+// -------------------------------------------------------- final ordered select --
+// count: per source tile, the elements of the bucket that sort before the k-th image and those equal to it
+__global__ __launch_bounds__(TK_THREADS) void topk_count_kernel(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ cand_keys,
+                                                                const uint32_t *__restrict__ state, uint32_t *__restrict__ tilecnt,
+                                                                int f32, uint32_t x)
+{
+    __shared__ uint32_t wl[TK_WAVES], we[TK_WAVES];
+    const uint32_t count = state[TK_SRC_COUNT];
+    const uint64_t lo64 = (uint64_t)blockIdx.x * LSB_TILE;
+    if (lo64 >= count) return;
+    const uint32_t lo = (uint32_t)lo64, tid = threadIdx.x;
+    const uint32_t *src = state[TK_ROUTE] == 1u ? cand_keys : keys;
+    const uint32_t kth = state[TK_KTH], lowest = kth & 0xff000000u;
+    uint32_t raw[TK_KPT];
+#pragma unroll
+    for (int u = 0; u < TK_KPT; ++u) {
+        const uint32_t i = lo + (uint32_t)u * TK_THREADS + tid;
+        raw[u] = (i < count && i >= lo) ? __builtin_nontemporal_load(src + i) : 0u;
+    }
+    uint32_t l = 0, e = 0;
+#pragma unroll
+    for (int u = 0; u < TK_KPT; ++u) {
+        const uint32_t i = lo + (uint32_t)u * TK_THREADS + tid;
+        const uint32_t img = twiddle_in(raw[u], f32, x);
+        const bool ok = i < count && i >= lo;
+        l += (ok && img >= lowest && img < kth) ? 1u : 0u;
+        e += (ok && img == kth) ? 1u : 0u;
+    }
+    l = wave_reduce_sum(l);
+    e = wave_reduce_sum(e);
+    if (lane_id() == 0) { wl[wave_id()] = l; we[wave_id()] = e; }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t sl = 0, se = 0;
+        for (int j = 0; j < TK_WAVES; ++j) { sl += wl[j]; se += we[j]; }
+        tilecnt[2u * blockIdx.x] = sl;
+        tilecnt[2u * blockIdx.x + 1u] = se;
+    }
+}
+
+// scan: one workgroup, exclusive prefixes of both counts over the source tiles, in place
+constexpr int TK_SCAN_THREADS = 1024;
+__global__ __launch_bounds__(TK_SCAN_THREADS) void topk_scan_kernel(const uint32_t *__restrict__ state, uint32_t *__restrict__ tilecnt)
+{
+    __shared__ uint32_t wsl[TK_SCAN_THREADS / WAVE], wse[TK_SCAN_THREADS / WAVE];
+    const uint32_t count = state[TK_SRC_COUNT];
+    const uint32_t tiles = (uint32_t)(((uint64_t)count + LSB_TILE - 1) / LSB_TILE);
+    const int w = wave_id(), lane = lane_id();
+    uint32_t carry_l = 0, carry_e = 0;
+    for (uint32_t base = 0; base < tiles; base += TK_SCAN_THREADS) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t l = i < tiles ? tilecnt[2u * i] : 0u, e = i < tiles ? tilecnt[2u * i + 1u] : 0u;
+        const uint32_t il = wave_inclusive_scan(l), ie = wave_inclusive_scan(e);
+        if (lane == 63) { wsl[w] = il; wse[w] = ie; }
+        __syncthreads();
+        uint32_t bl = 0, be = 0, tl = 0, te = 0;
+        for (int j = 0; j < TK_SCAN_THREADS / WAVE; ++j) {
+            const uint32_t a = wsl[j], b = wse[j];
+            if (j < w) { bl += a; be += b; }
+            tl += a; te += b;
+        }
+        if (i < tiles) {
+            tilecnt[2u * i] = carry_l + bl + il - l;
+            tilecnt[2u * i + 1u] = carry_e + be + ie - e;
+        }
+        carry_l += tl; carry_e += te;
+        __syncthreads();
+    }
+}
+
+// scatter: group A = the bucket's elements before the k-th image, behind the staged elements of the filter; group B = the
+// elements equal to it, behind all that sort before it, cut after `take` of them
+template <bool IDX>
+__global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ cand_keys,
+                                                                 const uint32_t *__restrict__ cand_idx, const uint32_t *__restrict__ state,
+                                                                 const uint32_t *__restrict__ tilecnt, uint32_t *__restrict__ stage_keys,
+                                                                 uint32_t *__restrict__ stage_idx, uint32_t k, int f32, uint32_t x)
+{
+    __shared__ uint32_t wcnt[2][TK_WAVES];
+    const uint32_t count = state[TK_SRC_COUNT];
+    const uint64_t lo64 = (uint64_t)blockIdx.x * LSB_TILE;
+    if (lo64 >= count) return;
+    const bool list = state[TK_ROUTE] == 1u;
+    const uint32_t kth = state[TK_KTH], lowest = kth & 0xff000000u, less = state[TK_LESS], take = state[TK_TAKE];
+    const uint32_t baseA = state[TK_STAGED0] + tilecnt[2u * blockIdx.x], baseB = less + tilecnt[2u * blockIdx.x + 1u];
+    const uint32_t limB = less + take < k ? less + take : k;
+    auto cls = [&](uint32_t raw) -> uint32_t {
+        const uint32_t img = twiddle_in(raw, f32, x);
+        return img == kth ? 2u : (img >= lowest && img < kth) ? 1u : 0u;
+    };
+    compact_tile<IDX>(list ? cand_keys : keys, list ? cand_idx : nullptr, (uint32_t)lo64, count, cls, baseA, k, stage_keys, stage_idx,
+                      baseB, limB, stage_keys, stage_idx, wcnt);
+}
+
+// --------------------------------------------------------------------- finish --
+__global__ __launch_bounds__(256) void topk_gather_kernel(const uint32_t *__restrict__ vals_in, const uint32_t *__restrict__ idx,
+                                                          uint32_t *__restrict__ vals_out, uint32_t k, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= k) return;
+    const uint32_t j = idx[i];
+    if (j < n) vals_out[i] = vals_in[j];
+}
+
+__global__ __launch_bounds__(256) void topk_iota_kernel(uint32_t *__restrict__ out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) out[i] = i;
+}
+
+// Route 3, one workgroup: copy the first k of the sorted array out and write the status words from it.
+__global__ __launch_bounds__(TK_THREADS) void topk_small_finish_kernel(const uint32_t *__restrict__ sk, const uint32_t *__restrict__ sv,
+                                                                       uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
+                                                                       uint32_t *__restrict__ state, uint32_t n, uint32_t k, int f32, uint32_t x)
+{
+    __shared__ uint32_t acc[2];
+    const uint32_t tid = threadIdx.x;
+    if (tid < 2) acc[tid] = 0;
+    __syncthreads();
+    const uint32_t kth = twiddle_in(sk[k - 1u], f32, x);
+    uint32_t less = 0, top = 0;
+    for (uint32_t i = tid; i < n; i += TK_THREADS) {
+        const uint32_t raw = sk[i], img = twiddle_in(raw, f32, x);
+        less += img < kth ? 1u : 0u;
+        top += (img >> 24) == (kth >> 24) ? 1u : 0u;
+        if (i < k) {
+            keys_out[i] = raw;
+            if (vals_out) vals_out[i] = sv[i];
+        }
+    }
+    less = wave_reduce_sum(less);
+    top = wave_reduce_sum(top);
+    if (lane_id() == 0) { atomicAdd(&acc[0], less); atomicAdd(&acc[1], top); }
+    __syncthreads();
+    if (tid < (uint32_t)TK_WORDS) {
+        uint32_t v = 0;
+        if (tid == TK_ROUTE) v = 3u;
+        else if (tid == TK_KTH) v = kth;
+        else if (tid == TK_LESS) v = acc[0];
+        else if (tid == TK_TAKE) v = k - acc[0];
+        else if (tid == TK_TOP) v = acc[1];
+        state[tid] = v;
+    }
+}
+
+static bool tk_overlaps(const void *a, size_t abytes, const void *b, size_t bbytes)
+{
+    if (!a || !b || !abytes || !bbytes) return false;
+    const char *p = (const char *)a, *q = (const char *)b;
+    return p < q + bbytes && q < p + abytes;
+}
+
+}  // namespace gs
+
+using namespace gs;
+
+extern "C" {
+
+size_t gs_topk_temp_bytes(uint64_t num_items, uint64_t k, int has_values)
+{
+    return tk_carve(nullptr, num_items, k, has_values != 0, nullptr) + GS_WS_SLACK;
+}
+
+int gs_topk_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
+                uint32_t *d_vals_out, uint64_t num_items, uint64_t k, int descending, int key_type, void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (num_items >= (1ull << 32) || k > num_items) return hipErrorInvalidValue;
+    if (key_type < GS_KEY_U32 || key_type > GS_KEY_F32) return hipErrorInvalidValue;
+    if (d_vals_in && !d_vals_out) return hipErrorInvalidValue;
+    if (k == 0 || num_items == 0) return hipSuccess;
+    const bool hv = d_vals_out != nullptr;
+    if (!d_keys_in || !d_keys_out) return hipErrorInvalidValue;
+    if (!d_temp || temp_bytes < gs_topk_temp_bytes(num_items, k, hv)) return hipErrorInvalidValue;
+    if ((((uintptr_t)d_keys_in | (uintptr_t)d_vals_in | (uintptr_t)d_keys_out | (uintptr_t)d_vals_out) & 3u) != 0) return hipErrorInvalidValue;
+    {
+        const void *arr[4] = {d_keys_in, d_vals_in, d_keys_out, d_vals_out};
+        const size_t bytes[4] = {(size_t)num_items * 4, (size_t)num_items * 4, (size_t)k * 4, (size_t)k * 4};
+        for (int i = 0; i < 4; ++i)
+            for (int j = i + 1; j < 4; ++j)
+                if (tk_overlaps(arr[i], bytes[i], arr[j], bytes[j])) return hipErrorInvalidValue;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t n = (uint32_t)num_items, kk = (uint32_t)k;
+    TopkWs ws;
+    tk_carve(gs_ws_base(d_temp), num_items, k, hv, &ws);
+    PassParams p = lsb_make_params(num_items, 24, 8);
+    lsb_twiddle_masks(key_type, descending, true, true, p);
+    int e;
+
+    if (n <= small_sort_capacity(hv)) {
+        if (small_sort_capacity(hv) > TK_MIN_CAND / 2) return hipErrorInvalidValue;   // (the copies below would not fit)
+        // route 3: the array fits one workgroup.  Sorted whole into the candidate area (keys | indices for the
+        // arguments form, values in the second list), then the first k are copied out.
+        uint32_t *sk = ws.cand_keys, *iota = ws.cand_keys + TK_MIN_CAND / 2, *sv = ws.cand_idx;
+        const uint32_t *vin = d_vals_in;
+        if (hv && !vin) {
+            KernelTimer kt(GS_K_OTHER, s);
+            hipLaunchKernelGGL(topk_iota_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, iota, n);
+            vin = iota;
+        }
+        if ((e = small_stable_sort(ws.scratch, 512, d_keys_in, sk, vin, hv ? sv : nullptr, n, 0, 32, p.f32_in, p.xor_in, p.f32_out,
+                                   p.xor_out, s)))
+            return e;
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(topk_small_finish_kernel, dim3(1), dim3(TK_THREADS), 0, s, sk, sv, d_keys_out, d_vals_out, ws.state, n, kk,
+                           p.f32_in, p.xor_in);
+        return (int)hipGetLastError();
+    }
+
+    // round one
+    if ((e = lsb_upsweep(d_keys_in, ws.spine, ws.prefix16, p, s))) return e;
+    if ((e = lsb_scan(ws.spine, ws.totals, p.grid, s))) return e;
+    const uint32_t cap = (uint32_t)tk_cand_cap(num_items);
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(topk_pick0_kernel, dim3(1), dim3(RADIX), 0, s, ws.totals, ws.state, ws.hist, n, kk, cap);
+    }
+    // filter
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        if (hv)
+            hipLaunchKernelGGL(topk_filter_kernel<true>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine, ws.prefix16, ws.state,
+                               ws.stage_keys, ws.stage_idx, ws.cand_keys, ws.cand_idx, n, p.grid, kk, cap, p.f32_in, p.xor_in);
+        else
+            hipLaunchKernelGGL(topk_filter_kernel<false>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine, ws.prefix16, ws.state,
+                               ws.stage_keys, ws.stage_idx, ws.cand_keys, ws.cand_idx, n, p.grid, kk, cap, p.f32_in, p.xor_in);
+    }
+    // rounds two to four
+    for (int r = 0; r < 3; ++r) {
+        const uint32_t shift = 16u - 8u * (uint32_t)r;
+        { KernelTimer kt(GS_K_OTHER, s);
+          hipLaunchKernelGGL(topk_hist_kernel, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.state,
+                             ws.hist + r * RADIX, shift, p.f32_in, p.xor_in); }
+        { KernelTimer kt(GS_K_OTHER, s);
+          hipLaunchKernelGGL(topk_pick_kernel, dim3(1), dim3(RADIX), 0, s, ws.hist + r * RADIX, ws.state, shift); }
+    }
+    // final ordered select
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL(topk_count_kernel, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.state, ws.tilecnt,
+                         p.f32_in, p.xor_in); }
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(TK_SCAN_THREADS), 0, s, ws.state, ws.tilecnt); }
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        if (hv)
+            hipLaunchKernelGGL(topk_select_kernel<true>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.cand_idx,
+                               ws.state, ws.tilecnt, ws.stage_keys, ws.stage_idx, kk, p.f32_in, p.xor_in);
+        else
+            hipLaunchKernelGGL(topk_select_kernel<false>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.cand_idx,
+                               ws.state, ws.tilecnt, ws.stage_keys, ws.stage_idx, kk, p.f32_in, p.xor_in);
+    }
+    if ((e = (int)hipGetLastError())) return e;
+    // finish: the stable sort of the k staged pairs; the indices are the values of the arguments form
+    uint32_t *idx_out = !hv ? nullptr : d_vals_in ? ws.idx_sorted : d_vals_out;
+    if ((e = gs_lsb_sort_copy_u32(ws.sort_ws, ws.sort_ws_bytes, ws.stage_keys, d_keys_out, hv ? ws.stage_idx : nullptr, idx_out, k, 0, 32,
+                                  descending, key_type, stream)))
+        return e;
+    if (d_vals_in) {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(topk_gather_kernel, dim3((kk + 255u) / 256u), dim3(256), 0, s, d_vals_in, ws.idx_sorted, d_vals_out, kk, n);
+    }
+    return (int)hipGetLastError();
+}
+
+int gs_topk_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (!out || num_items >= (1ull << 32) || k > num_items) return hipErrorInvalidValue;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (k == 0 || num_items == 0) return hipSuccess;   // such a call enqueued nothing
+    if (!d_temp) return hipErrorInvalidValue;
+    TopkWs ws;
+    tk_carve(gs_ws_base(d_temp), num_items, k, has_values != 0, &ws);
+    hipError_t e = hipMemcpyAsync(out, ws.state, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    return (int)e;
+}
+
+}  // extern "C"

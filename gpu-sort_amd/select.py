@@ -1,0 +1,109 @@
+"""Partial sort: the first k elements of the stable sort, by radix select (gs_topk_u32 in include/gpusort.h).
+
+DeviceTopK is two-phase like DeviceRadixSort (d_temp_storage=None returns the size); topk() is the convenience form that
+allocates outputs and workspace.  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
+(descending for the Max forms) on the same input: stable, keys in the caller's bit patterns, floats in the order of
+GS_KEY_F32 (negative NaNs first, positive NaNs last ascending; -0.0 before +0.0).
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from ._lib import lib, check
+from .lsb import _KEY_TYPES, _stream_ptr, _check_buf
+
+
+def _key_type_of(t, key_type):
+    if key_type is not None:
+        return key_type
+    kt = _KEY_TYPES.get(t.dtype, _lib.GS_KEY_U32)
+    if kt not in (_lib.GS_KEY_U32, _lib.GS_KEY_I32, _lib.GS_KEY_F32):
+        raise TypeError(f"DeviceTopK: 32-bit keys only (int32, float32, or uint32 by key_type), not {t.dtype}")
+    return kt
+
+
+class DeviceTopK:
+    """MinKeys / MaxKeys / MinPairs / MaxPairs: the k smallest (largest) keys, sorted, with their values.
+
+    d_values_in=None in the pairs forms writes the elements' input indices (u32 bit patterns in d_values_out): an argsort of
+    the top k.  The inputs are never written; d_keys_out / d_values_out need k elements and must not overlap anything."""
+
+    @staticmethod
+    def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, descending,
+             has_values, stream, key_type):
+        need = lib.gs_topk_temp_bytes(num_items, k, int(has_values))
+        if d_temp_storage is None:
+            return need
+        if d_keys_in.element_size() != 4:
+            raise TypeError("DeviceTopK: 32-bit keys only")
+        key_type = _key_type_of(d_keys_in, key_type)
+        _check_buf(d_keys_in, num_items, "d_keys_in")
+        _check_buf(d_keys_out, k, "d_keys_out")
+        if has_values:
+            if d_values_in is not None:
+                _check_buf(d_values_in, num_items, "d_values_in")
+            _check_buf(d_values_out, k, "d_values_out")
+        err = lib.gs_topk_u32(C.c_void_p(d_temp_storage.data_ptr()),
+                              min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                              d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
+                              d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
+                              num_items, k, int(descending), key_type, _stream_ptr(stream))
+        check(err, "gs_topk_u32")
+        return need
+
+    @staticmethod
+    def MinKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_items, k, stream=None, key_type=None):
+        return DeviceTopK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_items, k, False, False,
+                               stream, key_type)
+
+    @staticmethod
+    def MaxKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_items, k, stream=None, key_type=None):
+        return DeviceTopK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_items, k, True, False,
+                               stream, key_type)
+
+    @staticmethod
+    def MinPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, stream=None,
+                 key_type=None):
+        return DeviceTopK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k,
+                               False, True, stream, key_type)
+
+    @staticmethod
+    def MaxPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, stream=None,
+                 key_type=None):
+        return DeviceTopK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k,
+                               True, True, stream, key_type)
+
+    @staticmethod
+    def Status(d_temp_storage, num_items, k, has_values, stream=None):
+        """gs_topk_status: [route, image of the k-th element, elements before it, taken from its tie run, elements sharing
+        its top byte, 0, 0, 0] of the last call on d_temp_storage.  Synchronises the stream."""
+        out = (C.c_uint32 * 8)()
+        check(lib.gs_topk_status(C.c_void_p(d_temp_storage.data_ptr()), num_items, k, int(has_values), out, _stream_ptr(stream)),
+              "gs_topk_status")
+        return [int(x) for x in out]
+
+
+def topk(keys, k, largest=False, values=None, indices=False, stream=None):
+    """The k smallest (largest=True: largest) of `keys`, sorted, as (keys_out, values_out).
+
+    values: a 4-byte tensor of the same length, carried with the keys.  indices=True (without values): values_out holds the
+    input positions as int32 bit patterns of u32 indices.  Neither: values_out is None.  Allocates outputs and workspace."""
+    if values is not None and indices:
+        raise ValueError("topk: give values or indices=True, not both")
+    n = keys.numel()
+    if not 0 <= k <= n:
+        raise ValueError(f"topk: need 0 <= k <= {n}")
+    has_values = values is not None or indices
+    keys_out = torch.empty(k, dtype=keys.dtype, device=keys.device)
+    values_out = None
+    if has_values:
+        values_out = torch.empty(k, dtype=values.dtype if values is not None else torch.int32, device=keys.device)
+    if k == 0:
+        return keys_out, values_out
+    nbytes = lib.gs_topk_temp_bytes(n, k, int(has_values))
+    temp = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
+    if stream is not None:
+        temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
+    DeviceTopK._run(temp, nbytes, keys, keys_out, values, values_out, n, k, largest, has_values, stream, None)
+    return keys_out, values_out

@@ -339,6 +339,59 @@ int    gs_lsb_sort_narrow_large(void *d_temp, size_t temp_bytes, const void *d_k
                                 const void *d_vals_in, void *d_vals_out, uint64_t num_items, int key_type,
                                 int val_bytes, int begin_bit, int end_bit, int descending, void *stream);
 
+/* ---------------------------------------------------------------- top k --
+ * The first k elements of the stable sort, by radix select (gs_topk.hip): an ORDER BY ... LIMIT k, or
+ * the k best of a column of scores with their row ids, without sorting the rest.  The result is defined by the sort: with S =
+ * the output of gs_lsb_sort_copy_u32(..., 0, 32, descending, key_type) on the same input -- the stable sort on all 32 bits of
+ * key_type's order-preserving image (GS_KEY_U32 / I32 / F32), reversed when descending -- d_keys_out[0..k) and
+ * d_vals_out[0..k) are S[0..k), bit for bit.  Keys keep the caller's bit patterns (NaN payloads included); GS_KEY_F32 follows
+ * the order stated at the enum (negative NaNs first and positive NaNs last ascending, so positive NaNs first descending; -0.0
+ * before +0.0); where the cut falls inside a run of equal keys, the ones taken are those S puts first (ascending or
+ * descending: the lowest input indices).  Three forms:
+ *   keys only   d_vals_in == NULL and d_vals_out == NULL;
+ *   pairs       both given: values travel with their keys;
+ *   arguments   d_vals_in == NULL, d_vals_out != NULL: the values written are the elements' input indices (u32), an argsort
+ *               of the top k.
+ * has_values of the two queries is non-zero for pairs and arguments.
+ * The contract is gs_lsb_sort_narrow's: plain pointers, the inputs are never written, the outputs must not share a byte with
+ * the inputs or with each other, nothing outside [0, k) of the outputs is written, d_temp anywhere (the alignment paragraph
+ * above holds), num_items < 2^32 and 1 <= k <= num_items (k == 0 or num_items == 0 returns 0, writes nothing and needs no
+ * workspace).  The call only enqueues work on `stream` (no host read-back, allocation or synchronisation); the same kernels
+ * are launched in the same order whatever the data (every decision is taken on the device), so it may be captured into a HIP
+ * graph; calls may follow each other on one stream with one workspace, and two runs on the same input give identical bytes.
+ * Errors (hipErrorInvalidValue, checked before anything is enqueued, nothing written): a NULL or too-small workspace,
+ * k > num_items, num_items >= 2^32, a key_type other than GS_KEY_U32 / I32 / F32, d_vals_in without d_vals_out, a NULL key
+ * pointer, an array not aligned to 4 bytes, arrays that share a byte (inputs at num_items, outputs at k elements).
+ * Cost: two reads of the input plus work proportional to k and to the elements that share the top byte of the k-th one, as
+ * long as those fit the candidate list of C elements below (route 1); otherwise -- all keys in a narrow range, a heavy
+ * hitter -- the later rounds read the input itself, seven reads in all (route 2).  An array that fits one workgroup
+ * (<= 17408 elements) is sorted whole into the workspace and its first k copied out (route 3).  There is no "k too large to
+ * pay" shortcut: a large k only makes the final sort of the k selected elements the larger part of the call, and a whole-array
+ * sort inside the call would need a workspace of 20 bytes per element for every k, or a query that is not monotone in k.
+ * Workspace: a pure host function of its arguments, a multiple of 256, monotone in num_items and in k.  With tiles =
+ * max(1, ceil(num_items / 8192)), chunks = ceil(tiles / 8), C = max(65536, num_items / 32), V = 2 with has_values else 1, and
+ * every term rounded up to 256 bytes:
+ *   4096                                      the state block, the histograms of rounds two to four, small-sort scratch
+ * + 256 * 4 * chunks + 1024 + 256 * 2 * tiles the spine, digit totals and prefix16 of round one (the LSB upsweep at shift 24)
+ * + 8 * tiles                                 two counts per source tile of the final select
+ * + V * 4 * C                                 the candidate list: keys (and indices)
+ * + V * 4 * k                                 the staging area: the k selected keys (and indices)
+ * + has_values: 4 * k                         the sorted indices on their way through the gather of the pairs form
+ * + gs_lsb_copy_temp_bytes(k, has_values)     the workspace of the final sort
+ * + 256 bytes of alignment slack.                                                                                         */
+size_t gs_topk_temp_bytes(uint64_t num_items, uint64_t k, int has_values);
+int    gs_topk_u32(void *d_temp, size_t temp_bytes,
+                   const uint32_t *d_keys_in, const uint32_t *d_vals_in,
+                   uint32_t *d_keys_out, uint32_t *d_vals_out,
+                   uint64_t num_items, uint64_t k, int descending, int key_type, void *stream);
+/* What the last gs_topk_u32 on d_temp (same num_items, k and has_values) decided, after synchronising `stream`:
+ * out[0] = route (1 = candidate list, 2 = input re-read, 3 = whole-array sort of an array that fits one workgroup),
+ * out[1] = image of S[k - 1], the k-th element (key_type's order-preserving u32, complemented when descending),
+ * out[2] = elements whose image sorts strictly before it, out[3] = k - out[2], the number taken from its run of equal keys,
+ * out[4] = elements that share its top byte, out[5..7] = 0.  All zeros for k == 0 or num_items == 0.  Diagnostic: tests and
+ * benches read it.                                                                                                         */
+int    gs_topk_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream);
+
 /* Census of the last gs_msb_sort_u32 that used d_temp (read back after synchronising `stream`): what every level
  * partitioned and what it handed to local sorts.  SURVEY.md 8d: the MSB path's algorithmic bytes are data-dependent --
  * "the harness must log the per-pass census and compute bytes from it": level 0 moves every key once (12 B/key), a level
