@@ -1,5 +1,6 @@
-"""numpy reference of gs_topk_u32 (tests/test_topk_cpu.py, tests/test_topk_gpu.py): the image maps, a stable argsort, the first
-k, the status words, and the workspace formula of the header comment recomputed from its text."""
+"""numpy reference of gs_topk_u32 (tests/test_topk_cpu.py, tests/test_topk_gpu.py, tests/test_topk_edges_*.py): the image maps
+and their inverse, a stable argsort, the first k, the status words, and the workspace formula of the header comment recomputed
+from its text."""
 import numpy as np
 
 U32, I32, F32 = 0, 1, 2
@@ -18,6 +19,21 @@ def image(keys, key_type, descending=False):
     else:
         assert key_type == U32
     return (~k).astype(np.uint32) if descending else k.astype(np.uint32)
+
+
+def preimage(img, key_type, descending=False):
+    """The inverse of image(): the u32 bit patterns of the keys whose image is img."""
+    k = np.ascontiguousarray(img).view(np.uint32)
+    if descending:
+        k = ~k
+    if key_type == I32:
+        k = k ^ np.uint32(0x80000000)
+    elif key_type == F32:
+        nonneg = (k >> np.uint32(31)).astype(bool)      # the images of the non-negative floats have the top bit set
+        k = np.where(nonneg, k ^ np.uint32(0x80000000), ~k)
+    else:
+        assert key_type == U32
+    return np.ascontiguousarray(k, dtype=np.uint32)
 
 
 def ranks(keys, key_type, descending=False):
