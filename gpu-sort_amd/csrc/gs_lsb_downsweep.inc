@@ -79,15 +79,23 @@ __device__ uint32_t gs_phase_buf[131072 * 16];   // [block][phase], n <= 2^30
 // OFF64 = true: the tile belongs to one slice (< 2^31 keys) of a larger array (lsb_downsweep64_kernel): the spine,
 // prefix16 and totals are the slice's own, and dbase[d] is the absolute u64 output offset of the slice's run of digit
 // d, so the global base of a digit run is dbase[d] + (signed 32-bit in-slice offset) and the stores index with 64 bits.
+// CURSOR = true (gs_lsb_plan.hip, the second scatter of the PLANNED route): the order of the keys inside a digit run does not
+// matter, so the tile takes no base from a spine: all its keys share the digit below the scatter's (the input is sorted on
+// it), which selects one row of `cursor` ([lower digit][digit], initialised to the start of every (digit, lower digit)
+// group), and wave 0 claims count(d) places for every digit d with one returning add per digit.  The adds are issued after
+// barrier 1 and their returns are used just before barrier 3, behind the LDS scatter.  A tile whose first and last key
+// differ in the lower digit stores nothing and appends its index to irr[1..] (count in irr[0]): another kernel places it.
 constexpr uint32_t PIPE_SPIN_LIMIT = 1u << 18;   // polls (each >= one memory round trip) before a wait gives up
 
-template <bool HAS_VALUES, bool TAIL, int TW, bool BIG, bool PIPE, bool OFF64 = false>
+template <bool HAS_VALUES, bool TAIL, int TW, bool BIG, bool PIPE, bool OFF64 = false, bool CURSOR = false>
 __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES, OFF64> &sm, const uint32_t t,
     const uint32_t *__restrict__ keys_in, uint32_t *__restrict__ keys_out, const uint32_t *__restrict__ vals_in,
     uint32_t *__restrict__ vals_out, const uint32_t *__restrict__ spine, const uint16_t *__restrict__ prefix16,
     const uint32_t *__restrict__ totals, const PassParams &p, const uint64_t *__restrict__ sc, uint32_t tag,
-    uint32_t *__restrict__ error_word, const uint32_t tid_ = threadIdx.x, const uint64_t *__restrict__ dbase = nullptr)
+    uint32_t *__restrict__ error_word, const uint32_t tid_ = threadIdx.x, const uint64_t *__restrict__ dbase = nullptr,
+    uint32_t *__restrict__ cursor = nullptr, uint32_t *__restrict__ irr = nullptr, const uint32_t irr_cap = 0u)
 {
+    static_assert(!CURSOR || (!HAS_VALUES && !TAIL && !PIPE && !OFF64), "cursor mode: full tiles of keys-only three-launch passes");
 #ifdef GS_EXP_ALLWAVE_KEYS
     constexpr bool ALLWAVE = true;          // experiment: every wave computes its own bases for keys too (no second barrier)
 #else
@@ -151,6 +159,14 @@ __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES, OFF64> 
             }
         }
     }
+    // cursor mode, wave 0: the tile's first and last key (two scalar loads, used only before barrier 1)
+    [[maybe_unused]] uint32_t cur_lo = 0, cur_hi = 0, claim[4] = {0, 0, 0, 0};
+    if constexpr (CURSOR) {
+        if (w == 0) {
+            cur_lo = (tw_in(keys_in[tile_base]) >> (p.shift - (uint32_t)RADIX_BITS)) & (uint32_t)(RADIX - 1);
+            cur_hi = (tw_in(keys_in[tile_base + (LSB_TILE - 1)]) >> (p.shift - (uint32_t)RADIX_BITS)) & (uint32_t)(RADIX - 1);
+        }
+    }
     GS_PHASE(0);                                   // load issue
 #ifndef GS_EXP_RANK_PRIO
 #define GS_EXP_RANK_PRIO 0
@@ -174,7 +190,7 @@ __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES, OFF64> 
             const uint4 tot = reinterpret_cast<const uint4 *>(totals)[lane];
             dstart[0] = tot.x; dstart[1] = tot.y; dstart[2] = tot.z; dstart[3] = tot.w;
         }
-    } else if (w == 0) {
+    } else if (!CURSOR && w == 0) {
         const uint4 tot = reinterpret_cast<const uint4 *>(totals)[lane];
         const uint32_t lane_sum = tot.x + tot.y + tot.z + tot.w;
         const uint32_t ex = wave_inclusive_scan(lane_sum) - lane_sum;
@@ -186,7 +202,7 @@ __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES, OFF64> 
 
     // this tile's global offsets (wave 0): scanned chunk count + count of the chunk's earlier tiles
     uint32_t tbase[4] = {0, 0, 0, 0};
-    if (!TAIL && !PIPE && w == 0) {
+    if (!TAIL && !PIPE && !CURSOR && w == 0) {
         const uint32_t *sp = spine + (uint32_t)(4 * lane) * p.grid + t / LSB_CHUNK;
         const uint2 pf = reinterpret_cast<const uint2 *>(prefix16 + (size_t)t * RADIX)[lane];
         tbase[0] = sp[0] + (pf.x & 0xffffu);
@@ -285,11 +301,22 @@ __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES, OFF64> 
         // histogram addresses are recomputed after the barrier instead of kept live
         asm volatile("" : "+v"(pos[i]), "+v"(key[i]));
     }
+    if constexpr (CURSOR) {
+        if (w == 0 && lane == 0) {
+            const bool straddles = cur_lo != cur_hi;
+            sm.dead = straddles ? 1u : 0u;
+            if (straddles) {
+                const uint32_t at = atomicAdd(&irr[0], 1u);
+                if (at < irr_cap) irr[1u + at] = t;
+            }
+        }
+    }
     GS_PHASE_WAIT("lgkmcnt(0)");
     GS_PHASE(2);                                   // rank
     __syncthreads();
     GS_PHASE(3);                                   // barrier 1
     if (PIPE && !TAIL && sm.dead) return;          // the wait for this tile's offsets gave up: no global store (all waves alike)
+    if (CURSOR && sm.dead) return;                 // the tile straddles two rows of the cursors: listed, placed later
 
     // 3. wave histograms -> tile-absolute base of every (wave, digit) + global base per digit.
     //    4 digits per lane, b128 LDS accesses, DPP scan of the 256 digit totals.
@@ -329,7 +356,21 @@ __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES, OFF64> 
             ex[1] = ex[0] + run[0];
             ex[2] = ex[1] + run[1];
             ex[3] = ex[2] + run[2];
-            publish_gbase(ex, run);
+            if constexpr (CURSOR) {
+                // the tile-local starts go to `gbase` for now; lane l claims for digits l, 64 + l, 128 + l, 192 + l, so that
+                // each of the four adds covers 256 contiguous bytes of the row (LDS serves one wave's accesses in order)
+                reinterpret_cast<uint4 *>(sm.gbase)[lane] = make_uint4(ex[0], ex[1], ex[2], ex[3]);
+                uint32_t *row = cursor + (size_t)__builtin_amdgcn_readfirstlane(cur_lo) * RADIX;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int d = q * WAVE + lane;
+                    const uint32_t e0 = sm.gbase[d], e1 = sm.gbase[d == RADIX - 1 ? d : d + 1];
+                    const uint32_t cnt = (d == RADIX - 1 ? (uint32_t)LSB_TILE : e1) - e0;
+                    claim[q] = __hip_atomic_fetch_add(row + d, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            } else {
+                publish_gbase(ex, run);
+            }
             asm volatile("" ::: "memory");   // re-read the rows instead of keeping 32 registers live
             uint4 e4 = make_uint4(ex[0] << 2, ex[1] << 2, ex[2] << 2, ex[3] << 2);
 #pragma unroll
@@ -361,6 +402,17 @@ __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES, OFF64> 
             } else {
                 const uint32_t at = (pos[i] << 2) + wb[i];       // bytes
                 *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(sm.stage) + at) = key[i];
+            }
+        }
+    }
+    if constexpr (CURSOR) {
+        // the claims are back by now (or waited for here): global base of digit run = claimed place - tile-local start
+        if (w == 0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int d = q * WAVE + lane;
+                const uint32_t g = claim[q] - sm.gbase[d];
+                sm.gbase[d] = BIG ? g : g << 2;
             }
         }
     }

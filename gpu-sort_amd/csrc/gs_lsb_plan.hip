@@ -35,6 +35,12 @@ namespace gs {
 //   finish    lsb_plan_tasks_kernel turns the group table into the local sorts' task lists (nothing when CLASSIC), and the
 //             local sorts run in place over worst-case grids: with empty lists their blocks exit.
 // The buffer ping-pong is the four passes' on both routes, so the selector and the result buffer do not depend on the route.
+//   cursors   the finish sorts every group, so the second PLANNED scatter need not be stable: it only has to put every key
+//             into the range of its group, which the look knows exactly (offsets[]).  So it has no upsweep: a tile claims
+//             count(d2) places in group (d2, d1) with one returning add per d2 on a table of cursors (downsweep_tile's
+//             CURSOR mode), which the launch that would have been the upsweep sets to the groups' starts.  The few tiles
+//             that hold keys of more than one d1, and the partial last tile, are placed key by key by a small kernel
+//             afterwards.  GS_LSB_PLAN_SCATTER2=stable keeps the stable scatter with its upsweep.
 constexpr uint32_t PLAN_GROUPS = 65536;
 constexpr uint32_t PLAN_WORDS = PLAN_GROUPS / 2;          // 16-bit counters, two to a word: 128 KiB of LDS
 constexpr uint32_t PLAN_PLANNED = 1u, PLAN_CLASSIC = 2u;  // route word (0: no sort has run on this workspace)
@@ -49,6 +55,8 @@ constexpr uint32_t PLAN_LOOK_MAX_GRID = MI355X_CUS;       // one resident workgr
 constexpr uint32_t PLAN_BLOCKS = 128, PLAN_BLOCK_WORDS = PLAN_WORDS / PLAN_BLOCKS, PLAN_BLOCK_GROUPS = PLAN_GROUPS / PLAN_BLOCKS;
 constexpr int PLAN_SORT_BITS = 16;
 constexpr int PLAN_SKEW_LANES = 8;                      // look: lanes of a wave in one group from which a batch counts as skewed
+constexpr uint32_t PLAN_IRR_CAP = RADIX - 1;            // tiles of the first scatter's output that straddle two of its digit runs: one per boundary at most
+constexpr size_t PLAN_CURSOR_BYTES = (size_t)PLAN_GROUPS * sizeof(uint32_t);
 
 struct PlanBlock {
     // head: what gs_lsb_plan_status returns
@@ -56,12 +64,19 @@ struct PlanBlock {
     uint32_t shift[4];                                     // digit position of each pass slot
     uint32_t ups_skip[4];                                  // the slot's upsweep has nothing to do (the look left slot 1's counts)
     MsbLevel level[2];                                     // [0]: the finish's task counts; [1]: read by the sample look
-    uint32_t wg_bad[PLAN_LOOK_MAX_GRID];                   // look: the workgroup's table does not add up (a counter wrapped)
+    union {
+        uint32_t wg_bad[PLAN_LOOK_MAX_GRID];               // look: the workgroup's table does not add up (a counter wrapped)
+        // the same words once the decision has read them, until the next look: [0] = tiles of the second scatter left to the
+        // follow-up kernel (cursor mode; set to 0 with the cursors), [1..] = which
+        uint32_t irr[1 + PLAN_IRR_CAP];
+    };
     uint32_t blk_total[PLAN_BLOCKS], blk_max[PLAN_BLOCKS], blk_nonempty[PLAN_BLOCKS];
     uint32_t blk_class[PLAN_BLOCKS][MSB_NCLASS];           // groups per local-sort class among the block's 512 groups
     uint32_t blk_class_base[PLAN_BLOCKS][MSB_NCLASS];      // the same, summed over the earlier blocks
     uint32_t offsets[PLAN_GROUPS + 1];                     // exclusive scan of the group sizes
+    uint32_t cursor_mode;                                  // this sort's second scatter claims its places with cursors
 };
+static_assert(1 + PLAN_IRR_CAP <= PLAN_LOOK_MAX_GRID, "the list of straddling tiles fits the look's flags");
 static_assert(sizeof(MsbLevel) == 64 && offsetof(PlanBlock, level) == 64, "plan block layout");
 
 __device__ __forceinline__ int plan_class_of(uint32_t size)
@@ -271,7 +286,7 @@ __global__ __launch_bounds__(RADIX) void lsb_plan_reduce_kernel(const uint32_t *
 // writes the decision: PLANNED if and only if no look workgroup reported a wrapped counter, the sizes add up to n and no
 // group exceeds the largest local sort.  The level records of the finish are (re)written here on every sort, so stale
 // lists of an earlier sort on the same workspace never run.
-__global__ __launch_bounds__(RADIX) void lsb_plan_decide_kernel(PlanBlock *__restrict__ plan, uint32_t n, uint32_t parts)
+__global__ __launch_bounds__(RADIX) void lsb_plan_decide_kernel(PlanBlock *__restrict__ plan, uint32_t n, uint32_t parts, uint32_t cursor_on)
 {
     __shared__ uint32_t s_base, s_total, s_max, s_nz, s_cls[MSB_NCLASS], s_clsbase[MSB_NCLASS];
     const uint32_t tid = threadIdx.x, b = blockIdx.x;
@@ -319,6 +334,7 @@ __global__ __launch_bounds__(RADIX) void lsb_plan_decide_kernel(PlanBlock *__res
             plan->ups_skip[q] = planned && q != 1 ? 1u : 0u;   // PLANNED: slot 1 scans and scatters on the look's counts
         }
         plan->offsets[PLAN_GROUPS] = n;
+        plan->cursor_mode = planned && cursor_on ? 1u : 0u;
     }
 }
 
@@ -378,6 +394,104 @@ __global__ __launch_bounds__(LSB_THREADS, 6) void lsb_plan_downsweep_kernel(cons
     downsweep_tile<false, TAIL, TW, BIG, false>(sm, t, keys_in, keys_out, nullptr, nullptr, spine, prefix16, totals, p, nullptr, 0u, nullptr);
 }
 
+// The second pass slot's own kernels.  They are the slot kernels above, and in cursor mode (PLANNED, see the top):
+//   upsweep   sets the cursors, laid out [d1][d2] so that a tile's claims are four 256-byte wave instructions, to the starts
+//             of the groups (d2, d1), and the list of straddling tiles to empty (its words are the look's flags, which the
+//             decide kernel's workgroups are still reading when the mode is written); no look at the keys;
+//   scatter   downsweep_tile in CURSOR mode on the full tiles; the partial tile's launch returns;
+//   irregular places the keys of the listed tiles (one workgroup each) and of the partial tile (the last workgroup), every
+//             key by an add of 1 on its group's cursor.  The keys of a wave that share a group share one add where that is
+//             cheap: the first two groups met are one add each (sorted input: one or two groups per tile).
+template <bool PLAIN>
+__global__ __launch_bounds__(LSB_THREADS, GS_EXP_UPS_WPE) void lsb_plan_upsweep2_kernel(const uint32_t *__restrict__ keys,
+                                                                        uint32_t *__restrict__ spine, uint16_t *__restrict__ prefix16,
+                                                                        PlanBlock *__restrict__ plan, uint32_t *__restrict__ cursor,
+                                                                        PassParams p)
+{
+    __shared__ UpsweepSmem<false, false> sm;
+    if (plan->cursor_mode) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) plan->irr[0] = 0;
+        for (uint32_t i = blockIdx.x * (uint32_t)LSB_THREADS + threadIdx.x; i < PLAN_GROUPS; i += gridDim.x * (uint32_t)LSB_THREADS)
+            cursor[i] = plan->offsets[((i & (uint32_t)(RADIX - 1)) << RADIX_BITS) | (i >> RADIX_BITS)];
+        return;
+    }
+    const uint32_t sh = plan->shift[1];
+    if (sh == PLAN_SKIP || plan->ups_skip[1]) return;
+    p.shift = sh;
+    upsweep_chunk<false, false, PLAIN>(sm, keys, chunk_of_block(blockIdx.x, p.grid), spine, prefix16, nullptr, nullptr, p, PipeParams{});
+}
+
+template <bool TAIL, bool BIG>
+__global__ __launch_bounds__(LSB_THREADS, 6) void lsb_plan_scatter2_kernel(const uint32_t *__restrict__ keys_in, uint32_t *__restrict__ keys_out,
+                                                                           const uint32_t *__restrict__ totals, const uint32_t *__restrict__ spine,
+                                                                           const uint16_t *__restrict__ prefix16, PlanBlock *__restrict__ plan,
+                                                                           uint32_t *__restrict__ cursor, PassParams p)
+{
+    __shared__ __attribute__((aligned(16))) DownsweepSmem<false> sm;
+    const uint32_t sh = plan->shift[1];
+    if (sh == PLAN_SKIP) return;
+    p.shift = sh;
+    const uint32_t full_tiles = p.n / (uint32_t)LSB_TILE;
+    const uint32_t mode = plan->cursor_mode;
+    if constexpr (TAIL) {
+        if (mode) return;
+        downsweep_tile<false, true, 2, true, false>(sm, full_tiles, keys_in, keys_out, nullptr, nullptr, spine, prefix16, totals, p, nullptr, 0u,
+                                                    nullptr);
+    } else {
+        if (blockIdx.x >= full_tiles) return;
+        const uint32_t t = tile_of_item_wide(blockIdx.x, full_tiles);
+        if (mode)
+            downsweep_tile<false, false, 0, BIG, false, false, true>(sm, t, keys_in, keys_out, nullptr, nullptr, spine, prefix16, totals, p,
+                                                                     nullptr, 0u, nullptr, threadIdx.x, nullptr, cursor, plan->irr, PLAN_IRR_CAP);
+        else
+            downsweep_tile<false, false, 0, BIG, false>(sm, t, keys_in, keys_out, nullptr, nullptr, spine, prefix16, totals, p, nullptr, 0u,
+                                                        nullptr);
+    }
+}
+
+__global__ __launch_bounds__(LSB_THREADS) void lsb_plan_irregular_kernel(const uint32_t *__restrict__ keys_in, uint32_t *__restrict__ keys_out,
+                                                                         const PlanBlock *__restrict__ plan, uint32_t *__restrict__ cursor,
+                                                                         uint32_t n)
+{
+    if (!plan->cursor_mode) return;
+    const uint32_t full_tiles = n / (uint32_t)LSB_TILE;
+    uint32_t lo, len;
+    if (blockIdx.x == PLAN_IRR_CAP) {
+        lo = full_tiles * (uint32_t)LSB_TILE;
+        len = n - lo;
+    } else {
+        const uint32_t listed = plan->irr[0] < PLAN_IRR_CAP ? plan->irr[0] : PLAN_IRR_CAP;
+        if (blockIdx.x >= listed) return;
+        const uint32_t t = plan->irr[1u + blockIdx.x];
+        if (t >= full_tiles) return;
+        lo = t * (uint32_t)LSB_TILE;
+        len = (uint32_t)LSB_TILE;
+    }
+    const int lane = lane_id();
+    // (whole waves enter every round: i - lane is the wave's first index)
+    for (uint32_t i = threadIdx.x; i - (uint32_t)lane < len; i += (uint32_t)LSB_THREADS) {
+        const bool have = i < len;
+        const uint32_t k = have ? keys_in[lo + i] : 0u;
+        const uint32_t g = k >> 16, c = ((g & (uint32_t)(RADIX - 1)) << RADIX_BITS) | (g >> RADIX_BITS);   // cursor of group (d2, d1): [d1][d2]
+        unsigned long long rest = __builtin_amdgcn_ballot_w64(have);
+        uint32_t at = 0;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (rest == 0ull) break;
+            const int lead = __builtin_amdgcn_readfirstlane(__builtin_ctzll(rest));
+            const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)c, lead);
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(have && c == c0) & rest;
+            uint32_t first = 0;
+            if (lane == lead) first = __hip_atomic_fetch_add(cursor + c0, (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            first = (uint32_t)__builtin_amdgcn_readlane((int)first, lead);
+            if ((m >> lane) & 1ull) at = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            rest &= ~m;
+        }
+        if ((rest >> lane) & 1ull) at = __hip_atomic_fetch_add(cursor + c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (have && at < n) keys_out[at] = k;
+    }
+}
+
 // ------------------------------------------------------------------- host --
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -386,6 +500,12 @@ static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline bool plan_enabled()
 {
     static const bool v = [] { const char *e = getenv("GS_LSB_KEYS_PLAN"); return !(e && strcmp(e, "classic") == 0); }();
+    return v;
+}
+// GS_LSB_PLAN_SCATTER2=cursor|stable (default cursor): stable = the second PLANNED scatter keeps its upsweep and its order.
+static inline bool plan_cursor_enabled()
+{
+    static const bool v = [] { const char *e = getenv("GS_LSB_PLAN_SCATTER2"); return !(e && strcmp(e, "stable") == 0); }();
     return v;
 }
 // N_MAX: 65536 groups of uniform keys are binomial with mean m = n / 65536 and deviation sqrt(m); the largest of 65536 such
@@ -428,6 +548,10 @@ static inline size_t plan_block_offset(uint64_t n)
     return align256(a > b ? a : b);
 }
 static inline size_t plan_temp_bytes(uint64_t n) { return plan_block_offset(n) + align256(sizeof(PlanBlock)); }
+// The cursors take the last 256 KiB below the plan block: inside the task lists' region (never below 1 MiB), which is written
+// only after the last slot, and above the spine and the totals, which the scans of the later slots rewrite.  What lies there
+// during the first scatter -- the last rows of prefix16 -- is dead once that scatter has run, and the cursors are set after it.
+static inline uint32_t *plan_cursors(char *base, uint64_t n) { return (uint32_t *)(base + plan_block_offset(n) - PLAN_CURSOR_BYTES); }
 
 template <int TW, bool BIG>
 static void launch_plan_downsweep(const uint32_t *kin, uint32_t *kout, const LsbWorkspace &ws, const uint32_t *slot_shift,
@@ -439,6 +563,8 @@ static void launch_plan_downsweep(const uint32_t *kin, uint32_t *kout, const Lsb
 
 // one pass slot: upsweep, scan, downsweep (+ the partial last tile); `real`: a slot that scatters on both routes;
 // `ups_real`: its upsweep counts on both routes too (slot 1's does so only when CLASSIC, which the host does not know)
+static int lsb_plan_slot2(const uint32_t *kin, uint32_t *kout, const LsbWorkspace &ws, PlanBlock *plan, uint32_t *cursor,
+                          const PassParams &p, hipStream_t s);
 static int lsb_plan_slot(const uint32_t *kin, uint32_t *kout, const LsbWorkspace &ws, const uint32_t *slot_shift,
                          const uint32_t *slot_ups_skip, const PassParams &p, bool real, bool ups_real, hipStream_t s)
 {
@@ -471,6 +597,40 @@ static int lsb_plan_slot(const uint32_t *kin, uint32_t *kout, const LsbWorkspace
     return (int)hipGetLastError();
 }
 
+// The second slot with the cursor switch on: the same three steps from the slot's own kernels, then the follow-up kernel.
+// Its upsweep launch counts only when CLASSIC (when PLANNED it sets the cursors), so it is timed with the other such launches.
+static int lsb_plan_slot2(const uint32_t *kin, uint32_t *kout, const LsbWorkspace &ws, PlanBlock *plan, uint32_t *cursor,
+                          const PassParams &p, hipStream_t s)
+{
+    if (p.f32_in || p.f32_out || p.xor_in || p.xor_out) return hipErrorInvalidValue;   // a middle pass: keys travel twiddled
+    if ((char *)cursor < (char *)ws.prefix16) return hipErrorInvalidValue;             // (never: see plan_cursors)
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(lsb_plan_upsweep2_kernel<true>, dim3(p.grid), dim3(LSB_THREADS), 0, s, kin, ws.spine, ws.prefix16, plan, cursor, p);
+    }
+    if (const int e = lsb_scan_as(ws.spine, ws.totals, p.grid, s, GS_K_LSB_SCAN)) return e;   // (cursor mode: nothing reads it)
+    {
+        KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
+        if (p.n >= (uint32_t)LSB_TILE) {
+            if (p.n > (1u << 30))
+                hipLaunchKernelGGL((lsb_plan_scatter2_kernel<false, true>), dim3(p.ds_grid), dim3(LSB_THREADS), 0, s, kin, kout, ws.totals,
+                                   ws.spine, ws.prefix16, plan, cursor, p);
+            else
+                hipLaunchKernelGGL((lsb_plan_scatter2_kernel<false, false>), dim3(p.ds_grid), dim3(LSB_THREADS), 0, s, kin, kout, ws.totals,
+                                   ws.spine, ws.prefix16, plan, cursor, p);
+        }
+        if (p.n % (uint32_t)LSB_TILE)
+            hipLaunchKernelGGL((lsb_plan_scatter2_kernel<true, true>), dim3(1), dim3(LSB_THREADS), 0, s, kin, kout, ws.totals,
+                               (const uint32_t *)nullptr, (const uint16_t *)nullptr, plan, cursor, p);
+    }
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(lsb_plan_irregular_kernel, dim3(PLAN_IRR_CAP + (p.n % (uint32_t)LSB_TILE ? 1u : 0u)), dim3(LSB_THREADS), 0, s, kin,
+                           kout, plan, cursor, p.n);
+    }
+    return (int)hipGetLastError();
+}
+
 // the look: one workgroup per CU at most, each with room for its 128 KiB table in the alternate buffer; its spine and
 // prefix16 are those of a pass at shift 16 (lsb_make_params' grid)
 static int lsb_plan_look(const uint32_t *keys, uint32_t *alt, const LsbWorkspace &ws, PlanBlock *plan, uint64_t n, const PassParams &tw,
@@ -482,7 +642,7 @@ static int lsb_plan_look(const uint32_t *keys, uint32_t *alt, const LsbWorkspace
     hipLaunchKernelGGL(lsb_plan_look_kernel, dim3(parts), dim3(PLAN_LOOK_THREADS), 0, s, keys, alt, plan, ws.spine, ws.prefix16, (uint32_t)n,
                        chunks, tw.f32_in, tw.xor_in);
     hipLaunchKernelGGL(lsb_plan_reduce_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, alt, plan, parts);
-    hipLaunchKernelGGL(lsb_plan_decide_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, plan, (uint32_t)n, parts);
+    hipLaunchKernelGGL(lsb_plan_decide_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, plan, (uint32_t)n, parts, plan_cursor_enabled() ? 1u : 0u);
     return (int)hipGetLastError();
 }
 
@@ -504,7 +664,11 @@ int lsb_plan_sort(char *base, uint32_t *d_keys[2], int *selector, uint64_t n, in
     for (int slot = 0; slot < 4; ++slot) {
         PassParams p = lsb_make_params(n, 0, RADIX_BITS);   // (the shift comes from the plan)
         lsb_twiddle_masks(key_type, descending, slot == 0, slot == 3, p);
-        if ((e = lsb_plan_slot(d_keys[sel], d_keys[sel ^ 1], ws, &plan->shift[slot], &plan->ups_skip[slot], p, slot < 2, slot == 1, s))) return e;
+        if (slot == 1 && plan_cursor_enabled())
+            e = lsb_plan_slot2(d_keys[sel], d_keys[sel ^ 1], ws, plan, plan_cursors(base, n), p, s);
+        else
+            e = lsb_plan_slot(d_keys[sel], d_keys[sel ^ 1], ws, &plan->shift[slot], &plan->ups_skip[slot], p, slot < 2, slot == 1, s);
+        if (e) return e;
         sel ^= 1;
     }
     {
@@ -540,6 +704,28 @@ int gs_lsb_plan_status(void *d_temp, uint64_t num_items, uint32_t out[8], void *
     hipError_t e = hipMemcpyAsync(out, plan, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     return (int)e;
+}
+
+// out[0]: the last sort's second scatter ran in cursor mode; out[1]: tiles its follow-up kernel placed (listed tiles and the
+// partial tile); out[2]: the listed tiles alone; out[3]: 0.  All 0 when the sort was CLASSIC or the switch says stable.
+int gs_lsb_plan_cursor_status(void *d_temp, uint64_t num_items, uint32_t out[4], void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (!d_temp || !out || num_items >= (1ull << 32)) return hipErrorInvalidValue;
+    memset(out, 0, 4 * sizeof(uint32_t));
+    if (!plan_enabled() || !plan_size_ok(num_items)) return hipSuccess;
+    const PlanBlock *plan = (const PlanBlock *)(gs_ws_base(d_temp) + plan_block_offset(num_items));
+    uint32_t w[2] = {0, 0};
+    hipError_t e = hipMemcpyAsync(&w[0], &plan->cursor_mode, sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&w[1], &plan->irr[0], sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    if (w[0] == 1u) {
+        out[0] = 1;
+        out[2] = w[1];
+        out[1] = w[1] + (num_items % (uint64_t)LSB_TILE ? 1u : 0u);
+    }
+    return hipSuccess;
 }
 
 int gs_lsb_plan_look_only(void *d_temp, const void *d_keys, void *d_alt, uint64_t num_items, int key_type, int descending, void *stream)

@@ -162,6 +162,12 @@ int  gs_lsb_pipe_status(void *d_temp, uint64_t num_items, uint32_t *h_status, vo
  * out[7] are those of the wrapped counters.  All zeros for sizes outside the plan's window and when
  * the plan is switched off.  Diagnostic: tests read it.                                           */
 int  gs_lsb_plan_status(void *d_temp, uint64_t num_items, uint32_t out[8], void *stream);
+/* How the second scatter of that sort ran, after synchronising `stream`: out[0] = 1 when it claimed
+ * its places with cursors and had no upsweep (route 1, unless GS_LSB_PLAN_SCATTER2=stable), out[1] =
+ * tiles that its follow-up kernel placed key by key (tiles that straddle two runs of the first
+ * scatter, and the partial last tile), out[2] = the straddling tiles alone, out[3] = 0.  All zeros
+ * on route 2, with the stable scatter and wherever gs_lsb_plan_status reports zeros.  Diagnostic.  */
+int  gs_lsb_plan_cursor_status(void *d_temp, uint64_t num_items, uint32_t out[4], void *stream);
 /* Test hooks of the keys-only plan.  gs_lsb_plan_look_only runs the look alone (the fused look, the
  * reduction of its tables and the decision) on a workspace of gs_lsb_temp_bytes(num_items) bytes and
  * returns without sorting: d_keys is read, the first num_items * 4 bytes of d_alt are scratch.  What

@@ -5,13 +5,16 @@ once per loaded library) -- and the two sort the same input alternately.  Per ca
 the repetitions), what the plan decided, and whether both routes return the same bytes.
 
     python tools/plan_window.py [--sizes 27,28,29,30,max] [--dists uniform,zipf,...] [--reps 5] [--profile] [--out FILE.json]
+                                [--versus classic|stable]
 
---profile adds the per-kernel-id device times (gs_profile_*) of one more sort per route."""
+--versus stable compares the plan as built (its second scatter in cursor mode) with the plan whose second scatter is the stable
+one (the copy's first sort sees GS_LSB_PLAN_SCATTER2=stable) instead of with the four passes.  --profile adds the per-kernel-id device times (gs_profile_*) of one more sort per route."""
 import argparse, ctypes as C, json, os, shutil, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ["GS_LSB_PLAN_MIN_ITEMS"] = "65536"
 os.environ.pop("GS_LSB_KEYS_PLAN", None)
+os.environ.pop("GS_LSB_PLAN_SCATTER2", None)
 import torch
 import gpu_sort_amd as gs
 
@@ -23,6 +26,7 @@ ap.add_argument("--dists", default="uniform")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--profile", action="store_true")
 ap.add_argument("--out", default=None)
+ap.add_argument("--versus", choices=["classic", "stable"], default="classic")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 gen = torch.Generator(device=dev); gen.manual_seed(1)
@@ -79,12 +83,14 @@ def sort(L, temp, nb, a, b, n, prof=None):
 w = gs.generate_uniform_keys(1 << 17, device=dev); wb = torch.empty_like(w)
 wt = torch.empty(plan_lib.gs_lsb_temp_bytes(1 << 17, 0), dtype=torch.uint8, device=dev)
 sort(plan_lib, wt, wt.numel(), w, wb, 1 << 17)
-os.environ["GS_LSB_KEYS_PLAN"] = "classic"
+OTHER = args.versus
+switch = ("GS_LSB_KEYS_PLAN", "classic") if OTHER == "classic" else ("GS_LSB_PLAN_SCATTER2", "stable")
+os.environ[switch[0]] = switch[1]
 classic_lib = bind(C.CDLL(copy))
 sort(classic_lib, wt, wt.numel(), w, wb, 1 << 17)
 torch.cuda.synchronize()
-os.environ.pop("GS_LSB_KEYS_PLAN")
-libs = (("plan", plan_lib), ("classic", classic_lib))
+os.environ.pop(switch[0])
+libs = (("plan", plan_lib), (OTHER, classic_lib))
 rows = []
 for size in args.sizes.split(","):
     n = N_MAX if size == "max" else 1 << int(size)
@@ -93,7 +99,7 @@ for size in args.sizes.split(","):
     temp = torch.empty(nb, dtype=torch.uint8, device=dev)
     for dist in args.dists.split(","):
         src = make(dist, n).contiguous()
-        ms = {"plan": [], "classic": []}
+        ms = {"plan": [], OTHER: []}
         status = (C.c_uint32 * 8)()
         same = None
         for rep in range(args.reps + 1):
@@ -112,7 +118,7 @@ for size in args.sizes.split(","):
         for name in ms:
             v = sorted(ms[name])
             row[name + "_ms"] = {"median": round(v[len(v) // 2], 4), "min": round(v[0], 4), "max": round(v[-1], 4)}
-        row["plan_over_classic"] = round(row["plan_ms"]["median"] / row["classic_ms"]["median"], 4)
+        row["plan_over_" + OTHER] = round(row["plan_ms"]["median"] / row[OTHER + "_ms"]["median"], 4)
         if args.profile:
             for name, L in libs:
                 prof = C.c_void_p(L.gs_profile_create())
