@@ -1,7 +1,7 @@
 """Partial sort: the first k elements of the stable sort, by radix select (gs_topk_u32 in include/gpusort.h).
 
 DeviceTopK is two-phase like DeviceRadixSort (d_temp_storage=None returns the size); topk() is the convenience form that
-allocates outputs and workspace.  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
+allocates outputs and workspace.  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
 (descending for the Max forms) on the same input: stable, keys in the caller's bit patterns, floats in the order of
 GS_KEY_F32 (negative NaNs first, positive NaNs last ascending; -0.0 before +0.0).
 """
@@ -106,4 +106,130 @@ def topk(keys, k, largest=False, values=None, indices=False, stream=None):
     if stream is not None:
         temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
     DeviceTopK._run(temp, nbytes, keys, keys_out, values, values_out, n, k, largest, has_values, stream, None)
+    return keys_out, values_out
+
+
+def _check_rows_in(t, what):
+    """An input matrix: a device tensor of 4-byte elements whose data_ptr() is row 0 (it may be a strided view, so its extent
+    is the caller's statement: (num_rows - 1) * row_stride + num_cols elements)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.element_size() != 4:
+        raise ValueError(f"{what}: expected a device tensor of 4-byte elements")
+
+
+class DeviceTopKRows:
+    """MinKeys / MaxKeys / MinPairs / MaxPairs for every row of a matrix: row r is d_keys_in[r * row_stride .. + num_cols)
+    (flat element offsets), and its k smallest (largest), sorted, go to d_keys_out[r * k .. + k) with their values.
+
+    d_values_in=None in the pairs forms writes the elements' column indices (u32 bit patterns).  Each row's result is what
+    DeviceTopK gives for that row alone.  The size query is 0 for a shape the entry point refuses (k > MaxK(), ...)."""
+
+    @staticmethod
+    def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols, row_stride,
+             k, descending, has_values, stream, key_type):
+        need = lib.gs_topk_rows_temp_bytes(num_rows, num_cols, k, int(has_values))
+        if d_temp_storage is None:
+            return need
+        if d_keys_in.element_size() != 4:
+            raise TypeError("DeviceTopKRows: 32-bit keys only")
+        key_type = _key_type_of(d_keys_in, key_type)
+        _check_rows_in(d_keys_in, "d_keys_in")
+        _check_buf(d_keys_out, num_rows * k, "d_keys_out")
+        if has_values:
+            if d_values_in is not None:
+                _check_rows_in(d_values_in, "d_values_in")
+            _check_buf(d_values_out, num_rows * k, "d_values_out")
+        err = lib.gs_topk_rows_u32(C.c_void_p(d_temp_storage.data_ptr()),
+                                   min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                   d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
+                                   d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
+                                   num_rows, num_cols, row_stride, k, int(descending), key_type, _stream_ptr(stream))
+        check(err, "gs_topk_rows_u32")
+        return need
+
+    @staticmethod
+    def MinKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_rows, num_cols, row_stride, k, stream=None,
+                key_type=None):
+        return DeviceTopKRows._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_rows, num_cols,
+                                   row_stride, k, False, False, stream, key_type)
+
+    @staticmethod
+    def MaxKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_rows, num_cols, row_stride, k, stream=None,
+                key_type=None):
+        return DeviceTopKRows._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_rows, num_cols,
+                                   row_stride, k, True, False, stream, key_type)
+
+    @staticmethod
+    def MinPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols,
+                 row_stride, k, stream=None, key_type=None):
+        return DeviceTopKRows._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows,
+                                   num_cols, row_stride, k, False, True, stream, key_type)
+
+    @staticmethod
+    def MaxPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols,
+                 row_stride, k, stream=None, key_type=None):
+        return DeviceTopKRows._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows,
+                                   num_cols, row_stride, k, True, True, stream, key_type)
+
+    @staticmethod
+    def MaxK():
+        return int(lib.gs_topk_rows_max_k())
+
+    @staticmethod
+    def Plan(num_rows, num_cols, k, has_values=False):
+        """gs_topk_rows_plan: [path, select levels, CH, chunks per row at level 0, candidates per row after level 0, max k,
+        0, 0]; a pure host function.  Raises for a refused shape."""
+        out = (C.c_uint32 * 8)()
+        check(lib.gs_topk_rows_plan(num_rows, num_cols, k, int(has_values), out), "gs_topk_rows_plan")
+        return [int(x) for x in out]
+
+
+def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
+    """The k smallest (largest=True: largest) of every row of the 2-D tensor `keys`, sorted, as (keys_out, values_out) of shape
+    [rows, k].
+
+    The last dimension must be contiguous; the rows may sit at any stride >= cols (a column slice of a wider matrix).
+    values: a 4-byte tensor of the same shape and strides, carried with the keys.  indices=True (without values): values_out
+    holds the column indices as int32 bit patterns of u32.  Neither: values_out is None.  Allocates outputs and workspace.
+    A k above DeviceTopKRows.MaxK() is served by gs_topk_u32 row by row."""
+    if values is not None and indices:
+        raise ValueError("topk_rows: give values or indices=True, not both")
+    if keys.dim() != 2:
+        raise ValueError("topk_rows: a 2-D tensor, not %d-D" % keys.dim())
+    rows, cols = keys.shape
+    if cols > 1 and keys.stride(1) != 1:
+        raise ValueError("topk_rows: the last dimension must be contiguous")
+    if not 0 <= k <= cols:
+        raise ValueError(f"topk_rows: need 0 <= k <= {cols}")
+    stride = keys.stride(0) if rows > 1 else cols
+    if rows > 1 and stride < cols:
+        raise ValueError("topk_rows: rows overlap (stride %d < %d columns)" % (stride, cols))
+    if values is not None and (values.shape != keys.shape or values.element_size() != 4 or
+                               (cols > 1 and values.stride(1) != 1) or (rows > 1 and values.stride(0) != stride)):
+        raise ValueError("topk_rows: values must have the keys' shape and strides and 4-byte elements")
+    if keys.element_size() != 4:
+        raise TypeError("topk_rows: 32-bit keys only")
+    has_values = values is not None or indices
+    keys_out = torch.empty((rows, k), dtype=keys.dtype, device=keys.device)
+    values_out = None
+    if has_values:
+        values_out = torch.empty((rows, k), dtype=values.dtype if values is not None else torch.int32, device=keys.device)
+    if k == 0 or rows == 0:
+        return keys_out, values_out
+    nbytes = lib.gs_topk_rows_temp_bytes(rows, cols, k, int(has_values))
+    if nbytes == 0 and k > lib.gs_topk_rows_max_k() and rows * stride < (1 << 32) and rows * k < (1 << 32):
+        # refused for k alone: the flat top k of every row, one call each on one workspace
+        nbytes = lib.gs_topk_temp_bytes(cols, k, int(has_values))
+        temp = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
+        if stream is not None:
+            temp.record_stream(stream)
+        for r in range(rows):
+            DeviceTopK._run(temp, nbytes, keys[r], keys_out[r], None if values is None else values[r],
+                            values_out[r] if has_values else None, cols, k, largest, has_values, stream, None)
+        return keys_out, values_out
+    if nbytes == 0:
+        raise ValueError("topk_rows: gs_topk_rows_u32 refuses this shape (rows * stride and rows * k must be below 2^32)")
+    temp = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
+    if stream is not None:
+        temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
+    DeviceTopKRows._run(temp, nbytes, keys, keys_out, values, values_out, rows, cols, stride, k, largest, has_values, stream, None)
     return keys_out, values_out

@@ -398,6 +398,54 @@ int    gs_topk_u32(void *d_temp, size_t temp_bytes,
  * benches read it.                                                                                                         */
 int    gs_topk_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream);
 
+/* ------------------------------------------------------- top k of every row --
+ * The k best of every row of a matrix (gs_topk_rows.hip): MoE routing, top-k sampling over a
+ * vocabulary, beam search, re-ranking.  Row r is d_keys_in[r * row_stride .. r * row_stride + num_cols) (the values of the
+ * pairs form use the same stride), and its result is exactly what gs_topk_u32 above writes for that row alone, bit for bit:
+ * the first k of the stable sort on key_type's 32-bit image (GS_KEY_U32 / I32 / F32; complemented when descending), the
+ * lowest column indices where the cut falls inside a run of equal keys, the caller's bit patterns kept (NaN payloads and the
+ * order of the GS_KEY_F32 note included).  Row r's result goes to d_keys_out[r * k .. r * k + k) and the same range of
+ * d_vals_out: the outputs are dense with stride k.  The three forms are gs_topk_u32's: keys only; pairs; arguments
+ * (d_vals_in == NULL, d_vals_out != NULL), where the value written is the element's column index within its row (u32).
+ * The contract is gs_topk_u32's: plain pointers, the inputs are never written (the stride gap is never read either),
+ * nothing outside [0, num_rows * k) of the outputs is written, d_temp anywhere, enqueue-only (no host read-back, allocation
+ * or synchronisation), the launches are a function of the arguments alone (gs_topk_rows_plan reports them), so the call may
+ * be captured into a HIP graph; calls may follow each other on one stream with one workspace; two runs give identical
+ * bytes.  num_rows == 0, num_cols == 0 or k == 0 returns 0, writes nothing and needs no workspace (the query returns 0).
+ * Errors (hipErrorInvalidValue, checked before anything is enqueued, nothing written; the size query returns 0 for a
+ * refused shape, the convention of gs_lsb_narrow_temp_bytes): k > num_cols, k > gs_topk_rows_max_k() (1024: such callers
+ * keep gs_topk_u32 per row), row_stride < num_cols, num_rows * row_stride >= 2^32, num_rows * k >= 2^32, a key_type other
+ * than GS_KEY_U32 / I32 / F32, d_vals_in without d_vals_out, a NULL key pointer, a NULL or too-small workspace, an array
+ * not aligned to 4 bytes, arrays that share a byte (inputs at (num_rows - 1) * row_stride + num_cols elements, outputs at
+ * num_rows * k).
+ * Paths, by num_cols alone: up to 1024 columns one wave sorts a row in registers and stores its first k (path 1); up to
+ * CH = 8192 one workgroup reads the row once, selects the k-th image by radix select in registers and LDS, compacts the k
+ * selected (key, column) pairs in input order and sorts them with one wave (path 2); longer rows are cut into chunks of CH
+ * columns, every chunk gives its first min(k, chunk length) as sorted (key, column) pairs to a candidate row in the
+ * workspace, and the same kernel runs over the candidate rows, level after level, until a row fits one chunk (path 3).
+ * Workspace: a pure host function of its arguments, a multiple of 256, monotone in each of them.  With
+ * next(n) = (ceil(n / CH) - 1) * k + min(k, n - (ceil(n / CH) - 1) * CH), the candidates a row of n elements leaves,
+ * n1 = next(num_cols) if num_cols > CH else 0, n2 = next(n1) if n1 > CH else 0, V = 2 with has_values else 1, and every term
+ * rounded up to 256 bytes:
+ *   V * 4 * num_rows * n1                     the candidate rows of the even levels: keys (and columns)
+ * + V * 4 * num_rows * n2                     the candidate rows of the odd levels (later levels are shorter and alternate)
+ * + 256 bytes of alignment slack.
+ * Paths 1 and 2 copy no element into the workspace (n1 = n2 = 0).                                                          */
+size_t   gs_topk_rows_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values);
+int      gs_topk_rows_u32(void *d_temp, size_t temp_bytes,
+                          const uint32_t *d_keys_in, const uint32_t *d_vals_in,
+                          uint32_t *d_keys_out, uint32_t *d_vals_out,
+                          uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k,
+                          int descending, int key_type, void *stream);
+uint32_t gs_topk_rows_max_k(void);
+/* What gs_topk_rows_u32 launches for a shape: a pure host function (no device, no workspace, no synchronisation).
+ * out[0] = path (1 = one wave per row, 2 = one workgroup per row, 3 = chunked), out[1] = select levels launched (1 on paths
+ * 1 and 2), out[2] = CH, the elements one workgroup selects from, out[3] = chunks per row at level 0, out[4] = candidates per
+ * row after level 0 (k on paths 1 and 2, n1 of the workspace formula on path 3), out[5] = gs_topk_rows_max_k(), out[6..7] = 0.
+ * A refused shape (k > num_cols, k > max_k, num_rows * num_cols >= 2^32, num_rows * k >= 2^32) returns hipErrorInvalidValue
+ * and all zeros; a no-op shape returns 0 and all zeros.                                                                    */
+int      gs_topk_rows_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint32_t out[8]);
+
 /* Census of the last gs_msb_sort_u32 that used d_temp (read back after synchronising `stream`): what every level
  * partitioned and what it handed to local sorts.  SURVEY.md 8d: the MSB path's algorithmic bytes are data-dependent --
  * "the harness must log the per-pass census and compute bytes from it": level 0 moves every key once (12 B/key), a level

@@ -271,6 +271,62 @@ struct DeviceTopK {
     }
 };
 
+// The k best of every row of a matrix (gs_topk_rows_u32): row r is d_keys_in[r * row_stride .. + num_cols), its result --
+// what DeviceTopK gives for that row alone -- goes to d_keys_out[r * k .. + k) and the same range of d_values_out.  The forms
+// and the two phases are DeviceTopK's; in the pairs forms d_values_in == nullptr writes the elements' column indices.  A size
+// query of 0 with a non-empty shape means the shape is refused (k > gs_topk_rows_max_k(), ...): such callers keep DeviceTopK
+// per row.
+struct DeviceTopKRows {
+    template <typename KeyT, typename ValueT>
+    static hipError_t Dispatch(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                               const ValueT *d_values_in, ValueT *d_values_out, uint64_t num_rows, uint64_t num_cols,
+                               uint64_t row_stride, uint64_t k, bool descending, hipStream_t stream)
+    {
+        static_assert(sizeof(KeyT) == 4 && KeyTraits<KeyT>::type <= GS_KEY_F32, "unsigned int, int or float keys");
+        static_assert(sizeof(ValueT) == 4, "32-bit values only");
+        const bool has_values = d_values_out != nullptr;
+        if (d_temp_storage == nullptr) {
+            temp_storage_bytes = gs_topk_rows_temp_bytes(num_rows, num_cols, k, has_values);
+            return hipSuccess;
+        }
+        return static_cast<hipError_t>(gs_topk_rows_u32(
+            d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint32_t *>(d_keys_in),
+            reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint32_t *>(d_keys_out),
+            reinterpret_cast<uint32_t *>(d_values_out), num_rows, num_cols, row_stride, k, descending ? 1 : 0, KeyTraits<KeyT>::type,
+            stream));
+    }
+    template <typename KeyT>
+    static hipError_t MinKeys(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                              uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, uint32_t>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, nullptr, nullptr, num_rows, num_cols,
+                                        row_stride, k, false, stream);
+    }
+    template <typename KeyT>
+    static hipError_t MaxKeys(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                              uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, uint32_t>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, nullptr, nullptr, num_rows, num_cols,
+                                        row_stride, k, true, stream);
+    }
+    template <typename KeyT, typename ValueT>
+    static hipError_t MinPairs(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                               const ValueT *d_values_in, ValueT *d_values_out, uint64_t num_rows, uint64_t num_cols,
+                               uint64_t row_stride, uint64_t k, hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, ValueT>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows,
+                                      num_cols, row_stride, k, false, stream);
+    }
+    template <typename KeyT, typename ValueT>
+    static hipError_t MaxPairs(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                               const ValueT *d_values_in, ValueT *d_values_out, uint64_t num_rows, uint64_t num_cols,
+                               uint64_t row_stride, uint64_t k, hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, ValueT>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows,
+                                      num_cols, row_stride, k, true, stream);
+    }
+};
+
 // The stable sort of 2^32 elements and more (gs_lsb_sort_large, num_items < 2^40): DeviceRadixSort's DoubleBuffer overloads
 // with a uint64_t count, for 32- or 64-bit keys with no, 32-bit or 64-bit values, and (gs_lsb_sort_narrow_large) 8- and 16-bit
 // keys with no values or values of 1, 2, 4, 8 or 16 bytes, whose result lands in the alternate buffer.  A struct of its own rather than uint64_t
