@@ -11,6 +11,7 @@ import torch
 
 import topk_ref as R
 from guarded import Arena
+from topk_cases import DISTS, gen
 
 pytestmark = pytest.mark.gpu
 
@@ -23,40 +24,6 @@ ROUTES_SEEN = set()
 
 
 # ------------------------------------------------------------------------------------------------------- inputs --
-def gen(kind, n, seed=1, kt=U32):
-    rng = np.random.default_rng(seed * 1000003 + n)
-    if kind == "uniform":
-        k = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
-    elif kind == "equal":
-        k = np.full(n, 0x3F800000, np.uint32)
-    elif kind == "five":
-        k = np.array([0x00000007, 0x3F800000, 0x3F800001, 0xBF800000, 0xFFFFFFF0], np.uint32)[rng.integers(0, 5, n)]
-    elif kind == "topbyte":      # one top byte, random low bytes: rounds two to four do real work on the input itself
-        k = (rng.integers(0, 1 << 24, n, dtype=np.uint64).astype(np.uint32)) | np.uint32(0x42000000)
-    elif kind == "top3":         # the top three bytes shared
-        k = (rng.integers(0, 256, n, dtype=np.uint64).astype(np.uint32)) | np.uint32(0xC1A25500)
-    elif kind == "zipf":
-        k = (rng.zipf(1.3, size=n).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15) >> np.uint64(13)).astype(np.uint32)
-    elif kind == "sorted":
-        k = np.sort(rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32))
-    elif kind == "reversed":
-        k = np.sort(rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32))[::-1].copy()
-    elif kind == "special":      # the special sets of test_lsb_large_gpu.py, mixed into random keys
-        if kt == F32:
-            tiny = np.finfo(np.float32).smallest_subnormal
-            sp = np.array([0.0, -0.0, np.inf, -np.inf, tiny, -tiny, 1.5, -1.5, np.nan, -np.nan], np.float32).view(np.uint32)
-            sp = np.concatenate([sp, np.array([0x7FC00001], np.uint32)])      # a NaN payload
-        else:
-            mx = np.uint32(0xFFFFFFFF)
-            sp = np.array([0, 1, mx, mx - 1, mx >> 1, (mx >> 1) + 1], np.uint32)   # MIN, MAX, -1, 0 of the signed type
-        k = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
-        pick = rng.random(n) < 0.6
-        k[pick] = sp[rng.integers(0, sp.size, int(pick.sum()))]
-    else:
-        raise ValueError(kind)
-    return np.ascontiguousarray(k, dtype=np.uint32)
-
-
 def dev(a, cuda):
     return torch.from_numpy(np.ascontiguousarray(a).view(np.int32).copy()).to(cuda)
 
@@ -126,9 +93,6 @@ def test_sizes_and_k_values(gs, cuda, n):
 
 
 # ------------------------------------------------------------------------------------------------ distributions --
-DISTS = ["uniform", "equal", "five", "topbyte", "top3", "zipf", "sorted", "reversed", "special"]
-
-
 @pytest.mark.parametrize("kind", DISTS)
 def test_distributions_directions_forms_types(gs, cuda, kind):
     """Every distribution in both directions, the three forms and the three key types, at a size past the candidate list's

@@ -12,7 +12,7 @@ import torch
 import topk_ref as R
 import topk_rows_ref as RR
 from guarded import Arena
-from test_topk_gpu import DISTS, gen
+from topk_cases import DISTS, gen
 
 pytestmark = pytest.mark.gpu
 

@@ -3,7 +3,8 @@
 Every builder lays out IMAGES -- the order-preserving u32 words the kernels select on -- and returns the keys that have those
 images for the given key type and direction (topk_ref.preimage).  So the top-byte buckets, the tile layout and the k-th image
 are the same whatever the type and direction, and test_topk_edges_cpu.py holds each case to its intent (route, bucket size,
-cut) with the numpy reference alone, before a device sees it."""
+cut) with the numpy reference alone, before a device sees it.  gen() and DISTS are the exception: the distributions of key
+words that tests/test_topk_gpu.py and the rows tests mix across their inputs, kept here so that no builder imports a GPU file."""
 import numpy as np
 
 import topk_ref as R
@@ -38,6 +39,45 @@ def _low24(rng, count):
 
 def _keys(img, key_type, descending):
     return R.preimage(_u32(img), key_type, descending)
+
+
+# ------------------------------------------------------------------------------------ distributions of key words --
+DISTS = ["uniform", "equal", "five", "topbyte", "top3", "zipf", "sorted", "reversed", "special"]
+
+
+def gen(kind, n, seed=1, kt=U32):
+    """n key words (not images) of distribution `kind`: what tests/test_topk_gpu.py and the rows tests mix across their inputs."""
+    rng = np.random.default_rng(seed * 1000003 + n)
+    if kind == "uniform":
+        k = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    elif kind == "equal":
+        k = np.full(n, 0x3F800000, np.uint32)
+    elif kind == "five":
+        k = np.array([0x00000007, 0x3F800000, 0x3F800001, 0xBF800000, 0xFFFFFFF0], np.uint32)[rng.integers(0, 5, n)]
+    elif kind == "topbyte":      # one top byte, random low bytes: rounds two to four do real work on the input itself
+        k = (rng.integers(0, 1 << 24, n, dtype=np.uint64).astype(np.uint32)) | np.uint32(0x42000000)
+    elif kind == "top3":         # the top three bytes shared
+        k = (rng.integers(0, 256, n, dtype=np.uint64).astype(np.uint32)) | np.uint32(0xC1A25500)
+    elif kind == "zipf":
+        k = (rng.zipf(1.3, size=n).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15) >> np.uint64(13)).astype(np.uint32)
+    elif kind == "sorted":
+        k = np.sort(rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32))
+    elif kind == "reversed":
+        k = np.sort(rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32))[::-1].copy()
+    elif kind == "special":      # the special sets of test_lsb_large_gpu.py, mixed into random keys
+        if kt == F32:
+            tiny = np.finfo(np.float32).smallest_subnormal
+            sp = np.array([0.0, -0.0, np.inf, -np.inf, tiny, -tiny, 1.5, -1.5, np.nan, -np.nan], np.float32).view(np.uint32)
+            sp = np.concatenate([sp, np.array([0x7FC00001], np.uint32)])      # a NaN payload
+        else:
+            mx = np.uint32(0xFFFFFFFF)
+            sp = np.array([0, 1, mx, mx - 1, mx >> 1, (mx >> 1) + 1], np.uint32)   # MIN, MAX, -1, 0 of the signed type
+        k = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+        pick = rng.random(n) < 0.6
+        k[pick] = sp[rng.integers(0, sp.size, int(pick.sum()))]
+    else:
+        raise ValueError(kind)
+    return np.ascontiguousarray(k, dtype=np.uint32)
 
 
 # ------------------------------------------------------------------------------------------- plain distributions --
