@@ -10,7 +10,7 @@ Names follow the reference:
   SortPairsDescending           (lsb/cub/cub/device/device_radix_sort.cuh)
   DeviceRadixSortLarge          (the same four, stable, for 2^32 elements and more)
   DeviceTopK, topk              (the first k elements of the stable sort, by radix select; no reference counterpart)
-  DeviceTopKRows, topk_rows     (the same for every row of a matrix)
+  DeviceTopKRows, topk_rows     (the same for every row of a matrix; 32-bit keys, and int16 / uint16 / float16 / bfloat16)
   sortKeysGPU / sortPairsGPU    (lsb/sort.cu:25-76)
   rdxsrt_unstable_sort, rdxsrt_unstable_sort_keys/_pairs, RDXSRT_SortedSequence
                                 (msb/src/sort/gpu_radix_sort.h:31-34,197,511,544)

@@ -70,6 +70,8 @@ SIGNATURES = {
     "gs_topk_rows_u32": (i32, [vp, sz, vp, vp, vp, vp, u64, u64, u64, u64, i32, i32, vp]),
     "gs_topk_rows_max_k": (C.c_uint32, []),
     "gs_topk_rows_plan": (i32, [u64, u64, u64, i32, C.POINTER(C.c_uint32)]),
+    "gs_topk_rows_u16_temp_bytes": (sz, [u64, u64, u64, i32]),
+    "gs_topk_rows_u16": (i32, [vp, sz, vp, vp, vp, vp, u64, u64, u64, u64, i32, i32, vp]),
     "gs_msb_census": (i32, [vp, u64, i32, vp, vp]),
     "gs_msb_wide_census": (i32, [vp, u64, i32, i32, vp, vp]),
     "gs_msb_capacities": (None, [u64, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -24,61 +24,11 @@
 #include "gs_device.hpp"
 #include "gs_host.hpp"
 
+// the geometry, the wave sort, the select and the compaction (wave_sort_bits, tr_select, tr_compact: here on all 32 bits) and
+// the host's plan: shared with gs_topk_rows_narrow.hip
+#include "gs_topk_rows.inc"
+
 namespace gs {
-
-constexpr int TR_THREADS = 512;                  // 8 waves
-constexpr int TR_WAVES = TR_THREADS / WAVE;
-constexpr int TR_KPT = 16;
-constexpr uint32_t TR_CH = TR_THREADS * TR_KPT;  // 8192: the elements one workgroup selects from
-constexpr uint32_t TR_MAX_K = 1024;              // what one wave sorts: 16 per lane
-constexpr uint32_t TR_WAVE_COLS = 1024;          // longest row of path 1
-static_assert(TR_MAX_K <= TR_CH && TR_MAX_K == 16 * WAVE, "a chunk gives up to k sorted by one wave");
-
-// One wave: the stable LSD sort, on all 32 bits, of WKPT * 64 (image, value) pairs in registers; element i * 64 + lane is
-// key[i].  The passes of gs_seg_wave_body.inc: per-digit ranks by match_digit, the wave's own 256 counters, a scan of 4 per
-// lane, and a trip through the wave's staging rows.  All 64 lanes must be active.
-template <int WKPT, bool HV>
-__device__ __forceinline__ void wave_sort32(uint32_t (&key)[WKPT], uint32_t (&val)[HV ? WKPT : 1], uint32_t *__restrict__ my,
-                                            uint32_t *__restrict__ sk, uint32_t *__restrict__ sv)
-{
-    const int lane = lane_id();
-    auto fence = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
-    for (uint32_t sh = 0; sh < 32u; sh += (uint32_t)RADIX_BITS) {
-        uint32_t pos[WKPT];
-        reinterpret_cast<uint4 *>(my)[lane] = make_uint4(0u, 0u, 0u, 0u);
-        fence();
-#pragma unroll
-        for (int i = 0; i < WKPT; ++i) {
-            const uint32_t d = __builtin_amdgcn_ubfe(key[i], sh, RADIX_BITS);
-            uint32_t lo, hi;
-            match_digit(d, lo, hi);
-            const uint32_t lower = count_lower(lo, hi);
-            pos[i] = my[d] + lower;
-            if (lower == 0) my[d] += (uint32_t)(__popc(lo) + __popc(hi));   // one lane per digit: no two writers of a word
-            fence();
-        }
-        {   // exclusive scan of the 256 counters, 4 per lane
-            const uint4 c = reinterpret_cast<const uint4 *>(my)[lane];
-            const uint32_t sum = c.x + c.y + c.z + c.w;
-            const uint32_t ex = wave_inclusive_scan(sum) - sum;
-            reinterpret_cast<uint4 *>(my)[lane] = make_uint4(ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z);
-        }
-        fence();
-#pragma unroll
-        for (int i = 0; i < WKPT; ++i) {
-            const uint32_t at = pos[i] + my[__builtin_amdgcn_ubfe(key[i], sh, RADIX_BITS)];
-            sk[at] = key[i];
-            if (HV) sv[at] = val[i];
-        }
-        fence();
-#pragma unroll
-        for (int i = 0; i < WKPT; ++i) {
-            key[i] = sk[i * WAVE + lane];
-            if (HV) val[i] = sv[i * WAVE + lane];
-        }
-        fence();
-    }
-}
 
 // ------------------------------------------------------------------ path 1 --
 // One wave per row of up to WKPT * 64 columns, four rows per workgroup; waves past the last row leave (no barrier follows).
@@ -108,7 +58,7 @@ __global__ __launch_bounds__(256) void topk_rows_wave_kernel(const uint32_t *__r
         key[i] = idx < cols ? twiddle_in(key[i], f32, x) : 0xffffffffu;   // pads: last in position, largest in every digit
         if (HV) val[i] = idx;
     }
-    wave_sort32<WKPT, HV>(key, val, hist[w], stage_k[w], stage_v[HV ? w : 0]);
+    wave_sort_bits<32, WKPT, HV>(key, val, hist[w], stage_k[w], stage_v[HV ? w : 0]);
 #pragma unroll
     for (int i = 0; i < WKPT; ++i) {
         const uint32_t idx = (uint32_t)(i * WAVE + lane);
@@ -156,65 +106,10 @@ __global__ __launch_bounds__(TR_THREADS) void topk_rows_block_kernel(const uint3
 #pragma unroll
     for (int u = 0; u < TR_KPT; ++u) img[u] = twiddle_in(img[u], f32, x);
 
-    // radix select of the keff-th image, most significant byte first, on the registers
-    uint32_t prefix = 0, less = 0, krem = keff;
-    for (uint32_t shift = 24u;; shift -= 8u) {
-        const uint32_t mask = 0xffffff00u << shift;   // the bytes above this one (none in the first round)
-        if (tid < (uint32_t)RADIX) h[tid] = 0;
-        __syncthreads();
-        uint32_t lenv = len;
-        asm volatile("" : "+v"(lenv));   // compare again each round: sixteen range masks kept across the rounds would not fit the SGPRs
-#pragma unroll
-        for (int u = 0; u < TR_KPT; ++u) {
-            const uint32_t j = first + (uint32_t)u * WAVE;
-            if (j < lenv && ((img[u] ^ prefix) & mask) == 0u) hist_add(h, (img[u] >> shift) & 255u);
-        }
-        __syncthreads();
-        const uint32_t cnt = tid < (uint32_t)RADIX ? h[tid] : 0u;
-        const uint32_t ex = block_exclusive_scan_256(cnt, scratch, nullptr);
-        if (tid < (uint32_t)RADIX && ex < krem && krem - ex <= cnt) {
-            sel[0] = prefix | (tid << shift);
-            sel[1] = less + ex;
-            sel[2] = krem - ex;
-        }
-        __syncthreads();
-        prefix = sel[0]; less = sel[1]; krem = sel[2];
-        if (shift == 0u) break;
-    }
-    const uint32_t kth = prefix;   // less + krem == keff: the tie run is cut at keff
-
-    // ordered two-group compaction into LDS: group A (before the k-th image) at [0, less), group B (equal to it) behind,
-    // cut after `take`; (wave, row, lane) is input order
-    uint32_t nA = 0, nB = 0, lenc = len;
-    asm volatile("" : "+v"(lenc));   // (range compares again, as in the select rounds; once more before the scatter loop)
-#pragma unroll
-    for (int u = 0; u < TR_KPT; ++u) {
-        const uint32_t j = first + (uint32_t)u * WAVE;
-        nA += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(j < lenc && img[u] < kth));
-        nB += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(j < lenc && img[u] == kth));
-    }
-    if (lane == 0) { wcnt[0][w] = nA; wcnt[1][w] = nB; }
-    __syncthreads();
-    uint32_t baseA = 0, baseB = less;
-    for (uint32_t q = 0; q < w; ++q) { baseA += wcnt[0][q]; baseB += wcnt[1][q]; }
-    if (baseA < less || baseB < keff) {   // wave-uniform: this wave still has something to place
-        asm volatile("" : "+v"(lenc));
-#pragma unroll
-        for (int u = 0; u < TR_KPT; ++u) {
-            const uint32_t j = first + (uint32_t)u * WAVE;
-            asm volatile("" : "+v"(img[u]));   // ballot again: 32 masks kept from the counting loop would not fit the SGPRs
-            const bool a = j < lenc && img[u] < kth, b = j < lenc && img[u] == kth;
-            const unsigned long long mA = __builtin_amdgcn_ballot_w64(a), mB = __builtin_amdgcn_ballot_w64(b);
-            const uint32_t pos = a ? baseA + count_lower(mA) : baseB + count_lower(mB);
-            if ((a || b) && pos < keff && pos < (uint32_t)CAP) {   // (group A never passes `less`; group B is cut at keff = less + take)
-                stage_k[pos] = img[u];
-                if (HV) stage_v[pos] = SRC_IDX ? src_i[base + j] : lo + j;
-            }
-            baseA += (uint32_t)__popcll(mA);
-            baseB += (uint32_t)__popcll(mB);
-        }
-    }
-    __syncthreads();
+    // radix select of the keff-th image on the registers, then the ordered compaction of the keff selected pairs into LDS
+    uint32_t less;
+    const uint32_t kth = tr_select<32>(img, first, len, keff, tid, h, scratch, sel, less);
+    tr_compact<HV, SRC_IDX, CAP>(img, first, len, keff, kth, less, w, lane, wcnt, stage_k, stage_v, SRC_IDX ? src_i + base : nullptr, lo);
 
     // finish: one wave sorts the keff staged pairs and stores them
     if (w != 0) return;
@@ -225,7 +120,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_rows_block_kernel(const uint3
         key[i] = idx < keff ? stage_k[idx] : 0xffffffffu;   // pads: last in position, largest in every digit
         if (HV) val[i] = idx < keff ? stage_v[idx] : 0u;
     }
-    wave_sort32<WKPT, HV>(key, val, h, sort_k, sort_v);
+    wave_sort_bits<32, WKPT, HV>(key, val, h, sort_k, sort_v);
     const size_t out0 = (size_t)r * dst_stride + (size_t)c * k;
 #pragma unroll
     for (int i = 0; i < WKPT; ++i) {
@@ -241,54 +136,6 @@ __global__ __launch_bounds__(TR_THREADS) void topk_rows_block_kernel(const uint3
 }
 
 // ------------------------------------------------------------------------- host --
-struct RowsPlan {
-    uint32_t path, levels, chunks0, cand0;
-    uint64_t n[12];         // n[i]: elements per (candidate) row that level i reads
-};
-
-static inline uint64_t tr_next(uint64_t n, uint64_t k)
-{
-    const uint64_t ch = (n + TR_CH - 1) / TR_CH, tail = n - (ch - 1) * TR_CH;
-    return (ch - 1) * k + (k < tail ? k : tail);
-}
-
-static inline bool tr_mul_ge_2p32(uint64_t a, uint64_t b) { return a != 0 && b > 0xffffffffull / a; }
-
-// shape refusals shared by the plan, the size query and the call (row_stride is the call's own)
-static bool tr_shape_ok(uint64_t rows, uint64_t cols, uint64_t k)
-{
-    if (k > cols || k > TR_MAX_K) return false;
-    if (tr_mul_ge_2p32(rows, cols) || tr_mul_ge_2p32(rows, k)) return false;
-    return true;
-}
-
-static void tr_make_plan(uint64_t cols, uint64_t k, RowsPlan *p)
-{
-    *p = RowsPlan{};
-    p->n[0] = cols;
-    p->levels = 1;
-    p->chunks0 = 1;
-    p->cand0 = (uint32_t)k;
-    if (cols <= TR_WAVE_COLS) { p->path = 1; return; }
-    if (cols <= TR_CH) { p->path = 2; return; }
-    p->path = 3;
-    p->chunks0 = (uint32_t)((cols + TR_CH - 1) / TR_CH);
-    while (p->n[p->levels - 1] > TR_CH) {   // every level shrinks a full chunk from TR_CH to k <= TR_CH / 8: at most 5 levels below 2^32
-        p->n[p->levels] = tr_next(p->n[p->levels - 1], k);
-        ++p->levels;
-    }
-    p->cand0 = (uint32_t)p->n[1];
-}
-
-static inline size_t tr_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static bool tr_overlaps(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    if (!a || !b || !abytes || !bbytes) return false;
-    const char *p = (const char *)a, *q = (const char *)b;
-    return p < q + bbytes && q < p + abytes;
-}
-
 template <int WKPT, bool HV>
 static void tr_launch_wave(hipStream_t s, const uint32_t *ki, const uint32_t *vi, uint32_t *ko, uint32_t *vo, uint32_t rows, uint32_t cols,
                            uint32_t stride, uint32_t k, int f32, uint32_t x)

@@ -1,7 +1,8 @@
 """Partial sort: the first k elements of the stable sort, by radix select (gs_topk_u32 in include/gpusort.h).
 
 DeviceTopK is two-phase like DeviceRadixSort (d_temp_storage=None returns the size); topk() is the convenience form that
-allocates outputs and workspace.  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
+allocates outputs and workspace.  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
+gs_topk_rows_u16 for int16 / uint16 / float16 / bfloat16 keys, in the order of GS_KEY_F16 / BF16 at the enum).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
 (descending for the Max forms) on the same input: stable, keys in the caller's bit patterns, floats in the order of
 GS_KEY_F32 (negative NaNs first, positive NaNs last ascending; -0.0 before +0.0).
 """
@@ -109,11 +110,23 @@ def topk(keys, k, largest=False, values=None, indices=False, stream=None):
     return keys_out, values_out
 
 
-def _check_rows_in(t, what):
-    """An input matrix: a device tensor of 4-byte elements whose data_ptr() is row 0 (it may be a strided view, so its extent
-    is the caller's statement: (num_rows - 1) * row_stride + num_cols elements)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.element_size() != 4:
-        raise ValueError(f"{what}: expected a device tensor of 4-byte elements")
+_NARROW16 = (_lib.GS_KEY_U16, _lib.GS_KEY_I16, _lib.GS_KEY_F16, _lib.GS_KEY_BF16)     # what gs_topk_rows_u16 takes
+
+
+def _check_rows_in(t, what, elem=4):
+    """An input matrix: a device tensor of `elem`-byte elements whose data_ptr() is row 0 (it may be a strided view, so its
+    extent is the caller's statement: (num_rows - 1) * row_stride + num_cols elements)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.element_size() != elem:
+        raise ValueError(f"{what}: expected a device tensor of {elem}-byte elements")
+
+
+def _key_type16_of(t, key_type):
+    if key_type is None:
+        key_type = _KEY_TYPES.get(t.dtype)
+    if key_type not in _NARROW16:
+        raise TypeError(f"DeviceTopKRows: no 16-bit key category for {t.dtype} (int16, uint16, float16, bfloat16, or GS_KEY_U16 / "
+                        "I16 / F16 / BF16 by key_type)")
+    return key_type
 
 
 class DeviceTopKRows:
@@ -121,16 +134,24 @@ class DeviceTopKRows:
     (flat element offsets), and its k smallest (largest), sorted, go to d_keys_out[r * k .. + k) with their values.
 
     d_values_in=None in the pairs forms writes the elements' column indices (u32 bit patterns).  Each row's result is what
-    DeviceTopK gives for that row alone.  The size query is 0 for a shape the entry point refuses (k > MaxK(), ...)."""
+    DeviceTopK gives for that row alone.  The size query is 0 for a shape the entry point refuses (k > MaxK(), ...).
+
+    2-byte key tensors (int16, uint16, float16, bfloat16, or an explicit 16-bit key_type) go to gs_topk_rows_u16: the same
+    definition on the 16-bit image, values still 4 bytes.  The size query (d_temp_storage=None) sees no tensor: with a 16-bit
+    key_type it answers for gs_topk_rows_u16, without one for gs_topk_rows_u32, which is never the smaller of the two."""
 
     @staticmethod
     def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols, row_stride,
              k, descending, has_values, stream, key_type):
-        need = lib.gs_topk_rows_temp_bytes(num_rows, num_cols, k, int(has_values))
+        narrow = key_type in _NARROW16 if d_temp_storage is None or key_type is not None else d_keys_in.element_size() == 2
+        need = (lib.gs_topk_rows_u16_temp_bytes if narrow else lib.gs_topk_rows_temp_bytes)(num_rows, num_cols, k, int(has_values))
         if d_temp_storage is None:
             return need
+        if narrow:
+            return DeviceTopKRows._run16(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out,
+                                         num_rows, num_cols, row_stride, k, descending, has_values, stream, key_type, need)
         if d_keys_in.element_size() != 4:
-            raise TypeError("DeviceTopKRows: 32-bit keys only")
+            raise TypeError("DeviceTopKRows: 32-bit keys, or 16-bit keys with a 16-bit key type")
         key_type = _key_type_of(d_keys_in, key_type)
         _check_rows_in(d_keys_in, "d_keys_in")
         _check_buf(d_keys_out, num_rows * k, "d_keys_out")
@@ -144,6 +165,26 @@ class DeviceTopKRows:
                                    d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
                                    num_rows, num_cols, row_stride, k, int(descending), key_type, _stream_ptr(stream))
         check(err, "gs_topk_rows_u32")
+        return need
+
+    @staticmethod
+    def _run16(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols, row_stride,
+               k, descending, has_values, stream, key_type, need):
+        if d_keys_in.element_size() != 2:
+            raise TypeError("DeviceTopKRows: a 16-bit key_type needs 2-byte keys")
+        key_type = _key_type16_of(d_keys_in, key_type)
+        _check_rows_in(d_keys_in, "d_keys_in", 2)
+        _check_buf(d_keys_out, num_rows * k, "d_keys_out", 2)
+        if has_values:
+            if d_values_in is not None:
+                _check_rows_in(d_values_in, "d_values_in")
+            _check_buf(d_values_out, num_rows * k, "d_values_out")
+        err = lib.gs_topk_rows_u16(C.c_void_p(d_temp_storage.data_ptr()),
+                                   min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                   d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
+                                   d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
+                                   num_rows, num_cols, row_stride, k, int(descending), key_type, _stream_ptr(stream))
+        check(err, "gs_topk_rows_u16")
         return need
 
     @staticmethod
@@ -190,7 +231,8 @@ def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
     The last dimension must be contiguous; the rows may sit at any stride >= cols (a column slice of a wider matrix).
     values: a 4-byte tensor of the same shape and strides, carried with the keys.  indices=True (without values): values_out
     holds the column indices as int32 bit patterns of u32.  Neither: values_out is None.  Allocates outputs and workspace.
-    A k above DeviceTopKRows.MaxK() is served by gs_topk_u32 row by row."""
+    A k above DeviceTopKRows.MaxK() is served by gs_topk_u32 row by row.  2-byte keys (int16, uint16, float16, bfloat16) take
+    gs_topk_rows_u16; for them a k above MaxK() raises ValueError: there is no flat 16-bit top-k to loop over."""
     if values is not None and indices:
         raise ValueError("topk_rows: give values or indices=True, not both")
     if keys.dim() != 2:
@@ -206,8 +248,13 @@ def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
     if values is not None and (values.shape != keys.shape or values.element_size() != 4 or
                                (cols > 1 and values.stride(1) != 1) or (rows > 1 and values.stride(0) != stride)):
         raise ValueError("topk_rows: values must have the keys' shape and strides and 4-byte elements")
-    if keys.element_size() != 4:
-        raise TypeError("topk_rows: 32-bit keys only")
+    narrow = keys.element_size() == 2
+    if narrow:
+        _key_type16_of(keys, None)
+        if k > lib.gs_topk_rows_max_k():
+            raise ValueError("topk_rows: 16-bit keys need k <= %d" % lib.gs_topk_rows_max_k())
+    elif keys.element_size() != 4:
+        raise TypeError("topk_rows: 32-bit or 16-bit keys only")
     has_values = values is not None or indices
     keys_out = torch.empty((rows, k), dtype=keys.dtype, device=keys.device)
     values_out = None
@@ -215,8 +262,8 @@ def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
         values_out = torch.empty((rows, k), dtype=values.dtype if values is not None else torch.int32, device=keys.device)
     if k == 0 or rows == 0:
         return keys_out, values_out
-    nbytes = lib.gs_topk_rows_temp_bytes(rows, cols, k, int(has_values))
-    if nbytes == 0 and k > lib.gs_topk_rows_max_k() and rows * stride < (1 << 32) and rows * k < (1 << 32):
+    nbytes = (lib.gs_topk_rows_u16_temp_bytes if narrow else lib.gs_topk_rows_temp_bytes)(rows, cols, k, int(has_values))
+    if nbytes == 0 and not narrow and k > lib.gs_topk_rows_max_k() and rows * stride < (1 << 32) and rows * k < (1 << 32):
         # refused for k alone: the flat top k of every row, one call each on one workspace
         nbytes = lib.gs_topk_temp_bytes(cols, k, int(has_values))
         temp = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
@@ -227,7 +274,7 @@ def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
                             values_out[r] if has_values else None, cols, k, largest, has_values, stream, None)
         return keys_out, values_out
     if nbytes == 0:
-        raise ValueError("topk_rows: gs_topk_rows_u32 refuses this shape (rows * stride and rows * k must be below 2^32)")
+        raise ValueError("topk_rows: the entry point refuses this shape (rows * stride and rows * k must be below 2^32)")
     temp = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
     if stream is not None:
         temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it

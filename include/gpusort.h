@@ -438,13 +438,53 @@ int      gs_topk_rows_u32(void *d_temp, size_t temp_bytes,
                           uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k,
                           int descending, int key_type, void *stream);
 uint32_t gs_topk_rows_max_k(void);
-/* What gs_topk_rows_u32 launches for a shape: a pure host function (no device, no workspace, no synchronisation).
+/* What gs_topk_rows_u32 -- and gs_topk_rows_u16 below, which has the same geometry -- launches for a shape: a pure host
+ * function (no device, no workspace, no synchronisation).
  * out[0] = path (1 = one wave per row, 2 = one workgroup per row, 3 = chunked), out[1] = select levels launched (1 on paths
  * 1 and 2), out[2] = CH, the elements one workgroup selects from, out[3] = chunks per row at level 0, out[4] = candidates per
  * row after level 0 (k on paths 1 and 2, n1 of the workspace formula on path 3), out[5] = gs_topk_rows_max_k(), out[6..7] = 0.
  * A refused shape (k > num_cols, k > max_k, num_rows * num_cols >= 2^32, num_rows * k >= 2^32) returns hipErrorInvalidValue
  * and all zeros; a no-op shape returns 0 and all zeros.                                                                    */
 int      gs_topk_rows_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint32_t out[8]);
+
+/* ------------------------------------------- top k of every row, 16-bit keys --
+ * gs_topk_rows_u32 for 16-bit keys on kernels of their own (gs_topk_rows_narrow.hip): bfloat16 or half
+ * scores of a router, a vocabulary or a beam, without widening them.  key_type is GS_KEY_U16, GS_KEY_I16, GS_KEY_F16 or
+ * GS_KEY_BF16, in the order stated at the enum for gs_lsb_sort_narrow (GS_KEY_F32's map at width 16: negative NaNs first,
+ * positive NaNs last, -0 before +0).  Row r of the result is exactly the first k of the stable sort of row r on the 16-bit
+ * image (complemented when descending): the lowest column indices where the cut falls inside a run of equal keys, the
+ * caller's bit patterns kept.  Equivalently it is bit for bit what gs_topk_rows_u32 gives on the matrix (uint32_t)key << 16
+ * with the key type widened (U16 -> U32, I16 -> I32, F16 / BF16 -> F32), the returned keys shifted right by 16, values and
+ * column indices unchanged (for F16 too: the order is sign-magnitude on the bits, whatever the exponent width).
+ * Forms: keys only; pairs; arguments (d_vals_in == NULL, d_vals_out != NULL: the u32 column index).  Values are u32 and sit
+ * at the same row_stride counted in elements (row r's values start at d_vals_in + r * row_stride); the outputs are dense with
+ * stride k.  The contract is gs_topk_rows_u32's: the inputs are never written, the values of the stride gap never influence a
+ * result, nothing outside [0, num_rows * k) of the outputs is written, d_temp anywhere, enqueue-only (no host read-back,
+ * allocation or synchronisation), the launches are a function of the arguments alone, so the call may be captured into a HIP
+ * graph; calls may follow each other on one stream with one workspace; two runs give identical bytes.  num_rows == 0,
+ * num_cols == 0 or k == 0 returns 0, writes nothing and needs no workspace (the query returns 0).
+ * Errors (hipErrorInvalidValue, checked before anything is enqueued, nothing written; the size query returns 0 for a refused
+ * shape): k > num_cols, k > gs_topk_rows_max_k() (1024), row_stride < num_cols, num_rows * row_stride >= 2^32,
+ * num_rows * k >= 2^32, a key_type other than GS_KEY_U16 / I16 / F16 / BF16, d_vals_in without d_vals_out, a NULL key pointer,
+ * a NULL or too-small workspace, a key array not aligned to 2 bytes or a value array not aligned to 4, arrays that share a
+ * byte (inputs at (num_rows - 1) * row_stride + num_cols elements, outputs at num_rows * k; 2 bytes per key, 4 per value).
+ * Geometry: gs_topk_rows_u32's, on purpose -- path 1 up to 1024 columns, path 2 up to CH = 8192, path 3 chunked with the same
+ * next(n), gs_topk_rows_max_k() = 1024 -- so gs_topk_rows_plan above answers for both entry points.  Every key is read and
+ * written with one 2-byte access, so any row_stride and any k, odd ones included, are served alike.
+ * Workspace: candidate rows hold 16-bit keys and u32 columns.  With next(n), n1 and n2 as in gs_topk_rows_temp_bytes,
+ * hv = 1 with has_values else 0, and every term rounded up to 256 bytes:
+ *   2 * num_rows * n1                         the candidate keys of the even levels
+ * + hv * 4 * num_rows * n1                    their columns
+ * + 2 * num_rows * n2                         the candidate keys of the odd levels
+ * + hv * 4 * num_rows * n2                    their columns
+ * + 256 bytes of alignment slack.
+ * Never more than gs_topk_rows_temp_bytes of the same arguments.  Paths 1 and 2 copy no element into the workspace.        */
+size_t   gs_topk_rows_u16_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values);
+int      gs_topk_rows_u16(void *d_temp, size_t temp_bytes,
+                          const uint16_t *d_keys_in, const uint32_t *d_vals_in,
+                          uint16_t *d_keys_out, uint32_t *d_vals_out,
+                          uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k,
+                          int descending, int key_type, void *stream);
 
 /* Census of the last gs_msb_sort_u32 that used d_temp (read back after synchronising `stream`): what every level
  * partitioned and what it handed to local sorts.  SURVEY.md 8d: the MSB path's algorithmic bytes are data-dependent --

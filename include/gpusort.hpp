@@ -275,25 +275,40 @@ struct DeviceTopK {
 // what DeviceTopK gives for that row alone -- goes to d_keys_out[r * k .. + k) and the same range of d_values_out.  The forms
 // and the two phases are DeviceTopK's; in the pairs forms d_values_in == nullptr writes the elements' column indices.  A size
 // query of 0 with a non-empty shape means the shape is refused (k > gs_topk_rows_max_k(), ...): such callers keep DeviceTopK
-// per row.
+// per row.  2-byte keys (unsigned short, short, _Float16, __half, __hip_bfloat16) go to gs_topk_rows_u16 and its size query:
+// the same definition on the 16-bit image, 32-bit values at the same row_stride; there is no flat 16-bit DeviceTopK to keep.
 struct DeviceTopKRows {
     template <typename KeyT, typename ValueT>
     static hipError_t Dispatch(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
                                const ValueT *d_values_in, ValueT *d_values_out, uint64_t num_rows, uint64_t num_cols,
                                uint64_t row_stride, uint64_t k, bool descending, hipStream_t stream)
     {
-        static_assert(sizeof(KeyT) == 4 && KeyTraits<KeyT>::type <= GS_KEY_F32, "unsigned int, int or float keys");
+        static_assert(sizeof(KeyT) == 4 || sizeof(KeyT) == 2, "32-bit keys (unsigned int, int, float) or 16-bit keys");
         static_assert(sizeof(ValueT) == 4, "32-bit values only");
         const bool has_values = d_values_out != nullptr;
-        if (d_temp_storage == nullptr) {
-            temp_storage_bytes = gs_topk_rows_temp_bytes(num_rows, num_cols, k, has_values);
-            return hipSuccess;
+        if constexpr (sizeof(KeyT) == 2) {   // unsigned short, short, _Float16, __half, __hip_bfloat16: gs_topk_rows_u16
+            constexpr int kt = KeyTraits<KeyT>::type;
+            static_assert(kt == GS_KEY_U16 || kt == GS_KEY_I16 || kt == GS_KEY_F16 || kt == GS_KEY_BF16, "a 16-bit key type");
+            if (d_temp_storage == nullptr) {
+                temp_storage_bytes = gs_topk_rows_u16_temp_bytes(num_rows, num_cols, k, has_values);
+                return hipSuccess;
+            }
+            return static_cast<hipError_t>(gs_topk_rows_u16(
+                d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint16_t *>(d_keys_in),
+                reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint16_t *>(d_keys_out),
+                reinterpret_cast<uint32_t *>(d_values_out), num_rows, num_cols, row_stride, k, descending ? 1 : 0, kt, stream));
+        } else {
+            static_assert(KeyTraits<KeyT>::type <= GS_KEY_F32, "unsigned int, int or float keys");
+            if (d_temp_storage == nullptr) {
+                temp_storage_bytes = gs_topk_rows_temp_bytes(num_rows, num_cols, k, has_values);
+                return hipSuccess;
+            }
+            return static_cast<hipError_t>(gs_topk_rows_u32(
+                d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint32_t *>(d_keys_in),
+                reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint32_t *>(d_keys_out),
+                reinterpret_cast<uint32_t *>(d_values_out), num_rows, num_cols, row_stride, k, descending ? 1 : 0,
+                KeyTraits<KeyT>::type, stream));
         }
-        return static_cast<hipError_t>(gs_topk_rows_u32(
-            d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint32_t *>(d_keys_in),
-            reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint32_t *>(d_keys_out),
-            reinterpret_cast<uint32_t *>(d_values_out), num_rows, num_cols, row_stride, k, descending ? 1 : 0, KeyTraits<KeyT>::type,
-            stream));
     }
     template <typename KeyT>
     static hipError_t MinKeys(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
