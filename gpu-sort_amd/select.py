@@ -129,6 +129,13 @@ def _key_type16_of(t, key_type):
     return key_type
 
 
+# what the key width changes at the front end: the entry point, its size query, the key-type resolver, the key's bytes
+_ROWS_BY_WIDTH = {
+    32: ("gs_topk_rows_u32", "gs_topk_rows_temp_bytes", _key_type_of, 4),
+    16: ("gs_topk_rows_u16", "gs_topk_rows_u16_temp_bytes", _key_type16_of, 2),
+}
+
+
 class DeviceTopKRows:
     """MinKeys / MaxKeys / MinPairs / MaxPairs for every row of a matrix: row r is d_keys_in[r * row_stride .. + num_cols)
     (flat element offsets), and its k smallest (largest), sorted, go to d_keys_out[r * k .. + k) with their values.
@@ -144,47 +151,25 @@ class DeviceTopKRows:
     def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols, row_stride,
              k, descending, has_values, stream, key_type):
         narrow = key_type in _NARROW16 if d_temp_storage is None or key_type is not None else d_keys_in.element_size() == 2
-        need = (lib.gs_topk_rows_u16_temp_bytes if narrow else lib.gs_topk_rows_temp_bytes)(num_rows, num_cols, k, int(has_values))
+        entry, size_query, resolve, elem = _ROWS_BY_WIDTH[16 if narrow else 32]
+        need = getattr(lib, size_query)(num_rows, num_cols, k, int(has_values))
         if d_temp_storage is None:
             return need
-        if narrow:
-            return DeviceTopKRows._run16(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out,
-                                         num_rows, num_cols, row_stride, k, descending, has_values, stream, key_type, need)
-        if d_keys_in.element_size() != 4:
-            raise TypeError("DeviceTopKRows: 32-bit keys, or 16-bit keys with a 16-bit key type")
-        key_type = _key_type_of(d_keys_in, key_type)
-        _check_rows_in(d_keys_in, "d_keys_in")
-        _check_buf(d_keys_out, num_rows * k, "d_keys_out")
+        if d_keys_in.element_size() != elem:
+            raise TypeError("DeviceTopKRows: 32-bit keys, or 2-byte keys with a 16-bit key type")
+        key_type = resolve(d_keys_in, key_type)
+        _check_rows_in(d_keys_in, "d_keys_in", elem)
+        _check_buf(d_keys_out, num_rows * k, "d_keys_out", elem)
         if has_values:
             if d_values_in is not None:
                 _check_rows_in(d_values_in, "d_values_in")
             _check_buf(d_values_out, num_rows * k, "d_values_out")
-        err = lib.gs_topk_rows_u32(C.c_void_p(d_temp_storage.data_ptr()),
-                                   min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
-                                   d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
-                                   d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
-                                   num_rows, num_cols, row_stride, k, int(descending), key_type, _stream_ptr(stream))
-        check(err, "gs_topk_rows_u32")
-        return need
-
-    @staticmethod
-    def _run16(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols, row_stride,
-               k, descending, has_values, stream, key_type, need):
-        if d_keys_in.element_size() != 2:
-            raise TypeError("DeviceTopKRows: a 16-bit key_type needs 2-byte keys")
-        key_type = _key_type16_of(d_keys_in, key_type)
-        _check_rows_in(d_keys_in, "d_keys_in", 2)
-        _check_buf(d_keys_out, num_rows * k, "d_keys_out", 2)
-        if has_values:
-            if d_values_in is not None:
-                _check_rows_in(d_values_in, "d_values_in")
-            _check_buf(d_values_out, num_rows * k, "d_values_out")
-        err = lib.gs_topk_rows_u16(C.c_void_p(d_temp_storage.data_ptr()),
-                                   min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
-                                   d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
-                                   d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
-                                   num_rows, num_cols, row_stride, k, int(descending), key_type, _stream_ptr(stream))
-        check(err, "gs_topk_rows_u16")
+        err = getattr(lib, entry)(C.c_void_p(d_temp_storage.data_ptr()),
+                                  min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                  d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
+                                  d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
+                                  num_rows, num_cols, row_stride, k, int(descending), key_type, _stream_ptr(stream))
+        check(err, entry)
         return need
 
     @staticmethod
@@ -262,7 +247,7 @@ def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
         values_out = torch.empty((rows, k), dtype=values.dtype if values is not None else torch.int32, device=keys.device)
     if k == 0 or rows == 0:
         return keys_out, values_out
-    nbytes = (lib.gs_topk_rows_u16_temp_bytes if narrow else lib.gs_topk_rows_temp_bytes)(rows, cols, k, int(has_values))
+    nbytes = getattr(lib, _ROWS_BY_WIDTH[16 if narrow else 32][1])(rows, cols, k, int(has_values))
     if nbytes == 0 and not narrow and k > lib.gs_topk_rows_max_k() and rows * stride < (1 << 32) and rows * k < (1 << 32):
         # refused for k alone: the flat top k of every row, one call each on one workspace
         nbytes = lib.gs_topk_temp_bytes(cols, k, int(has_values))

@@ -448,7 +448,7 @@ uint32_t gs_topk_rows_max_k(void);
 int      gs_topk_rows_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint32_t out[8]);
 
 /* ------------------------------------------- top k of every row, 16-bit keys --
- * gs_topk_rows_u32 for 16-bit keys on kernels of their own (gs_topk_rows_narrow.hip): bfloat16 or half
+ * gs_topk_rows_u32 for 16-bit keys, its kernels instantiated for them (gs_topk_rows.hip): bfloat16 or half
  * scores of a router, a vocabulary or a beam, without widening them.  key_type is GS_KEY_U16, GS_KEY_I16, GS_KEY_F16 or
  * GS_KEY_BF16, in the order stated at the enum for gs_lsb_sort_narrow (GS_KEY_F32's map at width 16: negative NaNs first,
  * positive NaNs last, -0 before +0).  Row r of the result is exactly the first k of the stable sort of row r on the 16-bit

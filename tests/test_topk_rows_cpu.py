@@ -238,6 +238,10 @@ def test_plan_of_every_gpu_shape(gs):
         rc, p = _plan(gs, rows, cols, k)
         assert rc == 0 and p[:2] == [3, levels] and p[3] == -(-cols // RR.CH), (rows, cols, k, p)
         assert rows * cols <= 1 << 22
+    for rows, cols, k, levels in RR.MIDDLE_SHAPES:      # the smallest rows of three levels in their class: one column fewer has two
+        assert _plan(gs, rows, cols, k)[1][:2] == [3, 3] and _plan(gs, rows, cols - 1, k)[1][:2] == [3, 2], (cols, k)
+        assert _plan(gs, rows, cols, k)[1][4] == RR.CH + 1 and levels == 3
+    assert sorted(-(-k // 64) for _, _, k, _ in RR.MIDDLE_SHAPES) == [1, 4, 8]
     for cols, k, path, levels in RR.STRIDE_SHAPES:
         assert _plan(gs, 5, cols, k)[1][:2] == [path, levels], (cols, k)
     for rows, cols, k, path, levels in RR.GUARDED_SHAPES + RR.GRAPH_SHAPES + RR.REUSE_SHAPES:

@@ -61,6 +61,17 @@ def test_deep_levels_alternate_the_workspace_areas(gs, cuda, shape):
             c.check(rows, k, mode, plan=(3, levels))
 
 
+def test_three_levels_with_a_finishing_wave_of_one_per_lane(gs, cuda):
+    """k = 64: the middle level (carried columns in, a candidate row out) in the one class DEEP_SHAPES leaves out -- its three
+    and more levels are at k = 256 and above."""
+    rows, cols, k, levels = RR.MIDDLE_SHAPES[0]
+    assert k == 64 and not any(kk <= 64 for _, _, kk, _ in TC.DEEP_SHAPES)
+    for kt, desc, kinds in ((F32, True, ["special"]), (I32, False, ["five"])):
+        c = Case(gs, cuda, TC.dist_matrix(rows, cols, kt, 11, kinds), cols, kt, desc)
+        for mode in MODES:
+            c.check(rows, k, mode, plan=(3, levels))
+
+
 @pytest.mark.parametrize("rows,cols,k,levels", TC.DEEP_EQUAL)
 def test_deep_all_keys_equal_gives_the_first_columns(gs, cuda, rows, cols, k, levels):
     for kt, desc in ((I32, False), (F32, True)):

@@ -136,6 +136,17 @@ def test_path3_chunked(gs, cuda, shape):
             c.check(rows, k, mode, plan=(3, levels))
 
 
+@pytest.mark.parametrize("shape", RR.MIDDLE_SHAPES)
+def test_path3_middle_level_in_every_class_of_the_finishing_wave(gs, cuda, shape):
+    """Three levels at k = 64, 256 and 512: the middle level reads 16-bit candidate keys with their columns and writes a
+    candidate row again, with a finishing wave of 1, 4 and 8 per lane (PATH3_SHAPES has three levels at k = 1024 alone)."""
+    rows, cols, k, levels = shape
+    kt, desc, _ = rotate(2 + 3 * RR.MIDDLE_SHAPES.index(shape))
+    c = Case(gs, cuda, N.matrix16(rows, cols, kt, seed=80 + k, kinds=["five", "uniform", "special"]), cols, kt, desc)
+    for mode in MODES:
+        c.check(rows, k, mode, plan=(3, levels))
+
+
 # ---------------------------------------------------------------------------------------------------- alignment --
 ALIGN_SHAPES = [(257, 101, 1, 1), (1024, 1023, 1, 1), (4001, 65, 2, 1), (CH + 5, 1023, 3, 2)]     # (cols, odd k, path, levels)
 

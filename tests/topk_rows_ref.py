@@ -116,6 +116,10 @@ PATH3_SHAPES = [
 ]
 
 # the other tests' shapes, each with the (path, levels) it is meant to take
+# (rows, cols, k, levels): three levels with a finishing wave of 1, 4 and 8 per lane -- the smallest row whose level 0 leaves more
+# than one chunk of candidates, CH * (CH / k) + 1 columns -- so that the middle level (a source that carries columns, a
+# destination that is a candidate row again) runs in every class; THREE_LEVELS_COLS above is the one of 16 per lane
+MIDDLE_SHAPES = [(1, CH * (CH // k) + 1, k, 3) for k in (64, 256, 512)]
 STRIDE_SHAPES = [      # (cols, k, path, levels) at 5 rows and row_stride = cols + 3
     (5, 5, 1, 1), (64, 8, 1, 1), (257, 100, 1, 1), (1024, 1024, 1, 1), (1025, 64, 2, 1), (CH, 1024, 2, 1), (CH + 5, 1024, 3, 2),
     (2 * CH + 1, 50, 3, 2),
