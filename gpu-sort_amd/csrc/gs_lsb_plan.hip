@@ -34,6 +34,8 @@ namespace gs {
 //             and so do those of slot 1's upsweep when PLANNED: the look has done its work;
 //   finish    lsb_plan_tasks_kernel turns the group table into the local sorts' task lists (nothing when CLASSIC), and the
 //             local sorts run in place over worst-case grids: with empty lists their blocks exit.
+//   peek      that fixed sequence pays for both routes.  Outside stream capture the host reads the decision while the first
+//             slot runs and enqueues only what the route needs (see PlanPeek below); GS_LSB_PLAN_PEEK=0 keeps the fixed sequence.
 // The buffer ping-pong is the four passes' on both routes, so the selector and the result buffer do not depend on the route.
 //   cursors   the finish sorts every group, so the second PLANNED scatter need not be stable: it only has to put every key
 //             into the range of its group, which the look knows exactly (offsets[]).  So it has no upsweep: a tile claims
@@ -336,6 +338,17 @@ __global__ __launch_bounds__(RADIX) void lsb_plan_decide_kernel(PlanBlock *__res
         plan->offsets[PLAN_GROUPS] = n;
         plan->cursor_mode = planned && cursor_on ? 1u : 0u;
     }
+}
+
+// The host's look at the decision (see PlanPeek): the plan block's head and the scatter mode, to a pinned host mailbox.
+constexpr int PLAN_PEEK_WORDS = 9;   // route, max_group, nonempty, tasks[4], total, cursor_mode
+static_assert(offsetof(PlanBlock, total) == (PLAN_PEEK_WORDS - 2) * sizeof(uint32_t), "the head is eight words");
+__global__ void lsb_plan_peek_kernel(const PlanBlock *__restrict__ plan, uint32_t *mailbox)
+{
+    const uint32_t *head = &plan->route;
+    for (int i = 0; i < PLAN_PEEK_WORDS - 1; ++i) mailbox[i] = head[i];
+    mailbox[PLAN_PEEK_WORDS - 1] = plan->cursor_mode;
+    __threadfence_system();
 }
 
 // The finish's task lists: one task per non-empty group, in group order inside each class.  Nothing when CLASSIC.
@@ -646,6 +659,135 @@ static int lsb_plan_look(const uint32_t *keys, uint32_t *alt, const LsbWorkspace
     return (int)hipGetLastError();
 }
 
+// The second slot of a sort that the host has seen to be PLANNED in cursor mode: the cursor set-up, the scatter of the full
+// tiles and the follow-up kernel, which also places the partial tile.  No scan (nothing reads it) and no partial-tile launch
+// (it returns at once in this mode).
+static int lsb_plan_slot2_cursor(const uint32_t *kin, uint32_t *kout, const LsbWorkspace &ws, PlanBlock *plan, uint32_t *cursor,
+                                 const PassParams &p, hipStream_t s)
+{
+    if (p.f32_in || p.f32_out || p.xor_in || p.xor_out) return hipErrorInvalidValue;
+    if ((char *)cursor < (char *)ws.prefix16) return hipErrorInvalidValue;
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(lsb_plan_upsweep2_kernel<true>, dim3(p.grid), dim3(LSB_THREADS), 0, s, kin, ws.spine, ws.prefix16, plan, cursor, p);
+    }
+    if (p.n >= (uint32_t)LSB_TILE) {
+        KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
+        if (p.n > (1u << 30))
+            hipLaunchKernelGGL((lsb_plan_scatter2_kernel<false, true>), dim3(p.ds_grid), dim3(LSB_THREADS), 0, s, kin, kout, ws.totals,
+                               ws.spine, ws.prefix16, plan, cursor, p);
+        else
+            hipLaunchKernelGGL((lsb_plan_scatter2_kernel<false, false>), dim3(p.ds_grid), dim3(LSB_THREADS), 0, s, kin, kout, ws.totals,
+                               ws.spine, ws.prefix16, plan, cursor, p);
+    }
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(lsb_plan_irregular_kernel, dim3(PLAN_IRR_CAP + (p.n % (uint32_t)LSB_TILE ? 1u : 0u)), dim3(LSB_THREADS), 0, s, kin,
+                           kout, plan, cursor, p.n);
+    }
+    return (int)hipGetLastError();
+}
+
+// ---- the host's look at the decision.  The fixed sequence pays for both routes: a PLANNED sort launches two pass slots and
+// up to eight local-sort kernels that find nothing, a CLASSIC one the cursor set-up, the follow-up kernel, the task builder
+// and a finish over empty lists -- 0.3 ms at 2^30 keys, mostly workgroups that load one word and leave.  So, when the stream
+// is not being captured: right after the look a one-thread kernel copies the decision to a pinned host mailbox and an event
+// is recorded; the first slot, which is the same on both routes, is enqueued (milliseconds of work), and only then the host
+// waits for the event and enqueues what the route needs.  The discipline is the MSB sort's (MsbPeek in gs_msb.hip): one
+// mailbox per calling thread and device, released when the thread ends; under capture, with GS_LSB_PLAN_PEEK=0 (read once per
+// process) and on any failure the fixed sequence runs, which is right for any data.
+struct PlanPeek {
+    uint32_t *host = nullptr, *dev = nullptr;
+    hipEvent_t ev = nullptr;
+    int device = -1;
+    bool armed = false;
+};
+static bool plan_peek_enabled()
+{
+    static const bool on = [] { const char *e = getenv("GS_LSB_PLAN_PEEK"); return !(e && e[0] == '0'); }();
+    return on;
+}
+constexpr int PLAN_PEEK_DEVICES = 16;
+struct PlanPeekTable {
+    PlanPeek slot[PLAN_PEEK_DEVICES];
+    ~PlanPeekTable()
+    {
+        for (PlanPeek &pk : slot) {
+            if (pk.ev) (void)hipEventDestroy(pk.ev);
+            if (pk.host) (void)hipHostFree(pk.host);
+        }
+    }
+};
+// the calling thread's mailbox for the current device, or nullptr (then the caller runs the fixed sequence)
+static PlanPeek *plan_peek_get(hipStream_t s)
+{
+    if (!plan_peek_enabled()) return nullptr;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return nullptr; }
+    thread_local PlanPeekTable table;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PLAN_PEEK_DEVICES) { (void)hipGetLastError(); return nullptr; }
+    PlanPeek &pk = table.slot[dev];
+    if (pk.device != dev) {
+        void *h = nullptr, *d = nullptr;
+        if (hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocPortable) != hipSuccess ||
+            hipHostGetDevicePointer(&d, h, 0) != hipSuccess ||
+            hipEventCreateWithFlags(&pk.ev, hipEventDisableTiming) != hipSuccess) {
+            (void)hipGetLastError();
+            if (h) (void)hipHostFree(h);
+            pk.ev = nullptr;
+            return nullptr;
+        }
+        pk.host = (uint32_t *)h; pk.dev = (uint32_t *)d; pk.device = dev;
+    }
+    // a look armed by an earlier call that returned early (an error between arm and wait): its kernel may still be about
+    // to write the mailbox -- wait it out before the words are reused
+    if (pk.armed) { (void)hipEventSynchronize(pk.ev); (void)hipGetLastError(); }
+    pk.armed = false;
+    return &pk;
+}
+static void plan_peek_arm(PlanPeek *pk, const PlanBlock *plan, hipStream_t s)
+{
+    if (!pk) return;
+    for (int i = 0; i < PLAN_PEEK_WORDS; ++i) ((volatile uint32_t *)pk->host)[i] = 0;   // route 0: not plausible
+    KernelTimer kt(GS_K_OTHER, s);
+    hipLaunchKernelGGL(lsb_plan_peek_kernel, dim3(1), dim3(1), 0, s, plan, pk->dev);
+    pk->armed = hipGetLastError() == hipSuccess && hipEventRecord(pk->ev, s) == hipSuccess;
+    if (!pk->armed) (void)hipGetLastError();
+}
+struct PlanSeen { bool ok = false; uint32_t route = 0, tasks[MSB_NCLASS] = {0, 0, 0, 0}, cursor_mode = 0; };
+// to be called once the first slot has been enqueued behind the look (the device is busy while the host waits).  The words
+// must be plausible -- a route, all n keys counted when PLANNED and no more than n when CLASSIC, class counts that sum to the
+// non-empty groups (to 0 when CLASSIC), none above its list -- or the caller runs the fixed sequence.
+static PlanSeen plan_peek_wait(PlanPeek *pk, uint64_t n)
+{
+    PlanSeen seen;
+    if (!pk || !pk->armed) return seen;
+    pk->armed = false;
+    if (hipEventSynchronize(pk->ev) != hipSuccess) { (void)hipGetLastError(); return seen; }
+    uint32_t w[PLAN_PEEK_WORDS];
+    for (int i = 0; i < PLAN_PEEK_WORDS; ++i) w[i] = ((const volatile uint32_t *)pk->host)[i];
+    const uint32_t route = w[0], nonempty = w[2], total = w[7], mode = w[8];
+    if (route != PLAN_PLANNED && route != PLAN_CLASSIC) return seen;
+    // (CLASSIC after a counter of the look wrapped -- a group of 65536 keys or more in one workgroup: the words are those of
+    // the wrapped counters, and fewer than n keys were counted)
+    if (route == PLAN_PLANNED ? (uint64_t)total != n : (uint64_t)total > n) return seen;
+    if (mode > 1u || (mode && route != PLAN_PLANNED)) return seen;
+    uint64_t sum = 0;
+    for (int c = 0; c < MSB_NCLASS; ++c) {
+        if (w[3 + c] > plan_list_cap(n, c)) return seen;
+        sum += w[3 + c];
+    }
+    if (route == PLAN_PLANNED ? sum != nonempty : sum != 0) return seen;
+    seen.ok = true;
+    seen.route = route;
+    seen.cursor_mode = mode;
+    for (int c = 0; c < MSB_NCLASS; ++c) seen.tasks[c] = w[3 + c];
+    return seen;
+}
+// gs_lsb_plan_peek_status: what the calling thread's last planned sort did
+static thread_local uint32_t plan_peek_last[4] = {0, 0, 0, 0};
+
 int lsb_plan_sort(char *base, uint32_t *d_keys[2], int *selector, uint64_t n, int descending, int key_type, hipStream_t s)
 {
     const LsbWorkspace ws = lsb_carve(base, n);
@@ -661,15 +803,42 @@ int lsb_plan_sort(char *base, uint32_t *d_keys[2], int *selector, uint64_t n, in
     PassParams tw{};
     lsb_twiddle_masks(key_type, descending, true, true, tw);
     if ((e = lsb_plan_look(d_keys[sel], d_keys[sel ^ 1], ws, plan, n, tw, s))) return e;
+    PlanPeek *peek = plan_peek_get(s);
+    plan_peek_arm(peek, plan, s);
+    PlanSeen seen;   // (!ok: the fixed sequence)
+    plan_peek_last[0] = plan_peek_last[1] = 0; plan_peek_last[2] = 4; plan_peek_last[3] = (1u << MSB_NCLASS) - 1u;
+    // The buffer ping-pong counts four slots on every path: a slot that is not enqueued flips the selector like one that skips.
     for (int slot = 0; slot < 4; ++slot) {
         PassParams p = lsb_make_params(n, 0, RADIX_BITS);   // (the shift comes from the plan)
         lsb_twiddle_masks(key_type, descending, slot == 0, slot == 3, p);
-        if (slot == 1 && plan_cursor_enabled())
-            e = lsb_plan_slot2(d_keys[sel], d_keys[sel ^ 1], ws, plan, plan_cursors(base, n), p, s);
+        const uint32_t *kin = d_keys[sel];
+        uint32_t *kout = d_keys[sel ^ 1];
+        e = hipSuccess;
+        if (seen.ok && seen.route == PLAN_CLASSIC)          // the host has seen CLASSIC: every slot is a real pass
+            e = lsb_plan_slot(kin, kout, ws, &plan->shift[slot], &plan->ups_skip[slot], p, true, true, s);
+        else if (seen.ok && slot >= 2)                      // the host has seen PLANNED: slots 3 and 4 do nothing
+            ;
+        else if (seen.ok && slot == 1 && seen.cursor_mode)
+            e = lsb_plan_slot2_cursor(kin, kout, ws, plan, plan_cursors(base, n), p, s);
+        else if (slot == 1 && plan_cursor_enabled())
+            e = lsb_plan_slot2(kin, kout, ws, plan, plan_cursors(base, n), p, s);
         else
-            e = lsb_plan_slot(d_keys[sel], d_keys[sel ^ 1], ws, &plan->shift[slot], &plan->ups_skip[slot], p, slot < 2, slot == 1, s);
+            e = lsb_plan_slot(kin, kout, ws, &plan->shift[slot], &plan->ups_skip[slot], p, slot < 2, slot == 1, s);
         if (e) return e;
         sel ^= 1;
+        if (slot == 0) {
+            // the first slot is enqueued: now the host may wait for the look (the device is busy with that slot)
+            seen = plan_peek_wait(peek, n);
+            if (seen.ok) {
+                plan_peek_last[0] = 1; plan_peek_last[1] = seen.route; plan_peek_last[2] = seen.route == PLAN_PLANNED ? 2 : 4;
+                plan_peek_last[3] = 0;
+                for (int c = 0; c < MSB_NCLASS; ++c) plan_peek_last[3] |= seen.tasks[c] ? 1u << c : 0u;
+            }
+        }
+    }
+    if (seen.ok && seen.route == PLAN_CLASSIC) {            // the fourth pass has written the result
+        *selector = sel;
+        return hipSuccess;
     }
     {
         KernelTimer kt(GS_K_OTHER, s);
@@ -677,7 +846,7 @@ int lsb_plan_sort(char *base, uint32_t *d_keys[2], int *selector, uint64_t n, in
     }
     if ((e = (int)hipGetLastError())) return e;
     if ((e = msb_local_sorts_in_place(plan->level, lists.tasks, PLAN_GROUPS, PLAN_GROUPS, d_keys[sel], PLAN_SORT_BITS, n, tw.f32_out,
-                                      tw.xor_out, s)))
+                                      tw.xor_out, s, seen.ok ? seen.tasks : nullptr)))
         return e;
     *selector = sel;
     return hipSuccess;
@@ -725,6 +894,15 @@ int gs_lsb_plan_cursor_status(void *d_temp, uint64_t num_items, uint32_t out[4],
         out[2] = w[1];
         out[1] = w[1] + (num_items % (uint64_t)LSB_TILE ? 1u : 0u);
     }
+    return hipSuccess;
+}
+
+// The calling thread's last planned sort.  out[0]: the host looked at the decision; out[1]: the route it read (0: no look);
+// out[2]: pass slots enqueued, 2 or 4; out[3]: bit c set when class c's local sorts were enqueued.  All 0 before the first.
+int gs_lsb_plan_peek_status(uint32_t out[4])
+{
+    if (!out) return hipErrorInvalidValue;
+    memcpy(out, plan_peek_last, sizeof(plan_peek_last));
     return hipSuccess;
 }
 

@@ -1949,7 +1949,7 @@ static void launch_local_sorts(const MsbWs &ws, int L, uint32_t bound, const uin
 // gs_msb_tasks.hpp: the local sorts over lists the caller wrote (the keys-only plan of the LSB sort).  Only the fields the
 // local-sort path reads are filled in: msb_task_sample_kernel and msb_local_sort_kernel use level, tasks, max_tasks and caps.
 int msb_local_sorts_in_place(MsbLevel *level, MsbTask *const tasks[MSB_NCLASS], uint32_t max_tasks, uint32_t bound, uint32_t *keys,
-                             int sort_bits, uint64_t num_items, int f32_out, uint32_t xor_out, hipStream_t s)
+                             int sort_bits, uint64_t num_items, int f32_out, uint32_t xor_out, hipStream_t s, const uint32_t *known_tasks)
 {
     MsbWs ws{};
     ws.level = level;
@@ -1957,7 +1957,7 @@ int msb_local_sorts_in_place(MsbLevel *level, MsbTask *const tasks[MSB_NCLASS], 
     ws.max_tasks = max_tasks;
     ws.tile_shift = 13u;
     ws.key_bits = 32u;
-    launch_local_sorts<false>(ws, 0, bound, keys, keys, nullptr, nullptr, 0, 0u, f32_out, xor_out, s, sort_bits, num_items);
+    launch_local_sorts<false>(ws, 0, bound, keys, keys, nullptr, nullptr, 0, 0u, f32_out, xor_out, s, sort_bits, num_items, known_tasks);
     return (int)hipGetLastError();
 }
 

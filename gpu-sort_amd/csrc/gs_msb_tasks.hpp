@@ -48,8 +48,10 @@ struct MsbLevel {
 // max_tasks each; level[1] must exist: the sample look reads its bucket count), in place in `keys`: every task's keys are
 // in registers or LDS before its first store, and stores stay inside the task's range.  Keys are in twiddled form; the
 // output twiddle is applied on the way out.  No host wait: worst-case grids (`bound` tasks per class at most), blocks
-// that find no task exit.
+// that find no task exit.  `known_tasks`: the caller has read level[0].task_count on the host -- classes without tasks are
+// not launched and the grids are exact.
 int msb_local_sorts_in_place(MsbLevel *level, MsbTask *const tasks[MSB_NCLASS], uint32_t max_tasks, uint32_t bound, uint32_t *keys,
-                             int sort_bits, uint64_t num_items, int f32_out, uint32_t xor_out, hipStream_t s);
+                             int sort_bits, uint64_t num_items, int f32_out, uint32_t xor_out, hipStream_t s,
+                             const uint32_t *known_tasks = nullptr);
 
 }  // namespace gs

@@ -100,11 +100,21 @@ size_t gs_lsb_temp_bytes(uint64_t num_items, int has_values);
  * counts the keys of each of the 65536 values of the top 16 bits.  If every
  * such group fits the largest in-LDS local sort, two scatter passes (bits
  * 16-23, 24-31) and one local sort per group replace the four passes; if
- * not, the four passes run.  The decision is taken on the device: the same
- * kernels are launched in the same order whatever the data, nothing waits on
- * the host, the call can be captured in a graph, and the selector and the
- * result buffer are those of the four passes.  GS_LSB_KEYS_PLAN=classic
- * (environment, read once per process) switches the plan off.               */
+ * not, the four passes run.  The decision is taken on the device, and the
+ * selector and the result buffer are those of the four passes.
+ * GS_LSB_KEYS_PLAN=classic (environment, read once per process) switches
+ * the plan off.
+ * The host's look: such a call BLOCKS the calling thread until the look at
+ * the input has run on the device (0.8 ms at 2^30 keys on an idle stream,
+ * plus whatever the stream holds before it) -- with the first scatter pass
+ * already enqueued, so the device stays busy -- and then enqueues only the
+ * launches that the route needs; the result does not depend on it.  Unless:
+ * `stream` is being captured into a HIP graph, or GS_LSB_PLAN_PEEK=0 is set
+ * (environment, read once per process), or the pinned mailbox cannot be had
+ * or read; then one fixed launch sequence that serves both routes is
+ * enqueued whatever the data and nothing waits on the host.  (A host wait is
+ * not allowed while ANOTHER stream of the process is being captured in the
+ * global capture mode: set GS_LSB_PLAN_PEEK=0 there.)                       */
 int gs_lsb_sort_u32(void *d_temp, size_t temp_bytes,
                     uint32_t *d_keys[2], uint32_t *d_vals[2], int *selector,
                     uint64_t num_items, int begin_bit, int end_bit,
@@ -168,6 +178,13 @@ int  gs_lsb_plan_status(void *d_temp, uint64_t num_items, uint32_t out[8], void 
  * scatter, and the partial last tile), out[2] = the straddling tiles alone, out[3] = 0.  All zeros
  * on route 2, with the stable scatter and wherever gs_lsb_plan_status reports zeros.  Diagnostic.  */
 int  gs_lsb_plan_cursor_status(void *d_temp, uint64_t num_items, uint32_t out[4], void *stream);
+/* What the host did in the calling thread's last full-width keys-only gs_lsb_sort_u32 inside the
+ * plan's window (see "The host's look" at gs_lsb_sort_u32): out[0] = 1 if the host looked at the
+ * decision, else 0 (stream under capture, GS_LSB_PLAN_PEEK=0, no mailbox); out[1] = the route it
+ * read (0 without a look); out[2] = pass slots enqueued, 2 or 4; out[3] = bit c set when the local
+ * sorts of size class c were enqueued (0xf without a look, 0 on route 2).  No device access, no
+ * synchronisation; all zeros before the thread's first such sort.  Diagnostic: tests read it.      */
+int  gs_lsb_plan_peek_status(uint32_t out[4]);
 /* Test hooks of the keys-only plan.  gs_lsb_plan_look_only runs the look alone (the fused look, the
  * reduction of its tables and the decision) on a workspace of gs_lsb_temp_bytes(num_items) bytes and
  * returns without sorting: d_keys is read, the first num_items * 4 bytes of d_alt are scratch.  What

@@ -5,16 +5,18 @@ once per loaded library) -- and the two sort the same input alternately.  Per ca
 the repetitions), what the plan decided, and whether both routes return the same bytes.
 
     python tools/plan_window.py [--sizes 27,28,29,30,max] [--dists uniform,zipf,...] [--reps 5] [--profile] [--out FILE.json]
-                                [--versus classic|stable]
+                                [--versus classic|stable|nopeek]
 
 --versus stable compares the plan as built (its second scatter in cursor mode) with the plan whose second scatter is the stable
-one (the copy's first sort sees GS_LSB_PLAN_SCATTER2=stable) instead of with the four passes.  --profile adds the per-kernel-id device times (gs_profile_*) of one more sort per route."""
+one (the copy's first sort sees GS_LSB_PLAN_SCATTER2=stable) instead of with the four passes; --versus nopeek compares it with
+the plan whose host never looks at the decision (GS_LSB_PLAN_PEEK=0: one fixed launch sequence for both routes).  --profile adds the per-kernel-id device times (gs_profile_*) of one more sort per route."""
 import argparse, ctypes as C, json, os, shutil, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ["GS_LSB_PLAN_MIN_ITEMS"] = "65536"
 os.environ.pop("GS_LSB_KEYS_PLAN", None)
 os.environ.pop("GS_LSB_PLAN_SCATTER2", None)
+os.environ.pop("GS_LSB_PLAN_PEEK", None)
 import torch
 import gpu_sort_amd as gs
 
@@ -26,7 +28,7 @@ ap.add_argument("--dists", default="uniform")
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--profile", action="store_true")
 ap.add_argument("--out", default=None)
-ap.add_argument("--versus", choices=["classic", "stable"], default="classic")
+ap.add_argument("--versus", choices=["classic", "stable", "nopeek"], default="classic")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 gen = torch.Generator(device=dev); gen.manual_seed(1)
@@ -84,7 +86,7 @@ w = gs.generate_uniform_keys(1 << 17, device=dev); wb = torch.empty_like(w)
 wt = torch.empty(plan_lib.gs_lsb_temp_bytes(1 << 17, 0), dtype=torch.uint8, device=dev)
 sort(plan_lib, wt, wt.numel(), w, wb, 1 << 17)
 OTHER = args.versus
-switch = ("GS_LSB_KEYS_PLAN", "classic") if OTHER == "classic" else ("GS_LSB_PLAN_SCATTER2", "stable")
+switch = {"classic": ("GS_LSB_KEYS_PLAN", "classic"), "stable": ("GS_LSB_PLAN_SCATTER2", "stable"), "nopeek": ("GS_LSB_PLAN_PEEK", "0")}[OTHER]
 os.environ[switch[0]] = switch[1]
 classic_lib = bind(C.CDLL(copy))
 sort(classic_lib, wt, wt.numel(), w, wb, 1 << 17)
