@@ -22,6 +22,13 @@
 // group is filled in input order, so the stable finish reproduces S bit for bit.  No kernel waits on another workgroup
 // and no atomic decides a position: the only global atomics are the integer adds of the workgroups' histograms.
 // Arrays that fit one workgroup (route 3) are sorted whole into the workspace and the first k copied out.
+//
+// gs_topk_u16 is the same plan on the 16-bit image of GS_KEY_U16 / I16 / F16 / BF16, at two digits:
+// the pick, compaction, filter, histogram, count, select and route-3 kernels below are templates over the element type
+// (TkKey<T>: the image and the position of its top byte), instantiated for uint32_t and uint16_t.  Round one is the narrow
+// upsweep at shift 8 (narrow_slice_count: one spine column per tile, no prefix16), one round of histogram + pick finds the
+// low byte, and the finish is gs_lsb_sort_narrow.  Candidates and staged keys stay 2 bytes wide; indices are u32.  The one
+// routine of their own that 16-bit keys have is compact_tile16: the filter and the select read them two to an aligned word.
 #include "gs_device.hpp"
 #include "gs_lsb.hpp"
 
@@ -35,6 +42,18 @@ static_assert(TK_THREADS * TK_KPT == LSB_TILE, "the filter walks the tiles of th
 
 // state block (u32 words): 0..7 are gs_topk_status' words
 enum { TK_ROUTE = 0, TK_KTH = 1, TK_LESS = 2, TK_TAKE = 3, TK_TOP = 4, TK_STAGED0 = 8, TK_D0 = 9, TK_SRC_COUNT = 10, TK_WORDS = 64 };
+
+// What the element width changes in the kernels: the order-preserving image of a raw key (f: the float twiddle, x: the
+// uniform xor of sign flip and descending complement, at the key's own width) and the shift of the image's top byte.
+template <typename T> struct TkKey;
+template <> struct TkKey<uint32_t> {
+    static constexpr uint32_t TOP = 24;
+    static __device__ __forceinline__ uint32_t image(uint32_t raw, int f, uint32_t x) { return twiddle_in(raw, f, x); }
+};
+template <> struct TkKey<uint16_t> {
+    static constexpr uint32_t TOP = 8;
+    static __device__ __forceinline__ uint32_t image(uint32_t raw, int f, uint32_t x) { return (f ? float_flip<16>(raw) : raw) ^ x; }
+};
 
 struct TopkWs {
     uint32_t *state, *hist;          // [64], [3][256]
@@ -83,6 +102,7 @@ static size_t tk_carve(char *base, uint64_t n, uint64_t k, bool hv, TopkWs *ws)
 // ---------------------------------------------------------------- round one: pick --
 // One workgroup: the digit d0 whose run of S holds position k - 1.  Opens the state block and clears the histograms of
 // rounds two to four.
+template <uint32_t TOP>
 __global__ __launch_bounds__(RADIX) void topk_pick0_kernel(const uint32_t *__restrict__ totals, uint32_t *__restrict__ state,
                                                            uint32_t *__restrict__ hist, uint32_t n, uint32_t k, uint32_t cap)
 {
@@ -94,7 +114,7 @@ __global__ __launch_bounds__(RADIX) void topk_pick0_kernel(const uint32_t *__res
     if (ex < k && k - ex <= c) {
         const bool fits = c <= cap;
         state[TK_ROUTE] = fits ? 1u : 2u;
-        state[TK_KTH] = t << 24;
+        state[TK_KTH] = t << TOP;
         state[TK_LESS] = ex;
         state[TK_TAKE] = k - ex;
         state[TK_TOP] = c;
@@ -124,10 +144,10 @@ __global__ __launch_bounds__(RADIX) void topk_pick_kernel(const uint32_t *__rest
 // 2 = group B.  Element number r of a group inside the tile goes to position base + r of that group's arrays, when
 // below lim (group B's limit cuts the tie run; the others only fence the arrays).  IDX: also write the element's index --
 // src_idx[i], or i itself when src_idx is null.
-template <bool IDX, typename Cls>
-__device__ __forceinline__ void compact_tile(const uint32_t *__restrict__ src, const uint32_t *__restrict__ src_idx, uint32_t lo,
-                                             uint32_t count, Cls cls, uint32_t baseA, uint32_t limA, uint32_t *__restrict__ ak,
-                                             uint32_t *__restrict__ ai, uint32_t baseB, uint32_t limB, uint32_t *__restrict__ bk,
+template <bool IDX, typename T, typename Cls>
+__device__ __forceinline__ void compact_tile(const T *__restrict__ src, const uint32_t *__restrict__ src_idx, uint32_t lo,
+                                             uint32_t count, Cls cls, uint32_t baseA, uint32_t limA, T *__restrict__ ak,
+                                             uint32_t *__restrict__ ai, uint32_t baseB, uint32_t limB, T *__restrict__ bk,
                                              uint32_t *__restrict__ bi, uint32_t (*wcnt)[TK_WAVES])
 {
     const uint32_t w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
@@ -136,7 +156,7 @@ __device__ __forceinline__ void compact_tile(const uint32_t *__restrict__ src, c
 #pragma unroll
     for (int u = 0; u < TK_KPT; ++u) {
         const uint32_t i = first + (uint32_t)u * WAVE;
-        raw[u] = (i < count && i >= lo) ? __builtin_nontemporal_load(src + i) : 0u;
+        raw[u] = (i < count && i >= lo) ? (uint32_t)__builtin_nontemporal_load(src + i) : 0u;
     }
     uint32_t nA = 0, nB = 0;
 #pragma unroll
@@ -163,13 +183,13 @@ __device__ __forceinline__ void compact_tile(const uint32_t *__restrict__ src, c
         if (c[u] == 1u) {
             const uint32_t pos = baseA + count_lower(mA);
             if (pos < limA) {
-                ak[pos] = raw[u];
+                ak[pos] = (T)raw[u];
                 if (IDX) ai[pos] = src_idx ? src_idx[i] : i;
             }
         } else if (c[u] == 2u) {
             const uint32_t pos = baseB + count_lower(mB);
             if (pos < limB) {
-                bk[pos] = raw[u];
+                bk[pos] = (T)raw[u];
                 if (IDX) bi[pos] = src_idx ? src_idx[i] : i;
             }
         }
@@ -178,15 +198,99 @@ __device__ __forceinline__ void compact_tile(const uint32_t *__restrict__ src, c
     }
 }
 
+// The same for 16-bit keys with packed loads: a lane reads aligned 4-byte words of two neighbouring elements, eight rows of 64
+// words per wave, and a ninth word when the wave's span starts in the upper half of a word (the array may start at any even
+// address; only words that hold an element of the span are touched).  The input order is (wave, row, lane, position in
+// the word): word indices, and so element indices, still grow along it.
+#ifndef GS_TOPK16_PACKED
+#define GS_TOPK16_PACKED 1
+#endif
+template <bool IDX, typename Cls>
+__device__ __forceinline__ void compact_tile16(const uint16_t *__restrict__ src, const uint32_t *__restrict__ src_idx, uint32_t lo,
+                                               uint32_t count, Cls cls, uint32_t baseA, uint32_t limA, uint16_t *__restrict__ ak,
+                                               uint32_t *__restrict__ ai, uint32_t baseB, uint32_t limB, uint16_t *__restrict__ bk,
+                                               uint32_t *__restrict__ bi, uint32_t (*wcnt)[TK_WAVES])
+{
+    constexpr int ROWS = TK_KPT / 2 + 1;
+    constexpr uint32_t SPAN = (uint32_t)(WAVE * TK_KPT);          // elements of one wave
+    const uint32_t w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t e0 = lo + w * SPAN;                            // the wave's first element
+    const uint32_t len = (e0 >= lo && e0 < count) ? (count - e0 < SPAN ? count - e0 : SPAN) : 0u;
+    const uintptr_t addr = (uintptr_t)src + 2 * (uintptr_t)e0;
+    const uint32_t par = (uint32_t)(addr >> 1) & 1u;              // 1: element e0 is the upper half of its word
+    const uint32_t *W = reinterpret_cast<const uint32_t *>(addr - 2 * par);
+    uint32_t word[ROWS], c[ROWS];                                 // c: class of the lower element | class of the upper one << 2
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        const uint32_t j = (uint32_t)r * WAVE + lane, a = 2u * j - par;       // word j holds elements a and a + 1 of the span
+        word[r] = (a < len || a + 1u < len) ? __builtin_nontemporal_load(W + j) : 0u;     // (a = 0xffffffff for j = 0, par = 1)
+    }
+    uint32_t nA = 0, nB = 0;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        const uint32_t j = (uint32_t)r * WAVE + lane, a = 2u * j - par;
+        const uint32_t ca = a < len ? cls(word[r] & 0xffffu) : 0u, cb = a + 1u < len ? cls(word[r] >> 16) : 0u;
+        c[r] = ca | (cb << 2);
+        nA += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(ca == 1u)) + (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(cb == 1u));
+        nB += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(ca == 2u)) + (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(cb == 2u));
+    }
+    if (lane == 0) { wcnt[0][w] = nA; wcnt[1][w] = nB; }
+    __syncthreads();
+    uint32_t tot = 0;
+    for (uint32_t j = 0; j < (uint32_t)TK_WAVES; ++j) {
+        const uint32_t a = wcnt[0][j], b = wcnt[1][j];
+        tot += a + b;
+        if (j < w) { baseA += a; baseB += b; }
+    }
+    if (tot == 0) return;   // nothing of either group in this tile (workgroup-uniform)
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        const uint32_t j = (uint32_t)r * WAVE + lane, i = e0 + 2u * j - par;      // index of the lower element
+        asm volatile("" : "+v"(c[r]));   // ballot again, as in compact_tile
+        const uint32_t ca = c[r] & 3u, cb = c[r] >> 2;
+        const unsigned long long mA0 = __builtin_amdgcn_ballot_w64(ca == 1u), mA1 = __builtin_amdgcn_ballot_w64(cb == 1u);
+        const unsigned long long mB0 = __builtin_amdgcn_ballot_w64(ca == 2u), mB1 = __builtin_amdgcn_ballot_w64(cb == 2u);
+        const uint32_t pA = baseA + count_lower(mA0) + count_lower(mA1), pB = baseB + count_lower(mB0) + count_lower(mB1);
+        if (ca) {
+            const uint32_t pos = ca == 1u ? pA : pB;
+            if (pos < (ca == 1u ? limA : limB)) {
+                (ca == 1u ? ak : bk)[pos] = (uint16_t)word[r];
+                if (IDX) (ca == 1u ? ai : bi)[pos] = src_idx ? src_idx[i] : i;
+            }
+        }
+        if (cb) {
+            const uint32_t pos = cb == 1u ? pA + (ca == 1u ? 1u : 0u) : pB + (ca == 2u ? 1u : 0u);
+            if (pos < (cb == 1u ? limA : limB)) {
+                (cb == 1u ? ak : bk)[pos] = (uint16_t)(word[r] >> 16);
+                if (IDX) (cb == 1u ? ai : bi)[pos] = src_idx ? src_idx[i + 1u] : i + 1u;
+            }
+        }
+        baseA += (uint32_t)__popcll(mA0) + (uint32_t)__popcll(mA1);
+        baseB += (uint32_t)__popcll(mB0) + (uint32_t)__popcll(mB1);
+    }
+}
+
+// the compaction an element type takes
+template <bool IDX, typename T, typename Cls>
+__device__ __forceinline__ void compact_any(const T *__restrict__ src, const uint32_t *__restrict__ src_idx, uint32_t lo, uint32_t count,
+                                            Cls cls, uint32_t baseA, uint32_t limA, T *__restrict__ ak, uint32_t *__restrict__ ai,
+                                            uint32_t baseB, uint32_t limB, T *__restrict__ bk, uint32_t *__restrict__ bi,
+                                            uint32_t (*wcnt)[TK_WAVES])
+{
+    if constexpr (sizeof(T) == 2 && GS_TOPK16_PACKED) compact_tile16<IDX>(src, src_idx, lo, count, cls, baseA, limA, ak, ai, baseB, limB, bk, bi, wcnt);
+    else compact_tile<IDX>(src, src_idx, lo, count, cls, baseA, limA, ak, ai, baseB, limB, bk, bi, wcnt);
+}
+
 // --------------------------------------------------------------------- filter --
 // Second read of the input, one workgroup per tile of the upsweep.  Group A: top byte before d0 -> staging area, at the
 // number of such elements in front of the tile (sum over the digits below d0 of spine + prefix16).  Group B (route 1
-// only): top byte d0 -> candidate list, at spine[d0] + prefix16[d0].
-template <bool IDX>
-__global__ __launch_bounds__(TK_THREADS) void topk_filter_kernel(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ spine,
+// only): top byte d0 -> candidate list, at spine[d0] + prefix16[d0].  16-bit keys: round one was the narrow upsweep, whose
+// spine has one column per tile (grid = the number of tiles) and no prefix16, so spine[d][tile] alone is the digit's base.
+template <bool IDX, typename T>
+__global__ __launch_bounds__(TK_THREADS) void topk_filter_kernel(const T *__restrict__ keys, const uint32_t *__restrict__ spine,
                                                                  const uint16_t *__restrict__ prefix16, const uint32_t *__restrict__ state,
-                                                                 uint32_t *__restrict__ stage_keys, uint32_t *__restrict__ stage_idx,
-                                                                 uint32_t *__restrict__ cand_keys, uint32_t *__restrict__ cand_idx, uint32_t n,
+                                                                 T *__restrict__ stage_keys, uint32_t *__restrict__ stage_idx,
+                                                                 T *__restrict__ cand_keys, uint32_t *__restrict__ cand_idx, uint32_t n,
                                                                  uint32_t grid, uint32_t k, uint32_t cap, int f32, uint32_t x)
 {
     __shared__ uint32_t wcnt[2][TK_WAVES];
@@ -196,7 +300,9 @@ __global__ __launch_bounds__(TK_THREADS) void topk_filter_kernel(const uint32_t 
     const uint32_t d0 = state[TK_D0], route = state[TK_ROUTE];
     uint32_t below = 0;
     if (tid <= d0) {   // d0 < 256: only the digits that count are read
-        const uint32_t v = spine[(size_t)tid * grid + chunk] + prefix16[(size_t)tile * RADIX + tid];
+        uint32_t v;
+        if constexpr (sizeof(T) == 4) v = spine[(size_t)tid * grid + chunk] + prefix16[(size_t)tile * RADIX + tid];
+        else v = spine[(size_t)tid * grid + tile];
         if (tid < d0) below = v;
         if (tid == d0) cbase = v;
     }
@@ -207,16 +313,17 @@ __global__ __launch_bounds__(TK_THREADS) void topk_filter_kernel(const uint32_t 
     for (int j = 0; j < RADIX / WAVE; ++j) baseA += wsum[j];
     const uint32_t baseB = cbase;
     auto cls = [&](uint32_t raw) -> uint32_t {
-        const uint32_t tb = twiddle_in(raw, f32, x) >> 24;
+        const uint32_t tb = TkKey<T>::image(raw, f32, x) >> TkKey<T>::TOP;
         return tb < d0 ? 1u : (tb == d0 && route == 1u) ? 2u : 0u;
     };
-    compact_tile<IDX>(keys, nullptr, tile * (uint32_t)LSB_TILE, n, cls, baseA, k, stage_keys, stage_idx, baseB, cap, cand_keys, cand_idx, wcnt);
+    compact_any<IDX>(keys, (const uint32_t *)nullptr, tile * (uint32_t)LSB_TILE, n, cls, baseA, k, stage_keys, stage_idx, baseB, cap, cand_keys, cand_idx, wcnt);
 }
 
 // ------------------------------------------------------ rounds two to four: count --
 // Histogram of the byte at `shift` over the source elements whose bytes above it equal the prefix found so far.  LDS
 // histogram per workgroup, then one integer add per non-empty bin.
-__global__ __launch_bounds__(TK_THREADS) void topk_hist_kernel(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ cand_keys,
+template <typename T>
+__global__ __launch_bounds__(TK_THREADS) void topk_hist_kernel(const T *__restrict__ keys, const T *__restrict__ cand_keys,
                                                                const uint32_t *__restrict__ state, uint32_t *__restrict__ hist,
                                                                uint32_t shift, int f32, uint32_t x)
 {
@@ -225,7 +332,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_hist_kernel(const uint32_t *_
     const uint64_t lo64 = (uint64_t)blockIdx.x * LSB_TILE;
     if (lo64 >= count) return;
     const uint32_t lo = (uint32_t)lo64, tid = threadIdx.x;
-    const uint32_t *src = state[TK_ROUTE] == 1u ? cand_keys : keys;
+    const T *src = state[TK_ROUTE] == 1u ? cand_keys : keys;
     const uint32_t prefix = state[TK_KTH], mask = 0xffffff00u << shift;
     if (tid < (uint32_t)RADIX) h[tid] = 0;
     __syncthreads();
@@ -233,12 +340,12 @@ __global__ __launch_bounds__(TK_THREADS) void topk_hist_kernel(const uint32_t *_
 #pragma unroll
     for (int u = 0; u < TK_KPT; ++u) {
         const uint32_t i = lo + (uint32_t)u * TK_THREADS + tid;
-        raw[u] = (i < count && i >= lo) ? __builtin_nontemporal_load(src + i) : 0u;
+        raw[u] = (i < count && i >= lo) ? (uint32_t)__builtin_nontemporal_load(src + i) : 0u;
     }
 #pragma unroll
     for (int u = 0; u < TK_KPT; ++u) {
         const uint32_t i = lo + (uint32_t)u * TK_THREADS + tid;
-        const uint32_t img = twiddle_in(raw[u], f32, x);
+        const uint32_t img = TkKey<T>::image(raw[u], f32, x);
         if (i < count && i >= lo && ((img ^ prefix) & mask) == 0u) hist_add(h, (img >> shift) & 255u);
     }
     __syncthreads();
@@ -247,7 +354,8 @@ __global__ __launch_bounds__(TK_THREADS) void topk_hist_kernel(const uint32_t *_
 
 // -------------------------------------------------------- final ordered select --
 // count: per source tile, the elements of the bucket that sort before the k-th image and those equal to it
-__global__ __launch_bounds__(TK_THREADS) void topk_count_kernel(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ cand_keys,
+template <typename T>
+__global__ __launch_bounds__(TK_THREADS) void topk_count_kernel(const T *__restrict__ keys, const T *__restrict__ cand_keys,
                                                                 const uint32_t *__restrict__ state, uint32_t *__restrict__ tilecnt,
                                                                 int f32, uint32_t x)
 {
@@ -256,19 +364,19 @@ __global__ __launch_bounds__(TK_THREADS) void topk_count_kernel(const uint32_t *
     const uint64_t lo64 = (uint64_t)blockIdx.x * LSB_TILE;
     if (lo64 >= count) return;
     const uint32_t lo = (uint32_t)lo64, tid = threadIdx.x;
-    const uint32_t *src = state[TK_ROUTE] == 1u ? cand_keys : keys;
-    const uint32_t kth = state[TK_KTH], lowest = kth & 0xff000000u;
+    const T *src = state[TK_ROUTE] == 1u ? cand_keys : keys;
+    const uint32_t kth = state[TK_KTH], lowest = kth & (0xffu << TkKey<T>::TOP);
     uint32_t raw[TK_KPT];
 #pragma unroll
     for (int u = 0; u < TK_KPT; ++u) {
         const uint32_t i = lo + (uint32_t)u * TK_THREADS + tid;
-        raw[u] = (i < count && i >= lo) ? __builtin_nontemporal_load(src + i) : 0u;
+        raw[u] = (i < count && i >= lo) ? (uint32_t)__builtin_nontemporal_load(src + i) : 0u;
     }
     uint32_t l = 0, e = 0;
 #pragma unroll
     for (int u = 0; u < TK_KPT; ++u) {
         const uint32_t i = lo + (uint32_t)u * TK_THREADS + tid;
-        const uint32_t img = twiddle_in(raw[u], f32, x);
+        const uint32_t img = TkKey<T>::image(raw[u], f32, x);
         const bool ok = i < count && i >= lo;
         l += (ok && img >= lowest && img < kth) ? 1u : 0u;
         e += (ok && img == kth) ? 1u : 0u;
@@ -317,10 +425,10 @@ __global__ __launch_bounds__(TK_SCAN_THREADS) void topk_scan_kernel(const uint32
 
 // scatter: group A = the bucket's elements before the k-th image, behind the staged elements of the filter; group B = the
 // elements equal to it, behind all that sort before it, cut after `take` of them
-template <bool IDX>
-__global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ cand_keys,
+template <bool IDX, typename T>
+__global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const T *__restrict__ keys, const T *__restrict__ cand_keys,
                                                                  const uint32_t *__restrict__ cand_idx, const uint32_t *__restrict__ state,
-                                                                 const uint32_t *__restrict__ tilecnt, uint32_t *__restrict__ stage_keys,
+                                                                 const uint32_t *__restrict__ tilecnt, T *__restrict__ stage_keys,
                                                                  uint32_t *__restrict__ stage_idx, uint32_t k, int f32, uint32_t x)
 {
     __shared__ uint32_t wcnt[2][TK_WAVES];
@@ -328,14 +436,14 @@ __global__ __launch_bounds__(TK_THREADS) void topk_select_kernel(const uint32_t 
     const uint64_t lo64 = (uint64_t)blockIdx.x * LSB_TILE;
     if (lo64 >= count) return;
     const bool list = state[TK_ROUTE] == 1u;
-    const uint32_t kth = state[TK_KTH], lowest = kth & 0xff000000u, less = state[TK_LESS], take = state[TK_TAKE];
+    const uint32_t kth = state[TK_KTH], lowest = kth & (0xffu << TkKey<T>::TOP), less = state[TK_LESS], take = state[TK_TAKE];
     const uint32_t baseA = state[TK_STAGED0] + tilecnt[2u * blockIdx.x], baseB = less + tilecnt[2u * blockIdx.x + 1u];
     const uint32_t limB = less + take < k ? less + take : k;
     auto cls = [&](uint32_t raw) -> uint32_t {
-        const uint32_t img = twiddle_in(raw, f32, x);
+        const uint32_t img = TkKey<T>::image(raw, f32, x);
         return img == kth ? 2u : (img >= lowest && img < kth) ? 1u : 0u;
     };
-    compact_tile<IDX>(list ? cand_keys : keys, list ? cand_idx : nullptr, (uint32_t)lo64, count, cls, baseA, k, stage_keys, stage_idx,
+    compact_any<IDX>(list ? cand_keys : keys, list ? cand_idx : (const uint32_t *)nullptr, (uint32_t)lo64, count, cls, baseA, k, stage_keys, stage_idx,
                       baseB, limB, stage_keys, stage_idx, wcnt);
 }
 
@@ -356,22 +464,23 @@ __global__ __launch_bounds__(256) void topk_iota_kernel(uint32_t *__restrict__ o
 }
 
 // Route 3, one workgroup: copy the first k of the sorted array out and write the status words from it.
-__global__ __launch_bounds__(TK_THREADS) void topk_small_finish_kernel(const uint32_t *__restrict__ sk, const uint32_t *__restrict__ sv,
-                                                                       uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
+template <typename T>
+__global__ __launch_bounds__(TK_THREADS) void topk_small_finish_kernel(const T *__restrict__ sk, const uint32_t *__restrict__ sv,
+                                                                       T *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
                                                                        uint32_t *__restrict__ state, uint32_t n, uint32_t k, int f32, uint32_t x)
 {
     __shared__ uint32_t acc[2];
     const uint32_t tid = threadIdx.x;
     if (tid < 2) acc[tid] = 0;
     __syncthreads();
-    const uint32_t kth = twiddle_in(sk[k - 1u], f32, x);
+    const uint32_t kth = TkKey<T>::image(sk[k - 1u], f32, x);
     uint32_t less = 0, top = 0;
     for (uint32_t i = tid; i < n; i += TK_THREADS) {
-        const uint32_t raw = sk[i], img = twiddle_in(raw, f32, x);
+        const uint32_t raw = sk[i], img = TkKey<T>::image(raw, f32, x);
         less += img < kth ? 1u : 0u;
-        top += (img >> 24) == (kth >> 24) ? 1u : 0u;
+        top += (img >> TkKey<T>::TOP) == (kth >> TkKey<T>::TOP) ? 1u : 0u;
         if (i < k) {
-            keys_out[i] = raw;
+            keys_out[i] = (T)raw;
             if (vals_out) vals_out[i] = sv[i];
         }
     }
@@ -396,6 +505,51 @@ static bool tk_overlaps(const void *a, size_t abytes, const void *b, size_t bbyt
     const char *p = (const char *)a, *q = (const char *)b;
     return p < q + bbytes && q < p + abytes;
 }
+
+// ------------------------------------------------------------- 16-bit keys: host --
+struct TopkWs16 {
+    uint32_t *state, *hist;          // [64], [256]
+    uint32_t *spine, *totals;        // the narrow upsweep's: [256][tiles], [256]
+    uint32_t *tilecnt;
+    uint16_t *cand_keys;             // the candidate area: keys, then (has_values) indices; route 3 lays its arrays over both
+    uint32_t *cand_idx;
+    uint16_t *stage_keys;
+    uint32_t *stage_idx, *idx_sorted;
+    char *sort_ws;
+    size_t sort_ws_bytes;
+};
+
+// route 3's arrays inside the candidate area (at least 2 * TK_MIN_CAND = 128 KiB; 384 KiB with values): the sorted keys, the
+// sorted values, the iota of the arguments form, then the workspace of the sort of at most LSB_TILE elements
+constexpr size_t TK16_SMALL_VALS = (size_t)LSB_TILE * 2, TK16_SMALL_IOTA = TK16_SMALL_VALS + (size_t)LSB_TILE * 4,
+                 TK16_SMALL_WS = TK16_SMALL_IOTA + (size_t)LSB_TILE * 4;
+
+static size_t tk16_carve(char *base, uint64_t n, uint64_t k, bool hv, TopkWs16 *ws)
+{
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *p = (char *)((uintptr_t)base + off); off += tk_align(bytes); return p; };   // (base may be null: the size query)
+    char *head = take(4096);
+    char *spine = take((size_t)RADIX * 4 * tk_tiles(n));
+    char *totals = take(RADIX * 4);
+    char *tilecnt = take((size_t)8 * tk_tiles(n));
+    char *ck = take((size_t)2 * tk_cand_cap(n));
+    char *ci = hv ? take((size_t)4 * tk_cand_cap(n)) : nullptr;
+    char *sk = take((size_t)2 * k);
+    char *si = hv ? take((size_t)4 * k) : nullptr;
+    char *is = hv ? take((size_t)4 * k) : nullptr;
+    const size_t sort_bytes = gs_lsb_narrow_temp_bytes(k, GS_KEY_U16, hv ? 4 : 0);
+    char *sw = take(sort_bytes);
+    if (ws) {
+        ws->state = (uint32_t *)head; ws->hist = (uint32_t *)(head + 256);
+        ws->spine = (uint32_t *)spine; ws->totals = (uint32_t *)totals; ws->tilecnt = (uint32_t *)tilecnt;
+        ws->cand_keys = (uint16_t *)ck; ws->cand_idx = (uint32_t *)ci;
+        ws->stage_keys = (uint16_t *)sk; ws->stage_idx = (uint32_t *)si; ws->idx_sorted = (uint32_t *)is;
+        ws->sort_ws = sw; ws->sort_ws_bytes = sort_bytes;
+    }
+    return off;
+}
+
+static inline bool tk16_key_type_ok(int kt) { return kt == GS_KEY_U16 || kt == GS_KEY_I16 || kt == GS_KEY_F16 || kt == GS_KEY_BF16; }
 
 }  // namespace gs
 
@@ -450,7 +604,7 @@ int gs_topk_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, cons
                                    p.xor_out, s)))
             return e;
         KernelTimer kt(GS_K_OTHER, s);
-        hipLaunchKernelGGL(topk_small_finish_kernel, dim3(1), dim3(TK_THREADS), 0, s, sk, sv, d_keys_out, d_vals_out, ws.state, n, kk,
+        hipLaunchKernelGGL(topk_small_finish_kernel<uint32_t>, dim3(1), dim3(TK_THREADS), 0, s, sk, sv, d_keys_out, d_vals_out, ws.state, n, kk,
                            p.f32_in, p.xor_in);
         return (int)hipGetLastError();
     }
@@ -461,40 +615,40 @@ int gs_topk_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, cons
     const uint32_t cap = (uint32_t)tk_cand_cap(num_items);
     {
         KernelTimer kt(GS_K_OTHER, s);
-        hipLaunchKernelGGL(topk_pick0_kernel, dim3(1), dim3(RADIX), 0, s, ws.totals, ws.state, ws.hist, n, kk, cap);
+        hipLaunchKernelGGL(topk_pick0_kernel<24>, dim3(1), dim3(RADIX), 0, s, ws.totals, ws.state, ws.hist, n, kk, cap);
     }
     // filter
     {
         KernelTimer kt(GS_K_OTHER, s);
         if (hv)
-            hipLaunchKernelGGL(topk_filter_kernel<true>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine, ws.prefix16, ws.state,
+            hipLaunchKernelGGL((topk_filter_kernel<true, uint32_t>), dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine, ws.prefix16, ws.state,
                                ws.stage_keys, ws.stage_idx, ws.cand_keys, ws.cand_idx, n, p.grid, kk, cap, p.f32_in, p.xor_in);
         else
-            hipLaunchKernelGGL(topk_filter_kernel<false>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine, ws.prefix16, ws.state,
+            hipLaunchKernelGGL((topk_filter_kernel<false, uint32_t>), dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine, ws.prefix16, ws.state,
                                ws.stage_keys, ws.stage_idx, ws.cand_keys, ws.cand_idx, n, p.grid, kk, cap, p.f32_in, p.xor_in);
     }
     // rounds two to four
     for (int r = 0; r < 3; ++r) {
         const uint32_t shift = 16u - 8u * (uint32_t)r;
         { KernelTimer kt(GS_K_OTHER, s);
-          hipLaunchKernelGGL(topk_hist_kernel, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.state,
+          hipLaunchKernelGGL(topk_hist_kernel<uint32_t>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.state,
                              ws.hist + r * RADIX, shift, p.f32_in, p.xor_in); }
         { KernelTimer kt(GS_K_OTHER, s);
           hipLaunchKernelGGL(topk_pick_kernel, dim3(1), dim3(RADIX), 0, s, ws.hist + r * RADIX, ws.state, shift); }
     }
     // final ordered select
     { KernelTimer kt(GS_K_OTHER, s);
-      hipLaunchKernelGGL(topk_count_kernel, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.state, ws.tilecnt,
+      hipLaunchKernelGGL(topk_count_kernel<uint32_t>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.state, ws.tilecnt,
                          p.f32_in, p.xor_in); }
     { KernelTimer kt(GS_K_OTHER, s);
       hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(TK_SCAN_THREADS), 0, s, ws.state, ws.tilecnt); }
     {
         KernelTimer kt(GS_K_OTHER, s);
         if (hv)
-            hipLaunchKernelGGL(topk_select_kernel<true>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.cand_idx,
+            hipLaunchKernelGGL((topk_select_kernel<true, uint32_t>), dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.cand_idx,
                                ws.state, ws.tilecnt, ws.stage_keys, ws.stage_idx, kk, p.f32_in, p.xor_in);
         else
-            hipLaunchKernelGGL(topk_select_kernel<false>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.cand_idx,
+            hipLaunchKernelGGL((topk_select_kernel<false, uint32_t>), dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.cand_idx,
                                ws.state, ws.tilecnt, ws.stage_keys, ws.stage_idx, kk, p.f32_in, p.xor_in);
     }
     if ((e = (int)hipGetLastError())) return e;
@@ -519,6 +673,131 @@ int gs_topk_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values,
     if (!d_temp) return hipErrorInvalidValue;
     TopkWs ws;
     tk_carve(gs_ws_base(d_temp), num_items, k, has_values != 0, &ws);
+    hipError_t e = hipMemcpyAsync(out, ws.state, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    return (int)e;
+}
+
+// ------------------------------------------------------------------ 16-bit keys --
+size_t gs_topk_u16_temp_bytes(uint64_t num_items, uint64_t k, int has_values)
+{
+    if (k == 0 || num_items == 0) return 0;
+    return tk16_carve(nullptr, num_items, k, has_values != 0, nullptr) + GS_WS_SLACK;
+}
+
+int gs_topk_u16(void *d_temp, size_t temp_bytes, const uint16_t *d_keys_in, const uint32_t *d_vals_in, uint16_t *d_keys_out,
+                uint32_t *d_vals_out, uint64_t num_items, uint64_t k, int descending, int key_type, void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (num_items >= (1ull << 32) || k > num_items) return hipErrorInvalidValue;
+    if (!tk16_key_type_ok(key_type)) return hipErrorInvalidValue;
+    if (d_vals_in && !d_vals_out) return hipErrorInvalidValue;
+    if (k == 0 || num_items == 0) return hipSuccess;
+    const bool hv = d_vals_out != nullptr;
+    if (!d_keys_in || !d_keys_out) return hipErrorInvalidValue;
+    if (!d_temp || temp_bytes < gs_topk_u16_temp_bytes(num_items, k, hv)) return hipErrorInvalidValue;
+    if ((((uintptr_t)d_keys_in | (uintptr_t)d_keys_out) & 1u) != 0 || (((uintptr_t)d_vals_in | (uintptr_t)d_vals_out) & 3u) != 0)
+        return hipErrorInvalidValue;
+    {
+        const void *arr[4] = {d_keys_in, d_vals_in, d_keys_out, d_vals_out};
+        const size_t bytes[4] = {(size_t)num_items * 2, (size_t)num_items * 4, (size_t)k * 2, (size_t)k * 4};
+        for (int i = 0; i < 4; ++i)
+            for (int j = i + 1; j < 4; ++j)
+                if (tk_overlaps(arr[i], bytes[i], arr[j], bytes[j])) return hipErrorInvalidValue;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t n = (uint32_t)num_items, kk = (uint32_t)k;
+    TopkWs16 ws;
+    tk16_carve(gs_ws_base(d_temp), num_items, k, hv, &ws);
+    const int fk = (key_type == GS_KEY_F16 || key_type == GS_KEY_BF16) ? 1 : 0;
+    const uint32_t x = (key_type == GS_KEY_U16 ? 0u : 0x8000u) ^ (descending ? 0xffffu : 0u);   // the image stays 16 bits wide
+    const int vb = hv ? 4 : 0;
+    int e;
+
+    if (n <= (uint32_t)LSB_TILE) {
+        // route 3: one tile.  Sorted whole into the candidate area, then the first k are copied out.
+        char *area = (char *)ws.cand_keys;
+        const size_t sort_bytes = gs_lsb_narrow_temp_bytes(n, key_type, vb);
+        if (TK16_SMALL_WS + sort_bytes > (size_t)(hv ? 6 : 2) * TK_MIN_CAND) return hipErrorInvalidValue;   // (the copies would not fit)
+        uint16_t *sk = (uint16_t *)area;
+        uint32_t *sv = (uint32_t *)(area + TK16_SMALL_VALS), *iota = (uint32_t *)(area + TK16_SMALL_IOTA);
+        const uint32_t *vin = d_vals_in;
+        if (hv && !vin) {
+            KernelTimer kt(GS_K_OTHER, s);
+            hipLaunchKernelGGL(topk_iota_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, iota, n);
+            vin = iota;
+        }
+        if ((e = gs_lsb_sort_narrow(area + TK16_SMALL_WS, sort_bytes, d_keys_in, sk, hv ? vin : nullptr, hv ? sv : nullptr, n, key_type, vb,
+                                    0, 16, descending, stream)))
+            return e;
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(topk_small_finish_kernel<uint16_t>, dim3(1), dim3(TK_THREADS), 0, s, (const uint16_t *)sk, (const uint32_t *)sv,
+                           d_keys_out, d_vals_out, ws.state, n, kk, fk, x);
+        return (int)hipGetLastError();
+    }
+
+    // round one: the narrow upsweep on the image's top byte, its spine scan, the pick
+    const uint32_t tiles = (uint32_t)tk_tiles(num_items);
+    const LargeDigit dg = {8, 8, key_type, descending ? 1 : 0, true, true};
+    if ((e = narrow_slice_count(d_keys_in, num_items, 4, dg, ws.spine, ws.totals, s))) return e;
+    const uint32_t cap = (uint32_t)tk_cand_cap(num_items);
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(topk_pick0_kernel<8>, dim3(1), dim3(RADIX), 0, s, ws.totals, ws.state, ws.hist, n, kk, cap);
+    }
+    // filter
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        if (hv)
+            hipLaunchKernelGGL((topk_filter_kernel<true, uint16_t>), dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine,
+                               (const uint16_t *)nullptr, ws.state, ws.stage_keys, ws.stage_idx, ws.cand_keys, ws.cand_idx, n, tiles, kk, cap, fk, x);
+        else
+            hipLaunchKernelGGL((topk_filter_kernel<false, uint16_t>), dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine,
+                               (const uint16_t *)nullptr, ws.state, ws.stage_keys, ws.stage_idx, ws.cand_keys, ws.cand_idx, n, tiles, kk, cap, fk, x);
+    }
+    // round two: the low byte
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL(topk_hist_kernel<uint16_t>, dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, (const uint16_t *)ws.cand_keys, ws.state,
+                         ws.hist, 0u, fk, x); }
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL(topk_pick_kernel, dim3(1), dim3(RADIX), 0, s, ws.hist, ws.state, 0u); }
+    // final ordered select
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL(topk_count_kernel<uint16_t>, dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, (const uint16_t *)ws.cand_keys, ws.state,
+                         ws.tilecnt, fk, x); }
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(TK_SCAN_THREADS), 0, s, ws.state, ws.tilecnt); }
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        if (hv)
+            hipLaunchKernelGGL((topk_select_kernel<true, uint16_t>), dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, (const uint16_t *)ws.cand_keys,
+                               (const uint32_t *)ws.cand_idx, ws.state, ws.tilecnt, ws.stage_keys, ws.stage_idx, kk, fk, x);
+        else
+            hipLaunchKernelGGL((topk_select_kernel<false, uint16_t>), dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, (const uint16_t *)ws.cand_keys,
+                               (const uint32_t *)ws.cand_idx, ws.state, ws.tilecnt, ws.stage_keys, ws.stage_idx, kk, fk, x);
+    }
+    if ((e = (int)hipGetLastError())) return e;
+    // finish: the stable narrow sort of the k staged pairs; the indices are the values of the arguments form
+    uint32_t *idx_out = !hv ? nullptr : d_vals_in ? ws.idx_sorted : d_vals_out;
+    if ((e = gs_lsb_sort_narrow(ws.sort_ws, ws.sort_ws_bytes, ws.stage_keys, d_keys_out, hv ? ws.stage_idx : nullptr, idx_out, k, key_type, vb,
+                                0, 16, descending, stream)))
+        return e;
+    if (d_vals_in) {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(topk_gather_kernel, dim3((kk + 255u) / 256u), dim3(256), 0, s, d_vals_in, ws.idx_sorted, d_vals_out, kk, n);
+    }
+    return (int)hipGetLastError();
+}
+
+int gs_topk_u16_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (!out || num_items >= (1ull << 32) || k > num_items) return hipErrorInvalidValue;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (k == 0 || num_items == 0) return hipSuccess;   // such a call enqueued nothing
+    if (!d_temp) return hipErrorInvalidValue;
+    TopkWs16 ws;
+    tk16_carve(gs_ws_base(d_temp), num_items, k, has_values != 0, &ws);
     hipError_t e = hipMemcpyAsync(out, ws.state, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     return (int)e;

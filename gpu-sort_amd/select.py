@@ -1,7 +1,8 @@
 """Partial sort: the first k elements of the stable sort, by radix select (gs_topk_u32 in include/gpusort.h).
 
 DeviceTopK is two-phase like DeviceRadixSort (d_temp_storage=None returns the size); topk() is the convenience form that
-allocates outputs and workspace.  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
+allocates outputs and workspace.  DeviceTopK16 is DeviceTopK for a flat array of 2-byte keys (gs_topk_u16: int16 / uint16 /
+float16 / bfloat16); topk() sends such tensors there.  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
 gs_topk_rows_u16 for int16 / uint16 / float16 / bfloat16 keys, in the order of GS_KEY_F16 / BF16 at the enum).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
 (descending for the Max forms) on the same input: stable, keys in the caller's bit patterns, floats in the order of
 GS_KEY_F32 (negative NaNs first, positive NaNs last ascending; -0.0 before +0.0).
@@ -85,8 +86,85 @@ class DeviceTopK:
         return [int(x) for x in out]
 
 
+_NARROW16 = (_lib.GS_KEY_U16, _lib.GS_KEY_I16, _lib.GS_KEY_F16, _lib.GS_KEY_BF16)     # what gs_topk_u16 / gs_topk_rows_u16 take
+
+
+def _key_type16_of(t, key_type, who="DeviceTopKRows"):
+    if key_type is None:
+        key_type = _KEY_TYPES.get(t.dtype)
+    if key_type not in _NARROW16:
+        raise TypeError(f"{who}: no 16-bit key category for {t.dtype} (int16, uint16, float16, bfloat16, or GS_KEY_U16 / "
+                        "I16 / F16 / BF16 by key_type)")
+    return key_type
+
+
+class DeviceTopK16:
+    """DeviceTopK for a flat array of 16-bit keys (gs_topk_u16): MinKeys / MaxKeys / MinPairs / MaxPairs / Status.
+
+    The key type comes from the tensor's dtype (int16, uint16, float16, bfloat16) or from an explicit 16-bit key_type; the
+    result is the first k of DeviceRadixSort on the same keys, in the order of GS_KEY_F16 / BF16 at the enum for the float
+    types.  Values and indices are 4 bytes, as in DeviceTopK.  Keys of any other width raise TypeError."""
+
+    @staticmethod
+    def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, descending,
+             has_values, stream, key_type):
+        if key_type is not None and key_type not in _NARROW16:
+            raise TypeError("DeviceTopK16: key_type must be GS_KEY_U16 / I16 / F16 / BF16")
+        need = lib.gs_topk_u16_temp_bytes(num_items, k, int(has_values))
+        if d_temp_storage is None:
+            return need
+        if not isinstance(d_keys_in, torch.Tensor) or d_keys_in.element_size() != 2:
+            raise TypeError("DeviceTopK16: 16-bit keys only")
+        key_type = _key_type16_of(d_keys_in, key_type, "DeviceTopK16")
+        _check_buf(d_keys_in, num_items, "d_keys_in", elem=2)
+        _check_buf(d_keys_out, k, "d_keys_out", elem=2)
+        if has_values:
+            if d_values_in is not None:
+                _check_buf(d_values_in, num_items, "d_values_in")
+            _check_buf(d_values_out, k, "d_values_out")
+        err = lib.gs_topk_u16(C.c_void_p(d_temp_storage.data_ptr()),
+                              min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                              d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
+                              d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
+                              num_items, k, int(descending), key_type, _stream_ptr(stream))
+        check(err, "gs_topk_u16")
+        return need
+
+    @staticmethod
+    def MinKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_items, k, stream=None, key_type=None):
+        return DeviceTopK16._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_items, k, False, False,
+                                 stream, key_type)
+
+    @staticmethod
+    def MaxKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_items, k, stream=None, key_type=None):
+        return DeviceTopK16._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_items, k, True, False,
+                                 stream, key_type)
+
+    @staticmethod
+    def MinPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, stream=None,
+                 key_type=None):
+        return DeviceTopK16._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k,
+                                 False, True, stream, key_type)
+
+    @staticmethod
+    def MaxPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, stream=None,
+                 key_type=None):
+        return DeviceTopK16._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k,
+                                 True, True, stream, key_type)
+
+    @staticmethod
+    def Status(d_temp_storage, num_items, k, has_values, stream=None):
+        """gs_topk_u16_status: DeviceTopK.Status' words, the image 16 bits wide.  Synchronises the stream."""
+        out = (C.c_uint32 * 8)()
+        check(lib.gs_topk_u16_status(C.c_void_p(d_temp_storage.data_ptr()), num_items, k, int(has_values), out, _stream_ptr(stream)),
+              "gs_topk_u16_status")
+        return [int(x) for x in out]
+
+
 def topk(keys, k, largest=False, values=None, indices=False, stream=None):
     """The k smallest (largest=True: largest) of `keys`, sorted, as (keys_out, values_out).
+
+    2-byte keys (int16, uint16, float16, bfloat16) take gs_topk_u16 through DeviceTopK16, 4-byte keys gs_topk_u32.
 
     values: a 4-byte tensor of the same length, carried with the keys.  indices=True (without values): values_out holds the
     input positions as int32 bit patterns of u32 indices.  Neither: values_out is None.  Allocates outputs and workspace."""
@@ -100,17 +178,17 @@ def topk(keys, k, largest=False, values=None, indices=False, stream=None):
     values_out = None
     if has_values:
         values_out = torch.empty(k, dtype=values.dtype if values is not None else torch.int32, device=keys.device)
+    front = DeviceTopK16 if keys.element_size() == 2 else DeviceTopK
+    if front is DeviceTopK16:
+        _key_type16_of(keys, None, "topk")
     if k == 0:
         return keys_out, values_out
-    nbytes = lib.gs_topk_temp_bytes(n, k, int(has_values))
+    nbytes = front._run(None, 0, None, None, None, None, n, k, largest, has_values, stream, None)
     temp = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
     if stream is not None:
         temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
-    DeviceTopK._run(temp, nbytes, keys, keys_out, values, values_out, n, k, largest, has_values, stream, None)
+    front._run(temp, nbytes, keys, keys_out, values, values_out, n, k, largest, has_values, stream, None)
     return keys_out, values_out
-
-
-_NARROW16 = (_lib.GS_KEY_U16, _lib.GS_KEY_I16, _lib.GS_KEY_F16, _lib.GS_KEY_BF16)     # what gs_topk_rows_u16 takes
 
 
 def _check_rows_in(t, what, elem=4):
@@ -118,15 +196,6 @@ def _check_rows_in(t, what, elem=4):
     extent is the caller's statement: (num_rows - 1) * row_stride + num_cols elements)."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda or t.element_size() != elem:
         raise ValueError(f"{what}: expected a device tensor of {elem}-byte elements")
-
-
-def _key_type16_of(t, key_type):
-    if key_type is None:
-        key_type = _KEY_TYPES.get(t.dtype)
-    if key_type not in _NARROW16:
-        raise TypeError(f"DeviceTopKRows: no 16-bit key category for {t.dtype} (int16, uint16, float16, bfloat16, or GS_KEY_U16 / "
-                        "I16 / F16 / BF16 by key_type)")
-    return key_type
 
 
 # what the key width changes at the front end: the entry point, its size query, the key-type resolver, the key's bytes
@@ -217,7 +286,7 @@ def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
     values: a 4-byte tensor of the same shape and strides, carried with the keys.  indices=True (without values): values_out
     holds the column indices as int32 bit patterns of u32.  Neither: values_out is None.  Allocates outputs and workspace.
     A k above DeviceTopKRows.MaxK() is served by gs_topk_u32 row by row.  2-byte keys (int16, uint16, float16, bfloat16) take
-    gs_topk_rows_u16; for them a k above MaxK() raises ValueError: there is no flat 16-bit top-k to loop over."""
+    gs_topk_rows_u16; for them a k above MaxK() raises ValueError: such callers loop topk() over the rows."""
     if values is not None and indices:
         raise ValueError("topk_rows: give values or indices=True, not both")
     if keys.dim() != 2:
@@ -237,7 +306,7 @@ def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
     if narrow:
         _key_type16_of(keys, None)
         if k > lib.gs_topk_rows_max_k():
-            raise ValueError("topk_rows: 16-bit keys need k <= %d" % lib.gs_topk_rows_max_k())
+            raise ValueError("topk_rows: 16-bit keys need k <= %d; loop topk() over the rows for more" % lib.gs_topk_rows_max_k())
     elif keys.element_size() != 4:
         raise TypeError("topk_rows: 32-bit or 16-bit keys only")
     has_values = values is not None or indices

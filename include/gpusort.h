@@ -415,6 +415,55 @@ int    gs_topk_u32(void *d_temp, size_t temp_bytes,
  * benches read it.                                                                                                         */
 int    gs_topk_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream);
 
+/* ------------------------------------------------------- top k, 16-bit keys --
+ * gs_topk_u32 for a flat array of 16-bit keys, its kernels instantiated for them (gs_topk.hip): the
+ * best k of a column of bfloat16 or half scores with their row ids, without widening the keys or sorting the array.
+ * key_type is GS_KEY_U16, GS_KEY_I16, GS_KEY_F16 or GS_KEY_BF16, in the order stated at the enum (GS_KEY_F32's map at width
+ * 16: negative NaNs first, positive NaNs last, -0 before +0).  With S = the output of gs_lsb_sort_narrow(..., key_type,
+ * val_bytes = 0 or 4, begin_bit 0, end_bit 16, descending) on the same input, d_keys_out[0..k) and d_vals_out[0..k) are
+ * S[0..k), bit for bit: keys keep the caller's bit patterns, and where the cut falls inside a run of equal keys the lowest
+ * input indices are taken.  Equivalently it is bit for bit what gs_topk_u32 gives on the array (uint32_t)key << 16 with the
+ * key type widened (U16 -> U32, I16 -> I32, F16 / BF16 -> F32), the returned keys shifted right by 16, values and indices
+ * unchanged (for F16 too: the order is sign-magnitude on the bits, whatever the exponent width).
+ * Forms: gs_topk_u32's -- keys only; pairs, with u32 values; arguments (d_vals_in == NULL, d_vals_out != NULL: the u32 input
+ * index).  has_values of the two queries is non-zero for the last two.
+ * The contract is gs_topk_u32's: plain pointers, the inputs are never written, nothing outside [0, k) of the outputs is
+ * written, d_temp anywhere, 1 <= k <= num_items < 2^32 (k == 0 or num_items == 0 returns 0, writes nothing and needs no
+ * workspace: the query returns 0).  The call only enqueues work on `stream` (no host read-back, allocation or
+ * synchronisation); the same kernels are launched in the same order whatever the data (every decision is taken on the
+ * device), so it may be captured into a HIP graph on one plain stream; calls may follow each other on one stream with one
+ * workspace, and two runs on the same input give identical bytes.
+ * Errors (hipErrorInvalidValue, checked before anything is enqueued, nothing written): a NULL or too-small workspace,
+ * k > num_items, num_items >= 2^32, any other key_type, d_vals_in without d_vals_out, a NULL key pointer, a key array not
+ * aligned to 2 bytes or a value array not aligned to 4, arrays that share a byte (2 bytes per key, 4 per value; inputs at
+ * num_items elements, outputs at k).  A key array at an even address that is not a multiple of 4 is served like any other.
+ * Cost: two digits of 8 bits where gs_topk_u32 has four.  Round one (the narrow upsweep on the image's top byte) and the
+ * filter read the input once each, 2 bytes per key; one histogram round and the select then run over the candidate list of
+ * C elements when the elements sharing the k-th one's top byte fit it (route 1), otherwise over the input itself, five reads
+ * in all (route 2).  An array of one tile (num_items <= gs_lsb_narrow_tile(key_type, 4) = 8192) is sorted whole into the
+ * workspace and its first k copied out (route 3).  The finish is gs_lsb_sort_narrow of the k selected (key, index) pairs.
+ * Workspace: a pure host function of its arguments, a multiple of 256, monotone in num_items and in k.  With tiles =
+ * max(1, ceil(num_items / 8192)), C = max(65536, num_items / 32), hv = 1 with has_values else 0, and every term rounded up to
+ * 256 bytes:
+ *   4096                                      the state block, the histogram of round two, scratch
+ * + 256 * 4 * tiles + 1024                    the spine (one column per tile) and the digit totals of round one
+ * + 8 * tiles                                 two counts per source tile of the final select
+ * + 2 * C + hv * 4 * C                        the candidate list: 16-bit keys (and u32 indices); route 3's copies, iota and
+ *                                             sort workspace lie inside this area
+ * + 2 * k + hv * 4 * k                        the staging area: the k selected keys (and indices)
+ * + hv * 4 * k                                the sorted indices on their way through the gather of the pairs form
+ * + gs_lsb_narrow_temp_bytes(k, GS_KEY_U16, hv ? 4 : 0)   the workspace of the final sort
+ * + 256 bytes of alignment slack.                                                                                         */
+size_t gs_topk_u16_temp_bytes(uint64_t num_items, uint64_t k, int has_values);
+int    gs_topk_u16(void *d_temp, size_t temp_bytes,
+                   const uint16_t *d_keys_in, const uint32_t *d_vals_in,
+                   uint16_t *d_keys_out, uint32_t *d_vals_out,
+                   uint64_t num_items, uint64_t k, int descending, int key_type, void *stream);
+/* gs_topk_status for gs_topk_u16: out[0] = route (1, 2 or 3), out[1] = the 16-bit image of S[k - 1], complemented when
+ * descending, in the low 16 bits, out[2] = elements whose image sorts strictly before it, out[3] = k - out[2], out[4] =
+ * elements that share its top byte, out[5..7] = 0.  All zeros for k == 0 or num_items == 0.                                */
+int    gs_topk_u16_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream);
+
 /* ------------------------------------------------------- top k of every row --
  * The k best of every row of a matrix (gs_topk_rows.hip): MoE routing, top-k sampling over a
  * vocabulary, beam search, re-ranking.  Row r is d_keys_in[r * row_stride .. r * row_stride + num_cols) (the values of the

@@ -218,7 +218,8 @@ struct DeviceRadixSort {
 };
 
 // The first k elements of the stable sort (gs_topk_u32): Min* = of the ascending sort, Max* = of the descending one, for
-// unsigned int, int and float keys.  Two-phase like DeviceRadixSort (d_temp_storage == nullptr: size query).  The inputs are
+// unsigned int, int and float keys; 2-byte keys (unsigned short, short, _Float16, __half, __hip_bfloat16) go to gs_topk_u16
+// and its size query: the same definition on the 16-bit image, 32-bit values.  Two-phase like DeviceRadixSort (d_temp_storage == nullptr: size query).  The inputs are
 // never written; d_keys_out / d_values_out hold k elements.  In the pairs forms d_values_in == nullptr writes the elements'
 // input indices (an argsort of the top k): ValueT is then unsigned int.
 struct DeviceTopK {
@@ -227,17 +228,31 @@ struct DeviceTopK {
                                const ValueT *d_values_in, ValueT *d_values_out, uint64_t num_items, uint64_t k, bool descending,
                                hipStream_t stream)
     {
-        static_assert(sizeof(KeyT) == 4 && KeyTraits<KeyT>::type <= GS_KEY_F32, "unsigned int, int or float keys");
+        static_assert(sizeof(KeyT) == 4 || sizeof(KeyT) == 2, "32-bit keys (unsigned int, int, float) or 16-bit keys");
         static_assert(sizeof(ValueT) == 4, "32-bit values only");
         const bool has_values = d_values_out != nullptr;
-        if (d_temp_storage == nullptr) {
-            temp_storage_bytes = gs_topk_temp_bytes(num_items, k, has_values);
-            return hipSuccess;
+        if constexpr (sizeof(KeyT) == 2) {   // unsigned short, short, _Float16, __half, __hip_bfloat16: gs_topk_u16
+            constexpr int kt = KeyTraits<KeyT>::type;
+            static_assert(kt == GS_KEY_U16 || kt == GS_KEY_I16 || kt == GS_KEY_F16 || kt == GS_KEY_BF16, "a 16-bit key type");
+            if (d_temp_storage == nullptr) {
+                temp_storage_bytes = gs_topk_u16_temp_bytes(num_items, k, has_values);
+                return hipSuccess;
+            }
+            return static_cast<hipError_t>(gs_topk_u16(
+                d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint16_t *>(d_keys_in),
+                reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint16_t *>(d_keys_out),
+                reinterpret_cast<uint32_t *>(d_values_out), num_items, k, descending ? 1 : 0, kt, stream));
+        } else {
+            static_assert(KeyTraits<KeyT>::type <= GS_KEY_F32, "unsigned int, int or float keys");
+            if (d_temp_storage == nullptr) {
+                temp_storage_bytes = gs_topk_temp_bytes(num_items, k, has_values);
+                return hipSuccess;
+            }
+            return static_cast<hipError_t>(gs_topk_u32(
+                d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint32_t *>(d_keys_in),
+                reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint32_t *>(d_keys_out),
+                reinterpret_cast<uint32_t *>(d_values_out), num_items, k, descending ? 1 : 0, KeyTraits<KeyT>::type, stream));
         }
-        return static_cast<hipError_t>(gs_topk_u32(
-            d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint32_t *>(d_keys_in),
-            reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint32_t *>(d_keys_out),
-            reinterpret_cast<uint32_t *>(d_values_out), num_items, k, descending ? 1 : 0, KeyTraits<KeyT>::type, stream));
     }
     template <typename KeyT>
     static hipError_t MinKeys(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
@@ -276,7 +291,8 @@ struct DeviceTopK {
 // and the two phases are DeviceTopK's; in the pairs forms d_values_in == nullptr writes the elements' column indices.  A size
 // query of 0 with a non-empty shape means the shape is refused (k > gs_topk_rows_max_k(), ...): such callers keep DeviceTopK
 // per row.  2-byte keys (unsigned short, short, _Float16, __half, __hip_bfloat16) go to gs_topk_rows_u16 and its size query:
-// the same definition on the 16-bit image, 32-bit values at the same row_stride; there is no flat 16-bit DeviceTopK to keep.
+// the same definition on the 16-bit image, 32-bit values at the same row_stride; for a k it refuses, DeviceTopK serves 2-byte
+// keys too.
 struct DeviceTopKRows {
     template <typename KeyT, typename ValueT>
     static hipError_t Dispatch(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
