@@ -36,6 +36,24 @@ static inline char *gs_ws_base(void *d_temp)
 {
     return (char *)(((uintptr_t)d_temp + (GS_WS_ALIGN - 1)) & ~(uintptr_t)(GS_WS_ALIGN - 1));
 }
+// a carve's step: `bytes` rounded up to GS_WS_ALIGN
+static inline size_t gs_ws_align(size_t bytes) { return (bytes + (GS_WS_ALIGN - 1)) & ~(GS_WS_ALIGN - 1); }
+
+// Do two byte ranges share a byte?  A null or empty range shares none.
+static inline bool gs_ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes)
+{
+    if (!a || !b || !abytes || !bbytes) return false;
+    const char *p = (const char *)a, *q = (const char *)b;
+    return p < q + bbytes && q < p + abytes;
+}
+// Do any two of a call's four arrays (keys in, values in, keys out, values out) overlap?
+static inline bool gs_any_overlap4(const void *const arr[4], const size_t bytes[4])
+{
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (gs_ranges_overlap(arr[i], bytes[i], arr[j], bytes[j])) return true;
+    return false;
+}
 
 namespace gs {
 extern thread_local gs_profile *tl_profile;

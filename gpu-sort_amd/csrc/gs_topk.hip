@@ -29,6 +29,12 @@
 // upsweep at shift 8 (narrow_slice_count: one spine column per tile, no prefix16), one round of histogram + pick finds the
 // low byte, and the finish is gs_lsb_sort_narrow.  Candidates and staged keys stay 2 bytes wide; indices are u32.  The one
 // routine of their own that 16-bit keys have is compact_tile16: the filter and the select read them two to an aligned word.
+//
+// The host plan is written once too: tk_temp_bytes / tk_run / tk_status over a description of the width (TkKeys32, TkKeys16),
+// with one workspace carve, behind the six entry points.  The argument checks, the launches of the pick, filter, histogram,
+// count, scan, select, gather and of route 3's iota and copy-out are shared.  A width keeps what the plan calls by name: its
+// key types and twiddle, the shape of round one's tables, the launches that count the top byte, the number of rounds below
+// it, route 3's limit, arrays and sort, and the sort of the staged pairs with its size query.
 #include "gs_device.hpp"
 #include "gs_lsb.hpp"
 
@@ -55,49 +61,9 @@ template <> struct TkKey<uint16_t> {
     static __device__ __forceinline__ uint32_t image(uint32_t raw, int f, uint32_t x) { return (f ? float_flip<16>(raw) : raw) ^ x; }
 };
 
-struct TopkWs {
-    uint32_t *state, *hist;          // [64], [3][256]
-    char *scratch;                   // 512 bytes for small_stable_sort
-    uint32_t *spine, *totals;
-    uint16_t *prefix16;
-    uint32_t *tilecnt;               // [tiles][2]: {before the k-th image, equal to it} per source tile, scanned in place
-    uint32_t *cand_keys, *cand_idx;
-    uint32_t *stage_keys, *stage_idx;
-    uint32_t *idx_sorted;
-    char *sort_ws;
-    size_t sort_ws_bytes;
-};
-
-static inline size_t tk_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline uint64_t tk_tiles(uint64_t n) { const uint64_t t = (n + LSB_TILE - 1) / LSB_TILE; return t ? t : 1; }
 static inline uint64_t tk_grid(uint64_t n) { return (tk_tiles(n) + LSB_CHUNK - 1) / LSB_CHUNK; }
 static inline uint64_t tk_cand_cap(uint64_t n) { return n / 32 > TK_MIN_CAND ? n / 32 : TK_MIN_CAND; }
-
-static size_t tk_carve(char *base, uint64_t n, uint64_t k, bool hv, TopkWs *ws)
-{
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char *p = (char *)((uintptr_t)base + off); off += tk_align(bytes); return p; };   // (base may be null: the size query)
-    char *head = take(4096);
-    char *spine = take((size_t)RADIX * 4 * tk_grid(n));
-    char *totals = take(RADIX * 4);
-    char *prefix16 = take((size_t)RADIX * 2 * tk_tiles(n));
-    char *tilecnt = take((size_t)8 * tk_tiles(n));
-    char *ck = take((size_t)4 * tk_cand_cap(n));
-    char *ci = hv ? take((size_t)4 * tk_cand_cap(n)) : nullptr;
-    char *sk = take((size_t)4 * k);
-    char *si = hv ? take((size_t)4 * k) : nullptr;
-    char *is = hv ? take((size_t)4 * k) : nullptr;
-    const size_t sort_bytes = gs_lsb_copy_temp_bytes(k, hv ? 1 : 0);
-    char *sw = take(sort_bytes);
-    if (ws) {
-        ws->state = (uint32_t *)head; ws->hist = (uint32_t *)(head + 256); ws->scratch = head + 256 + 3 * RADIX * 4;
-        ws->spine = (uint32_t *)spine; ws->totals = (uint32_t *)totals; ws->prefix16 = (uint16_t *)prefix16;
-        ws->tilecnt = (uint32_t *)tilecnt; ws->cand_keys = (uint32_t *)ck; ws->cand_idx = (uint32_t *)ci;
-        ws->stage_keys = (uint32_t *)sk; ws->stage_idx = (uint32_t *)si; ws->idx_sorted = (uint32_t *)is;
-        ws->sort_ws = sw; ws->sort_ws_bytes = sort_bytes;
-    }
-    return off;
-}
 
 // ---------------------------------------------------------------- round one: pick --
 // One workgroup: the digit d0 whose run of S holds position k - 1.  Opens the state block and clears the histograms of
@@ -499,57 +465,282 @@ __global__ __launch_bounds__(TK_THREADS) void topk_small_finish_kernel(const T *
     }
 }
 
-static bool tk_overlaps(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    if (!a || !b || !abytes || !bbytes) return false;
-    const char *p = (const char *)a, *q = (const char *)b;
-    return p < q + bbytes && q < p + abytes;
-}
-
-// ------------------------------------------------------------- 16-bit keys: host --
-struct TopkWs16 {
-    uint32_t *state, *hist;          // [64], [256]
-    uint32_t *spine, *totals;        // the narrow upsweep's: [256][tiles], [256]
-    uint32_t *tilecnt;
-    uint16_t *cand_keys;             // the candidate area: keys, then (has_values) indices; route 3 lays its arrays over both
+// ----------------------------------------------------------------------- host --
+template <typename T> struct TopkWs {
+    uint32_t *state, *hist;          // [64], [3][256] (16-bit keys have one round: [256])
+    char *scratch;                   // 512 bytes for small_stable_sort (route 3 of 32-bit keys)
+    uint32_t *spine, *totals;
+    uint16_t *prefix16;              // null without KT::PREFIX16
+    uint32_t *tilecnt;               // [tiles][2]: {before the k-th image, equal to it} per source tile, scanned in place
+    T *cand_keys;                    // the candidate area: keys, then (has_values) indices; route 3 lays its arrays over both
     uint32_t *cand_idx;
-    uint16_t *stage_keys;
+    T *stage_keys;
     uint32_t *stage_idx, *idx_sorted;
     char *sort_ws;
     size_t sort_ws_bytes;
 };
 
-// route 3's arrays inside the candidate area (at least 2 * TK_MIN_CAND = 128 KiB; 384 KiB with values): the sorted keys, the
-// sorted values, the iota of the arguments form, then the workspace of the sort of at most LSB_TILE elements
+// route 3's arrays (inside the candidate area) and the workspace of its sort
+template <typename T> struct TopkSmall {
+    T *keys;
+    uint32_t *vals, *iota;
+    char *sort_ws;
+    size_t sort_ws_bytes;
+};
+
+// route 3's arrays for 16-bit keys, as offsets into the candidate area (at least 2 * TK_MIN_CAND = 128 KiB; 384 KiB with
+// values): the sorted keys, the sorted values, the iota of the arguments form, then the workspace of the sort of at most
+// LSB_TILE elements
 constexpr size_t TK16_SMALL_VALS = (size_t)LSB_TILE * 2, TK16_SMALL_IOTA = TK16_SMALL_VALS + (size_t)LSB_TILE * 4,
                  TK16_SMALL_WS = TK16_SMALL_IOTA + (size_t)LSB_TILE * 4;
 
-static size_t tk16_carve(char *base, uint64_t n, uint64_t k, bool hv, TopkWs16 *ws)
+// What the key width changes on the host, and nothing else; tk_temp_bytes / tk_run / tk_status below are the plan itself.
+//   T, type_ok, twiddle   the element, the key types the entry point takes, TkKey<T>::image's (f, x) for a type and direction
+//   spine_cols, PREFIX16  round one's tables: spine columns (one per chunk, or one per tile) and whether there is a prefix16
+//   sort_temp_bytes       the size query of sort_staged
+//   EMPTY_QUERY_IS_ZERO   the public size query answers 0 for k == 0 or n == 0
+//   small_limit / small_area / small_sort   route 3: the longest array it takes, its arrays (false: they would not fit) and
+//                         the stable sort of the whole array into them
+//   count_top_byte        round one's launches: per-digit totals and per-tile bases of the image's top byte
+//   ROUNDS                histogram + pick rounds below the top byte, at shifts 8 * (ROUNDS - 1), ..., 0
+//   sort_staged           the stable sort of the k staged (key, index) pairs into the outputs
+namespace {   // (their member functions are this file's alone: nothing is added to the library's symbols)
+struct TkKeys32 {
+    using T = uint32_t;
+    static constexpr bool PREFIX16 = true, EMPTY_QUERY_IS_ZERO = false;
+    static constexpr int ROUNDS = 3;
+    static bool type_ok(int key_type) { return key_type >= GS_KEY_U32 && key_type <= GS_KEY_F32; }
+    static void twiddle(int key_type, int descending, int *f, uint32_t *x)
+    {
+        PassParams p{};
+        lsb_twiddle_masks(key_type, descending, true, true, p);
+        *f = p.f32_in; *x = p.xor_in;
+    }
+    static uint64_t spine_cols(uint64_t n) { return tk_grid(n); }
+    static size_t sort_temp_bytes(uint64_t k, bool hv) { return gs_lsb_copy_temp_bytes(k, hv ? 1 : 0); }
+    static uint32_t small_limit(bool hv) { return small_sort_capacity(hv); }
+    // keys | indices of the arguments form in the first list, values in the second
+    static bool small_area(const TopkWs<T> &ws, uint32_t, bool hv, int, TopkSmall<T> *a)
+    {
+        if (small_sort_capacity(hv) > TK_MIN_CAND / 2) return false;
+        *a = {ws.cand_keys, ws.cand_idx, ws.cand_keys + TK_MIN_CAND / 2, ws.scratch, 512};
+        return true;
+    }
+    static int small_sort(const TopkSmall<T> &a, const T *keys_in, const uint32_t *vals_in, bool hv, uint32_t n, int key_type, int descending,
+                          hipStream_t s)
+    {
+        int f;
+        uint32_t x;
+        twiddle(key_type, descending, &f, &x);
+        return small_stable_sort(a.sort_ws, a.sort_ws_bytes, keys_in, a.keys, vals_in, hv ? a.vals : nullptr, n, 0, 32, f, x, f, x, s);
+    }
+    static int count_top_byte(const T *keys_in, uint64_t n, int key_type, int descending, const TopkWs<T> &ws, hipStream_t s)
+    {
+        PassParams p = lsb_make_params(n, 24, 8);
+        lsb_twiddle_masks(key_type, descending, true, true, p);
+        const int e = lsb_upsweep(keys_in, ws.spine, ws.prefix16, p, s);
+        return e ? e : lsb_scan(ws.spine, ws.totals, p.grid, s);
+    }
+    static int sort_staged(const TopkWs<T> &ws, T *keys_out, uint32_t *idx_out, uint64_t k, bool hv, int key_type, int descending, hipStream_t s)
+    {
+        return gs_lsb_sort_copy_u32(ws.sort_ws, ws.sort_ws_bytes, ws.stage_keys, keys_out, hv ? ws.stage_idx : nullptr, idx_out, k, 0, 32,
+                                    descending, key_type, s);
+    }
+};
+
+struct TkKeys16 {
+    using T = uint16_t;
+    static constexpr bool PREFIX16 = false, EMPTY_QUERY_IS_ZERO = true;
+    static constexpr int ROUNDS = 1;
+    static bool type_ok(int key_type) { return key_type == GS_KEY_U16 || key_type == GS_KEY_I16 || key_type == GS_KEY_F16 || key_type == GS_KEY_BF16; }
+    static void twiddle(int key_type, int descending, int *f, uint32_t *x)
+    {
+        *f = (key_type == GS_KEY_F16 || key_type == GS_KEY_BF16) ? 1 : 0;
+        *x = (key_type == GS_KEY_U16 ? 0u : 0x8000u) ^ (descending ? 0xffffu : 0u);   // the image stays 16 bits wide
+    }
+    static uint64_t spine_cols(uint64_t n) { return tk_tiles(n); }
+    static size_t sort_temp_bytes(uint64_t k, bool hv) { return gs_lsb_narrow_temp_bytes(k, GS_KEY_U16, hv ? 4 : 0); }
+    static uint32_t small_limit(bool) { return (uint32_t)LSB_TILE; }
+    static bool small_area(const TopkWs<T> &ws, uint32_t n, bool hv, int key_type, TopkSmall<T> *a)
+    {
+        char *area = (char *)ws.cand_keys;
+        const size_t sort_bytes = gs_lsb_narrow_temp_bytes(n, key_type, hv ? 4 : 0);
+        if (TK16_SMALL_WS + sort_bytes > (size_t)(hv ? 6 : 2) * TK_MIN_CAND) return false;
+        *a = {(T *)area, (uint32_t *)(area + TK16_SMALL_VALS), (uint32_t *)(area + TK16_SMALL_IOTA), area + TK16_SMALL_WS, sort_bytes};
+        return true;
+    }
+    static int small_sort(const TopkSmall<T> &a, const T *keys_in, const uint32_t *vals_in, bool hv, uint32_t n, int key_type, int descending,
+                          hipStream_t s)
+    {
+        return gs_lsb_sort_narrow(a.sort_ws, a.sort_ws_bytes, keys_in, a.keys, hv ? vals_in : nullptr, hv ? a.vals : nullptr, n, key_type,
+                                  hv ? 4 : 0, 0, 16, descending, s);
+    }
+    // the narrow upsweep and its spine scan
+    static int count_top_byte(const T *keys_in, uint64_t n, int key_type, int descending, const TopkWs<T> &ws, hipStream_t s)
+    {
+        const LargeDigit dg = {8, 8, key_type, descending ? 1 : 0, true, true};
+        return narrow_slice_count(keys_in, n, 4, dg, ws.spine, ws.totals, s);
+    }
+    static int sort_staged(const TopkWs<T> &ws, T *keys_out, uint32_t *idx_out, uint64_t k, bool hv, int key_type, int descending, hipStream_t s)
+    {
+        return gs_lsb_sort_narrow(ws.sort_ws, ws.sort_ws_bytes, ws.stage_keys, keys_out, hv ? ws.stage_idx : nullptr, idx_out, k, key_type,
+                                  hv ? 4 : 0, 0, 16, descending, s);
+    }
+};
+}  // namespace
+
+template <typename KT>
+static size_t tk_carve(char *base, uint64_t n, uint64_t k, bool hv, TopkWs<typename KT::T> *ws)
 {
+    using T = typename KT::T;
     size_t off = 0;
-    auto take = [&](size_t bytes) { char *p = (char *)((uintptr_t)base + off); off += tk_align(bytes); return p; };   // (base may be null: the size query)
+    auto take = [&](size_t bytes) { char *p = (char *)((uintptr_t)base + off); off += gs_ws_align(bytes); return p; };   // (base may be null: the size query)
     char *head = take(4096);
-    char *spine = take((size_t)RADIX * 4 * tk_tiles(n));
+    char *spine = take((size_t)RADIX * 4 * KT::spine_cols(n));
     char *totals = take(RADIX * 4);
+    char *prefix16 = KT::PREFIX16 ? take((size_t)RADIX * 2 * tk_tiles(n)) : nullptr;
     char *tilecnt = take((size_t)8 * tk_tiles(n));
-    char *ck = take((size_t)2 * tk_cand_cap(n));
+    char *ck = take(sizeof(T) * tk_cand_cap(n));
     char *ci = hv ? take((size_t)4 * tk_cand_cap(n)) : nullptr;
-    char *sk = take((size_t)2 * k);
+    char *sk = take(sizeof(T) * k);
     char *si = hv ? take((size_t)4 * k) : nullptr;
     char *is = hv ? take((size_t)4 * k) : nullptr;
-    const size_t sort_bytes = gs_lsb_narrow_temp_bytes(k, GS_KEY_U16, hv ? 4 : 0);
+    const size_t sort_bytes = KT::sort_temp_bytes(k, hv);
     char *sw = take(sort_bytes);
     if (ws) {
-        ws->state = (uint32_t *)head; ws->hist = (uint32_t *)(head + 256);
-        ws->spine = (uint32_t *)spine; ws->totals = (uint32_t *)totals; ws->tilecnt = (uint32_t *)tilecnt;
-        ws->cand_keys = (uint16_t *)ck; ws->cand_idx = (uint32_t *)ci;
-        ws->stage_keys = (uint16_t *)sk; ws->stage_idx = (uint32_t *)si; ws->idx_sorted = (uint32_t *)is;
+        ws->state = (uint32_t *)head; ws->hist = (uint32_t *)(head + 256); ws->scratch = head + 256 + 3 * RADIX * 4;
+        ws->spine = (uint32_t *)spine; ws->totals = (uint32_t *)totals; ws->prefix16 = (uint16_t *)prefix16;
+        ws->tilecnt = (uint32_t *)tilecnt; ws->cand_keys = (T *)ck; ws->cand_idx = (uint32_t *)ci;
+        ws->stage_keys = (T *)sk; ws->stage_idx = (uint32_t *)si; ws->idx_sorted = (uint32_t *)is;
         ws->sort_ws = sw; ws->sort_ws_bytes = sort_bytes;
     }
     return off;
 }
 
-static inline bool tk16_key_type_ok(int kt) { return kt == GS_KEY_U16 || kt == GS_KEY_I16 || kt == GS_KEY_F16 || kt == GS_KEY_BF16; }
+template <typename KT>
+static size_t tk_temp_bytes(uint64_t num_items, uint64_t k, int has_values)
+{
+    if (KT::EMPTY_QUERY_IS_ZERO && (k == 0 || num_items == 0)) return 0;
+    return tk_carve<KT>(nullptr, num_items, k, has_values != 0, nullptr) + GS_WS_SLACK;
+}
+
+// the launches that come in a form with indices (IDX) and one without
+template <bool IDX, typename T>
+static void tk_launch_filter(hipStream_t s, const T *keys_in, const TopkWs<T> &ws, uint32_t n, uint32_t tiles, uint32_t cols, uint32_t k,
+                             uint32_t cap, int f, uint32_t x)
+{
+    KernelTimer kt(GS_K_OTHER, s);
+    hipLaunchKernelGGL((topk_filter_kernel<IDX, T>), dim3(tiles), dim3(TK_THREADS), 0, s, keys_in, ws.spine, (const uint16_t *)ws.prefix16,
+                       ws.state, ws.stage_keys, ws.stage_idx, ws.cand_keys, ws.cand_idx, n, cols, k, cap, f, x);
+}
+
+template <bool IDX, typename T>
+static void tk_launch_select(hipStream_t s, const T *keys_in, const TopkWs<T> &ws, uint32_t tiles, uint32_t k, int f, uint32_t x)
+{
+    KernelTimer kt(GS_K_OTHER, s);
+    hipLaunchKernelGGL((topk_select_kernel<IDX, T>), dim3(tiles), dim3(TK_THREADS), 0, s, keys_in, (const T *)ws.cand_keys,
+                       (const uint32_t *)ws.cand_idx, ws.state, ws.tilecnt, ws.stage_keys, ws.stage_idx, k, f, x);
+}
+
+template <typename KT>
+static int tk_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_in, const uint32_t *d_vals_in, typename KT::T *d_keys_out,
+                  uint32_t *d_vals_out, uint64_t num_items, uint64_t k, int descending, int key_type, void *stream)
+{
+    using T = typename KT::T;
+    GS_CLEAR_STALE_ERROR();
+    if (num_items >= (1ull << 32) || k > num_items) return hipErrorInvalidValue;
+    if (!KT::type_ok(key_type)) return hipErrorInvalidValue;
+    if (d_vals_in && !d_vals_out) return hipErrorInvalidValue;
+    if (k == 0 || num_items == 0) return hipSuccess;
+    const bool hv = d_vals_out != nullptr;
+    if (!d_keys_in || !d_keys_out) return hipErrorInvalidValue;
+    if (!d_temp || temp_bytes < tk_temp_bytes<KT>(num_items, k, hv)) return hipErrorInvalidValue;
+    if ((((uintptr_t)d_keys_in | (uintptr_t)d_keys_out) & (sizeof(T) - 1)) != 0 || (((uintptr_t)d_vals_in | (uintptr_t)d_vals_out) & 3u) != 0)
+        return hipErrorInvalidValue;
+    {
+        const void *arr[4] = {d_keys_in, d_vals_in, d_keys_out, d_vals_out};
+        const size_t bytes[4] = {(size_t)num_items * sizeof(T), (size_t)num_items * 4, (size_t)k * sizeof(T), (size_t)k * 4};
+        if (gs_any_overlap4(arr, bytes)) return hipErrorInvalidValue;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t n = (uint32_t)num_items, kk = (uint32_t)k;
+    TopkWs<T> ws;
+    tk_carve<KT>(gs_ws_base(d_temp), num_items, k, hv, &ws);
+    int f, e;
+    uint32_t x;
+    KT::twiddle(key_type, descending, &f, &x);
+
+    if (n <= KT::small_limit(hv)) {
+        // route 3: the array fits one workgroup (32-bit keys) or one tile (16-bit keys).  Sorted whole into the candidate
+        // area, then the first k are copied out.
+        TopkSmall<T> a;
+        if (!KT::small_area(ws, n, hv, key_type, &a)) return hipErrorInvalidValue;   // (the copies would not fit)
+        const uint32_t *vin = d_vals_in;
+        if (hv && !vin) {
+            KernelTimer kt(GS_K_OTHER, s);
+            hipLaunchKernelGGL(topk_iota_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, a.iota, n);
+            vin = a.iota;
+        }
+        if ((e = KT::small_sort(a, d_keys_in, vin, hv, n, key_type, descending, s))) return e;
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(topk_small_finish_kernel<T>, dim3(1), dim3(TK_THREADS), 0, s, (const T *)a.keys, (const uint32_t *)a.vals, d_keys_out,
+                           d_vals_out, ws.state, n, kk, f, x);
+        return (int)hipGetLastError();
+    }
+
+    // round one: the top byte's counts, the pick
+    const uint32_t tiles = (uint32_t)tk_tiles(num_items), cols = (uint32_t)KT::spine_cols(num_items);
+    if ((e = KT::count_top_byte(d_keys_in, num_items, key_type, descending, ws, s))) return e;
+    const uint32_t cap = (uint32_t)tk_cand_cap(num_items);
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(topk_pick0_kernel<TkKey<T>::TOP>, dim3(1), dim3(RADIX), 0, s, ws.totals, ws.state, ws.hist, n, kk, cap);
+    }
+    // filter
+    if (hv) tk_launch_filter<true>(s, d_keys_in, ws, n, tiles, cols, kk, cap, f, x);
+    else tk_launch_filter<false>(s, d_keys_in, ws, n, tiles, cols, kk, cap, f, x);
+    // the rounds below the top byte
+    for (int r = 0; r < KT::ROUNDS; ++r) {
+        const uint32_t shift = 8u * (uint32_t)(KT::ROUNDS - 1 - r);
+        { KernelTimer kt(GS_K_OTHER, s);
+          hipLaunchKernelGGL(topk_hist_kernel<T>, dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, (const T *)ws.cand_keys, ws.state,
+                             ws.hist + r * RADIX, shift, f, x); }
+        { KernelTimer kt(GS_K_OTHER, s);
+          hipLaunchKernelGGL(topk_pick_kernel, dim3(1), dim3(RADIX), 0, s, ws.hist + r * RADIX, ws.state, shift); }
+    }
+    // final ordered select
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL(topk_count_kernel<T>, dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, (const T *)ws.cand_keys, ws.state, ws.tilecnt,
+                         f, x); }
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(TK_SCAN_THREADS), 0, s, ws.state, ws.tilecnt); }
+    if (hv) tk_launch_select<true>(s, d_keys_in, ws, tiles, kk, f, x);
+    else tk_launch_select<false>(s, d_keys_in, ws, tiles, kk, f, x);
+    if ((e = (int)hipGetLastError())) return e;
+    // finish: the stable sort of the k staged pairs; the indices are the values of the arguments form
+    uint32_t *idx_out = !hv ? nullptr : d_vals_in ? ws.idx_sorted : d_vals_out;
+    if ((e = KT::sort_staged(ws, d_keys_out, idx_out, k, hv, key_type, descending, s))) return e;
+    if (d_vals_in) {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(topk_gather_kernel, dim3((kk + 255u) / 256u), dim3(256), 0, s, d_vals_in, ws.idx_sorted, d_vals_out, kk, n);
+    }
+    return (int)hipGetLastError();
+}
+
+template <typename KT>
+static int tk_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (!out || num_items >= (1ull << 32) || k > num_items) return hipErrorInvalidValue;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (k == 0 || num_items == 0) return hipSuccess;   // such a call enqueued nothing
+    if (!d_temp) return hipErrorInvalidValue;
+    TopkWs<typename KT::T> ws;
+    tk_carve<KT>(gs_ws_base(d_temp), num_items, k, has_values != 0, &ws);
+    hipError_t e = hipMemcpyAsync(out, ws.state, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    return (int)e;
+}
 
 }  // namespace gs
 
@@ -557,250 +748,30 @@ using namespace gs;
 
 extern "C" {
 
-size_t gs_topk_temp_bytes(uint64_t num_items, uint64_t k, int has_values)
-{
-    return tk_carve(nullptr, num_items, k, has_values != 0, nullptr) + GS_WS_SLACK;
-}
+size_t gs_topk_temp_bytes(uint64_t num_items, uint64_t k, int has_values) { return tk_temp_bytes<TkKeys32>(num_items, k, has_values); }
+
+size_t gs_topk_u16_temp_bytes(uint64_t num_items, uint64_t k, int has_values) { return tk_temp_bytes<TkKeys16>(num_items, k, has_values); }
 
 int gs_topk_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
                 uint32_t *d_vals_out, uint64_t num_items, uint64_t k, int descending, int key_type, void *stream)
 {
-    GS_CLEAR_STALE_ERROR();
-    if (num_items >= (1ull << 32) || k > num_items) return hipErrorInvalidValue;
-    if (key_type < GS_KEY_U32 || key_type > GS_KEY_F32) return hipErrorInvalidValue;
-    if (d_vals_in && !d_vals_out) return hipErrorInvalidValue;
-    if (k == 0 || num_items == 0) return hipSuccess;
-    const bool hv = d_vals_out != nullptr;
-    if (!d_keys_in || !d_keys_out) return hipErrorInvalidValue;
-    if (!d_temp || temp_bytes < gs_topk_temp_bytes(num_items, k, hv)) return hipErrorInvalidValue;
-    if ((((uintptr_t)d_keys_in | (uintptr_t)d_vals_in | (uintptr_t)d_keys_out | (uintptr_t)d_vals_out) & 3u) != 0) return hipErrorInvalidValue;
-    {
-        const void *arr[4] = {d_keys_in, d_vals_in, d_keys_out, d_vals_out};
-        const size_t bytes[4] = {(size_t)num_items * 4, (size_t)num_items * 4, (size_t)k * 4, (size_t)k * 4};
-        for (int i = 0; i < 4; ++i)
-            for (int j = i + 1; j < 4; ++j)
-                if (tk_overlaps(arr[i], bytes[i], arr[j], bytes[j])) return hipErrorInvalidValue;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t n = (uint32_t)num_items, kk = (uint32_t)k;
-    TopkWs ws;
-    tk_carve(gs_ws_base(d_temp), num_items, k, hv, &ws);
-    PassParams p = lsb_make_params(num_items, 24, 8);
-    lsb_twiddle_masks(key_type, descending, true, true, p);
-    int e;
-
-    if (n <= small_sort_capacity(hv)) {
-        if (small_sort_capacity(hv) > TK_MIN_CAND / 2) return hipErrorInvalidValue;   // (the copies below would not fit)
-        // route 3: the array fits one workgroup.  Sorted whole into the candidate area (keys | indices for the
-        // arguments form, values in the second list), then the first k are copied out.
-        uint32_t *sk = ws.cand_keys, *iota = ws.cand_keys + TK_MIN_CAND / 2, *sv = ws.cand_idx;
-        const uint32_t *vin = d_vals_in;
-        if (hv && !vin) {
-            KernelTimer kt(GS_K_OTHER, s);
-            hipLaunchKernelGGL(topk_iota_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, iota, n);
-            vin = iota;
-        }
-        if ((e = small_stable_sort(ws.scratch, 512, d_keys_in, sk, vin, hv ? sv : nullptr, n, 0, 32, p.f32_in, p.xor_in, p.f32_out,
-                                   p.xor_out, s)))
-            return e;
-        KernelTimer kt(GS_K_OTHER, s);
-        hipLaunchKernelGGL(topk_small_finish_kernel<uint32_t>, dim3(1), dim3(TK_THREADS), 0, s, sk, sv, d_keys_out, d_vals_out, ws.state, n, kk,
-                           p.f32_in, p.xor_in);
-        return (int)hipGetLastError();
-    }
-
-    // round one
-    if ((e = lsb_upsweep(d_keys_in, ws.spine, ws.prefix16, p, s))) return e;
-    if ((e = lsb_scan(ws.spine, ws.totals, p.grid, s))) return e;
-    const uint32_t cap = (uint32_t)tk_cand_cap(num_items);
-    {
-        KernelTimer kt(GS_K_OTHER, s);
-        hipLaunchKernelGGL(topk_pick0_kernel<24>, dim3(1), dim3(RADIX), 0, s, ws.totals, ws.state, ws.hist, n, kk, cap);
-    }
-    // filter
-    {
-        KernelTimer kt(GS_K_OTHER, s);
-        if (hv)
-            hipLaunchKernelGGL((topk_filter_kernel<true, uint32_t>), dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine, ws.prefix16, ws.state,
-                               ws.stage_keys, ws.stage_idx, ws.cand_keys, ws.cand_idx, n, p.grid, kk, cap, p.f32_in, p.xor_in);
-        else
-            hipLaunchKernelGGL((topk_filter_kernel<false, uint32_t>), dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine, ws.prefix16, ws.state,
-                               ws.stage_keys, ws.stage_idx, ws.cand_keys, ws.cand_idx, n, p.grid, kk, cap, p.f32_in, p.xor_in);
-    }
-    // rounds two to four
-    for (int r = 0; r < 3; ++r) {
-        const uint32_t shift = 16u - 8u * (uint32_t)r;
-        { KernelTimer kt(GS_K_OTHER, s);
-          hipLaunchKernelGGL(topk_hist_kernel<uint32_t>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.state,
-                             ws.hist + r * RADIX, shift, p.f32_in, p.xor_in); }
-        { KernelTimer kt(GS_K_OTHER, s);
-          hipLaunchKernelGGL(topk_pick_kernel, dim3(1), dim3(RADIX), 0, s, ws.hist + r * RADIX, ws.state, shift); }
-    }
-    // final ordered select
-    { KernelTimer kt(GS_K_OTHER, s);
-      hipLaunchKernelGGL(topk_count_kernel<uint32_t>, dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.state, ws.tilecnt,
-                         p.f32_in, p.xor_in); }
-    { KernelTimer kt(GS_K_OTHER, s);
-      hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(TK_SCAN_THREADS), 0, s, ws.state, ws.tilecnt); }
-    {
-        KernelTimer kt(GS_K_OTHER, s);
-        if (hv)
-            hipLaunchKernelGGL((topk_select_kernel<true, uint32_t>), dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.cand_idx,
-                               ws.state, ws.tilecnt, ws.stage_keys, ws.stage_idx, kk, p.f32_in, p.xor_in);
-        else
-            hipLaunchKernelGGL((topk_select_kernel<false, uint32_t>), dim3(p.num_tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.cand_keys, ws.cand_idx,
-                               ws.state, ws.tilecnt, ws.stage_keys, ws.stage_idx, kk, p.f32_in, p.xor_in);
-    }
-    if ((e = (int)hipGetLastError())) return e;
-    // finish: the stable sort of the k staged pairs; the indices are the values of the arguments form
-    uint32_t *idx_out = !hv ? nullptr : d_vals_in ? ws.idx_sorted : d_vals_out;
-    if ((e = gs_lsb_sort_copy_u32(ws.sort_ws, ws.sort_ws_bytes, ws.stage_keys, d_keys_out, hv ? ws.stage_idx : nullptr, idx_out, k, 0, 32,
-                                  descending, key_type, stream)))
-        return e;
-    if (d_vals_in) {
-        KernelTimer kt(GS_K_OTHER, s);
-        hipLaunchKernelGGL(topk_gather_kernel, dim3((kk + 255u) / 256u), dim3(256), 0, s, d_vals_in, ws.idx_sorted, d_vals_out, kk, n);
-    }
-    return (int)hipGetLastError();
-}
-
-int gs_topk_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream)
-{
-    GS_CLEAR_STALE_ERROR();
-    if (!out || num_items >= (1ull << 32) || k > num_items) return hipErrorInvalidValue;
-    for (int i = 0; i < 8; ++i) out[i] = 0;
-    if (k == 0 || num_items == 0) return hipSuccess;   // such a call enqueued nothing
-    if (!d_temp) return hipErrorInvalidValue;
-    TopkWs ws;
-    tk_carve(gs_ws_base(d_temp), num_items, k, has_values != 0, &ws);
-    hipError_t e = hipMemcpyAsync(out, ws.state, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    return (int)e;
-}
-
-// ------------------------------------------------------------------ 16-bit keys --
-size_t gs_topk_u16_temp_bytes(uint64_t num_items, uint64_t k, int has_values)
-{
-    if (k == 0 || num_items == 0) return 0;
-    return tk16_carve(nullptr, num_items, k, has_values != 0, nullptr) + GS_WS_SLACK;
+    return tk_run<TkKeys32>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, num_items, k, descending, key_type, stream);
 }
 
 int gs_topk_u16(void *d_temp, size_t temp_bytes, const uint16_t *d_keys_in, const uint32_t *d_vals_in, uint16_t *d_keys_out,
                 uint32_t *d_vals_out, uint64_t num_items, uint64_t k, int descending, int key_type, void *stream)
 {
-    GS_CLEAR_STALE_ERROR();
-    if (num_items >= (1ull << 32) || k > num_items) return hipErrorInvalidValue;
-    if (!tk16_key_type_ok(key_type)) return hipErrorInvalidValue;
-    if (d_vals_in && !d_vals_out) return hipErrorInvalidValue;
-    if (k == 0 || num_items == 0) return hipSuccess;
-    const bool hv = d_vals_out != nullptr;
-    if (!d_keys_in || !d_keys_out) return hipErrorInvalidValue;
-    if (!d_temp || temp_bytes < gs_topk_u16_temp_bytes(num_items, k, hv)) return hipErrorInvalidValue;
-    if ((((uintptr_t)d_keys_in | (uintptr_t)d_keys_out) & 1u) != 0 || (((uintptr_t)d_vals_in | (uintptr_t)d_vals_out) & 3u) != 0)
-        return hipErrorInvalidValue;
-    {
-        const void *arr[4] = {d_keys_in, d_vals_in, d_keys_out, d_vals_out};
-        const size_t bytes[4] = {(size_t)num_items * 2, (size_t)num_items * 4, (size_t)k * 2, (size_t)k * 4};
-        for (int i = 0; i < 4; ++i)
-            for (int j = i + 1; j < 4; ++j)
-                if (tk_overlaps(arr[i], bytes[i], arr[j], bytes[j])) return hipErrorInvalidValue;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t n = (uint32_t)num_items, kk = (uint32_t)k;
-    TopkWs16 ws;
-    tk16_carve(gs_ws_base(d_temp), num_items, k, hv, &ws);
-    const int fk = (key_type == GS_KEY_F16 || key_type == GS_KEY_BF16) ? 1 : 0;
-    const uint32_t x = (key_type == GS_KEY_U16 ? 0u : 0x8000u) ^ (descending ? 0xffffu : 0u);   // the image stays 16 bits wide
-    const int vb = hv ? 4 : 0;
-    int e;
+    return tk_run<TkKeys16>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, num_items, k, descending, key_type, stream);
+}
 
-    if (n <= (uint32_t)LSB_TILE) {
-        // route 3: one tile.  Sorted whole into the candidate area, then the first k are copied out.
-        char *area = (char *)ws.cand_keys;
-        const size_t sort_bytes = gs_lsb_narrow_temp_bytes(n, key_type, vb);
-        if (TK16_SMALL_WS + sort_bytes > (size_t)(hv ? 6 : 2) * TK_MIN_CAND) return hipErrorInvalidValue;   // (the copies would not fit)
-        uint16_t *sk = (uint16_t *)area;
-        uint32_t *sv = (uint32_t *)(area + TK16_SMALL_VALS), *iota = (uint32_t *)(area + TK16_SMALL_IOTA);
-        const uint32_t *vin = d_vals_in;
-        if (hv && !vin) {
-            KernelTimer kt(GS_K_OTHER, s);
-            hipLaunchKernelGGL(topk_iota_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, iota, n);
-            vin = iota;
-        }
-        if ((e = gs_lsb_sort_narrow(area + TK16_SMALL_WS, sort_bytes, d_keys_in, sk, hv ? vin : nullptr, hv ? sv : nullptr, n, key_type, vb,
-                                    0, 16, descending, stream)))
-            return e;
-        KernelTimer kt(GS_K_OTHER, s);
-        hipLaunchKernelGGL(topk_small_finish_kernel<uint16_t>, dim3(1), dim3(TK_THREADS), 0, s, (const uint16_t *)sk, (const uint32_t *)sv,
-                           d_keys_out, d_vals_out, ws.state, n, kk, fk, x);
-        return (int)hipGetLastError();
-    }
-
-    // round one: the narrow upsweep on the image's top byte, its spine scan, the pick
-    const uint32_t tiles = (uint32_t)tk_tiles(num_items);
-    const LargeDigit dg = {8, 8, key_type, descending ? 1 : 0, true, true};
-    if ((e = narrow_slice_count(d_keys_in, num_items, 4, dg, ws.spine, ws.totals, s))) return e;
-    const uint32_t cap = (uint32_t)tk_cand_cap(num_items);
-    {
-        KernelTimer kt(GS_K_OTHER, s);
-        hipLaunchKernelGGL(topk_pick0_kernel<8>, dim3(1), dim3(RADIX), 0, s, ws.totals, ws.state, ws.hist, n, kk, cap);
-    }
-    // filter
-    {
-        KernelTimer kt(GS_K_OTHER, s);
-        if (hv)
-            hipLaunchKernelGGL((topk_filter_kernel<true, uint16_t>), dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine,
-                               (const uint16_t *)nullptr, ws.state, ws.stage_keys, ws.stage_idx, ws.cand_keys, ws.cand_idx, n, tiles, kk, cap, fk, x);
-        else
-            hipLaunchKernelGGL((topk_filter_kernel<false, uint16_t>), dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, ws.spine,
-                               (const uint16_t *)nullptr, ws.state, ws.stage_keys, ws.stage_idx, ws.cand_keys, ws.cand_idx, n, tiles, kk, cap, fk, x);
-    }
-    // round two: the low byte
-    { KernelTimer kt(GS_K_OTHER, s);
-      hipLaunchKernelGGL(topk_hist_kernel<uint16_t>, dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, (const uint16_t *)ws.cand_keys, ws.state,
-                         ws.hist, 0u, fk, x); }
-    { KernelTimer kt(GS_K_OTHER, s);
-      hipLaunchKernelGGL(topk_pick_kernel, dim3(1), dim3(RADIX), 0, s, ws.hist, ws.state, 0u); }
-    // final ordered select
-    { KernelTimer kt(GS_K_OTHER, s);
-      hipLaunchKernelGGL(topk_count_kernel<uint16_t>, dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, (const uint16_t *)ws.cand_keys, ws.state,
-                         ws.tilecnt, fk, x); }
-    { KernelTimer kt(GS_K_OTHER, s);
-      hipLaunchKernelGGL(topk_scan_kernel, dim3(1), dim3(TK_SCAN_THREADS), 0, s, ws.state, ws.tilecnt); }
-    {
-        KernelTimer kt(GS_K_OTHER, s);
-        if (hv)
-            hipLaunchKernelGGL((topk_select_kernel<true, uint16_t>), dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, (const uint16_t *)ws.cand_keys,
-                               (const uint32_t *)ws.cand_idx, ws.state, ws.tilecnt, ws.stage_keys, ws.stage_idx, kk, fk, x);
-        else
-            hipLaunchKernelGGL((topk_select_kernel<false, uint16_t>), dim3(tiles), dim3(TK_THREADS), 0, s, d_keys_in, (const uint16_t *)ws.cand_keys,
-                               (const uint32_t *)ws.cand_idx, ws.state, ws.tilecnt, ws.stage_keys, ws.stage_idx, kk, fk, x);
-    }
-    if ((e = (int)hipGetLastError())) return e;
-    // finish: the stable narrow sort of the k staged pairs; the indices are the values of the arguments form
-    uint32_t *idx_out = !hv ? nullptr : d_vals_in ? ws.idx_sorted : d_vals_out;
-    if ((e = gs_lsb_sort_narrow(ws.sort_ws, ws.sort_ws_bytes, ws.stage_keys, d_keys_out, hv ? ws.stage_idx : nullptr, idx_out, k, key_type, vb,
-                                0, 16, descending, stream)))
-        return e;
-    if (d_vals_in) {
-        KernelTimer kt(GS_K_OTHER, s);
-        hipLaunchKernelGGL(topk_gather_kernel, dim3((kk + 255u) / 256u), dim3(256), 0, s, d_vals_in, ws.idx_sorted, d_vals_out, kk, n);
-    }
-    return (int)hipGetLastError();
+int gs_topk_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream)
+{
+    return tk_status<TkKeys32>(d_temp, num_items, k, has_values, out, stream);
 }
 
 int gs_topk_u16_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream)
 {
-    GS_CLEAR_STALE_ERROR();
-    if (!out || num_items >= (1ull << 32) || k > num_items) return hipErrorInvalidValue;
-    for (int i = 0; i < 8; ++i) out[i] = 0;
-    if (k == 0 || num_items == 0) return hipSuccess;   // such a call enqueued nothing
-    if (!d_temp) return hipErrorInvalidValue;
-    TopkWs16 ws;
-    tk16_carve(gs_ws_base(d_temp), num_items, k, has_values != 0, &ws);
-    hipError_t e = hipMemcpyAsync(out, ws.state, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    return (int)e;
+    return tk_status<TkKeys16>(d_temp, num_items, k, has_values, out, stream);
 }
 
 }  // extern "C"

@@ -356,15 +356,6 @@ static inline void tr_make_plan(uint64_t cols, uint64_t k, RowsPlan *p)
     p->cand0 = (uint32_t)p->n[1];
 }
 
-static inline size_t tr_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static inline bool tr_overlaps(const void *a, size_t abytes, const void *b, size_t bbytes)
-{
-    if (!a || !b || !abytes || !bbytes) return false;
-    const char *p = (const char *)a, *q = (const char *)b;
-    return p < q + bbytes && q < p + abytes;
-}
-
 template <typename KT, int WKPT, bool HV>
 static void tr_launch_wave(hipStream_t s, const typename KT::T *ki, const uint32_t *vi, typename KT::T *ko, uint32_t *vo, uint32_t rows,
                            uint32_t cols, uint32_t stride, uint32_t k, int flt, uint32_t x)
@@ -421,8 +412,8 @@ static size_t tr_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, in
     tr_make_plan(num_cols, k, &p);
     size_t total = 0;
     for (uint32_t a = 1; a <= 2 && a < p.levels; ++a) {
-        total += tr_align(sizeof(typename KT::T) * num_rows * p.n[a]);
-        if (has_values) total += tr_align((size_t)4 * num_rows * p.n[a]);
+        total += gs_ws_align(sizeof(typename KT::T) * num_rows * p.n[a]);
+        if (has_values) total += gs_ws_align((size_t)4 * num_rows * p.n[a]);
     }
     return total + GS_WS_SLACK;
 }
@@ -448,9 +439,7 @@ static int tr_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_
         const size_t in_elems = (size_t)((num_rows - 1) * row_stride + num_cols), out_elems = (size_t)(num_rows * k);
         const void *arr[4] = {d_keys_in, d_vals_in, d_keys_out, d_vals_out};
         const size_t bytes[4] = {sizeof(T) * in_elems, 4 * in_elems, sizeof(T) * out_elems, 4 * out_elems};
-        for (int i = 0; i < 4; ++i)
-            for (int j = i + 1; j < 4; ++j)
-                if (tr_overlaps(arr[i], bytes[i], arr[j], bytes[j])) return hipErrorInvalidValue;
+        if (gs_any_overlap4(arr, bytes)) return hipErrorInvalidValue;
     }
     hipStream_t s = (hipStream_t)stream;
     const uint32_t rows = (uint32_t)num_rows, cols = (uint32_t)num_cols, stride = (uint32_t)row_stride, kk = (uint32_t)k;
@@ -480,8 +469,8 @@ static int tr_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_
     {
         size_t off = 0;
         for (uint32_t a = 0; a < 2 && a + 1 < p.levels; ++a) {
-            area_k[a] = (T *)(wsb + off); off += tr_align(sizeof(T) * num_rows * p.n[a + 1]);
-            if (hv) { area_i[a] = (uint32_t *)(wsb + off); off += tr_align((size_t)4 * num_rows * p.n[a + 1]); }
+            area_k[a] = (T *)(wsb + off); off += gs_ws_align(sizeof(T) * num_rows * p.n[a + 1]);
+            if (hv) { area_i[a] = (uint32_t *)(wsb + off); off += gs_ws_align((size_t)4 * num_rows * p.n[a + 1]); }
         }
     }
     for (uint32_t lvl = 0; lvl < p.levels; ++lvl) {

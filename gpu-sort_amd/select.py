@@ -25,67 +25,6 @@ def _key_type_of(t, key_type):
     return kt
 
 
-class DeviceTopK:
-    """MinKeys / MaxKeys / MinPairs / MaxPairs: the k smallest (largest) keys, sorted, with their values.
-
-    d_values_in=None in the pairs forms writes the elements' input indices (u32 bit patterns in d_values_out): an argsort of
-    the top k.  The inputs are never written; d_keys_out / d_values_out need k elements and must not overlap anything."""
-
-    @staticmethod
-    def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, descending,
-             has_values, stream, key_type):
-        need = lib.gs_topk_temp_bytes(num_items, k, int(has_values))
-        if d_temp_storage is None:
-            return need
-        if d_keys_in.element_size() != 4:
-            raise TypeError("DeviceTopK: 32-bit keys only")
-        key_type = _key_type_of(d_keys_in, key_type)
-        _check_buf(d_keys_in, num_items, "d_keys_in")
-        _check_buf(d_keys_out, k, "d_keys_out")
-        if has_values:
-            if d_values_in is not None:
-                _check_buf(d_values_in, num_items, "d_values_in")
-            _check_buf(d_values_out, k, "d_values_out")
-        err = lib.gs_topk_u32(C.c_void_p(d_temp_storage.data_ptr()),
-                              min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
-                              d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
-                              d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
-                              num_items, k, int(descending), key_type, _stream_ptr(stream))
-        check(err, "gs_topk_u32")
-        return need
-
-    @staticmethod
-    def MinKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_items, k, stream=None, key_type=None):
-        return DeviceTopK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_items, k, False, False,
-                               stream, key_type)
-
-    @staticmethod
-    def MaxKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_items, k, stream=None, key_type=None):
-        return DeviceTopK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_items, k, True, False,
-                               stream, key_type)
-
-    @staticmethod
-    def MinPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, stream=None,
-                 key_type=None):
-        return DeviceTopK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k,
-                               False, True, stream, key_type)
-
-    @staticmethod
-    def MaxPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, stream=None,
-                 key_type=None):
-        return DeviceTopK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k,
-                               True, True, stream, key_type)
-
-    @staticmethod
-    def Status(d_temp_storage, num_items, k, has_values, stream=None):
-        """gs_topk_status: [route, image of the k-th element, elements before it, taken from its tie run, elements sharing
-        its top byte, 0, 0, 0] of the last call on d_temp_storage.  Synchronises the stream."""
-        out = (C.c_uint32 * 8)()
-        check(lib.gs_topk_status(C.c_void_p(d_temp_storage.data_ptr()), num_items, k, int(has_values), out, _stream_ptr(stream)),
-              "gs_topk_status")
-        return [int(x) for x in out]
-
-
 _NARROW16 = (_lib.GS_KEY_U16, _lib.GS_KEY_I16, _lib.GS_KEY_F16, _lib.GS_KEY_BF16)     # what gs_topk_u16 / gs_topk_rows_u16 take
 
 
@@ -98,67 +37,92 @@ def _key_type16_of(t, key_type, who="DeviceTopKRows"):
     return key_type
 
 
-class DeviceTopK16:
+# what the key width changes at the flat front end: the name in messages, the entry point, its size query and status function,
+# the key-type resolver, the key's bytes, and the explicit key types refused before anything else (None: the entry point's own
+# refusal serves)
+_FLAT_BY_WIDTH = {
+    32: ("DeviceTopK", "gs_topk_u32", "gs_topk_temp_bytes", "gs_topk_status", _key_type_of, 4, None),
+    16: ("DeviceTopK16", "gs_topk_u16", "gs_topk_u16_temp_bytes", "gs_topk_u16_status",
+         lambda t, key_type: _key_type16_of(t, key_type, "DeviceTopK16"), 2, _NARROW16),
+}
+
+
+class DeviceTopK:
+    """MinKeys / MaxKeys / MinPairs / MaxPairs: the k smallest (largest) keys, sorted, with their values.
+
+    d_values_in=None in the pairs forms writes the elements' input indices (u32 bit patterns in d_values_out): an argsort of
+    the top k.  The inputs are never written; d_keys_out / d_values_out need k elements and must not overlap anything."""
+
+    _width = 32
+
+    @classmethod
+    def _run(cls, d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, descending,
+             has_values, stream, key_type):
+        who, entry, size_query, _, resolve, elem, explicit = _FLAT_BY_WIDTH[cls._width]
+        if key_type is not None and explicit is not None and key_type not in explicit:
+            raise TypeError(f"{who}: key_type must be GS_KEY_U16 / I16 / F16 / BF16")
+        need = getattr(lib, size_query)(num_items, k, int(has_values))
+        if d_temp_storage is None:
+            return need
+        if not isinstance(d_keys_in, torch.Tensor) or d_keys_in.element_size() != elem:
+            raise TypeError(f"{who}: {8 * elem}-bit keys only")
+        key_type = resolve(d_keys_in, key_type)
+        _check_buf(d_keys_in, num_items, "d_keys_in", elem)
+        _check_buf(d_keys_out, k, "d_keys_out", elem)
+        if has_values:
+            if d_values_in is not None:
+                _check_buf(d_values_in, num_items, "d_values_in")
+            _check_buf(d_values_out, k, "d_values_out")
+        err = getattr(lib, entry)(C.c_void_p(d_temp_storage.data_ptr()),
+                                  min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                  d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
+                                  d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
+                                  num_items, k, int(descending), key_type, _stream_ptr(stream))
+        check(err, entry)
+        return need
+
+    @classmethod
+    def MinKeys(cls, d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_items, k, stream=None, key_type=None):
+        return cls._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_items, k, False, False, stream,
+                        key_type)
+
+    @classmethod
+    def MaxKeys(cls, d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_items, k, stream=None, key_type=None):
+        return cls._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_items, k, True, False, stream,
+                        key_type)
+
+    @classmethod
+    def MinPairs(cls, d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, stream=None,
+                 key_type=None):
+        return cls._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, False,
+                        True, stream, key_type)
+
+    @classmethod
+    def MaxPairs(cls, d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, stream=None,
+                 key_type=None):
+        return cls._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, True,
+                        True, stream, key_type)
+
+    @classmethod
+    def Status(cls, d_temp_storage, num_items, k, has_values, stream=None):
+        """gs_topk_status / gs_topk_u16_status: [route, image of the k-th element (16 bits wide for 16-bit keys), elements before
+        it, taken from its tie run, elements sharing its top byte, 0, 0, 0] of the last call on d_temp_storage.  Synchronises
+        the stream."""
+        status = _FLAT_BY_WIDTH[cls._width][3]
+        out = (C.c_uint32 * 8)()
+        check(getattr(lib, status)(C.c_void_p(d_temp_storage.data_ptr()), num_items, k, int(has_values), out, _stream_ptr(stream)),
+              status)
+        return [int(x) for x in out]
+
+
+class DeviceTopK16(DeviceTopK):
     """DeviceTopK for a flat array of 16-bit keys (gs_topk_u16): MinKeys / MaxKeys / MinPairs / MaxPairs / Status.
 
     The key type comes from the tensor's dtype (int16, uint16, float16, bfloat16) or from an explicit 16-bit key_type; the
     result is the first k of DeviceRadixSort on the same keys, in the order of GS_KEY_F16 / BF16 at the enum for the float
     types.  Values and indices are 4 bytes, as in DeviceTopK.  Keys of any other width raise TypeError."""
 
-    @staticmethod
-    def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, descending,
-             has_values, stream, key_type):
-        if key_type is not None and key_type not in _NARROW16:
-            raise TypeError("DeviceTopK16: key_type must be GS_KEY_U16 / I16 / F16 / BF16")
-        need = lib.gs_topk_u16_temp_bytes(num_items, k, int(has_values))
-        if d_temp_storage is None:
-            return need
-        if not isinstance(d_keys_in, torch.Tensor) or d_keys_in.element_size() != 2:
-            raise TypeError("DeviceTopK16: 16-bit keys only")
-        key_type = _key_type16_of(d_keys_in, key_type, "DeviceTopK16")
-        _check_buf(d_keys_in, num_items, "d_keys_in", elem=2)
-        _check_buf(d_keys_out, k, "d_keys_out", elem=2)
-        if has_values:
-            if d_values_in is not None:
-                _check_buf(d_values_in, num_items, "d_values_in")
-            _check_buf(d_values_out, k, "d_values_out")
-        err = lib.gs_topk_u16(C.c_void_p(d_temp_storage.data_ptr()),
-                              min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
-                              d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
-                              d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
-                              num_items, k, int(descending), key_type, _stream_ptr(stream))
-        check(err, "gs_topk_u16")
-        return need
-
-    @staticmethod
-    def MinKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_items, k, stream=None, key_type=None):
-        return DeviceTopK16._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_items, k, False, False,
-                                 stream, key_type)
-
-    @staticmethod
-    def MaxKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_items, k, stream=None, key_type=None):
-        return DeviceTopK16._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_items, k, True, False,
-                                 stream, key_type)
-
-    @staticmethod
-    def MinPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, stream=None,
-                 key_type=None):
-        return DeviceTopK16._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k,
-                                 False, True, stream, key_type)
-
-    @staticmethod
-    def MaxPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, stream=None,
-                 key_type=None):
-        return DeviceTopK16._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k,
-                                 True, True, stream, key_type)
-
-    @staticmethod
-    def Status(d_temp_storage, num_items, k, has_values, stream=None):
-        """gs_topk_u16_status: DeviceTopK.Status' words, the image 16 bits wide.  Synchronises the stream."""
-        out = (C.c_uint32 * 8)()
-        check(lib.gs_topk_u16_status(C.c_void_p(d_temp_storage.data_ptr()), num_items, k, int(has_values), out, _stream_ptr(stream)),
-              "gs_topk_u16_status")
-        return [int(x) for x in out]
+    _width = 16
 
 
 def topk(keys, k, largest=False, values=None, indices=False, stream=None):

@@ -479,6 +479,67 @@ def test_device_topk16_two_phase_form_and_refusals(gs, cuda):
         gs.topk(x.to(torch.int8), 2)
 
 
+# --------------------------------------------------------------------------------------------------- launches --
+# (n, k, route): one tile (route 3); uniform key words (route 1); one top byte for all 70001 keys, 4465 more than the candidate
+# list of 65536 holds (route 2).  k = 100: the sort of the staged elements takes its small path; k = 40000: it spans tiles.
+LAUNCH_SHAPES = [(1000, 100, 3), (70001, 100, 1), (70001, 40000, 1), (70001, 100, 2), (70001, 40000, 2)]
+# {kernel name: launches} of KernelProfile.read(), per (key bits, n, k, route) in the order keys, pairs, arguments.  Recorded
+# on an MI355X from this test at the commit before the two widths' host plans became one (the commit that added gs_topk_u16),
+# not derived from the code.  'other' holds the top-k kernels themselves; the rest is the sort of the staged elements, for
+# 16-bit keys also round one's narrow upsweep and spine scan, and in route 3 the sort of the whole array.
+_SMALL32 = {'lsb_upsweep': 1, 'lsb_scan': 1, 'msb_local_sort': 1}
+_TILES32 = {'lsb_upsweep': 5, 'lsb_scan': 5, 'lsb_downsweep': 4}
+_NARROW = {'lsb_upsweep': 3, 'lsb_scan': 3, 'lsb_downsweep': 2}
+_ROUTE3_16 = {'lsb_upsweep': 2, 'lsb_scan': 2, 'lsb_downsweep': 2}
+LAUNCHES = {
+    (32, 1000, 100, 3): ({'msb_local_sort': 1, 'other': 1}, {'msb_local_sort': 1, 'other': 1}, {'msb_local_sort': 1, 'other': 2}),
+    (32, 70001, 100, 1): ({**_SMALL32, 'other': 11}, {**_SMALL32, 'other': 12}, {**_SMALL32, 'other': 11}),
+    (32, 70001, 40000, 1): ({**_TILES32, 'other': 11}, {**_TILES32, 'other': 12}, {**_TILES32, 'other': 11}),
+    (32, 70001, 100, 2): ({**_SMALL32, 'other': 11}, {**_SMALL32, 'other': 12}, {**_SMALL32, 'other': 11}),
+    (32, 70001, 40000, 2): ({**_TILES32, 'other': 11}, {**_TILES32, 'other': 12}, {**_TILES32, 'other': 11}),
+    (16, 1000, 100, 3): ({**_ROUTE3_16, 'other': 1}, {**_ROUTE3_16, 'other': 1}, {**_ROUTE3_16, 'other': 2}),
+    (16, 70001, 100, 1): ({**_NARROW, 'other': 7}, {**_NARROW, 'other': 8}, {**_NARROW, 'other': 7}),
+    (16, 70001, 40000, 1): ({**_NARROW, 'other': 7}, {**_NARROW, 'other': 8}, {**_NARROW, 'other': 7}),
+    (16, 70001, 100, 2): ({**_NARROW, 'other': 7}, {**_NARROW, 'other': 8}, {**_NARROW, 'other': 7}),
+    (16, 70001, 40000, 2): ({**_NARROW, 'other': 7}, {**_NARROW, 'other': 8}, {**_NARROW, 'other': 7}),
+}
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("n,k,route", LAUNCH_SHAPES)
+@pytest.mark.parametrize("bits", [32, 16])
+def test_launches_of_every_route_and_form(gs, cuda, bits, n, k, route, mode):
+    """The launches of one call, by kernel name, for both widths: the plan enqueues the same kernels whatever the data, so the
+    whole dict is pinned.  The route is read back from the status words, and the keys are the first k of the sorted words."""
+    front, np_t, torch_t, to_dev, to_host = ((gs.DeviceTopK16, np.uint16, torch.int16, dev16, host16) if bits == 16 else
+                                             (gs.DeviceTopK, np.uint32, torch.int32, dev32, host32))
+    words = np.random.default_rng(bits + n).integers(0, 1 << bits, n, dtype=np.uint64)
+    if route == 2:
+        words = (words >> np.uint64(8)) | np.uint64(0x42 << (bits - 8))
+    words = words.astype(np_t)
+    d_keys = to_dev(words, cuda)
+    ko = torch.empty(k, dtype=torch_t, device=cuda)
+    vo = torch.empty(k, dtype=torch.int32, device=cuda)
+    vals = torch.arange(n, dtype=torch.int32, device=cuda) if mode == PAIRS else None
+    kt = gs.GS_KEY_U16 if bits == 16 else gs.GS_KEY_U32
+    hv = mode != KEYS
+    if hv:
+        nb = front.MinPairs(None, 0, None, None, None, None, n, k)
+    else:
+        nb = front.MinKeys(None, 0, None, None, n, k)
+    temp = torch.empty(nb, dtype=torch.uint8, device=cuda)
+    with gs.KernelProfile() as prof:
+        if hv:
+            front.MinPairs(temp, nb, d_keys, ko, vals, vo, n, k, key_type=kt)
+        else:
+            front.MinKeys(temp, nb, d_keys, ko, n, k, key_type=kt)
+    got = {name: launches for name, (_, launches) in prof.read().items()}
+    print("LAUNCHES", (bits, n, k, route), mode, got)
+    assert front.Status(temp, n, k, hv)[0] == route
+    assert np.array_equal(to_host(ko), np.sort(words, kind="stable")[:k])
+    assert got == LAUNCHES[(bits, n, k, route)][MODES.index(mode)]
+
+
 def test_every_route_is_taken_in_this_file(gs, cuda):
     assert Case(gs, cuda, N.gen16("uniform", 4000, seed=1), U16, False).check(100, PAIRS) == 3
     assert Case(gs, cuda, N.gen16("uniform", 90000, seed=1), U16, False).check(100, PAIRS) == 1
