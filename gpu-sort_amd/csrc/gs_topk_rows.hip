@@ -1,6 +1,8 @@
 // gs_topk_rows.hip -- gs_topk_rows_u32 and gs_topk_rows_u16: the first k of the stable sort of every row of a matrix, for
 // 32-bit keys and 16-bit keys (section 10i).  One set of kernels and one host path, instantiated
 // over a key-traits type (TrKey32, TrKey16); one geometry and one plan, so gs_topk_rows_plan answers for both entry points.
+// gs_topk_segmented_u32 (section 10k), the same for ragged segments given by device offsets, follows them: it runs the same
+// device functions per record of lists that a classify kernel fills (see "ragged segments" below).
 //
 // Row r of the result is what gs_topk_u32 writes for row r alone, bit for bit.  Every row has the same length, so the
 // launches are decided on the host from num_cols and k:
@@ -170,12 +172,12 @@ __device__ __forceinline__ uint32_t tr_select(uint32_t (&img)[TR_KPT], uint32_t 
 }
 
 // The ordered two-group compaction of the selected elements into LDS: group A (before the k-th image) at [0, less), group B
-// (equal to it) behind, cut at keff; (wave, row, lane) is input order.  stage_v[pos] gets src_i[j] where the source carries
-// columns (SRC_IDX), otherwise col0 + j.  Ends with a workgroup barrier.
-template <bool HV, bool SRC_IDX, int CAP>
-__device__ __forceinline__ void tr_compact(uint32_t (&img)[TR_KPT], uint32_t first, uint32_t len, uint32_t keff, uint32_t kth, uint32_t less,
-                                           uint32_t w, uint32_t lane, uint32_t (&wcnt)[2][TR_WAVES], uint32_t *__restrict__ stage_k,
-                                           uint32_t *__restrict__ stage_v, const uint32_t *__restrict__ src_i, uint32_t col0)
+// (equal to it) behind, cut at keff; (wave, row, lane) is input order.  stage_v[pos] gets value_of(u, j), the value of element
+// j = first + u * 64 (img[u]).  Ends with a workgroup barrier.
+template <bool HV, int CAP, typename ValueOf>
+__device__ __forceinline__ void tr_compact_with(uint32_t (&img)[TR_KPT], uint32_t first, uint32_t len, uint32_t keff, uint32_t kth,
+                                                uint32_t less, uint32_t w, uint32_t lane, uint32_t (&wcnt)[2][TR_WAVES],
+                                                uint32_t *__restrict__ stage_k, uint32_t *__restrict__ stage_v, ValueOf value_of)
 {
     uint32_t nA = 0, nB = 0, lenc = len;
     asm volatile("" : "+v"(lenc));   // (range compares again, as in the select rounds; once more before the scatter loop)
@@ -200,13 +202,24 @@ __device__ __forceinline__ void tr_compact(uint32_t (&img)[TR_KPT], uint32_t fir
             const uint32_t pos = a ? baseA + count_lower(mA) : baseB + count_lower(mB);
             if ((a || b) && pos < keff && pos < (uint32_t)CAP) {   // (group A never passes `less`; group B is cut at keff = less + take)
                 stage_k[pos] = img[u];
-                if (HV) stage_v[pos] = SRC_IDX ? src_i[j] : col0 + j;
+                if (HV) stage_v[pos] = value_of(u, j);
             }
             baseA += (uint32_t)__popcll(mA);
             baseB += (uint32_t)__popcll(mB);
         }
     }
     __syncthreads();
+}
+
+// tr_compact_with for a source in memory: stage_v[pos] gets src_i[j] where the source carries columns (SRC_IDX), otherwise
+// col0 + j.
+template <bool HV, bool SRC_IDX, int CAP>
+__device__ __forceinline__ void tr_compact(uint32_t (&img)[TR_KPT], uint32_t first, uint32_t len, uint32_t keff, uint32_t kth, uint32_t less,
+                                           uint32_t w, uint32_t lane, uint32_t (&wcnt)[2][TR_WAVES], uint32_t *__restrict__ stage_k,
+                                           uint32_t *__restrict__ stage_v, const uint32_t *__restrict__ src_i, uint32_t col0)
+{
+    tr_compact_with<HV, CAP>(img, first, len, keff, kth, less, w, lane, wcnt, stage_k, stage_v,
+                             [=](int, uint32_t j) { return SRC_IDX ? src_i[j] : col0 + j; });
 }
 
 // ------------------------------------------------------------------ path 1 --
@@ -496,6 +509,548 @@ static int tr_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------ ragged segments --
+// gs_topk_segmented_u32: the k best of every segment of a flat array, the segments given by device
+// offsets.  The lengths are on the device, so a classify kernel sorts the segments into six lists of records by length and
+// the kernels above run per record: the four wave classes of path 1 (<= 64 / 256 / 512 / 1024 elements), the workgroup of
+// path 2 (<= CH), and for longer segments level 0 of path 3 per (record, chunk) task followed by ONE streaming final per
+// segment: a workgroup reads its candidate row CH elements at a time, the carried best k of the rounds before in front of the
+// new candidates, and selects again.  Carried elements are in the order the last compaction left them (group A in input
+// order, then the cut tie run in input order) and precede every new candidate, so equal images stay in position order from
+// round to round and the one stable wave sort at the end reproduces the definition.
+// Every record, task and cursor read from the workspace is clamped against the arguments before it becomes an address.
+constexpr uint32_t TS_MAX_GRID = 16384;   // workgroups per launch; the kernels stride over longer lists
+constexpr int TS_BLOCK = 4, TS_LONG = 5;   // lists 0..3: the wave classes
+// words of the state block: [0..4] the counts of the wave and block lists, [5] long segments that found room, [6] dropped
+// segments, [7] the chunk tasks of [5]; the cursors the long segments claim from: [8..9] chunk-task slots (64 bits: what
+// overlapping segments ask for together may pass 2^32), [10] records
+constexpr int TS_LONG_OK = 5, TS_DROPPED = 6, TS_TASKS_OK = 7, TS_TASK_CUR = 8, TS_REC_CUR = 10, TS_STATE_BYTES = 4096;
+
+struct TsRec { uint32_t base, len, seg, row; };   // row: the first chunk-task slot of a long segment (its candidate row is row * k)
+struct TsTask { uint32_t rec, chunk; };
+static_assert(sizeof(TsRec) == 16 && sizeof(TsTask) == 8, "the sizes of the header's workspace formula");
+
+struct TsWs {
+    uint32_t *state;
+    TsRec *list[6];
+    TsTask *tasks;
+    uint32_t *cand_k, *cand_p;   // candidate rows: images, and (with values) positions within the segment
+    uint32_t nseg, lmax, tmax;
+};
+
+// A kernel argument that is uniform but used rarely (an output pointer that only the finishing wave needs, a bound checked
+// once per record): kept in vector registers across the select and the compaction, whose ballots need the scalar ones.
+template <typename P> __device__ __forceinline__ P *ts_in_vgprs(P *p)
+{
+    unsigned long long v = (unsigned long long)(uintptr_t)p;
+    asm volatile("" : "+v"(v));
+    return (P *)(uintptr_t)v;
+}
+__device__ __forceinline__ uint32_t ts_in_vgpr(uint32_t v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+// a record of the kernels' own lists, clamped like a caller's offsets: false when nothing of it may be touched
+__device__ __forceinline__ bool ts_load_rec(const TsRec *__restrict__ list, uint32_t at, uint32_t num_items, uint32_t nseg, uint32_t cap,
+                                            uint32_t &base, uint32_t &len, uint32_t &seg, uint32_t &row)
+{
+    const uint4 rv = reinterpret_cast<const uint4 *>(list)[at];
+    base = __builtin_amdgcn_readfirstlane(rv.x); len = __builtin_amdgcn_readfirstlane(rv.y);
+    seg = __builtin_amdgcn_readfirstlane(rv.z); row = __builtin_amdgcn_readfirstlane(rv.w);
+    if (__builtin_amdgcn_readfirstlane(base >= num_items || seg >= nseg || len == 0u)) return false;
+    const uint32_t room = num_items - base, most = room < cap ? room : cap;
+    if (len > most) len = __builtin_amdgcn_readfirstlane(most);
+    return true;
+}
+
+// Four segments per thread, one LDS atomic per thread and list, one global atomic per workgroup and list (the pattern of
+// seg_classify_kernel).  A long segment claims a record slot and ceil(len / CH) chunk-task slots the same way: its share of
+// the workgroup's LDS counter (records and tasks packed into one word, so the two shares are taken in one order), then of
+// the two cursors the workgroup advanced once.  A claim is made once and never retried.  One that passes either capacity
+// drops the segment: count 0, nothing of it written (its record slot, if it got one, holds an empty record).  The cursors
+// only grow, so after one dropped segment a later one may be dropped although it alone would have fitted.
+__global__ __launch_bounds__(256) void topk_seg_classify_kernel(TsWs ws, const int *__restrict__ seg_begin, const int *__restrict__ seg_end,
+                                                                uint32_t num_items, uint32_t k, uint32_t *__restrict__ counts_out)
+{
+    constexpr int SPT = 4, NL = 5;
+    __shared__ uint32_t s_cnt[NL], s_base[NL + 1];   // s_base[NL]: the first record slot of the workgroup's long segments
+    __shared__ unsigned long long s_long, s_task_base;   // s_long: their number (high half) and their chunk tasks (low half)
+    const int tid = threadIdx.x;
+    const uint32_t nseg = ws.nseg;
+    for (uint32_t base = blockIdx.x * (256u * SPT); base < nseg; base += gridDim.x * (256u * SPT)) {
+        if (tid < NL) s_cnt[tid] = 0;
+        if (tid == NL) s_long = 0;
+        __syncthreads();
+        uint32_t b[SPT], size[SPT], off[NL], cnt[NL], lrec[SPT], ltask[SPT];
+        int list[SPT];
+#pragma unroll
+        for (int q = 0; q < NL; ++q) cnt[q] = 0;
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+            const uint32_t sg = base + (uint32_t)tid * SPT + j;
+            b[j] = 0; size[j] = 0; list[j] = -1;
+            if (sg < nseg) {
+                int lo = seg_begin[sg], hi = seg_end[sg];
+                if (lo < 0) lo = 0;                                 // offsets outside [0, num_items] are clamped so that they
+                if (hi > (int)num_items) hi = (int)num_items;       // cannot become out-of-bounds accesses
+                if (hi > lo) { b[j] = (uint32_t)lo; size[j] = (uint32_t)(hi - lo); }
+            }
+            const uint32_t sz = size[j];
+            lrec[j] = 0; ltask[j] = 0;
+            if (sz != 0u && sz <= TR_WAVE_COLS) list[j] = sz <= (uint32_t)WAVE ? 0 : sz <= 256u ? 1 : sz <= 512u ? 2 : 3;
+            else if (sz != 0u && sz <= TR_CH) list[j] = TS_BLOCK;
+            else if (sz != 0u) {          // rare: an LDS atomic each (1024 segments of fewer than 2^18 chunks: the low half holds them)
+                list[j] = TS_LONG;
+                const unsigned long long mine = atomicAdd(&s_long, (1ull << 32) | (unsigned long long)((sz + TR_CH - 1u) / TR_CH));
+                lrec[j] = (uint32_t)(mine >> 32);
+                ltask[j] = (uint32_t)mine;
+            }
+            if (sg < nseg && counts_out && list[j] != TS_LONG) counts_out[sg] = sz < k ? sz : k;
+#pragma unroll
+            for (int q = 0; q < NL; ++q) cnt[q] += list[j] == q ? 1u : 0u;
+        }
+#pragma unroll
+        for (int q = 0; q < NL; ++q) off[q] = cnt[q] ? atomicAdd(&s_cnt[q], cnt[q]) : 0u;       // LDS
+        __syncthreads();
+        if (tid < NL && s_cnt[tid] != 0u) s_base[tid] = atomicAdd(&ws.state[tid], s_cnt[tid]);
+        if (tid == NL && s_long != 0ull) {
+            s_base[NL] = atomicAdd(&ws.state[TS_REC_CUR], (uint32_t)(s_long >> 32));
+            s_task_base = atomicAdd(reinterpret_cast<unsigned long long *>(ws.state + TS_TASK_CUR), s_long & 0xffffffffull);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SPT; ++j) {
+#pragma unroll
+            for (int q = 0; q < NL; ++q) {
+                if (list[j] != q) continue;
+                const uint32_t at = s_base[q] + off[q]++;
+                if (at < nseg) ws.list[q][at] = TsRec{b[j], size[j], base + (uint32_t)tid * SPT + j, 0u};
+            }
+            if (list[j] == TS_LONG) {
+                const uint32_t sg = base + (uint32_t)tid * SPT + j, chunks = (size[j] + TR_CH - 1u) / TR_CH;
+                const uint32_t rec = s_base[NL] + lrec[j];
+                const unsigned long long task = s_task_base + ltask[j];
+                const bool fits = rec < ws.lmax && task + chunks <= (unsigned long long)ws.tmax;
+                if (fits) {
+                    ws.list[TS_LONG][rec] = TsRec{b[j], size[j], sg, (uint32_t)task};
+                    atomicAdd(&ws.state[TS_LONG_OK], 1u);
+                    atomicAdd(&ws.state[TS_TASKS_OK], chunks);
+                } else {
+                    if (rec < ws.lmax) ws.list[TS_LONG][rec] = TsRec{0u, 0u, 0u, 0u};
+                    atomicAdd(&ws.state[TS_DROPPED], 1u);
+                }
+                if (counts_out) counts_out[sg] = fits ? (size[j] < k ? size[j] : k) : 0u;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// topk_rows_wave_kernel per record of wave list LIST: base and length from the record, stores at seg * k + idx for idx < kept.
+template <typename KT, int WKPT, bool HV>
+__global__ __launch_bounds__(256) void topk_seg_wave_kernel(TsWs ws, const typename KT::T *__restrict__ keys,
+                                                            const uint32_t *__restrict__ vals_in, typename KT::T *__restrict__ keys_out,
+                                                            uint32_t *__restrict__ vals_out, uint32_t num_items, uint32_t k, int flt, uint32_t x)
+{
+    using T = typename KT::T;
+    constexpr int CAP = WKPT * WAVE, LIST = WKPT == 1 ? 0 : WKPT == 4 ? 1 : WKPT == 8 ? 2 : 3;
+    __shared__ __attribute__((aligned(16))) uint32_t hist[4][RADIX];
+    __shared__ uint32_t stage_k[4][CAP];
+    __shared__ uint32_t stage_v[HV ? 4 : 1][HV ? CAP : 1];
+    const int w = wave_id(), lane = lane_id();
+    uint32_t count = ws.state[LIST];
+    if (count > ws.nseg) count = ws.nseg;
+    for (uint32_t t = blockIdx.x * 4u + (uint32_t)w; t < count; t += gridDim.x * 4u) {
+        uint32_t base, cols, seg, row;
+        if (!ts_load_rec(ws.list[LIST], t, num_items, ws.nseg, (uint32_t)CAP, base, cols, seg, row)) continue;
+        const size_t in0 = base, out0 = (size_t)seg * k;
+        const uint32_t kept = k < cols ? k : cols;
+        uint32_t key[WKPT], val[HV ? WKPT : 1];
+        const uint32_t last = cols - 1u;
+#pragma unroll
+        for (int i = 0; i < WKPT; ++i) {
+            const uint32_t idx = (uint32_t)(i * WAVE + lane);
+            key[i] = (uint32_t)__builtin_nontemporal_load(keys + in0 + (idx < last ? idx : last));   // past the end: the last element again
+        }
+#pragma unroll
+        for (int i = 0; i < WKPT; ++i) {
+            const uint32_t idx = (uint32_t)(i * WAVE + lane);
+            key[i] = idx < cols ? KT::in(key[i], flt, x) : KT::PAD;   // pads: last in position, largest in every digit
+            if (HV) val[i] = idx;
+        }
+        wave_sort_bits<KT::BITS, WKPT, HV>(key, val, hist[w], stage_k[w], stage_v[HV ? w : 0]);
+#pragma unroll
+        for (int i = 0; i < WKPT; ++i) {
+            const uint32_t idx = (uint32_t)(i * WAVE + lane);
+            if (idx < kept) {
+                keys_out[out0 + idx] = (T)KT::out(key[i], flt, x);
+                if (HV) vals_out[out0 + idx] = vals_in ? vals_in[in0 + (val[i] < cols ? val[i] : last)] : val[i];
+            }
+        }
+    }
+}
+
+// topk_rows_block_kernel's body per record of the block list, or (CHUNK) per (record, chunk) task of the long list.  The
+// block list's results go to the caller's outputs at seg * k; a chunk's min(k, chunk length) sorted (image, position in the
+// segment) pairs go to slot row + chunk of the candidate area (every chunk but the last gives k, so the segment's candidate
+// row is dense).  Candidate rows hold images: the final reads them as they are.
+template <typename KT, int WKPT, bool HV, bool CHUNK>
+__global__ __launch_bounds__(TR_THREADS) void topk_seg_block_kernel(TsWs ws, const typename KT::T *__restrict__ keys,
+                                                                    const uint32_t *__restrict__ vals_in,
+                                                                    typename KT::T *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
+                                                                    uint32_t num_items, uint32_t k, int flt, uint32_t x)
+{
+    using T = typename KT::T;
+    constexpr int CAP = WKPT * WAVE;
+    __shared__ __attribute__((aligned(16))) uint32_t h[RADIX];   // the select's histogram, then the finishing wave's counters
+    __shared__ uint32_t scratch[8];
+    __shared__ uint32_t sel[3];
+    __shared__ uint32_t wcnt[2][TR_WAVES];
+    __shared__ uint32_t stage_k[CAP], sort_k[CAP];
+    __shared__ uint32_t stage_v[HV ? CAP : 1], sort_v[HV ? CAP : 1];
+    const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    uint32_t count, nrec = 0;
+    if (CHUNK) {   // the cursors, not the counts of completed claims: a dropped segment leaves a hole behind it
+        count = ws.state[TS_TASK_CUR + 1] != 0u ? ws.tmax : ws.state[TS_TASK_CUR];
+        nrec = ws.state[TS_REC_CUR];
+        if (count > ws.tmax) count = ws.tmax;
+        if (nrec > ws.lmax) nrec = ws.lmax;
+        nrec = ts_in_vgpr(nrec);
+    } else {
+        count = ws.state[TS_BLOCK];
+        if (count > ws.nseg) count = ws.nseg;
+    }
+    const TsRec *const recs = ts_in_vgprs(ws.list[CHUNK ? TS_LONG : TS_BLOCK]);
+    const TsTask *const tasks = ts_in_vgprs(ws.tasks);
+    uint32_t *const dst_ck = ts_in_vgprs(ws.cand_k), *const dst_cp = ts_in_vgprs(ws.cand_p);
+    const uint32_t *const vin = ts_in_vgprs(vals_in);
+    T *const kout = ts_in_vgprs(keys_out);
+    uint32_t *const vout = ts_in_vgprs(vals_out);
+    const uint32_t nseg = ts_in_vgpr(ws.nseg), tmax = ts_in_vgpr(ws.tmax), nitems = ts_in_vgpr(num_items);
+    for (uint32_t t = blockIdx.x; t < count; t += gridDim.x) {   // (t and everything decided from it are uniform: the barriers are safe)
+        uint32_t base, slen, seg, row, c = 0, at = t;
+        if (CHUNK) {
+            const TsTask task = tasks[t];
+            at = __builtin_amdgcn_readfirstlane(task.rec); c = __builtin_amdgcn_readfirstlane(task.chunk);
+            if (__builtin_amdgcn_readfirstlane(at >= nrec)) continue;
+        }
+        if (!ts_load_rec(recs, at, nitems, nseg, CHUNK ? nitems : TR_CH, base, slen, seg, row)) continue;
+        // (a slot whose claim was dropped was never written by the expand kernel: whatever it holds is not the task of this slot)
+        if (CHUNK && __builtin_amdgcn_readfirstlane(c >= (slen + TR_CH - 1u) / TR_CH || row >= tmax || c >= tmax - row || row + c != t)) continue;
+        const uint32_t lo = c * TR_CH, len = slen - lo < TR_CH ? slen - lo : TR_CH, keff = k < len ? k : len;
+        const size_t in0 = (size_t)base + lo;
+
+        uint32_t img[TR_KPT];
+#pragma unroll
+        for (int u = 0; u < TR_KPT; ++u) {
+            const uint32_t j = first + (uint32_t)u * WAVE;
+            img[u] = j < len ? (uint32_t)__builtin_nontemporal_load(keys + in0 + j) : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < TR_KPT; ++u) img[u] = KT::in(img[u], flt, x);
+
+        uint32_t less;
+        const uint32_t kth = tr_select<KT::BITS>(img, first, len, keff, tid, h, scratch, sel, less);
+        tr_compact<HV, false, CAP>(img, first, len, keff, kth, less, w, lane, wcnt, stage_k, stage_v, nullptr, lo);
+
+        if (w == 0) {   // finish: one wave sorts the keff staged pairs and stores them
+            uint32_t key[WKPT], val[HV ? WKPT : 1];
+#pragma unroll
+            for (int i = 0; i < WKPT; ++i) {
+                const uint32_t idx = (uint32_t)i * WAVE + lane;
+                key[i] = idx < keff ? stage_k[idx] : KT::PAD;   // pads: last in position, largest in every digit
+                if (HV) val[i] = idx < keff ? stage_v[idx] : 0u;
+            }
+            wave_sort_bits<KT::BITS, WKPT, HV>(key, val, h, sort_k, sort_v);
+            const size_t out0 = CHUNK ? (size_t)(row + c) * k : (size_t)seg * k;
+#pragma unroll
+            for (int i = 0; i < WKPT; ++i) {
+                const uint32_t idx = (uint32_t)i * WAVE + lane;
+                if (idx < keff) {
+                    if (CHUNK) {
+                        dst_ck[out0 + idx] = key[i];
+                        if (HV) dst_cp[out0 + idx] = val[i];
+                    } else {
+                        kout[out0 + idx] = (T)KT::out(key[i], flt, x);
+                        if (HV) vout[out0 + idx] = vin ? vin[(size_t)base + (val[i] < slen ? val[i] : slen - 1u)] : val[i];
+                    }
+                }
+            }
+        }
+        __syncthreads();   // the finishing wave is done with h and the stage before the next record's select
+    }
+}
+
+// One workgroup per long record writes the (record, chunk) pairs of its task slots.
+__global__ __launch_bounds__(256) void topk_seg_expand_kernel(TsWs ws, uint32_t num_items)
+{
+    uint32_t nrec = ws.state[TS_REC_CUR];
+    if (nrec > ws.lmax) nrec = ws.lmax;
+    for (uint32_t r = blockIdx.x; r < nrec; r += gridDim.x) {
+        uint32_t base, len, seg, row;
+        if (!ts_load_rec(ws.list[TS_LONG], r, num_items, ws.nseg, num_items, base, len, seg, row)) continue;
+        const uint32_t chunks = (len + TR_CH - 1u) / TR_CH;
+        if (row >= ws.tmax || chunks > ws.tmax - row) continue;
+        for (uint32_t c = threadIdx.x; c < chunks; c += 256u) ws.tasks[row + c] = TsTask{r, c};
+    }
+}
+
+// The streaming final: one workgroup per long record.  A round holds a virtual chunk of up to CH elements in registers:
+// the kc carried pairs from the stage first, in the order the last compaction left them, then the next CH - kc candidates
+// of the segment's row; tr_select and the compaction put the best min(k, elements so far) back into the stage.  After the
+// last round wave 0 sorts the stage and stores.  A row that fits one chunk is one round.
+template <typename KT, int WKPT, bool HV>
+__global__ __launch_bounds__(TR_THREADS) void topk_seg_final_kernel(TsWs ws, const uint32_t *__restrict__ vals_in,
+                                                                    typename KT::T *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
+                                                                    uint32_t num_items, uint32_t k, int flt, uint32_t x)
+{
+    using T = typename KT::T;
+    constexpr int CAP = WKPT * WAVE;
+    __shared__ __attribute__((aligned(16))) uint32_t h[RADIX];
+    __shared__ uint32_t scratch[8];
+    __shared__ uint32_t sel[3];
+    __shared__ uint32_t wcnt[2][TR_WAVES];
+    __shared__ uint32_t stage_k[CAP], sort_k[CAP];
+    __shared__ uint32_t stage_v[HV ? CAP : 1], sort_v[HV ? CAP : 1];
+    const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    uint32_t nrec = ws.state[TS_REC_CUR];
+    if (nrec > ws.lmax) nrec = ws.lmax;
+    const TsRec *const recs = ts_in_vgprs(ws.list[TS_LONG]);
+    const uint32_t *const src_ck = ts_in_vgprs(ws.cand_k), *const src_cp = ts_in_vgprs(ws.cand_p);
+    const uint32_t *const vin = ts_in_vgprs(vals_in);
+    T *const kout = ts_in_vgprs(keys_out);
+    uint32_t *const vout = ts_in_vgprs(vals_out);
+    const uint32_t nseg = ts_in_vgpr(ws.nseg), tmax = ts_in_vgpr(ws.tmax), nitems = ts_in_vgpr(num_items);
+    for (uint32_t r = blockIdx.x; r < nrec; r += gridDim.x) {
+        uint32_t base, slen, seg, row;
+        if (!ts_load_rec(recs, r, nitems, nseg, nitems, base, slen, seg, row)) continue;
+        const uint32_t chunks = (slen + TR_CH - 1u) / TR_CH, tail = slen - (chunks - 1u) * TR_CH;
+        if (__builtin_amdgcn_readfirstlane(row >= tmax || chunks > tmax - row)) continue;
+        const uint32_t n1 = (chunks - 1u) * k + (k < tail ? k : tail);      // next(len): the candidates the chunks left
+        const uint32_t *ck = src_ck + (size_t)row * k, *cp = src_cp + (size_t)row * k;
+        base = ts_in_vgpr(base); slen = ts_in_vgpr(slen); seg = ts_in_vgpr(seg);   // for the stores at the end
+        uint32_t kc = 0, pos = 0;
+        do {
+            const uint32_t room = TR_CH - kc, left = n1 - pos, take = left < room ? left : room, len = kc + take;
+            const uint32_t keff = k < len ? k : len;
+            uint32_t img[TR_KPT], val[HV ? TR_KPT : 1];
+#pragma unroll
+            for (int u = 0; u < TR_KPT; ++u) {
+                const uint32_t j = first + (uint32_t)u * WAVE;
+                if (j < kc) {
+                    img[u] = stage_k[j];
+                    if (HV) val[u] = stage_v[j];
+                } else if (j < len) {
+                    img[u] = __builtin_nontemporal_load(ck + pos + (j - kc));
+                    if (HV) val[u] = __builtin_nontemporal_load(cp + pos + (j - kc));
+                } else {
+                    img[u] = 0u;
+                    if (HV) val[u] = 0u;
+                }
+            }
+            uint32_t less;   // (the select's first barrier orders the stage reads above before the compaction's writes)
+            const uint32_t kth = tr_select<KT::BITS>(img, first, len, keff, tid, h, scratch, sel, less);
+            tr_compact_with<HV, CAP>(img, first, len, keff, kth, less, w, lane, wcnt, stage_k, stage_v,
+                                     [&](int u, uint32_t) { return val[HV ? u : 0]; });
+            kc = keff;
+            pos += take;
+        } while (pos < n1);
+
+        if (w == 0) {
+            uint32_t key[WKPT], val[HV ? WKPT : 1];
+#pragma unroll
+            for (int i = 0; i < WKPT; ++i) {
+                const uint32_t idx = (uint32_t)i * WAVE + lane;
+                key[i] = idx < kc ? stage_k[idx] : KT::PAD;
+                if (HV) val[i] = idx < kc ? stage_v[idx] : 0u;
+            }
+            wave_sort_bits<KT::BITS, WKPT, HV>(key, val, h, sort_k, sort_v);
+            const size_t out0 = (size_t)seg * k;
+#pragma unroll
+            for (int i = 0; i < WKPT; ++i) {
+                const uint32_t idx = (uint32_t)i * WAVE + lane;
+                if (idx < kc) {
+                    kout[out0 + idx] = (T)KT::out(key[i], flt, x);
+                    if (HV) vout[out0 + idx] = vin ? vin[(size_t)base + (val[i] < slen ? val[i] : slen - 1u)] : val[i];
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- host
+struct TsGeom { uint64_t lmax, tmax; };
+
+static inline bool ts_shape_ok(uint64_t num_items, uint64_t num_segments, uint64_t k)
+{
+    return k <= TR_MAX_K && num_items < (1ull << 31) && !tr_mul_ge_2p32(num_segments, k);
+}
+
+static inline TsGeom ts_geom(uint64_t num_items, uint64_t num_segments)
+{
+    TsGeom g;
+    g.lmax = num_items / (TR_CH + 1);
+    if (g.lmax > num_segments) g.lmax = num_segments;
+    g.tmax = g.lmax ? num_items / TR_CH + g.lmax : 0;
+    return g;
+}
+
+// the carve and the size query in one walk (base may be null: the query)
+static size_t ts_carve(char *base, uint64_t num_items, uint64_t num_segments, uint64_t k, bool hv, TsWs *ws)
+{
+    const TsGeom g = ts_geom(num_items, num_segments);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *p = (char *)((uintptr_t)base + off); off += gs_ws_align(bytes); return p; };
+    TsWs w{};
+    w.state = (uint32_t *)take(TS_STATE_BYTES);
+    for (int q = 0; q < 5; ++q) w.list[q] = (TsRec *)take(sizeof(TsRec) * num_segments);
+    w.list[TS_LONG] = (TsRec *)take(sizeof(TsRec) * g.lmax);
+    w.tasks = (TsTask *)take(sizeof(TsTask) * g.tmax);
+    w.cand_k = (uint32_t *)take((size_t)4 * k * g.tmax);
+    w.cand_p = w.cand_k;
+    if (hv) w.cand_p = (uint32_t *)take((size_t)4 * k * g.tmax);
+    w.nseg = (uint32_t)num_segments; w.lmax = (uint32_t)g.lmax; w.tmax = (uint32_t)g.tmax;
+    if (ws) *ws = w;
+    return off;
+}
+
+static size_t ts_temp_bytes(uint64_t num_items, uint64_t num_segments, uint64_t k, int has_values)
+{
+    if (!ts_shape_ok(num_items, num_segments, k)) return 0;
+    if (num_items == 0 || num_segments == 0 || k == 0) return 0;
+    return ts_carve(nullptr, num_items, num_segments, k, has_values != 0, nullptr) + GS_WS_SLACK;
+}
+
+// the launch groups of a shape: bit 0 wave, bit 1 block, bit 2 long
+static inline uint32_t ts_groups(uint64_t num_items) { return 1u | (num_items > TR_WAVE_COLS ? 2u : 0u) | (num_items > TR_CH ? 4u : 0u); }
+static inline uint32_t ts_launches(uint32_t groups) { return 2u + 4u + ((groups & 2u) ? 1u : 0u) + ((groups & 4u) ? 3u : 0u); }
+
+template <typename KT, int WKPT, bool HV>
+static void ts_launch_wave(hipStream_t s, const TsWs &ws, uint32_t grid, const typename KT::T *ki, const uint32_t *vi, typename KT::T *ko,
+                           uint32_t *vo, uint32_t n, uint32_t k, int flt, uint32_t x)
+{
+    KernelTimer kt(GS_K_OTHER, s);
+    hipLaunchKernelGGL((topk_seg_wave_kernel<KT, WKPT, HV>), dim3(grid), dim3(256), 0, s, ws, ki, vi, ko, vo, n, k, flt, x);
+}
+
+template <typename KT, int WKPT, bool HV>
+static void ts_launch_select(hipStream_t s, const TsWs &ws, uint32_t groups, const typename KT::T *ki, const uint32_t *vi,
+                             typename KT::T *ko, uint32_t *vo, uint32_t n, uint32_t k, int flt, uint32_t x)
+{
+    const uint32_t gb = ws.nseg < TS_MAX_GRID ? ws.nseg : TS_MAX_GRID;
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL((topk_seg_block_kernel<KT, WKPT, HV, false>), dim3(gb), dim3(TR_THREADS), 0, s, ws, ki, vi, ko, vo, n, k, flt, x); }
+    if (!(groups & 4u)) return;
+    const uint32_t gl = ws.lmax < TS_MAX_GRID ? ws.lmax : TS_MAX_GRID, gt = ws.tmax < TS_MAX_GRID ? ws.tmax : TS_MAX_GRID;
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL(topk_seg_expand_kernel, dim3(gl), dim3(256), 0, s, ws, n); }
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL((topk_seg_block_kernel<KT, WKPT, HV, true>), dim3(gt), dim3(TR_THREADS), 0, s, ws, ki, vi, ko, vo, n, k, flt, x); }
+    { KernelTimer kt(GS_K_OTHER, s);
+      hipLaunchKernelGGL((topk_seg_final_kernel<KT, WKPT, HV>), dim3(gl), dim3(TR_THREADS), 0, s, ws, vi, ko, vo, n, k, flt, x); }
+}
+
+template <typename KT>
+static int ts_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_in, const uint32_t *d_vals_in, typename KT::T *d_keys_out,
+                  uint32_t *d_vals_out, uint32_t *d_counts_out, uint64_t num_items, uint32_t num_segments, const int32_t *d_begin_offsets,
+                  const int32_t *d_end_offsets, uint64_t k, int descending, int key_type, void *stream)
+{
+    using T = typename KT::T;
+    GS_CLEAR_STALE_ERROR();
+    if (!ts_shape_ok(num_items, num_segments, k)) return hipErrorInvalidValue;
+    if (!KT::type_ok(key_type)) return hipErrorInvalidValue;
+    if (d_vals_in && !d_vals_out) return hipErrorInvalidValue;
+    if (num_items == 0 || num_segments == 0 || k == 0) return hipSuccess;
+    const bool hv = d_vals_out != nullptr;
+    if (!d_keys_in || !d_keys_out || !d_begin_offsets || !d_end_offsets) return hipErrorInvalidValue;
+    if (!d_temp || temp_bytes < ts_temp_bytes(num_items, num_segments, k, hv)) return hipErrorInvalidValue;
+    if ((((uintptr_t)d_keys_in | (uintptr_t)d_keys_out) & (sizeof(T) - 1)) != 0) return hipErrorInvalidValue;
+    if ((((uintptr_t)d_vals_in | (uintptr_t)d_vals_out | (uintptr_t)d_counts_out | (uintptr_t)d_begin_offsets | (uintptr_t)d_end_offsets) & 3u) != 0)
+        return hipErrorInvalidValue;
+    {   // no array may share a byte with another, except that the two offset arrays (both only read) may: begin + 1 == end is usual
+        const size_t out_elems = (size_t)num_segments * k;
+        const void *arr[7] = {d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_counts_out, d_begin_offsets, d_end_offsets};
+        const size_t bytes[7] = {sizeof(T) * num_items, 4 * num_items, sizeof(T) * out_elems, 4 * out_elems, (size_t)4 * num_segments,
+                                 (size_t)4 * num_segments, (size_t)4 * num_segments};
+        for (int i = 0; i < 7; ++i)
+            for (int j = i + 1; j < 7; ++j)
+                if (!(i == 5 && j == 6) && gs_ranges_overlap(arr[i], bytes[i], arr[j], bytes[j])) return hipErrorInvalidValue;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t n = (uint32_t)num_items, kk = (uint32_t)k;
+    const int flt = KT::is_float(key_type);
+    const uint32_t x = KT::xor_of(key_type, descending);
+    TsWs ws;
+    ts_carve(gs_ws_base(d_temp), num_items, num_segments, k, hv, &ws);
+    const uint32_t groups = ts_groups(num_items);
+
+    hipError_t e = zero_async(ws.state, TS_STATE_BYTES, s);
+    if (e != hipSuccess) return (int)e;
+    { KernelTimer kt(GS_K_OTHER, s);
+      const uint32_t g = (num_segments + 1023u) / 1024u;
+      hipLaunchKernelGGL(topk_seg_classify_kernel, dim3(g < 4096u ? g : 4096u), dim3(256), 0, s, ws, d_begin_offsets, d_end_offsets, n, kk,
+                         d_counts_out); }
+    {
+        const uint32_t wg = (num_segments + 3u) / 4u, grid = wg < TS_MAX_GRID ? wg : TS_MAX_GRID;
+#define GS_TS_WAVE(W)                                                                                               \
+    do {                                                                                                            \
+        if (hv) ts_launch_wave<KT, W, true>(s, ws, grid, d_keys_in, d_vals_in, d_keys_out, d_vals_out, n, kk, flt, x); \
+        else ts_launch_wave<KT, W, false>(s, ws, grid, d_keys_in, d_vals_in, d_keys_out, d_vals_out, n, kk, flt, x);   \
+    } while (0)
+        GS_TS_WAVE(1); GS_TS_WAVE(4); GS_TS_WAVE(8); GS_TS_WAVE(16);
+#undef GS_TS_WAVE
+    }
+    if (groups & 2u) {
+#define GS_TS_SELECT(W)                                                                                                  \
+    do {                                                                                                                 \
+        if (hv) ts_launch_select<KT, W, true>(s, ws, groups, d_keys_in, d_vals_in, d_keys_out, d_vals_out, n, kk, flt, x); \
+        else ts_launch_select<KT, W, false>(s, ws, groups, d_keys_in, d_vals_in, d_keys_out, d_vals_out, n, kk, flt, x);   \
+    } while (0)
+        if (kk <= 64) GS_TS_SELECT(1);
+        else if (kk <= 256) GS_TS_SELECT(4);
+        else if (kk <= 512) GS_TS_SELECT(8);
+        else GS_TS_SELECT(16);
+#undef GS_TS_SELECT
+    }
+    return (int)hipGetLastError();
+}
+
+static int ts_plan(uint64_t num_items, uint32_t num_segments, uint64_t k, uint32_t out[8])
+{
+    if (!out) return hipErrorInvalidValue;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!ts_shape_ok(num_items, num_segments, k)) return hipErrorInvalidValue;
+    if (num_items == 0 || num_segments == 0 || k == 0) return hipSuccess;   // such a call enqueues nothing
+    const TsGeom g = ts_geom(num_items, num_segments);
+    out[0] = ts_groups(num_items); out[1] = ts_launches(out[0]); out[2] = TR_CH; out[3] = (uint32_t)g.lmax; out[4] = (uint32_t)g.tmax;
+    out[5] = TR_MAX_K;
+    return hipSuccess;
+}
+
+static int ts_status(void *d_temp, uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values, uint32_t out[8], void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (!out) return hipErrorInvalidValue;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!ts_shape_ok(num_items, num_segments, k)) return hipErrorInvalidValue;
+    if (num_items == 0 || num_segments == 0 || k == 0) return hipSuccess;   // such a call enqueued nothing
+    if (!d_temp) return hipErrorInvalidValue;
+    TsWs ws;
+    ts_carve(gs_ws_base(d_temp), num_items, num_segments, k, has_values != 0, &ws);
+    uint32_t st[16];
+    hipError_t e = hipMemcpyAsync(st, ws.state, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    for (int q = 0; q < 5; ++q) out[q] = st[q];
+    out[5] = st[TS_LONG_OK]; out[6] = st[TS_TASKS_OK]; out[7] = st[TS_DROPPED];
+    return hipSuccess;
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -541,6 +1096,31 @@ int gs_topk_rows_u16(void *d_temp, size_t temp_bytes, const uint16_t *d_keys_in,
 {
     return tr_run<TrKey16>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, num_rows, num_cols, row_stride, k, descending,
                            key_type, stream);
+}
+
+size_t gs_topk_segmented_temp_bytes(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values)
+{
+    return ts_temp_bytes(num_items, num_segments, k, has_values);
+}
+
+int gs_topk_segmented_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
+                          uint32_t *d_vals_out, uint32_t *d_counts_out, uint64_t num_items, uint32_t num_segments,
+                          const int32_t *d_begin_offsets, const int32_t *d_end_offsets, uint64_t k, int descending, int key_type, void *stream)
+{
+    return ts_run<TrKey32>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_counts_out, num_items, num_segments,
+                           d_begin_offsets, d_end_offsets, k, descending, key_type, stream);
+}
+
+int gs_topk_segmented_plan(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values, uint32_t out[8])
+{
+    (void)has_values;
+    return ts_plan(num_items, num_segments, k, out);
+}
+
+int gs_topk_segmented_status(void *d_temp, uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values, uint32_t out[8],
+                             void *stream)
+{
+    return ts_status(d_temp, num_items, num_segments, k, has_values, out, stream);
 }
 
 }  // extern "C"

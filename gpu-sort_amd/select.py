@@ -2,7 +2,8 @@
 
 DeviceTopK is two-phase like DeviceRadixSort (d_temp_storage=None returns the size); topk() is the convenience form that
 allocates outputs and workspace.  DeviceTopK16 is DeviceTopK for a flat array of 2-byte keys (gs_topk_u16: int16 / uint16 /
-float16 / bfloat16); topk() sends such tensors there.  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
+float16 / bfloat16); topk() sends such tensors there.  DeviceTopKSegmented / topk_segmented() are the same for every ragged segment given by device offsets
+(gs_topk_segmented_u32).  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
 gs_topk_rows_u16 for int16 / uint16 / float16 / bfloat16 keys, in the order of GS_KEY_F16 / BF16 at the enum).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
 (descending for the Max forms) on the same input: stable, keys in the caller's bit patterns, floats in the order of
 GS_KEY_F32 (negative NaNs first, positive NaNs last ascending; -0.0 before +0.0).
@@ -298,3 +299,138 @@ def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
         temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
     DeviceTopKRows._run(temp, nbytes, keys, keys_out, values, values_out, rows, cols, stride, k, largest, has_values, stream, None)
     return keys_out, values_out
+
+
+class DeviceTopKSegmented:
+    """MinKeys / MaxKeys / MinPairs / MaxPairs for every segment of a flat array (gs_topk_segmented_u32): segment s is
+    d_keys_in[d_begin_offsets[s] .. d_end_offsets[s]) (int32 offsets on the device, clamped to [0, num_items] there), and its
+    min(k, length) smallest (largest), sorted, go to d_keys_out[s * k ..) with their values; d_counts_out[s] (may be None) gets
+    that number, and the slots behind it are not written.
+
+    d_values_in=None in the pairs forms writes the elements' positions within their segment (u32 bit patterns).  Each
+    segment's result is what DeviceTopK gives for that segment alone.  Two-phase like DeviceTopKRows: d_temp_storage=None
+    returns the size, which is 0 for a shape the entry point refuses (k > MaxK(), num_items >= 2^31, ...).  32-bit keys."""
+
+    @staticmethod
+    def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, d_counts_out, num_items,
+             num_segments, d_begin_offsets, d_end_offsets, k, descending, has_values, stream, key_type):
+        need = lib.gs_topk_segmented_temp_bytes(num_items, num_segments, k, int(has_values))
+        if d_temp_storage is None:
+            return need
+        if not isinstance(d_keys_in, torch.Tensor) or d_keys_in.element_size() != 4:
+            raise TypeError("DeviceTopKSegmented: 32-bit keys only")
+        key_type = _key_type_of(d_keys_in, key_type)
+        _check_buf(d_keys_in, num_items, "d_keys_in")
+        _check_buf(d_keys_out, num_segments * k, "d_keys_out")
+        _check_buf(d_begin_offsets, num_segments, "d_begin_offsets")
+        _check_buf(d_end_offsets, num_segments, "d_end_offsets")
+        if d_counts_out is not None:
+            _check_buf(d_counts_out, num_segments, "d_counts_out")
+        if has_values:
+            if d_values_in is not None:
+                _check_buf(d_values_in, num_items, "d_values_in")
+            _check_buf(d_values_out, num_segments * k, "d_values_out")
+        err = lib.gs_topk_segmented_u32(C.c_void_p(d_temp_storage.data_ptr()),
+                                        min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                        d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
+                                        d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
+                                        d_counts_out.data_ptr() if d_counts_out is not None else None, num_items, num_segments,
+                                        d_begin_offsets.data_ptr(), d_end_offsets.data_ptr(), k, int(descending), key_type,
+                                        _stream_ptr(stream))
+        check(err, "gs_topk_segmented_u32")
+        return need
+
+    @staticmethod
+    def MinKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_counts_out, num_items, num_segments, d_begin_offsets,
+                d_end_offsets, k, stream=None, key_type=None):
+        return DeviceTopKSegmented._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, d_counts_out, num_items,
+                                        num_segments, d_begin_offsets, d_end_offsets, k, False, False, stream, key_type)
+
+    @staticmethod
+    def MaxKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_counts_out, num_items, num_segments, d_begin_offsets,
+                d_end_offsets, k, stream=None, key_type=None):
+        return DeviceTopKSegmented._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, d_counts_out, num_items,
+                                        num_segments, d_begin_offsets, d_end_offsets, k, True, False, stream, key_type)
+
+    @staticmethod
+    def MinPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, d_counts_out, num_items,
+                 num_segments, d_begin_offsets, d_end_offsets, k, stream=None, key_type=None):
+        return DeviceTopKSegmented._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out,
+                                        d_counts_out, num_items, num_segments, d_begin_offsets, d_end_offsets, k, False, True, stream,
+                                        key_type)
+
+    @staticmethod
+    def MaxPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, d_counts_out, num_items,
+                 num_segments, d_begin_offsets, d_end_offsets, k, stream=None, key_type=None):
+        return DeviceTopKSegmented._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out,
+                                        d_counts_out, num_items, num_segments, d_begin_offsets, d_end_offsets, k, True, True, stream,
+                                        key_type)
+
+    @staticmethod
+    def MaxK():
+        return int(lib.gs_topk_rows_max_k())
+
+    @staticmethod
+    def Plan(num_items, num_segments, k, has_values=False):
+        """gs_topk_segmented_plan: [launch groups (bit 0 wave, 1 workgroup, 2 long), kernel launches, CH, Lmax, Tmax, max k, 0,
+        0]; a pure host function.  Raises for a refused shape."""
+        out = (C.c_uint32 * 8)()
+        check(lib.gs_topk_segmented_plan(num_items, num_segments, k, int(has_values), out), "gs_topk_segmented_plan")
+        return [int(x) for x in out]
+
+    @staticmethod
+    def Status(d_temp_storage, num_items, num_segments, k, has_values, stream=None):
+        """gs_topk_segmented_status: [segments in the four wave lists, the workgroup list, the long list, chunk tasks, dropped
+        segments] of the last call on d_temp_storage.  Synchronises the stream."""
+        out = (C.c_uint32 * 8)()
+        check(lib.gs_topk_segmented_status(C.c_void_p(d_temp_storage.data_ptr()), num_items, num_segments, k, int(has_values), out,
+                                           _stream_ptr(stream)), "gs_topk_segmented_status")
+        return [int(x) for x in out]
+
+
+def topk_segmented(keys, offsets, k, largest=False, values=None, indices=False, stream=None, end_offsets=None):
+    """The k smallest (largest=True: largest) of every segment of the 1-D tensor `keys`, sorted, as (keys_out [S, k],
+    values_out [S, k] or None, counts [S] int32).
+
+    offsets: an int32 device tensor of S + 1 elements, segment s being keys[offsets[s] : offsets[s + 1]]; or, with end_offsets
+    given, the S begins, segment s being keys[offsets[s] : end_offsets[s]] (any order, gaps, repeats; see gs_topk_segmented_u32
+    for overlaps).  counts[s] = min(k, length of segment s); the slots of row s past counts[s] are unspecified.
+    values: a 4-byte tensor of the keys' length, carried with the keys.  indices=True (without values): values_out holds the
+    positions within the segment as int32 bit patterns of u32.  Neither: values_out is None.  Allocates outputs and workspace."""
+    if values is not None and indices:
+        raise ValueError("topk_segmented: give values or indices=True, not both")
+    if keys.dim() != 1 or keys.element_size() != 4:
+        raise TypeError("topk_segmented: a 1-D tensor of 32-bit keys")
+    if offsets.dtype != torch.int32 or (end_offsets is not None and end_offsets.dtype != torch.int32):
+        raise TypeError("topk_segmented: int32 offsets")
+    if end_offsets is None:
+        if offsets.numel() < 1:
+            raise ValueError("topk_segmented: offsets needs S + 1 elements")
+        begins, ends, segs = offsets[:-1], offsets[1:], offsets.numel() - 1
+    else:
+        if end_offsets.numel() != offsets.numel():
+            raise ValueError("topk_segmented: as many ends as begins")
+        begins, ends, segs = offsets, end_offsets, offsets.numel()
+    n = keys.numel()
+    if k < 0:
+        raise ValueError("topk_segmented: need k >= 0")
+    if values is not None and (values.numel() != n or values.element_size() != 4 or values.dim() != 1):
+        raise ValueError("topk_segmented: values must have the keys' length and 4-byte elements")
+    has_values = values is not None or indices
+    keys_out = torch.empty((segs, k), dtype=keys.dtype, device=keys.device)
+    values_out = None
+    if has_values:
+        values_out = torch.empty((segs, k), dtype=values.dtype if values is not None else torch.int32, device=keys.device)
+    counts = torch.zeros(segs, dtype=torch.int32, device=keys.device)
+    if k == 0 or segs == 0 or n == 0:
+        return keys_out, values_out, counts
+    nbytes = lib.gs_topk_segmented_temp_bytes(n, segs, k, int(has_values))
+    if nbytes == 0:
+        raise ValueError("topk_segmented: the entry point refuses this shape (k <= %d, fewer than 2^31 keys, segments * k below 2^32)"
+                         % lib.gs_topk_rows_max_k())
+    temp = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
+    if stream is not None:
+        temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
+    DeviceTopKSegmented._run(temp, nbytes, keys.contiguous(), keys_out, values, values_out, counts, n, segs, begins, ends, k, largest,
+                             has_values, stream, None)
+    return keys_out, values_out, counts

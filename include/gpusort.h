@@ -552,6 +552,78 @@ int      gs_topk_rows_u16(void *d_temp, size_t temp_bytes,
                           uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k,
                           int descending, int key_type, void *stream);
 
+/* ------------------------------------------------ top k of every ragged segment --
+ * The k best of every segment of a flat array, the segments given by device offsets (gs_topk_rows.hip, DESIGN.md section
+ * 10k): per-query candidate lists, variable-length sequences, per-image box scores, the neighbour lists of a CSR graph.
+ * The offsets are those of gs_segmented_sort_u32 (cub::DeviceSegmentedRadixSort).
+ * Segment s is d_keys_in[b .. e) with b = max(d_begin_offsets[s], 0) and e = min(d_end_offsets[s], num_items); it is empty
+ * when e <= b.  The clamping happens on the device.  With len = e - b and kept = min(k, len), d_keys_out[s * k .. s * k + kept)
+ * and the same range of d_vals_out are exactly what gs_topk_u32 writes for that sub-array alone with k = kept, bit for bit:
+ * the first kept of the stable sort on key_type's 32-bit image (GS_KEY_U32 / I32 / F32; complemented when descending), the
+ * lowest positions where the cut falls inside a run of equal keys, the caller's bit patterns kept (the NaN order of the
+ * GS_KEY_F32 note included).  d_counts_out[s] = kept (u32); the array may be NULL.  Output slots [s * k + kept, (s + 1) * k)
+ * are NOT written.
+ * Forms: keys only; pairs (d_vals_out gets d_vals_in[b + position]: d_vals_in is flat and indexed like the keys);
+ * arguments (d_vals_in == NULL, d_vals_out != NULL), where the value written is the element's position within its segment,
+ * counted from the clamped b, as u32 -- the column index of gs_topk_rows_u32.
+ * Segments may come in any order, leave gaps, repeat and, up to CH = 8192 elements each, overlap freely (the input is only
+ * read): a sliding window is a list of offsets.  The lengths of the segments LONGER than CH must together not exceed
+ * num_items, which holds whenever those segments do not overlap.  Where they do exceed it, a long segment that finds no
+ * room in the workspace is DROPPED: d_counts_out[s] = 0, nothing of it is written, and gs_topk_segmented_status counts it
+ * (the room is claimed from cursors that only grow: after one dropped segment, later long ones may be dropped as well).
+ * The contract is gs_topk_rows_u32's: plain pointers, inputs and offsets are never written, nothing is written outside
+ * [0, num_segments * k) of the outputs, [0, num_segments) of the counts and the workspace, d_temp anywhere, enqueue-only (no
+ * host read-back, allocation or synchronisation); the launches are a function of (num_items, num_segments, k, has_values)
+ * alone (gs_topk_segmented_plan reports them without a device), so the call may be captured into a HIP graph on one plain
+ * stream; calls may follow each other on one stream with one workspace; two runs give identical output bytes (the
+ * workspace bytes may differ: the lists are filled in device order).  num_items == 0, num_segments == 0 or k == 0 returns 0,
+ * writes nothing and needs no workspace (the query returns 0).
+ * Errors (hipErrorInvalidValue, checked before anything is enqueued, nothing written; the size query returns 0 for a
+ * refused shape): k > gs_topk_rows_max_k() (1024), num_items >= 2^31 (int offsets), num_segments * k >= 2^32, a key_type other
+ * than GS_KEY_U32 / I32 / F32, d_vals_in without d_vals_out, NULL keys or NULL offsets, a NULL or too-small workspace, an array
+ * not aligned to 4 bytes, arrays that share a byte (inputs at num_items elements, outputs at num_segments * k, the counts
+ * and the offsets at num_segments; the two offset arrays, both only read, may share bytes with each other, as in
+ * end = begin + 1).  k may exceed num_items or any segment's length: that is what kept is for.
+ * Launches: the state block is zeroed; a classify kernel writes every count and sorts the segments by length into six lists
+ * of records; four wave kernels take the segments of up to 64 / 256 / 512 / 1024 elements, one wave per segment (path 1 of
+ * gs_topk_rows_u32); one kernel takes those of up to CH, one workgroup per segment (path 2); longer segments take three
+ * launches: their (segment, chunk of CH) tasks are written, every task gives its first min(k, chunk length) as sorted
+ * (key, position) pairs to the segment's candidate row (level 0 of path 3), and ONE workgroup per segment streams that row
+ * with a running best k, CH - k new candidates per round.  The host leaves out only what the arguments exclude: no
+ * workgroup or long-segment launches when num_items <= 1024, no long-segment launches when num_items <= CH.
+ * Cost of a very long segment: its final is one workgroup's sequential rounds, ceil(len / CH) * k / (CH - k) of them (a
+ * row that fits one chunk, ceil(len / CH) * k <= CH, is one round); a caller with a few huge segments keeps gs_topk_u32.
+ * Workspace: a pure host function of its arguments, a multiple of 256, monotone in each of them.  With S = num_segments,
+ * n = num_items, Lmax = min(S, n / (CH + 1)), Tmax = n / CH + Lmax (0 when Lmax is 0), V = 2 with has_values else 1, a
+ * record of 16 bytes (base, length, segment, first task slot: four u32), a task of 8 bytes (record, chunk: two u32), and
+ * every term rounded up to 256 bytes:
+ *   4096                                      the state block: list counts, the long segments' claim, the dropped word
+ * + 5 * (16 * S)                              the four wave lists and the workgroup list, each sized for S records
+ * + 16 * Lmax                                 the long records
+ * + 8 * Tmax                                  the chunk tasks
+ * + V * (4 * k * Tmax)                        the candidate rows: images (and positions), k per task slot
+ * + 256 bytes of alignment slack.
+ * The long-segment areas vanish when n <= CH (Lmax = Tmax = 0).                                                           */
+size_t gs_topk_segmented_temp_bytes(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values);
+int    gs_topk_segmented_u32(void *d_temp, size_t temp_bytes,
+                             const uint32_t *d_keys_in, const uint32_t *d_vals_in,
+                             uint32_t *d_keys_out, uint32_t *d_vals_out, uint32_t *d_counts_out,
+                             uint64_t num_items, uint32_t num_segments,
+                             const int32_t *d_begin_offsets, const int32_t *d_end_offsets,
+                             uint64_t k, int descending, int key_type, void *stream);
+/* What gs_topk_segmented_u32 launches for a shape: a pure host function (no device, no workspace, no synchronisation).
+ * out[0] = bit mask of the launch groups the call enqueues (bit 0 the wave kernels, bit 1 the workgroup kernel, bit 2 the
+ * long-segment kernels), out[1] = kernel launches (6, 7 or 10: the zeroing and the classify kernel included), out[2] = CH,
+ * out[3] = Lmax, out[4] = Tmax, out[5] = gs_topk_rows_max_k(), out[6..7] = 0.  A refused shape (k > max k, num_items >= 2^31,
+ * num_segments * k >= 2^32) returns hipErrorInvalidValue and all zeros; a no-op shape returns 0 and all zeros.              */
+int    gs_topk_segmented_plan(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values, uint32_t out[8]);
+/* What the last gs_topk_segmented_u32 on d_temp (same num_items, num_segments, k and has_values) decided, after
+ * synchronising `stream`: out[0..3] = segments in the four wave lists (<= 64, <= 256, <= 512, <= 1024 elements), out[4] =
+ * the workgroup list (1025 .. CH), out[5] = the long list (> CH, dropped ones not counted), out[6] = chunk tasks, out[7] =
+ * dropped segments.  All zeros for a no-op shape.  Diagnostic: tests and benches read it.                                   */
+int    gs_topk_segmented_status(void *d_temp, uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values,
+                                uint32_t out[8], void *stream);
+
 /* Census of the last gs_msb_sort_u32 that used d_temp (read back after synchronising `stream`): what every level
  * partitioned and what it handed to local sorts.  SURVEY.md 8d: the MSB path's algorithmic bytes are data-dependent --
  * "the harness must log the per-pass census and compute bytes from it": level 0 moves every key once (12 B/key), a level
