@@ -66,7 +66,7 @@ def make_keys(n, kind):
         pref = torch.randint(0, 1 << 16, (P,), device=dev, generator=g)
         which = torch.randint(0, P, (n,), device=dev, generator=g)
         which[torch.rand(n, device=dev, generator=g) < 0.15] = 0
-        D = int(rng.choice([1, 2, 7, 100, 255, 256, 1000, 2047, 2048, 2049, 5000]))
+        D = int(rng.choice([1, 2, 7, 100, 255, 256, 512, 513, 1000, 1024, 1025, 2047, 2048, 2049, 5000]))
         tail = (torch.randint(0, D, (n,), device=dev, generator=g) * 40503 + which * 977) & 0xFFFF
         k = ((pref[which] << 16) | tail).to(torch.int64)
         k = torch.where(k >= 2**31, k - 2**32, k).to(torch.int32)
