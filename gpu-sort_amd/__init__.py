@@ -12,7 +12,7 @@ Names follow the reference:
   DeviceTopK, topk              (the first k elements of the stable sort, by radix select; no reference counterpart)
   DeviceTopK16                  (DeviceTopK for a flat array of int16 / uint16 / float16 / bfloat16 keys; topk() routes them)
   DeviceTopKRows, topk_rows     (the same for every row of a matrix; 32-bit keys, and int16 / uint16 / float16 / bfloat16)
-  DeviceTopKSegmented, topk_segmented   (the same for every ragged segment given by device offsets; 32-bit keys)
+  DeviceTopKSegmented, topk_segmented   (the same for every ragged segment given by device offsets; 32-bit keys, and int16 / uint16 / float16 / bfloat16)
   sortKeysGPU / sortPairsGPU    (lsb/sort.cu:25-76)
   rdxsrt_unstable_sort, rdxsrt_unstable_sort_keys/_pairs, RDXSRT_SortedSequence
                                 (msb/src/sort/gpu_radix_sort.h:31-34,197,511,544)

@@ -1,8 +1,9 @@
 // gs_topk_rows.hip -- gs_topk_rows_u32 and gs_topk_rows_u16: the first k of the stable sort of every row of a matrix, for
 // 32-bit keys and 16-bit keys (section 10i).  One set of kernels and one host path, instantiated
 // over a key-traits type (TrKey32, TrKey16); one geometry and one plan, so gs_topk_rows_plan answers for both entry points.
-// gs_topk_segmented_u32 (section 10k), the same for ragged segments given by device offsets, follows them: it runs the same
-// device functions per record of lists that a classify kernel fills (see "ragged segments" below).
+// gs_topk_segmented_u32 (section 10k) and gs_topk_segmented_u16 (section 10l), the same for ragged segments given by device
+// offsets, follow them: they run the same device functions per record of lists that a classify kernel fills (see "ragged
+// segments" below), instantiated over the same two key-traits types.
 //
 // Row r of the result is what gs_topk_u32 writes for row r alone, bit for bit.  Every row has the same length, so the
 // launches are decided on the host from num_cols and k:
@@ -510,7 +511,7 @@ static int tr_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_
 }
 
 // ------------------------------------------------------------ ragged segments --
-// gs_topk_segmented_u32: the k best of every segment of a flat array, the segments given by device
+// gs_topk_segmented_u32 / _u16 (DESIGN.md sections 10k, 10l): the k best of every segment of a flat array, the segments given by device
 // offsets.  The lengths are on the device, so a classify kernel sorts the segments into six lists of records by length and
 // the kernels above run per record: the four wave classes of path 1 (<= 64 / 256 / 512 / 1024 elements), the workgroup of
 // path 2 (<= CH), and for longer segments level 0 of path 3 per (record, chunk) task followed by ONE streaming final per
@@ -534,7 +535,8 @@ struct TsWs {
     uint32_t *state;
     TsRec *list[6];
     TsTask *tasks;
-    uint32_t *cand_k, *cand_p;   // candidate rows: images, and (with values) positions within the segment
+    void *cand_k;                // candidate rows: images, as wide as the key (KT::T), and
+    uint32_t *cand_p;            // (with values) positions within the segment
     uint32_t nseg, lmax, tmax;
 };
 
@@ -695,7 +697,8 @@ __global__ __launch_bounds__(256) void topk_seg_wave_kernel(TsWs ws, const typen
 // topk_rows_block_kernel's body per record of the block list, or (CHUNK) per (record, chunk) task of the long list.  The
 // block list's results go to the caller's outputs at seg * k; a chunk's min(k, chunk length) sorted (image, position in the
 // segment) pairs go to slot row + chunk of the candidate area (every chunk but the last gives k, so the segment's candidate
-// row is dense).  Candidate rows hold images: the final reads them as they are.
+// row is dense).  Candidate rows hold images, stored KT::T wide (the image of a 16-bit key has a zero upper half): the final
+// widens them back into the register.
 template <typename KT, int WKPT, bool HV, bool CHUNK>
 __global__ __launch_bounds__(TR_THREADS) void topk_seg_block_kernel(TsWs ws, const typename KT::T *__restrict__ keys,
                                                                     const uint32_t *__restrict__ vals_in,
@@ -725,7 +728,8 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_block_kernel(TsWs ws, con
     }
     const TsRec *const recs = ts_in_vgprs(ws.list[CHUNK ? TS_LONG : TS_BLOCK]);
     const TsTask *const tasks = ts_in_vgprs(ws.tasks);
-    uint32_t *const dst_ck = ts_in_vgprs(ws.cand_k), *const dst_cp = ts_in_vgprs(ws.cand_p);
+    T *const dst_ck = ts_in_vgprs((T *)ws.cand_k);
+    uint32_t *const dst_cp = ts_in_vgprs(ws.cand_p);
     const uint32_t *const vin = ts_in_vgprs(vals_in);
     T *const kout = ts_in_vgprs(keys_out);
     uint32_t *const vout = ts_in_vgprs(vals_out);
@@ -751,6 +755,10 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_block_kernel(TsWs ws, con
         }
 #pragma unroll
         for (int u = 0; u < TR_KPT; ++u) img[u] = KT::in(img[u], flt, x);
+        // where the result goes, and the segment the values come from: for the stores at the end.  The 16-bit kernels with
+        // values are two scalar registers short across the select; the 32-bit ones are not, and keep the code they had.
+        uint32_t slot = CHUNK ? row + c : seg, vbase = base, vlen = slen;
+        if (sizeof(T) == 2) { slot = ts_in_vgpr(slot); vbase = ts_in_vgpr(vbase); vlen = ts_in_vgpr(vlen); }
 
         uint32_t less;
         const uint32_t kth = tr_select<KT::BITS>(img, first, len, keff, tid, h, scratch, sel, less);
@@ -765,17 +773,17 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_block_kernel(TsWs ws, con
                 if (HV) val[i] = idx < keff ? stage_v[idx] : 0u;
             }
             wave_sort_bits<KT::BITS, WKPT, HV>(key, val, h, sort_k, sort_v);
-            const size_t out0 = CHUNK ? (size_t)(row + c) * k : (size_t)seg * k;
+            const size_t out0 = (size_t)slot * k;
 #pragma unroll
             for (int i = 0; i < WKPT; ++i) {
                 const uint32_t idx = (uint32_t)i * WAVE + lane;
                 if (idx < keff) {
                     if (CHUNK) {
-                        dst_ck[out0 + idx] = key[i];
+                        dst_ck[out0 + idx] = (T)key[i];
                         if (HV) dst_cp[out0 + idx] = val[i];
                     } else {
                         kout[out0 + idx] = (T)KT::out(key[i], flt, x);
-                        if (HV) vout[out0 + idx] = vin ? vin[(size_t)base + (val[i] < slen ? val[i] : slen - 1u)] : val[i];
+                        if (HV) vout[out0 + idx] = vin ? vin[(size_t)vbase + (val[i] < vlen ? val[i] : vlen - 1u)] : val[i];
                     }
                 }
             }
@@ -820,7 +828,8 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_final_kernel(TsWs ws, con
     uint32_t nrec = ws.state[TS_REC_CUR];
     if (nrec > ws.lmax) nrec = ws.lmax;
     const TsRec *const recs = ts_in_vgprs(ws.list[TS_LONG]);
-    const uint32_t *const src_ck = ts_in_vgprs(ws.cand_k), *const src_cp = ts_in_vgprs(ws.cand_p);
+    const T *const src_ck = ts_in_vgprs((const T *)ws.cand_k);
+    const uint32_t *const src_cp = ts_in_vgprs(ws.cand_p);
     const uint32_t *const vin = ts_in_vgprs(vals_in);
     T *const kout = ts_in_vgprs(keys_out);
     uint32_t *const vout = ts_in_vgprs(vals_out);
@@ -831,7 +840,8 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_final_kernel(TsWs ws, con
         const uint32_t chunks = (slen + TR_CH - 1u) / TR_CH, tail = slen - (chunks - 1u) * TR_CH;
         if (__builtin_amdgcn_readfirstlane(row >= tmax || chunks > tmax - row)) continue;
         const uint32_t n1 = (chunks - 1u) * k + (k < tail ? k : tail);      // next(len): the candidates the chunks left
-        const uint32_t *ck = src_ck + (size_t)row * k, *cp = src_cp + (size_t)row * k;
+        const T *ck = src_ck + (size_t)row * k;
+        const uint32_t *cp = src_cp + (size_t)row * k;
         base = ts_in_vgpr(base); slen = ts_in_vgpr(slen); seg = ts_in_vgpr(seg);   // for the stores at the end
         uint32_t kc = 0, pos = 0;
         do {
@@ -845,7 +855,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_final_kernel(TsWs ws, con
                     img[u] = stage_k[j];
                     if (HV) val[u] = stage_v[j];
                 } else if (j < len) {
-                    img[u] = __builtin_nontemporal_load(ck + pos + (j - kc));
+                    img[u] = (uint32_t)__builtin_nontemporal_load(ck + pos + (j - kc));
                     if (HV) val[u] = __builtin_nontemporal_load(cp + pos + (j - kc));
                 } else {
                     img[u] = 0u;
@@ -900,8 +910,9 @@ static inline TsGeom ts_geom(uint64_t num_items, uint64_t num_segments)
     return g;
 }
 
-// the carve and the size query in one walk (base may be null: the query)
-static size_t ts_carve(char *base, uint64_t num_items, uint64_t num_segments, uint64_t k, bool hv, TsWs *ws)
+// the carve and the size query in one walk (base may be null: the query).  key_bytes: the width of a candidate image, the
+// only term that depends on the key; the state block comes first at both widths, so ts_status reads either workspace.
+static size_t ts_carve(char *base, uint64_t num_items, uint64_t num_segments, uint64_t k, bool hv, size_t key_bytes, TsWs *ws)
 {
     const TsGeom g = ts_geom(num_items, num_segments);
     size_t off = 0;
@@ -911,19 +922,19 @@ static size_t ts_carve(char *base, uint64_t num_items, uint64_t num_segments, ui
     for (int q = 0; q < 5; ++q) w.list[q] = (TsRec *)take(sizeof(TsRec) * num_segments);
     w.list[TS_LONG] = (TsRec *)take(sizeof(TsRec) * g.lmax);
     w.tasks = (TsTask *)take(sizeof(TsTask) * g.tmax);
-    w.cand_k = (uint32_t *)take((size_t)4 * k * g.tmax);
-    w.cand_p = w.cand_k;
+    w.cand_k = take(key_bytes * k * g.tmax);
+    w.cand_p = (uint32_t *)w.cand_k;   // (never read without values)
     if (hv) w.cand_p = (uint32_t *)take((size_t)4 * k * g.tmax);
     w.nseg = (uint32_t)num_segments; w.lmax = (uint32_t)g.lmax; w.tmax = (uint32_t)g.tmax;
     if (ws) *ws = w;
     return off;
 }
 
-static size_t ts_temp_bytes(uint64_t num_items, uint64_t num_segments, uint64_t k, int has_values)
+static size_t ts_temp_bytes(uint64_t num_items, uint64_t num_segments, uint64_t k, int has_values, size_t key_bytes)
 {
     if (!ts_shape_ok(num_items, num_segments, k)) return 0;
     if (num_items == 0 || num_segments == 0 || k == 0) return 0;
-    return ts_carve(nullptr, num_items, num_segments, k, has_values != 0, nullptr) + GS_WS_SLACK;
+    return ts_carve(nullptr, num_items, num_segments, k, has_values != 0, key_bytes, nullptr) + GS_WS_SLACK;
 }
 
 // the launch groups of a shape: bit 0 wave, bit 1 block, bit 2 long
@@ -968,7 +979,7 @@ static int ts_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_
     if (num_items == 0 || num_segments == 0 || k == 0) return hipSuccess;
     const bool hv = d_vals_out != nullptr;
     if (!d_keys_in || !d_keys_out || !d_begin_offsets || !d_end_offsets) return hipErrorInvalidValue;
-    if (!d_temp || temp_bytes < ts_temp_bytes(num_items, num_segments, k, hv)) return hipErrorInvalidValue;
+    if (!d_temp || temp_bytes < ts_temp_bytes(num_items, num_segments, k, hv, sizeof(T))) return hipErrorInvalidValue;
     if ((((uintptr_t)d_keys_in | (uintptr_t)d_keys_out) & (sizeof(T) - 1)) != 0) return hipErrorInvalidValue;
     if ((((uintptr_t)d_vals_in | (uintptr_t)d_vals_out | (uintptr_t)d_counts_out | (uintptr_t)d_begin_offsets | (uintptr_t)d_end_offsets) & 3u) != 0)
         return hipErrorInvalidValue;
@@ -986,7 +997,7 @@ static int ts_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_
     const int flt = KT::is_float(key_type);
     const uint32_t x = KT::xor_of(key_type, descending);
     TsWs ws;
-    ts_carve(gs_ws_base(d_temp), num_items, num_segments, k, hv, &ws);
+    ts_carve(gs_ws_base(d_temp), num_items, num_segments, k, hv, sizeof(T), &ws);
     const uint32_t groups = ts_groups(num_items);
 
     hipError_t e = zero_async(ws.state, TS_STATE_BYTES, s);
@@ -1041,7 +1052,7 @@ static int ts_status(void *d_temp, uint64_t num_items, uint32_t num_segments, ui
     if (num_items == 0 || num_segments == 0 || k == 0) return hipSuccess;   // such a call enqueued nothing
     if (!d_temp) return hipErrorInvalidValue;
     TsWs ws;
-    ts_carve(gs_ws_base(d_temp), num_items, num_segments, k, has_values != 0, &ws);
+    ts_carve(gs_ws_base(d_temp), num_items, num_segments, k, has_values != 0, 4, &ws);   // (only the state block, the first term, is read)
     uint32_t st[16];
     hipError_t e = hipMemcpyAsync(st, ws.state, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
@@ -1100,7 +1111,12 @@ int gs_topk_rows_u16(void *d_temp, size_t temp_bytes, const uint16_t *d_keys_in,
 
 size_t gs_topk_segmented_temp_bytes(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values)
 {
-    return ts_temp_bytes(num_items, num_segments, k, has_values);
+    return ts_temp_bytes(num_items, num_segments, k, has_values, 4);
+}
+
+size_t gs_topk_segmented_u16_temp_bytes(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values)
+{
+    return ts_temp_bytes(num_items, num_segments, k, has_values, 2);
 }
 
 int gs_topk_segmented_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
@@ -1108,6 +1124,14 @@ int gs_topk_segmented_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_key
                           const int32_t *d_begin_offsets, const int32_t *d_end_offsets, uint64_t k, int descending, int key_type, void *stream)
 {
     return ts_run<TrKey32>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_counts_out, num_items, num_segments,
+                           d_begin_offsets, d_end_offsets, k, descending, key_type, stream);
+}
+
+int gs_topk_segmented_u16(void *d_temp, size_t temp_bytes, const uint16_t *d_keys_in, const uint32_t *d_vals_in, uint16_t *d_keys_out,
+                          uint32_t *d_vals_out, uint32_t *d_counts_out, uint64_t num_items, uint32_t num_segments,
+                          const int32_t *d_begin_offsets, const int32_t *d_end_offsets, uint64_t k, int descending, int key_type, void *stream)
+{
+    return ts_run<TrKey16>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_counts_out, num_items, num_segments,
                            d_begin_offsets, d_end_offsets, k, descending, key_type, stream);
 }
 

@@ -3,7 +3,7 @@
 DeviceTopK is two-phase like DeviceRadixSort (d_temp_storage=None returns the size); topk() is the convenience form that
 allocates outputs and workspace.  DeviceTopK16 is DeviceTopK for a flat array of 2-byte keys (gs_topk_u16: int16 / uint16 /
 float16 / bfloat16); topk() sends such tensors there.  DeviceTopKSegmented / topk_segmented() are the same for every ragged segment given by device offsets
-(gs_topk_segmented_u32).  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
+(gs_topk_segmented_u32, and gs_topk_segmented_u16 for int16 / uint16 / float16 / bfloat16 keys).  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
 gs_topk_rows_u16 for int16 / uint16 / float16 / bfloat16 keys, in the order of GS_KEY_F16 / BF16 at the enum).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
 (descending for the Max forms) on the same input: stable, keys in the caller's bit patterns, floats in the order of
 GS_KEY_F32 (negative NaNs first, positive NaNs last ascending; -0.0 before +0.0).
@@ -301,6 +301,14 @@ def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
     return keys_out, values_out
 
 
+# the same table for the ragged segments
+_SEG_BY_WIDTH = {
+    32: ("gs_topk_segmented_u32", "gs_topk_segmented_temp_bytes", _key_type_of, 4),
+    16: ("gs_topk_segmented_u16", "gs_topk_segmented_u16_temp_bytes",
+         lambda t, key_type: _key_type16_of(t, key_type, "DeviceTopKSegmented"), 2),
+}
+
+
 class DeviceTopKSegmented:
     """MinKeys / MaxKeys / MinPairs / MaxPairs for every segment of a flat array (gs_topk_segmented_u32): segment s is
     d_keys_in[d_begin_offsets[s] .. d_end_offsets[s]) (int32 offsets on the device, clamped to [0, num_items] there), and its
@@ -309,19 +317,29 @@ class DeviceTopKSegmented:
 
     d_values_in=None in the pairs forms writes the elements' positions within their segment (u32 bit patterns).  Each
     segment's result is what DeviceTopK gives for that segment alone.  Two-phase like DeviceTopKRows: d_temp_storage=None
-    returns the size, which is 0 for a shape the entry point refuses (k > MaxK(), num_items >= 2^31, ...).  32-bit keys."""
+    returns the size, which is 0 for a shape the entry point refuses (k > MaxK(), num_items >= 2^31, ...).
+
+    2-byte key tensors (int16, uint16, float16, bfloat16, or an explicit 16-bit key_type) go to gs_topk_segmented_u16: the same
+    definition on the 16-bit image, values, counts and offsets still 4 bytes.  The size query (d_temp_storage=None) sees no
+    tensor: with a 16-bit key_type it answers for gs_topk_segmented_u16, without one for gs_topk_segmented_u32, which is never
+    the smaller of the two.  Plan() and Status() serve both widths."""
 
     @staticmethod
     def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, d_counts_out, num_items,
              num_segments, d_begin_offsets, d_end_offsets, k, descending, has_values, stream, key_type):
-        need = lib.gs_topk_segmented_temp_bytes(num_items, num_segments, k, int(has_values))
+        if d_temp_storage is None or key_type is not None:
+            narrow = key_type in _NARROW16
+        else:
+            narrow = isinstance(d_keys_in, torch.Tensor) and d_keys_in.element_size() == 2
+        entry, size_query, resolve, elem = _SEG_BY_WIDTH[16 if narrow else 32]
+        need = getattr(lib, size_query)(num_items, num_segments, k, int(has_values))
         if d_temp_storage is None:
             return need
-        if not isinstance(d_keys_in, torch.Tensor) or d_keys_in.element_size() != 4:
-            raise TypeError("DeviceTopKSegmented: 32-bit keys only")
-        key_type = _key_type_of(d_keys_in, key_type)
-        _check_buf(d_keys_in, num_items, "d_keys_in")
-        _check_buf(d_keys_out, num_segments * k, "d_keys_out")
+        if not isinstance(d_keys_in, torch.Tensor) or d_keys_in.element_size() != elem:
+            raise TypeError("DeviceTopKSegmented: 32-bit keys, or 2-byte keys with a 16-bit key type")
+        key_type = resolve(d_keys_in, key_type)
+        _check_buf(d_keys_in, num_items, "d_keys_in", elem)
+        _check_buf(d_keys_out, num_segments * k, "d_keys_out", elem)
         _check_buf(d_begin_offsets, num_segments, "d_begin_offsets")
         _check_buf(d_end_offsets, num_segments, "d_end_offsets")
         if d_counts_out is not None:
@@ -330,14 +348,14 @@ class DeviceTopKSegmented:
             if d_values_in is not None:
                 _check_buf(d_values_in, num_items, "d_values_in")
             _check_buf(d_values_out, num_segments * k, "d_values_out")
-        err = lib.gs_topk_segmented_u32(C.c_void_p(d_temp_storage.data_ptr()),
-                                        min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
-                                        d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
-                                        d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
-                                        d_counts_out.data_ptr() if d_counts_out is not None else None, num_items, num_segments,
-                                        d_begin_offsets.data_ptr(), d_end_offsets.data_ptr(), k, int(descending), key_type,
-                                        _stream_ptr(stream))
-        check(err, "gs_topk_segmented_u32")
+        err = getattr(lib, entry)(C.c_void_p(d_temp_storage.data_ptr()),
+                                  min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                  d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
+                                  d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
+                                  d_counts_out.data_ptr() if d_counts_out is not None else None, num_items, num_segments,
+                                  d_begin_offsets.data_ptr(), d_end_offsets.data_ptr(), k, int(descending), key_type,
+                                  _stream_ptr(stream))
+        check(err, entry)
         return need
 
     @staticmethod
@@ -396,11 +414,15 @@ def topk_segmented(keys, offsets, k, largest=False, values=None, indices=False, 
     given, the S begins, segment s being keys[offsets[s] : end_offsets[s]] (any order, gaps, repeats; see gs_topk_segmented_u32
     for overlaps).  counts[s] = min(k, length of segment s); the slots of row s past counts[s] are unspecified.
     values: a 4-byte tensor of the keys' length, carried with the keys.  indices=True (without values): values_out holds the
-    positions within the segment as int32 bit patterns of u32.  Neither: values_out is None.  Allocates outputs and workspace."""
+    positions within the segment as int32 bit patterns of u32.  Neither: values_out is None.  Allocates outputs and workspace.
+    2-byte keys (int16, uint16, float16, bfloat16) take gs_topk_segmented_u16 and come back in the input dtype."""
     if values is not None and indices:
         raise ValueError("topk_segmented: give values or indices=True, not both")
-    if keys.dim() != 1 or keys.element_size() != 4:
-        raise TypeError("topk_segmented: a 1-D tensor of 32-bit keys")
+    if keys.dim() != 1 or keys.element_size() not in (2, 4):
+        raise TypeError("topk_segmented: a 1-D tensor of 32-bit or 16-bit keys")
+    narrow = keys.element_size() == 2
+    if narrow:
+        _key_type16_of(keys, None, "topk_segmented")
     if offsets.dtype != torch.int32 or (end_offsets is not None and end_offsets.dtype != torch.int32):
         raise TypeError("topk_segmented: int32 offsets")
     if end_offsets is None:
@@ -424,7 +446,7 @@ def topk_segmented(keys, offsets, k, largest=False, values=None, indices=False, 
     counts = torch.zeros(segs, dtype=torch.int32, device=keys.device)
     if k == 0 or segs == 0 or n == 0:
         return keys_out, values_out, counts
-    nbytes = lib.gs_topk_segmented_temp_bytes(n, segs, k, int(has_values))
+    nbytes = getattr(lib, _SEG_BY_WIDTH[16 if narrow else 32][1])(n, segs, k, int(has_values))
     if nbytes == 0:
         raise ValueError("topk_segmented: the entry point refuses this shape (k <= %d, fewer than 2^31 keys, segments * k below 2^32)"
                          % lib.gs_topk_rows_max_k())

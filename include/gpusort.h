@@ -611,18 +611,57 @@ int    gs_topk_segmented_u32(void *d_temp, size_t temp_bytes,
                              uint64_t num_items, uint32_t num_segments,
                              const int32_t *d_begin_offsets, const int32_t *d_end_offsets,
                              uint64_t k, int descending, int key_type, void *stream);
-/* What gs_topk_segmented_u32 launches for a shape: a pure host function (no device, no workspace, no synchronisation).
+/* What gs_topk_segmented_u32 -- and gs_topk_segmented_u16 below, which has the same geometry -- launches for a shape: a pure
+ * host function (no device, no workspace, no synchronisation).
  * out[0] = bit mask of the launch groups the call enqueues (bit 0 the wave kernels, bit 1 the workgroup kernel, bit 2 the
  * long-segment kernels), out[1] = kernel launches (6, 7 or 10: the zeroing and the classify kernel included), out[2] = CH,
  * out[3] = Lmax, out[4] = Tmax, out[5] = gs_topk_rows_max_k(), out[6..7] = 0.  A refused shape (k > max k, num_items >= 2^31,
  * num_segments * k >= 2^32) returns hipErrorInvalidValue and all zeros; a no-op shape returns 0 and all zeros.              */
 int    gs_topk_segmented_plan(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values, uint32_t out[8]);
-/* What the last gs_topk_segmented_u32 on d_temp (same num_items, num_segments, k and has_values) decided, after
+/* What the last gs_topk_segmented_u32 or gs_topk_segmented_u16 on d_temp (same num_items, num_segments, k and has_values)
+ * decided (the state block is the first term of both workspaces, so a workspace of either entry point is read as it is), after
  * synchronising `stream`: out[0..3] = segments in the four wave lists (<= 64, <= 256, <= 512, <= 1024 elements), out[4] =
  * the workgroup list (1025 .. CH), out[5] = the long list (> CH, dropped ones not counted), out[6] = chunk tasks, out[7] =
  * dropped segments.  All zeros for a no-op shape.  Diagnostic: tests and benches read it.                                   */
 int    gs_topk_segmented_status(void *d_temp, uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values,
                                 uint32_t out[8], void *stream);
+
+/* -------------------------------- top k of every ragged segment, 16-bit keys --
+ * gs_topk_segmented_u32 for 16-bit keys, its kernels instantiated for them (gs_topk_rows.hip): bfloat16 or
+ * half candidate scores, logits of variable-length sequences, box scores, CSR weights, without widening them.  key_type is
+ * GS_KEY_U16, GS_KEY_I16, GS_KEY_F16 or GS_KEY_BF16, in the order stated at the enum for gs_lsb_sort_narrow (GS_KEY_F32's map
+ * at width 16: negative NaNs first, positive NaNs last, -0 before +0; the image complemented at 16 bits when descending).
+ * With b, e, len and kept = min(k, len) as at gs_topk_segmented_u32, d_keys_out[s * k .. s * k + kept) and the same range of
+ * d_vals_out are bit for bit what gs_topk_u16 writes for d_keys_in[b .. e) alone with k = kept; d_counts_out[s] = kept; the
+ * slots behind are NOT written.  Equivalently it is what gs_topk_segmented_u32 gives on (uint32_t)key << 16 with the key type
+ * widened (U16 -> U32, I16 -> I32, F16 / BF16 -> F32) and the returned keys shifted right by 16, values and positions
+ * unchanged.  Forms: keys only; pairs; arguments (d_vals_in == NULL, d_vals_out != NULL: the u32 position within the clamped
+ * segment).
+ * The contract is gs_topk_segmented_u32's, word for word, with 2-byte keys: the key arrays need 2-byte alignment, any even
+ * address is served like any other and a segment may start at any element (every key is read and written with one 2-byte
+ * access); the overlap checks count 2 bytes per key; values, counts and offsets stay u32 / int32, aligned to 4.  Unchanged:
+ * the limits (k <= gs_topk_rows_max_k(), num_items < 2^31, num_segments * k < 2^32), the order of the checks, refused calls
+ * write nothing and their size query is 0, no-op shapes return 0 with a size query of 0, segments of up to CH = 8192 elements
+ * may overlap freely, the drop rule for long segments that find no room, enqueue-only and graph-capturable on one plain
+ * stream, identical output bytes on two runs.
+ * Geometry: gs_topk_segmented_u32's, on purpose -- six lists, CH = 8192, the same Lmax and Tmax, the same 6 / 7 / 10 launches
+ * for a shape -- so gs_topk_segmented_plan above answers for both entry points, and gs_topk_segmented_status reads the state
+ * of a workspace of this one as it is (the state block is the first term of both workspaces).
+ * Workspace: a pure host function of its arguments, a multiple of 256, monotone in each of them.  The candidate rows hold
+ * 16-bit images and u32 positions.  With S, Lmax and Tmax as in gs_topk_segmented_temp_bytes, hv = 1 with has_values else 0,
+ * and every term rounded up to 256 bytes:
+ *   4096 + 5 * (16 * S) + 16 * Lmax + 8 * Tmax  the state block, the lists, the long records and the chunk tasks
+ * + 2 * k * Tmax                              the candidate images, 16 bits wide
+ * + hv * 4 * k * Tmax                         their positions
+ * + 256 bytes of alignment slack.
+ * The long-segment terms vanish when num_items <= CH.  Never more than gs_topk_segmented_temp_bytes of the same arguments.  */
+size_t gs_topk_segmented_u16_temp_bytes(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values);
+int    gs_topk_segmented_u16(void *d_temp, size_t temp_bytes,
+                             const uint16_t *d_keys_in, const uint32_t *d_vals_in,
+                             uint16_t *d_keys_out, uint32_t *d_vals_out, uint32_t *d_counts_out,
+                             uint64_t num_items, uint32_t num_segments,
+                             const int32_t *d_begin_offsets, const int32_t *d_end_offsets,
+                             uint64_t k, int descending, int key_type, void *stream);
 
 /* Census of the last gs_msb_sort_u32 that used d_temp (read back after synchronising `stream`): what every level
  * partitioned and what it handed to local sorts.  SURVEY.md 8d: the MSB path's algorithmic bytes are data-dependent --

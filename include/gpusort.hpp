@@ -363,7 +363,8 @@ struct DeviceTopKRows {
 // for that segment alone -- go to d_keys_out[s * k ..) and the same range of d_values_out, and d_counts_out[s] (may be nullptr)
 // gets that number; the slots behind it are not written.  The forms and the two phases are DeviceTopKRows'; in the pairs forms
 // d_values_in == nullptr writes the elements' positions within their segment.  A size query of 0 with a non-empty shape means
-// the shape is refused (k > gs_topk_rows_max_k(), num_items >= 2^31, ...).  32-bit keys.
+// the shape is refused (k > gs_topk_rows_max_k(), num_items >= 2^31, ...).  32-bit keys (gs_topk_segmented_u32) or 16-bit keys
+// (unsigned short, short, _Float16, __half, __hip_bfloat16: gs_topk_segmented_u16), chosen by sizeof(KeyT); values stay 32-bit.
 struct DeviceTopKSegmented {
     template <typename KeyT, typename ValueT>
     static hipError_t Dispatch(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
@@ -371,18 +372,34 @@ struct DeviceTopKSegmented {
                                uint32_t num_segments, const int *d_begin_offsets, const int *d_end_offsets, uint64_t k,
                                bool descending, hipStream_t stream)
     {
-        static_assert(sizeof(KeyT) == 4 && KeyTraits<KeyT>::type <= GS_KEY_F32, "unsigned int, int or float keys");
+        static_assert(sizeof(KeyT) == 4 || sizeof(KeyT) == 2,
+                      "32-bit keys (unsigned int, int, float) or 16-bit keys (unsigned short, short, half, bfloat16)");
         static_assert(sizeof(ValueT) == 4, "32-bit values only");
         const bool has_values = d_values_out != nullptr;
-        if (d_temp_storage == nullptr) {
-            temp_storage_bytes = gs_topk_segmented_temp_bytes(num_items, num_segments, k, has_values);
-            return hipSuccess;
+        if constexpr (sizeof(KeyT) == 2) {   // gs_topk_segmented_u16
+            constexpr int kt = KeyTraits<KeyT>::type;
+            static_assert(kt == GS_KEY_U16 || kt == GS_KEY_I16 || kt == GS_KEY_F16 || kt == GS_KEY_BF16, "a 16-bit key type");
+            if (d_temp_storage == nullptr) {
+                temp_storage_bytes = gs_topk_segmented_u16_temp_bytes(num_items, num_segments, k, has_values);
+                return hipSuccess;
+            }
+            return static_cast<hipError_t>(gs_topk_segmented_u16(
+                d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint16_t *>(d_keys_in),
+                reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint16_t *>(d_keys_out),
+                reinterpret_cast<uint32_t *>(d_values_out), d_counts_out, num_items, num_segments, d_begin_offsets, d_end_offsets,
+                k, descending ? 1 : 0, kt, stream));
+        } else {
+            static_assert(KeyTraits<KeyT>::type <= GS_KEY_F32, "unsigned int, int or float keys");
+            if (d_temp_storage == nullptr) {
+                temp_storage_bytes = gs_topk_segmented_temp_bytes(num_items, num_segments, k, has_values);
+                return hipSuccess;
+            }
+            return static_cast<hipError_t>(gs_topk_segmented_u32(
+                d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint32_t *>(d_keys_in),
+                reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint32_t *>(d_keys_out),
+                reinterpret_cast<uint32_t *>(d_values_out), d_counts_out, num_items, num_segments, d_begin_offsets, d_end_offsets,
+                k, descending ? 1 : 0, KeyTraits<KeyT>::type, stream));
         }
-        return static_cast<hipError_t>(gs_topk_segmented_u32(
-            d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint32_t *>(d_keys_in),
-            reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint32_t *>(d_keys_out),
-            reinterpret_cast<uint32_t *>(d_values_out), d_counts_out, num_items, num_segments, d_begin_offsets, d_end_offsets, k,
-            descending ? 1 : 0, KeyTraits<KeyT>::type, stream));
     }
     template <typename KeyT>
     static hipError_t MinKeys(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
