@@ -70,6 +70,9 @@ SIGNATURES = {
     "gs_topk_u16_temp_bytes": (sz, [u64, u64, i32]),
     "gs_topk_u16": (i32, [vp, sz, vp, vp, vp, vp, u64, u64, i32, i32, vp]),
     "gs_topk_u16_status": (i32, [vp, u64, u64, i32, C.POINTER(C.c_uint32), vp]),
+    "gs_topk_u64_temp_bytes": (sz, [u64, u64, i32]),
+    "gs_topk_u64": (i32, [vp, sz, vp, vp, vp, vp, u64, u64, i32, i32, vp]),
+    "gs_topk_u64_status": (i32, [vp, u64, u64, i32, C.POINTER(C.c_uint32), vp]),
     "gs_topk_rows_temp_bytes": (sz, [u64, u64, u64, i32]),
     "gs_topk_rows_u32": (i32, [vp, sz, vp, vp, vp, vp, u64, u64, u64, u64, i32, i32, vp]),
     "gs_topk_rows_max_k": (C.c_uint32, []),

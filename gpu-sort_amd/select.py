@@ -2,7 +2,7 @@
 
 DeviceTopK is two-phase like DeviceRadixSort (d_temp_storage=None returns the size); topk() is the convenience form that
 allocates outputs and workspace.  DeviceTopK16 is DeviceTopK for a flat array of 2-byte keys (gs_topk_u16: int16 / uint16 /
-float16 / bfloat16); topk() sends such tensors there.  DeviceTopKSegmented / topk_segmented() are the same for every ragged segment given by device offsets
+float16 / bfloat16) and DeviceTopK64 for 8-byte keys (gs_topk_u64: int64 / uint64 / float64); topk() sends such tensors there.  DeviceTopKSegmented / topk_segmented() are the same for every ragged segment given by device offsets
 (gs_topk_segmented_u32, and gs_topk_segmented_u16 for int16 / uint16 / float16 / bfloat16 keys).  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
 gs_topk_rows_u16 for int16 / uint16 / float16 / bfloat16 keys, in the order of GS_KEY_F16 / BF16 at the enum).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
 (descending for the Max forms) on the same input: stable, keys in the caller's bit patterns, floats in the order of
@@ -41,10 +41,24 @@ def _key_type16_of(t, key_type, who="DeviceTopKRows"):
 # what the key width changes at the flat front end: the name in messages, the entry point, its size query and status function,
 # the key-type resolver, the key's bytes, and the explicit key types refused before anything else (None: the entry point's own
 # refusal serves)
+_WIDE64 = (_lib.GS_KEY_U64, _lib.GS_KEY_I64, _lib.GS_KEY_F64)                          # what gs_topk_u64 takes
+
+
+def _key_type64_of(t, key_type, who="DeviceTopK64"):
+    if key_type is None:
+        key_type = _KEY_TYPES.get(t.dtype)
+    if key_type not in _WIDE64:
+        raise TypeError(f"{who}: no 64-bit key category for {t.dtype} (int64, float64, uint64, or GS_KEY_U64 / I64 / F64 by "
+                        "key_type)")
+    return key_type
+
+
 _FLAT_BY_WIDTH = {
-    32: ("DeviceTopK", "gs_topk_u32", "gs_topk_temp_bytes", "gs_topk_status", _key_type_of, 4, None),
+    32: ("DeviceTopK", "gs_topk_u32", "gs_topk_temp_bytes", "gs_topk_status", _key_type_of, 4, None, ""),
     16: ("DeviceTopK16", "gs_topk_u16", "gs_topk_u16_temp_bytes", "gs_topk_u16_status",
-         lambda t, key_type: _key_type16_of(t, key_type, "DeviceTopK16"), 2, _NARROW16),
+         lambda t, key_type: _key_type16_of(t, key_type, "DeviceTopK16"), 2, _NARROW16, "GS_KEY_U16 / I16 / F16 / BF16"),
+    64: ("DeviceTopK64", "gs_topk_u64", "gs_topk_u64_temp_bytes", "gs_topk_u64_status", _key_type64_of, 8, _WIDE64,
+         "GS_KEY_U64 / I64 / F64"),
 }
 
 
@@ -59,9 +73,9 @@ class DeviceTopK:
     @classmethod
     def _run(cls, d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_items, k, descending,
              has_values, stream, key_type):
-        who, entry, size_query, _, resolve, elem, explicit = _FLAT_BY_WIDTH[cls._width]
+        who, entry, size_query, _, resolve, elem, explicit, names = _FLAT_BY_WIDTH[cls._width]
         if key_type is not None and explicit is not None and key_type not in explicit:
-            raise TypeError(f"{who}: key_type must be GS_KEY_U16 / I16 / F16 / BF16")
+            raise TypeError(f"{who}: key_type must be {names}")
         need = getattr(lib, size_query)(num_items, k, int(has_values))
         if d_temp_storage is None:
             return need
@@ -126,10 +140,22 @@ class DeviceTopK16(DeviceTopK):
     _width = 16
 
 
+class DeviceTopK64(DeviceTopK):
+    """DeviceTopK for a flat array of 64-bit keys (gs_topk_u64): MinKeys / MaxKeys / MinPairs / MaxPairs / Status.
+
+    The key type comes from the tensor's dtype (int64, float64, uint64) or from an explicit 64-bit key_type; the result is the
+    first k of DeviceRadixSort on the same keys, float64 in the order of GS_KEY_F32 at the enum.  Values and indices are 4
+    bytes, as in DeviceTopK.  Status() is [route, low and high word of the k-th image, elements before it, taken from its tie
+    run, D, passes over the input, elements of the bucket or tie run].  Keys of any other width raise TypeError."""
+
+    _width = 64
+
+
 def topk(keys, k, largest=False, values=None, indices=False, stream=None):
     """The k smallest (largest=True: largest) of `keys`, sorted, as (keys_out, values_out).
 
-    2-byte keys (int16, uint16, float16, bfloat16) take gs_topk_u16 through DeviceTopK16, 4-byte keys gs_topk_u32.
+    2-byte keys (int16, uint16, float16, bfloat16) take gs_topk_u16 through DeviceTopK16, 8-byte keys (int64, float64, uint64)
+    gs_topk_u64 through DeviceTopK64, 4-byte keys gs_topk_u32.
 
     values: a 4-byte tensor of the same length, carried with the keys.  indices=True (without values): values_out holds the
     input positions as int32 bit patterns of u32 indices.  Neither: values_out is None.  Allocates outputs and workspace."""
@@ -143,9 +169,11 @@ def topk(keys, k, largest=False, values=None, indices=False, stream=None):
     values_out = None
     if has_values:
         values_out = torch.empty(k, dtype=values.dtype if values is not None else torch.int32, device=keys.device)
-    front = DeviceTopK16 if keys.element_size() == 2 else DeviceTopK
+    front = {2: DeviceTopK16, 8: DeviceTopK64}.get(keys.element_size(), DeviceTopK)
     if front is DeviceTopK16:
         _key_type16_of(keys, None, "topk")
+    elif front is DeviceTopK64:
+        _key_type64_of(keys, None, "topk")
     if k == 0:
         return keys_out, values_out
     nbytes = front._run(None, 0, None, None, None, None, n, k, largest, has_values, stream, None)

@@ -464,6 +464,71 @@ int    gs_topk_u16(void *d_temp, size_t temp_bytes,
  * elements that share its top byte, out[5..7] = 0.  All zeros for k == 0 or num_items == 0.                                */
 int    gs_topk_u16_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream);
 
+/* ------------------------------------------------------- top k, 64-bit keys --
+ * gs_topk_u32 for a flat array of 64-bit keys (gs_topk.hip): the ORDER BY ... LIMIT k of an int64 id or
+ * timestamp column, of double scores, of 64-bit hashes, without sorting the column.  key_type is GS_KEY_U64, GS_KEY_I64 or
+ * GS_KEY_F64.  With S = the output of gs_lsb_sort_wide (key_bytes 8, val_bytes 0 or 4, bits 0..64, descending, key_type) on
+ * the same input, d_keys_out[0..k) and d_vals_out[0..k) are S[0..k), bit for bit: keys keep the caller's bit patterns (NaN
+ * payloads included), GS_KEY_F64 follows GS_KEY_F32's order (negative NaNs first and positive NaNs last ascending, -0 before
+ * +0), and where the cut falls inside a run of equal keys the lowest input indices are taken.
+ * Forms: gs_topk_u32's -- keys only; pairs, with u32 values; arguments (d_vals_in == NULL, d_vals_out != NULL: the u32 input
+ * index).  has_values of the two queries is non-zero for the last two.
+ * The contract is gs_topk_u32's: plain pointers, the inputs are never written, nothing outside [0, k) of the outputs is
+ * written, d_temp anywhere, 1 <= k <= num_items < 2^32 (k == 0 or num_items == 0 returns 0, writes nothing and needs no
+ * workspace: the query returns 0).  The call only enqueues work on `stream`; the launches are a function of the arguments
+ * alone (every decision is taken on the device), so it may be captured into a HIP graph on one plain stream; calls may follow
+ * each other on one stream with one workspace, two runs on the same input give identical bytes, and no atomic decides a
+ * position (the only global atomics are the integer adds of the histograms and the AND / OR of the reductions).
+ * Errors (hipErrorInvalidValue, checked before anything is enqueued, nothing written): a NULL or too-small workspace,
+ * k > num_items, num_items >= 2^32, any other key_type, d_vals_in without d_vals_out, a NULL key pointer, a key array not
+ * aligned to 8 bytes or a value array not aligned to 4, arrays that share a byte (8 bytes per key, 4 per value; inputs at
+ * num_items elements, outputs at k).
+ * The way down.  With C = max(65536, num_items / 32), byte 7 the top byte of the 64-bit image, krem = k and M = all elements:
+ *   1. A counting round over the input reads it once: it counts byte j of the image over M (first round: j = 7) and reduces
+ *      the AND and the OR of the images of M.  It picks the digit d whose bucket holds the krem-th element, subtracts from krem
+ *      the elements of M below d and narrows M to that bucket (c elements).  D is the number of such rounds.
+ *   2. If c <= C the descent over the input stops: the bucket goes to the candidate list in input order (route 1).
+ *   3. Otherwise the next round counts the next lower byte at which AND and OR of this round's M differ; the bytes between
+ *      are constant over M, so over the bucket, and are filled into the k-th image from the AND without a round.  If no byte
+ *      is left, M is the run of keys equal to the k-th image and longer than C (route 2): its first krem elements are staged
+ *      directly from the input.  Otherwise go to 1.
+ *   4. On route 1 the remaining bytes are found by histogram rounds over the list, one per byte (constant bytes are not
+ *      skipped there), and the ordered select runs over the list.
+ *   5. The finish is gs_lsb_sort_wide of the k staged (key, index) pairs inside the workspace and a copy-out; the pairs form
+ *      also gathers.
+ * There is no route 3: an array of one element takes the same launches, and num_items <= C always fits at D = 1.  Every
+ * launch of the worst case is always enqueued -- eight input rounds and seven list rounds, about sixty launches with the
+ * finish; the workgroups of a launch that the state block says is not needed return at once.
+ * Passes over the input: exactly 2 when D == 1 -- round one is the wide upsweep at shift 56, whose spine and prefix16 place the
+ * elements that the second read stages (everything before digit d, and the bucket: into the list on route 1, or its first
+ * krem elements on route 2); D + 2 otherwise -- round one, the second read (which then is round two: it reduces AND / OR of
+ * round one's M and of the bucket, and counts all seven lower bytes of the bucket, since the byte to count is known only
+ * when the read is over), rounds three to D, then a count and a scatter that stage everything below the final bucket and
+ * move the bucket.  D + 1 is not reached.
+ * Workspace: a pure host function of its arguments, a multiple of 256, monotone in num_items and in k.  With tiles =
+ * max(1, ceil(num_items / 4096)), chunks = ceil(tiles / 8), C as above, hv = 1 with has_values else 0, and every term rounded
+ * up to 256 bytes:
+ *   221184                                    the state block, the AND / OR pairs, the histograms (those of the rounds over
+ *                                             the input in 16 copies, which the picks sum)
+ * + 256 * 4 * chunks + 1024 + 256 * 2 * tiles the spine, digit totals and prefix16 of round one (the wide upsweep at shift 56)
+ * + 8 * tiles                                 two counts per source tile of a select
+ * + 8 * C + hv * 4 * C                        the candidate list: keys (and indices)
+ * + 2 * (8 * k) + hv * 2 * (4 * k)            the staged keys (and indices) and the second buffer of their sort
+ * + gs_lsb_wide_temp_bytes(k, 8, hv ? 4 : 0)  the workspace of the final sort
+ * + 256 bytes of alignment slack.
+ * At num_items = 2^28, k = 2^20 with values that is 161 MiB, under an eighth of the 2 GiB of keys.                          */
+size_t gs_topk_u64_temp_bytes(uint64_t num_items, uint64_t k, int has_values);
+int    gs_topk_u64(void *d_temp, size_t temp_bytes,
+                   const uint64_t *d_keys_in, const uint32_t *d_vals_in,
+                   uint64_t *d_keys_out, uint32_t *d_vals_out,
+                   uint64_t num_items, uint64_t k, int descending, int key_type, void *stream);
+/* What the last gs_topk_u64 on d_temp (same num_items, k and has_values) decided, after synchronising `stream`:
+ * out[0] = route (1 or 2), out[1], out[2] = low and high word of the image of S[k - 1] (complemented when descending),
+ * out[3] = elements whose image sorts strictly before it, out[4] = k - out[3], out[5] = D, out[6] = passes over the input,
+ * out[7] = elements of the bucket moved to the list (route 1) or of the tie run (route 2).  All zeros for k == 0 or
+ * num_items == 0.                                                                                                         */
+int    gs_topk_u64_status(void *d_temp, uint64_t num_items, uint64_t k, int has_values, uint32_t out[8], void *stream);
+
 /* ------------------------------------------------------- top k of every row --
  * The k best of every row of a matrix (gs_topk_rows.hip): MoE routing, top-k sampling over a
  * vocabulary, beam search, re-ranking.  Row r is d_keys_in[r * row_stride .. r * row_stride + num_cols) (the values of the

@@ -36,9 +36,18 @@ def _kernels(build_dir, tmp, tag):
         # "..." is llvm-objdump's elision of a run of zero bytes.  As the LAST line of a function it is the padding between the
         # function's final instruction and the next symbol, which moves with the link order and is not code: only there is it
         # dropped.  A run of zeros anywhere inside a function is kept and compared.
+        # The same holds for the run of `s_nop 0` / `s_code_end` behind a function's final s_endpgm: the assembler's fill up to
+        # the next symbol or, for the last kernel of the code object, to the end of the text section -- which kernel that is
+        # changes when kernels are added behind it.  Only a run that directly follows an s_endpgm at the end of the listing
+        # is dropped.
         for k in code:
             while code[k] and code[k][-1].strip() == "...":
                 code[k].pop()
+            end = len(code[k])
+            while end and code[k][end - 1].strip() in ("s_nop 0", "s_code_end", "..."):
+                end -= 1
+            if end and code[k][end - 1].strip() == "s_endpgm":
+                del code[k][end:]
         notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", base + ".co"], text=True)
         for block in notes.split("  - .agpr_count")[1:]:
             name = re.search(r"\.name:\s+(\S+)", block)
