@@ -1,6 +1,7 @@
-// gs_topk_rows.hip -- gs_topk_rows_u32 and gs_topk_rows_u16: the first k of the stable sort of every row of a matrix, for
-// 32-bit keys and 16-bit keys (section 10i).  One set of kernels and one host path, instantiated
-// over a key-traits type (TrKey32, TrKey16); one geometry and one plan, so gs_topk_rows_plan answers for both entry points.
+// gs_topk_rows.hip -- gs_topk_rows_u32, gs_topk_rows_u16 and gs_topk_rows_u64: the first k of the stable sort of every row of a
+// matrix, for 32-bit keys, 16-bit keys (section 10i) and 64-bit keys (section 10n).  One set of kernels
+// and one host path, instantiated over a key-traits type (TrKey32, TrKey16, TrKey64); one geometry and one plan, so
+// gs_topk_rows_plan answers for all three entry points.
 // gs_topk_segmented_u32 (section 10k) and gs_topk_segmented_u16 (section 10l), the same for ragged segments given by device
 // offsets, follow them: they run the same device functions per record of lists that a classify kernel fills (see "ragged
 // segments" below), instantiated over the same two key-traits types.
@@ -38,6 +39,27 @@
 //   the passes   two digit passes in the wave sort and two select rounds (shift 8, then 0) in place of four.
 //   the memory   one 2-byte load or store per key, so a row base r * row_stride and an output base r * k may be odd: nothing
 //                wider than an element is ever touched.  Candidate rows hold 16-bit keys and u32 columns.
+//
+// 64-bit keys: row r of the result is bit for bit what gs_topk_u64 gives for that row alone; on the matrix (uint64_t)key << 32
+// of 32-bit keys with the key type widened it is what gs_topk_rows_u32 gives, the keys shifted back.  What the width changes:
+//
+//   the image    a 64-bit word in a register pair (the traits' image type I; uint32_t for the two other widths); the LDS
+//                staging rows, the select's prefix and mask are 64 bits wide, values and columns stay u32.  The pad image is
+//                all ones -- again an ORDINARY image (the u64 maximum, the positive NaN 0xffff...f ascending): a pad loses
+//                to a real key of that image by position alone, in the stable wave sort (pads sit behind every real element
+//                at the start, carry the largest digit in every pass, and every pass is stable) and in the select (pads are
+//                out of range and never counted or placed).
+//   the passes   up to eight, but only for bytes that can decide.  The wave sort reduces the AND and the OR of the real
+//                elements' images over the wave and runs the pass of a byte only where AND ^ OR is non-zero there.  A
+//                skipped pass would have been the identity: the real elements share the digit, so the stable pass keeps
+//                their order, and the pads, whose digit is at least as large and which are already behind every real
+//                element, stay where they are.  The decision is wave-uniform: the rows of one path-1 workgroup may run
+//                different pass sets, and no barrier follows.  The select reduces AND and OR over the workgroup's in-range
+//                elements once; a round whose byte is constant takes that byte into the prefix without a histogram, and a
+//                chunk of one image runs no round (less = 0, the tie run cut at keff).  That decision is workgroup-uniform:
+//                every thread reaches every __syncthreads.
+//   the memory   one 8-byte load or store per key; candidate rows hold 8-byte keys and u32 columns.
+//   the mask     the kernels take the xor mask as one 32-bit argument at every width (see TrKey64::xmask).
 #include "gs_device.hpp"
 #include "gs_host.hpp"
 
@@ -53,9 +75,10 @@ static_assert(TR_MAX_K <= TR_CH && TR_MAX_K == 16 * WAVE, "a chunk gives up to k
 
 // What the key width changes.  T: the element in memory; BITS: the width of the image, which sits in a 32-bit register;
 // PAD: the image of an element past the end (largest in every digit); in / out: the caller's bit pattern to the image and
-// back, flt for the float types, x the xor mask of xor_of; type_ok / is_float / xor_of: the key types the entry point takes.
+// back, flt for the float types, x the xor mask xmask(xor_of); type_ok / is_float / xor_of: the key types the entry point takes.
 struct TrKey32 {
     using T = uint32_t;
+    using I = uint32_t;
     static constexpr int BITS = 32;
     static constexpr uint32_t PAD = 0xffffffffu;
     static __device__ __forceinline__ uint32_t in(uint32_t k, int flt, uint32_t x) { return twiddle_in(k, flt, x); }
@@ -66,10 +89,12 @@ struct TrKey32 {
     {
         return (key_type == GS_KEY_I32 ? 0x80000000u : 0u) ^ (descending ? 0xffffffffu : 0u);
     }
+    static __device__ __forceinline__ uint32_t xmask(uint32_t x) { return x; }
 };
 
 struct TrKey16 {
     using T = uint16_t;
+    using I = uint32_t;
     static constexpr int BITS = 16;
     static constexpr uint32_t PAD = 0xffffu;   // the image's bits; an ordinary image too (see the header)
     static __device__ __forceinline__ uint32_t in(uint32_t k, int flt, uint32_t x) { return (flt ? float_flip<16>(k) : k) ^ x; }
@@ -84,6 +109,33 @@ struct TrKey16 {
     }
     static int is_float(int key_type) { return key_type == GS_KEY_F16 || key_type == GS_KEY_BF16; }
     static uint32_t xor_of(int key_type, int descending) { return (key_type == GS_KEY_U16 ? 0u : 0x8000u) ^ (descending ? PAD : 0u); }
+    static __device__ __forceinline__ uint32_t xmask(uint32_t x) { return x; }
+};
+
+// 64-bit keys: the image fills a register pair, and so do the prefix and the mask of the select and the words of the staging
+// rows.  PAD is all ones -- an ordinary image (the u64 maximum, the positive NaN 0xffff...f ascending): see the header.
+struct TrKey64 {
+    using T = uint64_t;
+    using I = uint64_t;
+    static constexpr int BITS = 64;
+    static constexpr uint64_t PAD = ~0ull;
+    static __device__ __forceinline__ uint64_t in(uint64_t k, int flt, uint64_t x)
+    {
+        if (flt) k ^= (uint64_t)((int64_t)k >> 63) | 0x8000000000000000ull;
+        return k ^ x;
+    }
+    static __device__ __forceinline__ uint64_t out(uint64_t k, int flt, uint64_t x)
+    {
+        k ^= x;
+        if (flt) k ^= ~(uint64_t)((int64_t)k >> 63) | 0x8000000000000000ull;
+        return k;
+    }
+    static bool type_ok(int key_type) { return key_type >= GS_KEY_U64 && key_type <= GS_KEY_F64; }
+    static int is_float(int key_type) { return key_type == GS_KEY_F64; }
+    // The kernels take the xor mask as one 32-bit argument at every width: here its upper half.  The lower half is all ones
+    // exactly when descending, which is bit 0 of the upper half (0, 0x80000000, 0xffffffff or 0x7fffffff).
+    static uint32_t xor_of(int key_type, int descending) { return (key_type == GS_KEY_I64 ? 0x80000000u : 0u) ^ (descending ? 0xffffffffu : 0u); }
+    static __device__ __forceinline__ uint64_t xmask(uint32_t x) { return ((uint64_t)x << 32) | (uint32_t)(0u - (x & 1u)); }
 };
 
 // One wave: the stable LSD sort, on the low BITS bits, of WKPT * 64 (image, value) pairs in registers; element i * 64 + lane
@@ -91,8 +143,8 @@ struct TrKey16 {
 // lane, and a trip through the wave's staging rows.  All 64 lanes must be active.  BITS / 8 passes: four for a 32-bit image,
 // two for a 16-bit one (whose upper half is zero in every element, so the two passes left out would move nothing).
 template <int BITS, int WKPT, bool HV>
-__device__ __forceinline__ void wave_sort_bits(uint32_t (&key)[WKPT], uint32_t (&val)[HV ? WKPT : 1], uint32_t *__restrict__ my,
-                                               uint32_t *__restrict__ sk, uint32_t *__restrict__ sv)
+__device__ __forceinline__ void wave_sort_bits(uint32_t (&key)[WKPT], uint32_t (&val)[HV ? WKPT : 1], uint32_t /*nreal*/,
+                                               uint32_t *__restrict__ my, uint32_t *__restrict__ sk, uint32_t *__restrict__ sv)
 {
     static_assert(BITS == 16 || BITS == 32, "whole digits of a 16- or 32-bit image");
     const int lane = lane_id();
@@ -121,6 +173,85 @@ __device__ __forceinline__ void wave_sort_bits(uint32_t (&key)[WKPT], uint32_t (
 #pragma unroll
         for (int i = 0; i < WKPT; ++i) {
             const uint32_t at = pos[i] + my[__builtin_amdgcn_ubfe(key[i], sh, RADIX_BITS)];
+            sk[at] = key[i];
+            if (HV) sv[at] = val[i];
+        }
+        fence();
+#pragma unroll
+        for (int i = 0; i < WKPT; ++i) {
+            key[i] = sk[i * WAVE + lane];
+            if (HV) val[i] = sv[i * WAVE + lane];
+        }
+        fence();
+    }
+}
+
+// A 64-bit value that is the same in every lane, from its halves: in scalar registers.  (readfirstlane returns an int: each
+// half goes through uint32_t, or the low one would sign-extend into the high one.)
+__device__ __forceinline__ uint64_t uniform64(uint32_t lo, uint32_t hi)
+{
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(hi) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(lo);
+}
+
+// AND and OR of a 64-bit value over the wave, in every lane.
+__device__ __forceinline__ void wave_and_or64(uint64_t &a, uint64_t &o)
+{
+    uint32_t al = (uint32_t)a, ah = (uint32_t)(a >> 32), ol = (uint32_t)o, oh = (uint32_t)(o >> 32);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        al &= __shfl_xor(al, d, WAVE); ah &= __shfl_xor(ah, d, WAVE);
+        ol |= __shfl_xor(ol, d, WAVE); oh |= __shfl_xor(oh, d, WAVE);
+    }
+    a = uniform64(al, ah);
+    o = uniform64(ol, oh);
+}
+
+// The same sort for a 64-bit image in a register pair; the staging row sk holds 64-bit words.  Elements i * 64 + lane below
+// nreal are real, the others pads (all ones, behind every real element).  A digit pass runs only for a byte in which two
+// real images differ (AND ^ OR over the real elements, reduced over the wave: a wave-uniform decision, so the waves of one
+// workgroup may run different pass sets -- nothing here waits on another wave).  A skipped pass would have been the
+// identity: the real elements share the digit, so a stable pass keeps them in order, and the pads, whose digit is the
+// largest, stay behind them where they already are.
+template <int BITS, int WKPT, bool HV>
+__device__ __forceinline__ void wave_sort_bits(uint64_t (&key)[WKPT], uint32_t (&val)[HV ? WKPT : 1], uint32_t nreal,
+                                               uint32_t *__restrict__ my, uint64_t *__restrict__ sk, uint32_t *__restrict__ sv)
+{
+    static_assert(BITS == 64, "whole digits of a 64-bit image");
+    const int lane = lane_id();
+    auto fence = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); };
+    uint64_t all_and = ~0ull, all_or = 0ull;
+#pragma unroll
+    for (int i = 0; i < WKPT; ++i) {
+        if ((uint32_t)(i * WAVE + lane) < nreal) { all_and &= key[i]; all_or |= key[i]; }
+    }
+    wave_and_or64(all_and, all_or);
+    const uint64_t differ = all_and ^ all_or;   // (no real element: ~0, every pass runs on pads alone)
+#pragma unroll 1
+    for (uint32_t sh = 0; sh < 64u; sh += (uint32_t)RADIX_BITS) {
+        if (((differ >> sh) & 255ull) == 0ull) continue;
+        uint32_t pos[WKPT];
+        reinterpret_cast<uint4 *>(my)[lane] = make_uint4(0u, 0u, 0u, 0u);
+        fence();
+#pragma unroll
+        for (int i = 0; i < WKPT; ++i) {
+            const uint32_t d = (uint32_t)(key[i] >> sh) & 255u;
+            uint32_t lo, hi;
+            match_digit(d, lo, hi);
+            const uint32_t lower = count_lower(lo, hi);
+            pos[i] = my[d] + lower;
+            if (lower == 0) my[d] += (uint32_t)(__popc(lo) + __popc(hi));   // one lane per digit: no two writers of a word
+            fence();
+        }
+        {   // exclusive scan of the 256 counters, 4 per lane
+            const uint4 c = reinterpret_cast<const uint4 *>(my)[lane];
+            const uint32_t sum = c.x + c.y + c.z + c.w;
+            const uint32_t ex = wave_inclusive_scan(sum) - sum;
+            reinterpret_cast<uint4 *>(my)[lane] = make_uint4(ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z);
+        }
+        fence();
+#pragma unroll
+        for (int i = 0; i < WKPT; ++i) {
+            const uint32_t at = pos[i] + my[(uint32_t)(key[i] >> sh) & 255u];
             sk[at] = key[i];
             if (HV) sv[at] = val[i];
         }
@@ -172,13 +303,74 @@ __device__ __forceinline__ uint32_t tr_select(uint32_t (&img)[TR_KPT], uint32_t 
     return prefix;   // less + krem == keff: the tie run is cut at keff
 }
 
+// The same select for a 64-bit image: prefix and mask are 64 bits wide.  The AND and the OR of the in-range images are reduced
+// over the workgroup once; a round whose byte is the same in all of them takes that byte into the prefix without a histogram
+// (every in-range element still matches the prefix there, so the round would have put all of them into one bin and picked
+// it), and a chunk of one image runs no round: less = 0 and the tie run is cut at keff.  The reduced words are the same in
+// every thread, so every thread reaches the same barriers.
+template <int BITS>
+__device__ __forceinline__ uint64_t tr_select(uint64_t (&img)[TR_KPT], uint32_t first, uint32_t len, uint32_t keff, uint32_t tid,
+                                              uint32_t *__restrict__ h, uint32_t *__restrict__ scratch, uint32_t *__restrict__ sel,
+                                              uint32_t &less)
+{
+    static_assert(BITS == 64, "whole digits of a 64-bit image");
+    __shared__ uint64_t red[2][TR_WAVES];
+    __shared__ uint64_t sel_prefix;
+    uint64_t all_and = ~0ull, all_or = 0ull;
+#pragma unroll
+    for (int u = 0; u < TR_KPT; ++u) {
+        const uint32_t j = first + (uint32_t)u * WAVE;
+        if (j < len) { all_and &= img[u]; all_or |= img[u]; }
+    }
+    wave_and_or64(all_and, all_or);
+    if ((tid & 63u) == 0u) { red[0][tid >> 6] = all_and; red[1][tid >> 6] = all_or; }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < TR_WAVES; ++q) { all_and &= red[0][q]; all_or |= red[1][q]; }
+    all_and = uniform64((uint32_t)all_and, (uint32_t)(all_and >> 32));
+    all_or = uniform64((uint32_t)all_or, (uint32_t)(all_or >> 32));
+    const uint64_t differ = all_and ^ all_or;
+    uint64_t prefix = 0;
+    uint32_t krem = keff;
+    less = 0;
+#pragma unroll 1
+    for (int b = 7; b >= 0; --b) {
+        const uint32_t shift = (uint32_t)b * 8u;
+        if (((differ >> shift) & 255ull) == 0ull) {   // workgroup-uniform
+            prefix |= all_and & (255ull << shift);
+            continue;
+        }
+        const uint64_t mask = b == 7 ? 0ull : ~0ull << (shift + 8u);   // the bytes above this one
+        if (tid < (uint32_t)RADIX) h[tid] = 0;
+        __syncthreads();
+        uint32_t lenv = len;
+        asm volatile("" : "+v"(lenv));   // (as in the 32-bit select)
+#pragma unroll
+        for (int u = 0; u < TR_KPT; ++u) {
+            const uint32_t j = first + (uint32_t)u * WAVE;
+            if (j < lenv && ((img[u] ^ prefix) & mask) == 0ull) hist_add(h, (uint32_t)(img[u] >> shift) & 255u);
+        }
+        __syncthreads();
+        const uint32_t cnt = tid < (uint32_t)RADIX ? h[tid] : 0u;
+        const uint32_t ex = block_exclusive_scan_256(cnt, scratch, nullptr);
+        if (tid < (uint32_t)RADIX && ex < krem && krem - ex <= cnt) {
+            sel_prefix = prefix | ((uint64_t)tid << shift);
+            sel[1] = less + ex;
+            sel[2] = krem - ex;
+        }
+        __syncthreads();
+        prefix = sel_prefix; less = sel[1]; krem = sel[2];
+    }
+    return prefix;   // less + krem == keff: the tie run is cut at keff
+}
+
 // The ordered two-group compaction of the selected elements into LDS: group A (before the k-th image) at [0, less), group B
 // (equal to it) behind, cut at keff; (wave, row, lane) is input order.  stage_v[pos] gets value_of(u, j), the value of element
 // j = first + u * 64 (img[u]).  Ends with a workgroup barrier.
-template <bool HV, int CAP, typename ValueOf>
-__device__ __forceinline__ void tr_compact_with(uint32_t (&img)[TR_KPT], uint32_t first, uint32_t len, uint32_t keff, uint32_t kth,
+template <bool HV, int CAP, typename I, typename ValueOf>
+__device__ __forceinline__ void tr_compact_with(I (&img)[TR_KPT], uint32_t first, uint32_t len, uint32_t keff, I kth,
                                                 uint32_t less, uint32_t w, uint32_t lane, uint32_t (&wcnt)[2][TR_WAVES],
-                                                uint32_t *__restrict__ stage_k, uint32_t *__restrict__ stage_v, ValueOf value_of)
+                                                I *__restrict__ stage_k, uint32_t *__restrict__ stage_v, ValueOf value_of)
 {
     uint32_t nA = 0, nB = 0, lenc = len;
     asm volatile("" : "+v"(lenc));   // (range compares again, as in the select rounds; once more before the scatter loop)
@@ -214,9 +406,9 @@ __device__ __forceinline__ void tr_compact_with(uint32_t (&img)[TR_KPT], uint32_
 
 // tr_compact_with for a source in memory: stage_v[pos] gets src_i[j] where the source carries columns (SRC_IDX), otherwise
 // col0 + j.
-template <bool HV, bool SRC_IDX, int CAP>
-__device__ __forceinline__ void tr_compact(uint32_t (&img)[TR_KPT], uint32_t first, uint32_t len, uint32_t keff, uint32_t kth, uint32_t less,
-                                           uint32_t w, uint32_t lane, uint32_t (&wcnt)[2][TR_WAVES], uint32_t *__restrict__ stage_k,
+template <bool HV, bool SRC_IDX, int CAP, typename I>
+__device__ __forceinline__ void tr_compact(I (&img)[TR_KPT], uint32_t first, uint32_t len, uint32_t keff, I kth, uint32_t less,
+                                           uint32_t w, uint32_t lane, uint32_t (&wcnt)[2][TR_WAVES], I *__restrict__ stage_k,
                                            uint32_t *__restrict__ stage_v, const uint32_t *__restrict__ src_i, uint32_t col0)
 {
     tr_compact_with<HV, CAP>(img, first, len, keff, kth, less, w, lane, wcnt, stage_k, stage_v,
@@ -228,23 +420,26 @@ __device__ __forceinline__ void tr_compact(uint32_t (&img)[TR_KPT], uint32_t fir
 template <typename KT, int WKPT, bool HV>
 __global__ __launch_bounds__(256) void topk_rows_wave_kernel(const typename KT::T *__restrict__ keys, const uint32_t *__restrict__ vals_in,
                                                              typename KT::T *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
-                                                             uint32_t rows, uint32_t cols, uint32_t stride, uint32_t k, int flt, uint32_t x)
+                                                             uint32_t rows, uint32_t cols, uint32_t stride, uint32_t k, int flt, uint32_t x32)
 {
     using T = typename KT::T;
+    using I = typename KT::I;
+    const I x = KT::xmask(x32);
     constexpr int CAP = WKPT * WAVE;
     __shared__ __attribute__((aligned(16))) uint32_t hist[4][RADIX];
-    __shared__ uint32_t stage_k[4][CAP];
+    __shared__ I stage_k[4][CAP];
     __shared__ uint32_t stage_v[HV ? 4 : 1][HV ? CAP : 1];
     const int w = wave_id(), lane = lane_id();
     const uint32_t r = blockIdx.x * 4u + (uint32_t)w;
     if (r >= rows) return;
     const size_t in0 = (size_t)r * stride, out0 = (size_t)r * k;
-    uint32_t key[WKPT], val[HV ? WKPT : 1];
+    I key[WKPT];
+    uint32_t val[HV ? WKPT : 1];
     const uint32_t last = cols - 1u;
 #pragma unroll
     for (int i = 0; i < WKPT; ++i) {
         const uint32_t idx = (uint32_t)(i * WAVE + lane);
-        key[i] = (uint32_t)__builtin_nontemporal_load(keys + in0 + (idx < last ? idx : last));   // past the end: the row's last element again
+        key[i] = (I)__builtin_nontemporal_load(keys + in0 + (idx < last ? idx : last));   // past the end: the row's last element again
     }
 #pragma unroll
     for (int i = 0; i < WKPT; ++i) {
@@ -252,7 +447,7 @@ __global__ __launch_bounds__(256) void topk_rows_wave_kernel(const typename KT::
         key[i] = idx < cols ? KT::in(key[i], flt, x) : KT::PAD;   // pads: last in position, largest in every digit
         if (HV) val[i] = idx;
     }
-    wave_sort_bits<KT::BITS, WKPT, HV>(key, val, hist[w], stage_k[w], stage_v[HV ? w : 0]);
+    wave_sort_bits<KT::BITS, WKPT, HV>(key, val, cols, hist[w], stage_k[w], stage_v[HV ? w : 0]);
 #pragma unroll
     for (int i = 0; i < WKPT; ++i) {
         const uint32_t idx = (uint32_t)(i * WAVE + lane);
@@ -276,15 +471,17 @@ __global__ __launch_bounds__(TR_THREADS) void topk_rows_block_kernel(const typen
                                                                      uint32_t chunks, typename KT::T *__restrict__ dst_k,
                                                                      uint32_t *__restrict__ dst_v, uint32_t dst_stride,
                                                                      const uint32_t *__restrict__ vals_in, uint32_t vals_stride,
-                                                                     uint32_t vals_cols, uint32_t k, int flt, uint32_t x)
+                                                                     uint32_t vals_cols, uint32_t k, int flt, uint32_t x32)
 {
     using T = typename KT::T;
+    using I = typename KT::I;
+    const I x = KT::xmask(x32);
     constexpr int CAP = WKPT * WAVE;
     __shared__ __attribute__((aligned(16))) uint32_t h[RADIX];   // the select's histogram, then the finishing wave's counters
     __shared__ uint32_t scratch[8];
     __shared__ uint32_t sel[3];
     __shared__ uint32_t wcnt[2][TR_WAVES];
-    __shared__ uint32_t stage_k[CAP], sort_k[CAP];
+    __shared__ I stage_k[CAP], sort_k[CAP];
     __shared__ uint32_t stage_v[HV ? CAP : 1], sort_v[HV ? CAP : 1];
     const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
     const uint32_t r = blockIdx.x / chunks, c = blockIdx.x - r * chunks;
@@ -292,30 +489,31 @@ __global__ __launch_bounds__(TR_THREADS) void topk_rows_block_kernel(const typen
     const size_t base = (size_t)r * src_stride + lo;
     const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
 
-    uint32_t img[TR_KPT];
+    I img[TR_KPT];
 #pragma unroll
     for (int u = 0; u < TR_KPT; ++u) {
         const uint32_t j = first + (uint32_t)u * WAVE;
-        img[u] = j < len ? (uint32_t)__builtin_nontemporal_load(src_k + base + j) : 0u;
+        img[u] = j < len ? (I)__builtin_nontemporal_load(src_k + base + j) : (I)0u;
     }
 #pragma unroll
     for (int u = 0; u < TR_KPT; ++u) img[u] = KT::in(img[u], flt, x);
 
     // radix select of the keff-th image on the registers, then the ordered compaction of the keff selected pairs into LDS
     uint32_t less;
-    const uint32_t kth = tr_select<KT::BITS>(img, first, len, keff, tid, h, scratch, sel, less);
+    const I kth = tr_select<KT::BITS>(img, first, len, keff, tid, h, scratch, sel, less);
     tr_compact<HV, SRC_IDX, CAP>(img, first, len, keff, kth, less, w, lane, wcnt, stage_k, stage_v, SRC_IDX ? src_i + base : nullptr, lo);
 
     // finish: one wave sorts the keff staged pairs and stores them
     if (w != 0) return;
-    uint32_t key[WKPT], val[HV ? WKPT : 1];
+    I key[WKPT];
+    uint32_t val[HV ? WKPT : 1];
 #pragma unroll
     for (int i = 0; i < WKPT; ++i) {
         const uint32_t idx = (uint32_t)i * WAVE + lane;
         key[i] = idx < keff ? stage_k[idx] : KT::PAD;   // pads: last in position, largest in every digit
         if (HV) val[i] = idx < keff ? stage_v[idx] : 0u;
     }
-    wave_sort_bits<KT::BITS, WKPT, HV>(key, val, h, sort_k, sort_v);
+    wave_sort_bits<KT::BITS, WKPT, HV>(key, val, keff, h, sort_k, sort_v);
     const size_t out0 = (size_t)r * dst_stride + (size_t)c * k;
 #pragma unroll
     for (int i = 0; i < WKPT; ++i) {
@@ -379,7 +577,8 @@ static void tr_launch_wave(hipStream_t s, const typename KT::T *ki, const uint32
                        flt, x);
 }
 
-template <typename T> struct BlockArgs {
+template <typename KT> struct BlockArgs {
+    using T = typename KT::T;
     const T *src_k;
     const uint32_t *src_i;
     uint32_t src_stride, n, chunks;
@@ -393,7 +592,7 @@ template <typename T> struct BlockArgs {
 };
 
 template <typename KT, int WKPT, bool HV, bool SRC_IDX, bool FINAL>
-static void tr_launch_block4(hipStream_t s, const BlockArgs<typename KT::T> &a)
+static void tr_launch_block4(hipStream_t s, const BlockArgs<KT> &a)
 {
     KernelTimer kt(GS_K_OTHER, s);
     hipLaunchKernelGGL((topk_rows_block_kernel<KT, WKPT, HV, SRC_IDX, FINAL>), dim3(a.rows * a.chunks), dim3(TR_THREADS), 0, s, a.src_k,
@@ -402,7 +601,7 @@ static void tr_launch_block4(hipStream_t s, const BlockArgs<typename KT::T> &a)
 }
 
 template <typename KT, int WKPT>
-static void tr_launch_block(hipStream_t s, const BlockArgs<typename KT::T> &a, bool hv, bool src_idx, bool final)
+static void tr_launch_block(hipStream_t s, const BlockArgs<KT> &a, bool hv, bool src_idx, bool final)
 {
     if (!hv) {   // keys alone: no columns to read or carry
         if (final) tr_launch_block4<KT, WKPT, false, false, true>(s, a);
@@ -489,7 +688,7 @@ static int tr_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_
     }
     for (uint32_t lvl = 0; lvl < p.levels; ++lvl) {
         const bool final = lvl + 1 == p.levels;
-        BlockArgs<T> a;
+        BlockArgs<KT> a;
         a.src_k = lvl == 0 ? d_keys_in : area_k[(lvl - 1) & 1];
         a.src_i = lvl == 0 ? nullptr : area_i[(lvl - 1) & 1];
         a.src_stride = lvl == 0 ? stride : (uint32_t)p.n[lvl];
@@ -682,7 +881,7 @@ __global__ __launch_bounds__(256) void topk_seg_wave_kernel(TsWs ws, const typen
             key[i] = idx < cols ? KT::in(key[i], flt, x) : KT::PAD;   // pads: last in position, largest in every digit
             if (HV) val[i] = idx;
         }
-        wave_sort_bits<KT::BITS, WKPT, HV>(key, val, hist[w], stage_k[w], stage_v[HV ? w : 0]);
+        wave_sort_bits<KT::BITS, WKPT, HV>(key, val, cols, hist[w], stage_k[w], stage_v[HV ? w : 0]);
 #pragma unroll
         for (int i = 0; i < WKPT; ++i) {
             const uint32_t idx = (uint32_t)(i * WAVE + lane);
@@ -772,7 +971,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_block_kernel(TsWs ws, con
                 key[i] = idx < keff ? stage_k[idx] : KT::PAD;   // pads: last in position, largest in every digit
                 if (HV) val[i] = idx < keff ? stage_v[idx] : 0u;
             }
-            wave_sort_bits<KT::BITS, WKPT, HV>(key, val, h, sort_k, sort_v);
+            wave_sort_bits<KT::BITS, WKPT, HV>(key, val, keff, h, sort_k, sort_v);
             const size_t out0 = (size_t)slot * k;
 #pragma unroll
             for (int i = 0; i < WKPT; ++i) {
@@ -878,7 +1077,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_final_kernel(TsWs ws, con
                 key[i] = idx < kc ? stage_k[idx] : KT::PAD;
                 if (HV) val[i] = idx < kc ? stage_v[idx] : 0u;
             }
-            wave_sort_bits<KT::BITS, WKPT, HV>(key, val, h, sort_k, sort_v);
+            wave_sort_bits<KT::BITS, WKPT, HV>(key, val, kc, h, sort_k, sort_v);
             const size_t out0 = (size_t)seg * k;
 #pragma unroll
             for (int i = 0; i < WKPT; ++i) {
@@ -1093,6 +1292,11 @@ size_t gs_topk_rows_u16_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_
     return tr_temp_bytes<TrKey16>(num_rows, num_cols, k, has_values);
 }
 
+size_t gs_topk_rows_u64_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values)
+{
+    return tr_temp_bytes<TrKey64>(num_rows, num_cols, k, has_values);
+}
+
 int gs_topk_rows_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
                      uint32_t *d_vals_out, uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, int descending,
                      int key_type, void *stream)
@@ -1106,6 +1310,14 @@ int gs_topk_rows_u16(void *d_temp, size_t temp_bytes, const uint16_t *d_keys_in,
                      int key_type, void *stream)
 {
     return tr_run<TrKey16>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, num_rows, num_cols, row_stride, k, descending,
+                           key_type, stream);
+}
+
+int gs_topk_rows_u64(void *d_temp, size_t temp_bytes, const uint64_t *d_keys_in, const uint32_t *d_vals_in, uint64_t *d_keys_out,
+                     uint32_t *d_vals_out, uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, int descending,
+                     int key_type, void *stream)
+{
+    return tr_run<TrKey64>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, num_rows, num_cols, row_stride, k, descending,
                            key_type, stream);
 }
 

@@ -4,7 +4,8 @@ DeviceTopK is two-phase like DeviceRadixSort (d_temp_storage=None returns the si
 allocates outputs and workspace.  DeviceTopK16 is DeviceTopK for a flat array of 2-byte keys (gs_topk_u16: int16 / uint16 /
 float16 / bfloat16) and DeviceTopK64 for 8-byte keys (gs_topk_u64: int64 / uint64 / float64); topk() sends such tensors there.  DeviceTopKSegmented / topk_segmented() are the same for every ragged segment given by device offsets
 (gs_topk_segmented_u32, and gs_topk_segmented_u16 for int16 / uint16 / float16 / bfloat16 keys).  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
-gs_topk_rows_u16 for int16 / uint16 / float16 / bfloat16 keys, in the order of GS_KEY_F16 / BF16 at the enum).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
+gs_topk_rows_u16 for int16 / uint16 / float16 / bfloat16 keys, in the order of GS_KEY_F16 / BF16 at the enum); DeviceTopKRows64 /
+topk_rows64() are the rows form for 8-byte keys (gs_topk_rows_u64: int64 / uint64 / float64).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
 (descending for the Max forms) on the same input: stable, keys in the caller's bit patterns, floats in the order of
 GS_KEY_F32 (negative NaNs first, positive NaNs last ascending; -0.0 before +0.0).
 """
@@ -326,6 +327,119 @@ def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
     if stream is not None:
         temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
     DeviceTopKRows._run(temp, nbytes, keys, keys_out, values, values_out, rows, cols, stride, k, largest, has_values, stream, None)
+    return keys_out, values_out
+
+
+class DeviceTopKRows64:
+    """DeviceTopKRows for a matrix of 64-bit keys (gs_topk_rows_u64): MinKeys / MaxKeys / MinPairs / MaxPairs / MaxK / Plan.
+
+    The key type comes from the tensor's dtype (int64, float64, uint64) or from an explicit GS_KEY_U64 / I64 / F64; each row's
+    result is what DeviceTopK64 gives for that row alone, float64 in the order of GS_KEY_F32 at the enum.  Values and column
+    indices are 4 bytes.  Two-phase: d_temp_storage=None returns the size, 0 for a shape the entry point refuses.  Keys of
+    any other width and any other key_type raise TypeError.  The geometry is DeviceTopKRows': Plan() is the same answer."""
+
+    @staticmethod
+    def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols, row_stride,
+             k, descending, has_values, stream, key_type):
+        if key_type is not None and key_type not in _WIDE64:
+            raise TypeError("DeviceTopKRows64: key_type must be GS_KEY_U64 / I64 / F64")
+        need = lib.gs_topk_rows_u64_temp_bytes(num_rows, num_cols, k, int(has_values))
+        if d_temp_storage is None:
+            return need
+        if not isinstance(d_keys_in, torch.Tensor) or d_keys_in.element_size() != 8:
+            raise TypeError("DeviceTopKRows64: 64-bit keys only")
+        key_type = _key_type64_of(d_keys_in, key_type, "DeviceTopKRows64")
+        _check_rows_in(d_keys_in, "d_keys_in", 8)
+        _check_buf(d_keys_out, num_rows * k, "d_keys_out", 8)
+        if has_values:
+            if d_values_in is not None:
+                _check_rows_in(d_values_in, "d_values_in")
+            _check_buf(d_values_out, num_rows * k, "d_values_out")
+        err = lib.gs_topk_rows_u64(C.c_void_p(d_temp_storage.data_ptr()),
+                                   min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                   d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
+                                   d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
+                                   num_rows, num_cols, row_stride, k, int(descending), key_type, _stream_ptr(stream))
+        check(err, "gs_topk_rows_u64")
+        return need
+
+    @staticmethod
+    def MinKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_rows, num_cols, row_stride, k, stream=None,
+                key_type=None):
+        return DeviceTopKRows64._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_rows, num_cols,
+                                     row_stride, k, False, False, stream, key_type)
+
+    @staticmethod
+    def MaxKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_rows, num_cols, row_stride, k, stream=None,
+                key_type=None):
+        return DeviceTopKRows64._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_rows, num_cols,
+                                     row_stride, k, True, False, stream, key_type)
+
+    @staticmethod
+    def MinPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols,
+                 row_stride, k, stream=None, key_type=None):
+        return DeviceTopKRows64._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows,
+                                     num_cols, row_stride, k, False, True, stream, key_type)
+
+    @staticmethod
+    def MaxPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols,
+                 row_stride, k, stream=None, key_type=None):
+        return DeviceTopKRows64._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows,
+                                     num_cols, row_stride, k, True, True, stream, key_type)
+
+    MaxK = staticmethod(DeviceTopKRows.MaxK)
+    Plan = staticmethod(DeviceTopKRows.Plan)
+
+
+def topk_rows64(keys, k, largest=False, values=None, indices=False, stream=None):
+    """topk_rows() for a 2-D tensor of 8-byte keys (int64, float64, uint64): the k smallest (largest=True: largest) of every row,
+    sorted, as (keys_out, values_out) of shape [rows, k], through gs_topk_rows_u64.
+
+    The checks and the return shapes are topk_rows()': the last dimension contiguous, rows at any stride >= cols, values a
+    4-byte tensor of the same shape and strides, indices=True for the column indices as int32 bit patterns of u32.  A k above
+    DeviceTopKRows64.MaxK() is served by gs_topk_u64 row by row on one workspace.  Any other key width raises TypeError."""
+    if values is not None and indices:
+        raise ValueError("topk_rows64: give values or indices=True, not both")
+    if keys.dim() != 2:
+        raise ValueError("topk_rows64: a 2-D tensor, not %d-D" % keys.dim())
+    rows, cols = keys.shape
+    if cols > 1 and keys.stride(1) != 1:
+        raise ValueError("topk_rows64: the last dimension must be contiguous")
+    if not 0 <= k <= cols:
+        raise ValueError(f"topk_rows64: need 0 <= k <= {cols}")
+    stride = keys.stride(0) if rows > 1 else cols
+    if rows > 1 and stride < cols:
+        raise ValueError("topk_rows64: rows overlap (stride %d < %d columns)" % (stride, cols))
+    if values is not None and (values.shape != keys.shape or values.element_size() != 4 or
+                               (cols > 1 and values.stride(1) != 1) or (rows > 1 and values.stride(0) != stride)):
+        raise ValueError("topk_rows64: values must have the keys' shape and strides and 4-byte elements")
+    if keys.element_size() != 8:
+        raise TypeError("topk_rows64: 64-bit keys only (int64, float64, uint64)")
+    _key_type64_of(keys, None, "topk_rows64")
+    has_values = values is not None or indices
+    keys_out = torch.empty((rows, k), dtype=keys.dtype, device=keys.device)
+    values_out = None
+    if has_values:
+        values_out = torch.empty((rows, k), dtype=values.dtype if values is not None else torch.int32, device=keys.device)
+    if k == 0 or rows == 0:
+        return keys_out, values_out
+    nbytes = lib.gs_topk_rows_u64_temp_bytes(rows, cols, k, int(has_values))
+    if nbytes == 0 and k > lib.gs_topk_rows_max_k() and rows * stride < (1 << 32) and rows * k < (1 << 32):
+        # refused for k alone: the flat top k of every row, one call each on one workspace
+        nbytes = lib.gs_topk_u64_temp_bytes(cols, k, int(has_values))
+        temp = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
+        if stream is not None:
+            temp.record_stream(stream)
+        for r in range(rows):
+            DeviceTopK64._run(temp, nbytes, keys[r], keys_out[r], None if values is None else values[r],
+                              values_out[r] if has_values else None, cols, k, largest, has_values, stream, None)
+        return keys_out, values_out
+    if nbytes == 0:
+        raise ValueError("topk_rows64: the entry point refuses this shape (rows * stride and rows * k must be below 2^32)")
+    temp = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
+    if stream is not None:
+        temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
+    DeviceTopKRows64._run(temp, nbytes, keys, keys_out, values, values_out, rows, cols, stride, k, largest, has_values, stream, None)
     return keys_out, values_out
 
 

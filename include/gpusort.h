@@ -617,6 +617,48 @@ int      gs_topk_rows_u16(void *d_temp, size_t temp_bytes,
                           uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k,
                           int descending, int key_type, void *stream);
 
+/* ------------------------------------------- top k of every row, 64-bit keys --
+ * gs_topk_rows_u32 for 64-bit keys, its kernels instantiated for them (gs_topk_rows.hip): a matrix of
+ * int64 ids or timestamps, double scores or 64-bit hashes -- a per-group ORDER BY ... LIMIT k, per-query candidate lists scored
+ * in double precision, a k-way merge of per-shard lists.  key_type is GS_KEY_U64, GS_KEY_I64 or GS_KEY_F64; doubles take the
+ * order stated at the enum (negative NaNs first, positive NaNs last, -0 before +0).  Row r of the result is bit for bit what
+ * gs_topk_u64 writes for that row alone: the first k of the stable sort of row r on the full 64-bit order-preserving image
+ * (complemented when descending), the lowest column indices where the cut falls inside a run of equal keys, the caller's
+ * bit patterns kept (NaN payloads included).  On the matrix (uint64_t)key << 32 of 32-bit keys, with the key type widened
+ * (U32 -> U64, I32 -> I64, F32 -> F64), it gives what gs_topk_rows_u32 gives on the keys themselves, the returned keys
+ * shifted right by 32, values and column indices unchanged.
+ * Forms: keys only; pairs; arguments (d_vals_in == NULL, d_vals_out != NULL: the u32 column index).  Values are u32 and sit
+ * at the same row_stride counted in elements; the outputs are dense with stride k.  The contract is gs_topk_rows_u32's: the
+ * inputs are never written, the values of the stride gap never influence a result, nothing outside [0, num_rows * k) of the
+ * outputs is written, d_temp anywhere, enqueue-only (no host read-back, allocation or synchronisation, no global atomic), the
+ * launches are a function of the arguments alone, so the call may be captured into a HIP graph; calls may follow each other
+ * on one stream with one workspace; two runs give identical bytes.  num_rows == 0, num_cols == 0 or k == 0 returns 0, writes
+ * nothing and needs no workspace (the query returns 0).
+ * Errors (hipErrorInvalidValue, checked before anything is enqueued, nothing written; the size query returns 0 for a refused
+ * shape): k > num_cols, k > gs_topk_rows_max_k() (1024), row_stride < num_cols, num_rows * row_stride >= 2^32,
+ * num_rows * k >= 2^32, a key_type other than GS_KEY_U64 / I64 / F64, d_vals_in without d_vals_out, a NULL key pointer,
+ * a NULL or too-small workspace, a key array not aligned to 8 bytes or a value array not aligned to 4, arrays that share a
+ * byte (inputs at (num_rows - 1) * row_stride + num_cols elements, outputs at num_rows * k; 8 bytes per key, 4 per value).
+ * Geometry: gs_topk_rows_u32's, on purpose -- path 1 up to 1024 columns, path 2 up to CH = 8192, path 3 chunked with the same
+ * next(n), gs_topk_rows_max_k() = 1024 -- so gs_topk_rows_plan above answers for all three entry points.  What the width
+ * adds: the kernels reduce the AND and the OR of a row's (or chunk's) images and leave out every digit pass of the wave sort
+ * and every round of the select whose byte is the same in all of them, so int64 ids below 2^24, timestamps of one day or
+ * widened 32-bit keys cost as many passes as they have bytes that differ, and a row of one key costs none.
+ * Workspace: candidate rows hold 8-byte keys and u32 columns.  With next(n), n1 and n2 as in gs_topk_rows_temp_bytes,
+ * hv = 1 with has_values else 0, and every term rounded up to 256 bytes:
+ *   8 * num_rows * n1                         the candidate keys of the even levels
+ * + hv * 4 * num_rows * n1                    their columns
+ * + 8 * num_rows * n2                         the candidate keys of the odd levels
+ * + hv * 4 * num_rows * n2                    their columns
+ * + 256 bytes of alignment slack.
+ * Never more than twice gs_topk_rows_temp_bytes of the same arguments.  Paths 1 and 2 copy no element into the workspace.  */
+size_t   gs_topk_rows_u64_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values);
+int      gs_topk_rows_u64(void *d_temp, size_t temp_bytes,
+                          const uint64_t *d_keys_in, const uint32_t *d_vals_in,
+                          uint64_t *d_keys_out, uint32_t *d_vals_out,
+                          uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k,
+                          int descending, int key_type, void *stream);
+
 /* ------------------------------------------------ top k of every ragged segment --
  * The k best of every segment of a flat array, the segments given by device offsets (gs_topk_rows.hip, DESIGN.md section
  * 10k): per-query candidate lists, variable-length sequences, per-image box scores, the neighbour lists of a CSR graph.

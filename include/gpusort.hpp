@@ -305,17 +305,30 @@ struct DeviceTopK {
 // query of 0 with a non-empty shape means the shape is refused (k > gs_topk_rows_max_k(), ...): such callers keep DeviceTopK
 // per row.  2-byte keys (unsigned short, short, _Float16, __half, __hip_bfloat16) go to gs_topk_rows_u16 and its size query:
 // the same definition on the 16-bit image, 32-bit values at the same row_stride; for a k it refuses, DeviceTopK serves 2-byte
-// keys too.
+// keys too.  8-byte keys (unsigned long long, long long, double, and long where it has 64 bits) go to gs_topk_rows_u64: the
+// same definition on the 64-bit image, 32-bit values; for a k it refuses, DeviceTopK serves 8-byte keys too.
 struct DeviceTopKRows {
     template <typename KeyT, typename ValueT>
     static hipError_t Dispatch(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
                                const ValueT *d_values_in, ValueT *d_values_out, uint64_t num_rows, uint64_t num_cols,
                                uint64_t row_stride, uint64_t k, bool descending, hipStream_t stream)
     {
-        static_assert(sizeof(KeyT) == 4 || sizeof(KeyT) == 2, "32-bit keys (unsigned int, int, float) or 16-bit keys");
+        static_assert(sizeof(KeyT) == 4 || sizeof(KeyT) == 2 || sizeof(KeyT) == 8,
+                      "32-bit keys (unsigned int, int, float), 16-bit keys or 64-bit keys");
         static_assert(sizeof(ValueT) == 4, "32-bit values only");
         const bool has_values = d_values_out != nullptr;
-        if constexpr (sizeof(KeyT) == 2) {   // unsigned short, short, _Float16, __half, __hip_bfloat16: gs_topk_rows_u16
+        if constexpr (sizeof(KeyT) == 8) {   // unsigned long long, long long, double (long where it has 64 bits): gs_topk_rows_u64
+            constexpr int kt = KeyTraits<KeyT>::type;
+            static_assert(kt == GS_KEY_U64 || kt == GS_KEY_I64 || kt == GS_KEY_F64, "a 64-bit key type");
+            if (d_temp_storage == nullptr) {
+                temp_storage_bytes = gs_topk_rows_u64_temp_bytes(num_rows, num_cols, k, has_values);
+                return hipSuccess;
+            }
+            return static_cast<hipError_t>(gs_topk_rows_u64(
+                d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint64_t *>(d_keys_in),
+                reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint64_t *>(d_keys_out),
+                reinterpret_cast<uint32_t *>(d_values_out), num_rows, num_cols, row_stride, k, descending ? 1 : 0, kt, stream));
+        } else if constexpr (sizeof(KeyT) == 2) {   // unsigned short, short, _Float16, __half, __hip_bfloat16: gs_topk_rows_u16
             constexpr int kt = KeyTraits<KeyT>::type;
             static_assert(kt == GS_KEY_U16 || kt == GS_KEY_I16 || kt == GS_KEY_F16 || kt == GS_KEY_BF16, "a 16-bit key type");
             if (d_temp_storage == nullptr) {
