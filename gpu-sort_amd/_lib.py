@@ -85,6 +85,8 @@ SIGNATURES = {
     "gs_topk_segmented_u32": (i32, [vp, sz, vp, vp, vp, vp, vp, u64, C.c_uint32, vp, vp, u64, i32, i32, vp]),
     "gs_topk_segmented_u16_temp_bytes": (sz, [u64, C.c_uint32, u64, i32]),
     "gs_topk_segmented_u16": (i32, [vp, sz, vp, vp, vp, vp, vp, u64, C.c_uint32, vp, vp, u64, i32, i32, vp]),
+    "gs_topk_segmented_u64_temp_bytes": (sz, [u64, C.c_uint32, u64, i32]),
+    "gs_topk_segmented_u64": (i32, [vp, sz, vp, vp, vp, vp, vp, u64, C.c_uint32, vp, vp, u64, i32, i32, vp]),
     "gs_topk_segmented_plan": (i32, [u64, C.c_uint32, u64, i32, C.POINTER(C.c_uint32)]),
     "gs_topk_segmented_status": (i32, [vp, u64, C.c_uint32, u64, i32, C.POINTER(C.c_uint32), vp]),
     "gs_msb_census": (i32, [vp, u64, i32, vp, vp]),

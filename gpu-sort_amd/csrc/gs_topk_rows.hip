@@ -2,9 +2,9 @@
 // matrix, for 32-bit keys, 16-bit keys (section 10i) and 64-bit keys (section 10n).  One set of kernels
 // and one host path, instantiated over a key-traits type (TrKey32, TrKey16, TrKey64); one geometry and one plan, so
 // gs_topk_rows_plan answers for all three entry points.
-// gs_topk_segmented_u32 (section 10k) and gs_topk_segmented_u16 (section 10l), the same for ragged segments given by device
-// offsets, follow them: they run the same device functions per record of lists that a classify kernel fills (see "ragged
-// segments" below), instantiated over the same two key-traits types.
+// gs_topk_segmented_u32 (section 10k), gs_topk_segmented_u16 (section 10l) and gs_topk_segmented_u64 (section 10o), the same for
+// ragged segments given by device offsets, follow them: they run the same device functions per record of lists that a classify
+// kernel fills (see "ragged segments" below), instantiated over the same three key-traits types.
 //
 // Row r of the result is what gs_topk_u32 writes for row r alone, bit for bit.  Every row has the same length, so the
 // launches are decided on the host from num_cols and k:
@@ -710,7 +710,7 @@ static int tr_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_
 }
 
 // ------------------------------------------------------------ ragged segments --
-// gs_topk_segmented_u32 / _u16 (DESIGN.md sections 10k, 10l): the k best of every segment of a flat array, the segments given by device
+// gs_topk_segmented_u32 / _u16 / _u64 (DESIGN.md sections 10k, 10l, 10o): the k best of every segment of a flat array, the segments given by device
 // offsets.  The lengths are on the device, so a classify kernel sorts the segments into six lists of records by length and
 // the kernels above run per record: the four wave classes of path 1 (<= 64 / 256 / 512 / 1024 elements), the workgroup of
 // path 2 (<= CH), and for longer segments level 0 of path 3 per (record, chunk) task followed by ONE streaming final per
@@ -850,15 +850,19 @@ __global__ __launch_bounds__(256) void topk_seg_classify_kernel(TsWs ws, const i
 }
 
 // topk_rows_wave_kernel per record of wave list LIST: base and length from the record, stores at seg * k + idx for idx < kept.
+// (The 64-bit wave sort decides its passes per wave: the four segments of a workgroup may run different sets, and no
+// workgroup barrier follows anywhere in this kernel.)
 template <typename KT, int WKPT, bool HV>
 __global__ __launch_bounds__(256) void topk_seg_wave_kernel(TsWs ws, const typename KT::T *__restrict__ keys,
                                                             const uint32_t *__restrict__ vals_in, typename KT::T *__restrict__ keys_out,
-                                                            uint32_t *__restrict__ vals_out, uint32_t num_items, uint32_t k, int flt, uint32_t x)
+                                                            uint32_t *__restrict__ vals_out, uint32_t num_items, uint32_t k, int flt, uint32_t x32)
 {
     using T = typename KT::T;
+    using I = typename KT::I;
+    const I x = KT::xmask(x32);
     constexpr int CAP = WKPT * WAVE, LIST = WKPT == 1 ? 0 : WKPT == 4 ? 1 : WKPT == 8 ? 2 : 3;
     __shared__ __attribute__((aligned(16))) uint32_t hist[4][RADIX];
-    __shared__ uint32_t stage_k[4][CAP];
+    __shared__ I stage_k[4][CAP];
     __shared__ uint32_t stage_v[HV ? 4 : 1][HV ? CAP : 1];
     const int w = wave_id(), lane = lane_id();
     uint32_t count = ws.state[LIST];
@@ -868,12 +872,13 @@ __global__ __launch_bounds__(256) void topk_seg_wave_kernel(TsWs ws, const typen
         if (!ts_load_rec(ws.list[LIST], t, num_items, ws.nseg, (uint32_t)CAP, base, cols, seg, row)) continue;
         const size_t in0 = base, out0 = (size_t)seg * k;
         const uint32_t kept = k < cols ? k : cols;
-        uint32_t key[WKPT], val[HV ? WKPT : 1];
+        I key[WKPT];
+        uint32_t val[HV ? WKPT : 1];
         const uint32_t last = cols - 1u;
 #pragma unroll
         for (int i = 0; i < WKPT; ++i) {
             const uint32_t idx = (uint32_t)(i * WAVE + lane);
-            key[i] = (uint32_t)__builtin_nontemporal_load(keys + in0 + (idx < last ? idx : last));   // past the end: the last element again
+            key[i] = (I)__builtin_nontemporal_load(keys + in0 + (idx < last ? idx : last));   // past the end: the last element again
         }
 #pragma unroll
         for (int i = 0; i < WKPT; ++i) {
@@ -902,15 +907,17 @@ template <typename KT, int WKPT, bool HV, bool CHUNK>
 __global__ __launch_bounds__(TR_THREADS) void topk_seg_block_kernel(TsWs ws, const typename KT::T *__restrict__ keys,
                                                                     const uint32_t *__restrict__ vals_in,
                                                                     typename KT::T *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
-                                                                    uint32_t num_items, uint32_t k, int flt, uint32_t x)
+                                                                    uint32_t num_items, uint32_t k, int flt, uint32_t x32)
 {
     using T = typename KT::T;
+    using I = typename KT::I;
+    const I x = KT::xmask(x32);
     constexpr int CAP = WKPT * WAVE;
     __shared__ __attribute__((aligned(16))) uint32_t h[RADIX];   // the select's histogram, then the finishing wave's counters
     __shared__ uint32_t scratch[8];
     __shared__ uint32_t sel[3];
     __shared__ uint32_t wcnt[2][TR_WAVES];
-    __shared__ uint32_t stage_k[CAP], sort_k[CAP];
+    __shared__ I stage_k[CAP], sort_k[CAP];
     __shared__ uint32_t stage_v[HV ? CAP : 1], sort_v[HV ? CAP : 1];
     const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
     const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
@@ -946,25 +953,27 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_block_kernel(TsWs ws, con
         const uint32_t lo = c * TR_CH, len = slen - lo < TR_CH ? slen - lo : TR_CH, keff = k < len ? k : len;
         const size_t in0 = (size_t)base + lo;
 
-        uint32_t img[TR_KPT];
+        I img[TR_KPT];
 #pragma unroll
         for (int u = 0; u < TR_KPT; ++u) {
             const uint32_t j = first + (uint32_t)u * WAVE;
-            img[u] = j < len ? (uint32_t)__builtin_nontemporal_load(keys + in0 + j) : 0u;
+            img[u] = j < len ? (I)__builtin_nontemporal_load(keys + in0 + j) : (I)0u;
         }
 #pragma unroll
         for (int u = 0; u < TR_KPT; ++u) img[u] = KT::in(img[u], flt, x);
         // where the result goes, and the segment the values come from: for the stores at the end.  The 16-bit kernels with
-        // values are two scalar registers short across the select; the 32-bit ones are not, and keep the code they had.
+        // values are two scalar registers short across the select; the 32-bit ones are not, and keep the code they had; the
+        // 64-bit ones are not either (at most 104 scalar registers, no spill: DESIGN.md section 10o).
         uint32_t slot = CHUNK ? row + c : seg, vbase = base, vlen = slen;
         if (sizeof(T) == 2) { slot = ts_in_vgpr(slot); vbase = ts_in_vgpr(vbase); vlen = ts_in_vgpr(vlen); }
 
         uint32_t less;
-        const uint32_t kth = tr_select<KT::BITS>(img, first, len, keff, tid, h, scratch, sel, less);
+        const I kth = tr_select<KT::BITS>(img, first, len, keff, tid, h, scratch, sel, less);
         tr_compact<HV, false, CAP>(img, first, len, keff, kth, less, w, lane, wcnt, stage_k, stage_v, nullptr, lo);
 
         if (w == 0) {   // finish: one wave sorts the keff staged pairs and stores them
-            uint32_t key[WKPT], val[HV ? WKPT : 1];
+            I key[WKPT];
+            uint32_t val[HV ? WKPT : 1];
 #pragma unroll
             for (int i = 0; i < WKPT; ++i) {
                 const uint32_t idx = (uint32_t)i * WAVE + lane;
@@ -1012,15 +1021,17 @@ __global__ __launch_bounds__(256) void topk_seg_expand_kernel(TsWs ws, uint32_t 
 template <typename KT, int WKPT, bool HV>
 __global__ __launch_bounds__(TR_THREADS) void topk_seg_final_kernel(TsWs ws, const uint32_t *__restrict__ vals_in,
                                                                     typename KT::T *__restrict__ keys_out, uint32_t *__restrict__ vals_out,
-                                                                    uint32_t num_items, uint32_t k, int flt, uint32_t x)
+                                                                    uint32_t num_items, uint32_t k, int flt, uint32_t x32)
 {
     using T = typename KT::T;
+    using I = typename KT::I;
+    const I x = KT::xmask(x32);
     constexpr int CAP = WKPT * WAVE;
     __shared__ __attribute__((aligned(16))) uint32_t h[RADIX];
     __shared__ uint32_t scratch[8];
     __shared__ uint32_t sel[3];
     __shared__ uint32_t wcnt[2][TR_WAVES];
-    __shared__ uint32_t stage_k[CAP], sort_k[CAP];
+    __shared__ I stage_k[CAP], sort_k[CAP];
     __shared__ uint32_t stage_v[HV ? CAP : 1], sort_v[HV ? CAP : 1];
     const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
     const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
@@ -1046,7 +1057,8 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_final_kernel(TsWs ws, con
         do {
             const uint32_t room = TR_CH - kc, left = n1 - pos, take = left < room ? left : room, len = kc + take;
             const uint32_t keff = k < len ? k : len;
-            uint32_t img[TR_KPT], val[HV ? TR_KPT : 1];
+            I img[TR_KPT];
+            uint32_t val[HV ? TR_KPT : 1];
 #pragma unroll
             for (int u = 0; u < TR_KPT; ++u) {
                 const uint32_t j = first + (uint32_t)u * WAVE;
@@ -1054,15 +1066,20 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_final_kernel(TsWs ws, con
                     img[u] = stage_k[j];
                     if (HV) val[u] = stage_v[j];
                 } else if (j < len) {
-                    img[u] = (uint32_t)__builtin_nontemporal_load(ck + pos + (j - kc));
+                    img[u] = (I)__builtin_nontemporal_load(ck + pos + (j - kc));
                     if (HV) val[u] = __builtin_nontemporal_load(cp + pos + (j - kc));
                 } else {
-                    img[u] = 0u;
+                    img[u] = (I)0u;
                     if (HV) val[u] = 0u;
                 }
             }
-            uint32_t less;   // (the select's first barrier orders the stage reads above before the compaction's writes)
-            const uint32_t kth = tr_select<KT::BITS>(img, first, len, keff, tid, h, scratch, sel, less);
+            // The select's first barrier orders the stage reads above before the compaction's writes.  The 64-bit select always
+            // has one: the barrier behind its `red` words comes first whatever rounds it then skips.  Its AND / OR run over
+            // img[] of this virtual chunk, the carried pairs and the new candidates alike, so a byte that only one carried
+            // element varies still gets its round.  Between this round's reads of `red` (and of the picked prefix) and the next
+            // round's writes lie the two barriers of the compaction.
+            uint32_t less;
+            const I kth = tr_select<KT::BITS>(img, first, len, keff, tid, h, scratch, sel, less);
             tr_compact_with<HV, CAP>(img, first, len, keff, kth, less, w, lane, wcnt, stage_k, stage_v,
                                      [&](int u, uint32_t) { return val[HV ? u : 0]; });
             kc = keff;
@@ -1070,7 +1087,8 @@ __global__ __launch_bounds__(TR_THREADS) void topk_seg_final_kernel(TsWs ws, con
         } while (pos < n1);
 
         if (w == 0) {
-            uint32_t key[WKPT], val[HV ? WKPT : 1];
+            I key[WKPT];
+            uint32_t val[HV ? WKPT : 1];
 #pragma unroll
             for (int i = 0; i < WKPT; ++i) {
                 const uint32_t idx = (uint32_t)i * WAVE + lane;
@@ -1110,7 +1128,7 @@ static inline TsGeom ts_geom(uint64_t num_items, uint64_t num_segments)
 }
 
 // the carve and the size query in one walk (base may be null: the query).  key_bytes: the width of a candidate image, the
-// only term that depends on the key; the state block comes first at both widths, so ts_status reads either workspace.
+// only term that depends on the key; the state block comes first at every width, so ts_status reads any of the workspaces.
 static size_t ts_carve(char *base, uint64_t num_items, uint64_t num_segments, uint64_t k, bool hv, size_t key_bytes, TsWs *ws)
 {
     const TsGeom g = ts_geom(num_items, num_segments);
@@ -1331,6 +1349,11 @@ size_t gs_topk_segmented_u16_temp_bytes(uint64_t num_items, uint32_t num_segment
     return ts_temp_bytes(num_items, num_segments, k, has_values, 2);
 }
 
+size_t gs_topk_segmented_u64_temp_bytes(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values)
+{
+    return ts_temp_bytes(num_items, num_segments, k, has_values, 8);
+}
+
 int gs_topk_segmented_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
                           uint32_t *d_vals_out, uint32_t *d_counts_out, uint64_t num_items, uint32_t num_segments,
                           const int32_t *d_begin_offsets, const int32_t *d_end_offsets, uint64_t k, int descending, int key_type, void *stream)
@@ -1344,6 +1367,14 @@ int gs_topk_segmented_u16(void *d_temp, size_t temp_bytes, const uint16_t *d_key
                           const int32_t *d_begin_offsets, const int32_t *d_end_offsets, uint64_t k, int descending, int key_type, void *stream)
 {
     return ts_run<TrKey16>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_counts_out, num_items, num_segments,
+                           d_begin_offsets, d_end_offsets, k, descending, key_type, stream);
+}
+
+int gs_topk_segmented_u64(void *d_temp, size_t temp_bytes, const uint64_t *d_keys_in, const uint32_t *d_vals_in, uint64_t *d_keys_out,
+                          uint32_t *d_vals_out, uint32_t *d_counts_out, uint64_t num_items, uint32_t num_segments,
+                          const int32_t *d_begin_offsets, const int32_t *d_end_offsets, uint64_t k, int descending, int key_type, void *stream)
+{
+    return ts_run<TrKey64>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_counts_out, num_items, num_segments,
                            d_begin_offsets, d_end_offsets, k, descending, key_type, stream);
 }
 

@@ -3,7 +3,8 @@
 DeviceTopK is two-phase like DeviceRadixSort (d_temp_storage=None returns the size); topk() is the convenience form that
 allocates outputs and workspace.  DeviceTopK16 is DeviceTopK for a flat array of 2-byte keys (gs_topk_u16: int16 / uint16 /
 float16 / bfloat16) and DeviceTopK64 for 8-byte keys (gs_topk_u64: int64 / uint64 / float64); topk() sends such tensors there.  DeviceTopKSegmented / topk_segmented() are the same for every ragged segment given by device offsets
-(gs_topk_segmented_u32, and gs_topk_segmented_u16 for int16 / uint16 / float16 / bfloat16 keys).  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
+(gs_topk_segmented_u32, and gs_topk_segmented_u16 for int16 / uint16 / float16 / bfloat16 keys); DeviceTopKSegmented64 /
+topk_segmented64() are the segmented form for 8-byte keys (gs_topk_segmented_u64: int64 / uint64 / float64).  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
 gs_topk_rows_u16 for int16 / uint16 / float16 / bfloat16 keys, in the order of GS_KEY_F16 / BF16 at the enum); DeviceTopKRows64 /
 topk_rows64() are the rows form for 8-byte keys (gs_topk_rows_u64: int64 / uint64 / float64).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
 (descending for the Max forms) on the same input: stable, keys in the caller's bit patterns, floats in the order of
@@ -597,4 +598,123 @@ def topk_segmented(keys, offsets, k, largest=False, values=None, indices=False, 
         temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
     DeviceTopKSegmented._run(temp, nbytes, keys.contiguous(), keys_out, values, values_out, counts, n, segs, begins, ends, k, largest,
                              has_values, stream, None)
+    return keys_out, values_out, counts
+
+
+class DeviceTopKSegmented64:
+    """DeviceTopKSegmented for a flat array of 64-bit keys (gs_topk_segmented_u64): MinKeys / MaxKeys / MinPairs / MaxPairs /
+    MaxK / Plan / Status.
+
+    The key type comes from the tensor's dtype (int64, float64, uint64) or from an explicit GS_KEY_U64 / I64 / F64; each
+    segment's result is what DeviceTopK64 gives for that segment alone, float64 in the order of GS_KEY_F32 at the enum.
+    Values, positions, counts and offsets are 4 bytes.  Two-phase: d_temp_storage=None returns the size, 0 for a shape the
+    entry point refuses.  Keys of any other width and any other key_type raise TypeError.  The geometry is
+    DeviceTopKSegmented's: Plan() is the same answer, and Status() reads a workspace of either class."""
+
+    @staticmethod
+    def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, d_counts_out, num_items,
+             num_segments, d_begin_offsets, d_end_offsets, k, descending, has_values, stream, key_type):
+        if key_type is not None and key_type not in _WIDE64:
+            raise TypeError("DeviceTopKSegmented64: key_type must be GS_KEY_U64 / I64 / F64")
+        need = lib.gs_topk_segmented_u64_temp_bytes(num_items, num_segments, k, int(has_values))
+        if d_temp_storage is None:
+            return need
+        if not isinstance(d_keys_in, torch.Tensor) or d_keys_in.element_size() != 8:
+            raise TypeError("DeviceTopKSegmented64: 64-bit keys only")
+        key_type = _key_type64_of(d_keys_in, key_type, "DeviceTopKSegmented64")
+        _check_buf(d_keys_in, num_items, "d_keys_in", 8)
+        _check_buf(d_keys_out, num_segments * k, "d_keys_out", 8)
+        _check_buf(d_begin_offsets, num_segments, "d_begin_offsets")
+        _check_buf(d_end_offsets, num_segments, "d_end_offsets")
+        if d_counts_out is not None:
+            _check_buf(d_counts_out, num_segments, "d_counts_out")
+        if has_values:
+            if d_values_in is not None:
+                _check_buf(d_values_in, num_items, "d_values_in")
+            _check_buf(d_values_out, num_segments * k, "d_values_out")
+        err = lib.gs_topk_segmented_u64(C.c_void_p(d_temp_storage.data_ptr()),
+                                        min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                        d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
+                                        d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
+                                        d_counts_out.data_ptr() if d_counts_out is not None else None, num_items, num_segments,
+                                        d_begin_offsets.data_ptr(), d_end_offsets.data_ptr(), k, int(descending), key_type,
+                                        _stream_ptr(stream))
+        check(err, "gs_topk_segmented_u64")
+        return need
+
+    @staticmethod
+    def MinKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_counts_out, num_items, num_segments, d_begin_offsets,
+                d_end_offsets, k, stream=None, key_type=None):
+        return DeviceTopKSegmented64._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, d_counts_out,
+                                          num_items, num_segments, d_begin_offsets, d_end_offsets, k, False, False, stream, key_type)
+
+    @staticmethod
+    def MaxKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_counts_out, num_items, num_segments, d_begin_offsets,
+                d_end_offsets, k, stream=None, key_type=None):
+        return DeviceTopKSegmented64._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, d_counts_out,
+                                          num_items, num_segments, d_begin_offsets, d_end_offsets, k, True, False, stream, key_type)
+
+    @staticmethod
+    def MinPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, d_counts_out, num_items,
+                 num_segments, d_begin_offsets, d_end_offsets, k, stream=None, key_type=None):
+        return DeviceTopKSegmented64._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out,
+                                          d_counts_out, num_items, num_segments, d_begin_offsets, d_end_offsets, k, False, True,
+                                          stream, key_type)
+
+    @staticmethod
+    def MaxPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, d_counts_out, num_items,
+                 num_segments, d_begin_offsets, d_end_offsets, k, stream=None, key_type=None):
+        return DeviceTopKSegmented64._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out,
+                                          d_counts_out, num_items, num_segments, d_begin_offsets, d_end_offsets, k, True, True,
+                                          stream, key_type)
+
+    MaxK = staticmethod(DeviceTopKSegmented.MaxK)
+    Plan = staticmethod(DeviceTopKSegmented.Plan)
+    Status = staticmethod(DeviceTopKSegmented.Status)
+
+
+def topk_segmented64(keys, offsets, k, largest=False, values=None, indices=False, stream=None, end_offsets=None):
+    """topk_segmented() for a 1-D tensor of 8-byte keys (int64, float64, uint64): the k smallest (largest=True: largest) of
+    every segment, sorted, as (keys_out [S, k], values_out [S, k] or None, counts [S] int32), through gs_topk_segmented_u64.
+
+    The arguments, the checks and the return shapes are topk_segmented()'s: int32 device offsets of S + 1 elements, or begins
+    and end_offsets; values a 4-byte tensor of the keys' length; indices=True for the positions within the segment as int32
+    bit patterns of u32.  The keys come back in the input dtype.  Any other key width raises TypeError."""
+    if values is not None and indices:
+        raise ValueError("topk_segmented64: give values or indices=True, not both")
+    if keys.dim() != 1 or keys.element_size() != 8:
+        raise TypeError("topk_segmented64: a 1-D tensor of 64-bit keys (int64, float64, uint64)")
+    _key_type64_of(keys, None, "topk_segmented64")
+    if offsets.dtype != torch.int32 or (end_offsets is not None and end_offsets.dtype != torch.int32):
+        raise TypeError("topk_segmented64: int32 offsets")
+    if end_offsets is None:
+        if offsets.numel() < 1:
+            raise ValueError("topk_segmented64: offsets needs S + 1 elements")
+        begins, ends, segs = offsets[:-1], offsets[1:], offsets.numel() - 1
+    else:
+        if end_offsets.numel() != offsets.numel():
+            raise ValueError("topk_segmented64: as many ends as begins")
+        begins, ends, segs = offsets, end_offsets, offsets.numel()
+    n = keys.numel()
+    if k < 0:
+        raise ValueError("topk_segmented64: need k >= 0")
+    if values is not None and (values.numel() != n or values.element_size() != 4 or values.dim() != 1):
+        raise ValueError("topk_segmented64: values must have the keys' length and 4-byte elements")
+    has_values = values is not None or indices
+    keys_out = torch.empty((segs, k), dtype=keys.dtype, device=keys.device)
+    values_out = None
+    if has_values:
+        values_out = torch.empty((segs, k), dtype=values.dtype if values is not None else torch.int32, device=keys.device)
+    counts = torch.zeros(segs, dtype=torch.int32, device=keys.device)
+    if k == 0 or segs == 0 or n == 0:
+        return keys_out, values_out, counts
+    nbytes = lib.gs_topk_segmented_u64_temp_bytes(n, segs, k, int(has_values))
+    if nbytes == 0:
+        raise ValueError("topk_segmented64: the entry point refuses this shape (k <= %d, fewer than 2^31 keys, segments * k below "
+                         "2^32)" % lib.gs_topk_rows_max_k())
+    temp = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
+    if stream is not None:
+        temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
+    DeviceTopKSegmented64._run(temp, nbytes, keys.contiguous(), keys_out, values, values_out, counts, n, segs, begins, ends, k,
+                               largest, has_values, stream, None)
     return keys_out, values_out, counts

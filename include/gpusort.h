@@ -718,15 +718,15 @@ int    gs_topk_segmented_u32(void *d_temp, size_t temp_bytes,
                              uint64_t num_items, uint32_t num_segments,
                              const int32_t *d_begin_offsets, const int32_t *d_end_offsets,
                              uint64_t k, int descending, int key_type, void *stream);
-/* What gs_topk_segmented_u32 -- and gs_topk_segmented_u16 below, which has the same geometry -- launches for a shape: a pure
+/* What gs_topk_segmented_u32 -- and gs_topk_segmented_u16 / _u64 below, which have the same geometry -- launches for a shape: a pure
  * host function (no device, no workspace, no synchronisation).
  * out[0] = bit mask of the launch groups the call enqueues (bit 0 the wave kernels, bit 1 the workgroup kernel, bit 2 the
  * long-segment kernels), out[1] = kernel launches (6, 7 or 10: the zeroing and the classify kernel included), out[2] = CH,
  * out[3] = Lmax, out[4] = Tmax, out[5] = gs_topk_rows_max_k(), out[6..7] = 0.  A refused shape (k > max k, num_items >= 2^31,
  * num_segments * k >= 2^32) returns hipErrorInvalidValue and all zeros; a no-op shape returns 0 and all zeros.              */
 int    gs_topk_segmented_plan(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values, uint32_t out[8]);
-/* What the last gs_topk_segmented_u32 or gs_topk_segmented_u16 on d_temp (same num_items, num_segments, k and has_values)
- * decided (the state block is the first term of both workspaces, so a workspace of either entry point is read as it is), after
+/* What the last gs_topk_segmented_u32, _u16 or _u64 on d_temp (same num_items, num_segments, k and has_values)
+ * decided (the state block is the first term of every workspace, so a workspace of any entry point is read as it is), after
  * synchronising `stream`: out[0..3] = segments in the four wave lists (<= 64, <= 256, <= 512, <= 1024 elements), out[4] =
  * the workgroup list (1025 .. CH), out[5] = the long list (> CH, dropped ones not counted), out[6] = chunk tasks, out[7] =
  * dropped segments.  All zeros for a no-op shape.  Diagnostic: tests and benches read it.                                   */
@@ -766,6 +766,44 @@ size_t gs_topk_segmented_u16_temp_bytes(uint64_t num_items, uint32_t num_segment
 int    gs_topk_segmented_u16(void *d_temp, size_t temp_bytes,
                              const uint16_t *d_keys_in, const uint32_t *d_vals_in,
                              uint16_t *d_keys_out, uint32_t *d_vals_out, uint32_t *d_counts_out,
+                             uint64_t num_items, uint32_t num_segments,
+                             const int32_t *d_begin_offsets, const int32_t *d_end_offsets,
+                             uint64_t k, int descending, int key_type, void *stream);
+
+/* -------------------------------- top k of every ragged segment, 64-bit keys --
+ * gs_topk_segmented_u32 for 64-bit keys, its kernels instantiated for them (gs_topk_rows.hip): int64 ids
+ * or timestamps, double scores or 64-bit hashes grouped by device offsets -- per-query candidate lists, a per-group
+ * ORDER BY ... LIMIT k, per-sequence sampling with ragged lengths.  key_type is GS_KEY_U64, GS_KEY_I64 or GS_KEY_F64; doubles
+ * take the order stated at the enum (negative NaNs first, positive NaNs last, -0 before +0).
+ * With b, e, len and kept = min(k, len) as at gs_topk_segmented_u32, d_keys_out[s * k .. s * k + kept) and the same range of
+ * d_vals_out are bit for bit what gs_topk_u64 writes for d_keys_in[b .. e) alone with k = kept; d_counts_out[s] = kept; the
+ * slots behind are NOT written.  Equivalently it is what gs_topk_segmented_u32 gives on (uint64_t)key << 32 of 32-bit keys with
+ * the key type widened (U32 -> U64, I32 -> I64, F32 -> F64) and the returned keys shifted right by 32, values and positions
+ * unchanged.  Forms: keys only; pairs; arguments (d_vals_in == NULL, d_vals_out != NULL: the u32 position within the clamped
+ * segment).
+ * The contract is gs_topk_segmented_u32's, word for word, with 8-byte keys: the key arrays need 8-byte alignment (a pointer
+ * at 4 mod 8 is refused with hipErrorInvalidValue and nothing is written); the overlap checks count 8 bytes per key; values,
+ * counts and offsets stay u32 / int32, aligned to 4.  Unchanged: the limits (k <= gs_topk_rows_max_k(), num_items < 2^31,
+ * num_segments * k < 2^32), the order of the checks, refused calls write nothing and their size query is 0, no-op shapes
+ * return 0 with a size query of 0, segments of up to CH = 8192 elements may overlap freely, the drop rule for long segments
+ * that find no room, enqueue-only and graph-capturable on one plain stream, identical output bytes on two runs.  A caller with
+ * a few huge segments keeps gs_topk_u64 per segment.
+ * Geometry: gs_topk_segmented_u32's, on purpose -- six lists, CH = 8192, the same Lmax and Tmax, the same 6 / 7 / 10 launches
+ * for a shape -- so gs_topk_segmented_plan above answers for all three entry points, and gs_topk_segmented_status reads the
+ * state of a workspace of this one as it is (the state block is the first term of all three workspaces).  What the width adds
+ * is gs_topk_rows_u64's: the kernels reduce the AND and the OR of a segment's (or chunk's, or streaming round's) images and
+ * leave out every digit pass and every select round whose byte is the same in all of them.
+ * Workspace: a pure host function of its arguments, a multiple of 256, monotone in each of them.  The candidate rows hold
+ * 8-byte images and u32 positions.  With S, Lmax and Tmax as in gs_topk_segmented_temp_bytes, hv = 1 with has_values else 0,
+ * and _a() rounding up to 256 bytes:
+ *   4096 + 5 * _a(16 * S) + _a(16 * Lmax) + _a(8 * Tmax) + _a(8 * k * Tmax) + hv * _a(4 * k * Tmax) + 256
+ * (the state block, the five lists, the long records, the chunk tasks, the candidate images, their positions, the alignment
+ * slack).  The long-segment terms vanish when num_items <= CH.  Never more than twice gs_topk_segmented_temp_bytes of the
+ * same arguments.  */
+size_t gs_topk_segmented_u64_temp_bytes(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values);
+int    gs_topk_segmented_u64(void *d_temp, size_t temp_bytes,
+                             const uint64_t *d_keys_in, const uint32_t *d_vals_in,
+                             uint64_t *d_keys_out, uint32_t *d_vals_out, uint32_t *d_counts_out,
                              uint64_t num_items, uint32_t num_segments,
                              const int32_t *d_begin_offsets, const int32_t *d_end_offsets,
                              uint64_t k, int descending, int key_type, void *stream);

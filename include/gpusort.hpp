@@ -390,7 +390,8 @@ struct DeviceTopKRows {
 // gets that number; the slots behind it are not written.  The forms and the two phases are DeviceTopKRows'; in the pairs forms
 // d_values_in == nullptr writes the elements' positions within their segment.  A size query of 0 with a non-empty shape means
 // the shape is refused (k > gs_topk_rows_max_k(), num_items >= 2^31, ...).  32-bit keys (gs_topk_segmented_u32) or 16-bit keys
-// (unsigned short, short, _Float16, __half, __hip_bfloat16: gs_topk_segmented_u16), chosen by sizeof(KeyT); values stay 32-bit.
+// (unsigned short, short, _Float16, __half, __hip_bfloat16: gs_topk_segmented_u16) or 64-bit keys (unsigned long long, long
+// long, double, and long where it has 64 bits: gs_topk_segmented_u64), chosen by sizeof(KeyT); values stay 32-bit.
 struct DeviceTopKSegmented {
     template <typename KeyT, typename ValueT>
     static hipError_t Dispatch(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
@@ -398,11 +399,23 @@ struct DeviceTopKSegmented {
                                uint32_t num_segments, const int *d_begin_offsets, const int *d_end_offsets, uint64_t k,
                                bool descending, hipStream_t stream)
     {
-        static_assert(sizeof(KeyT) == 4 || sizeof(KeyT) == 2,
-                      "32-bit keys (unsigned int, int, float) or 16-bit keys (unsigned short, short, half, bfloat16)");
+        static_assert(sizeof(KeyT) == 4 || sizeof(KeyT) == 2 || sizeof(KeyT) == 8,
+                      "32-bit keys (unsigned int, int, float), 16-bit keys (unsigned short, short, half, bfloat16) or 64-bit keys");
         static_assert(sizeof(ValueT) == 4, "32-bit values only");
         const bool has_values = d_values_out != nullptr;
-        if constexpr (sizeof(KeyT) == 2) {   // gs_topk_segmented_u16
+        if constexpr (sizeof(KeyT) == 8) {   // unsigned long long, long long, double (long where it has 64 bits): gs_topk_segmented_u64
+            constexpr int kt = KeyTraits<KeyT>::type;
+            static_assert(kt == GS_KEY_U64 || kt == GS_KEY_I64 || kt == GS_KEY_F64, "a 64-bit key type");
+            if (d_temp_storage == nullptr) {
+                temp_storage_bytes = gs_topk_segmented_u64_temp_bytes(num_items, num_segments, k, has_values);
+                return hipSuccess;
+            }
+            return static_cast<hipError_t>(gs_topk_segmented_u64(
+                d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint64_t *>(d_keys_in),
+                reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint64_t *>(d_keys_out),
+                reinterpret_cast<uint32_t *>(d_values_out), d_counts_out, num_items, num_segments, d_begin_offsets, d_end_offsets,
+                k, descending ? 1 : 0, kt, stream));
+        } else if constexpr (sizeof(KeyT) == 2) {   // gs_topk_segmented_u16
             constexpr int kt = KeyTraits<KeyT>::type;
             static_assert(kt == GS_KEY_U16 || kt == GS_KEY_I16 || kt == GS_KEY_F16 || kt == GS_KEY_BF16, "a 16-bit key type");
             if (d_temp_storage == nullptr) {
