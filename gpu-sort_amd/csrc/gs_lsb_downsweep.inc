@@ -85,9 +85,10 @@ __device__ uint32_t gs_phase_buf[131072 * 16];   // [block][phase], n <= 2^30
 // group), and wave 0 claims count(d) places for every digit d with one returning add per digit.  The adds are issued after
 // barrier 1 and their returns are used just before barrier 3, behind the LDS scatter.  A tile whose first and last key
 // differ in the lower digit stores nothing and appends its index to irr[1..] (count in irr[0]): another kernel places it.
+// RANK_FREE = true (cursor mode only): step 2 ranks with one returning LDS add per key instead of the stable ballot match.
 constexpr uint32_t PIPE_SPIN_LIMIT = 1u << 18;   // polls (each >= one memory round trip) before a wait gives up
 
-template <bool HAS_VALUES, bool TAIL, int TW, bool BIG, bool PIPE, bool OFF64 = false, bool CURSOR = false>
+template <bool HAS_VALUES, bool TAIL, int TW, bool BIG, bool PIPE, bool OFF64 = false, bool CURSOR = false, bool RANK_FREE = false>
 __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES, OFF64> &sm, const uint32_t t,
     const uint32_t *__restrict__ keys_in, uint32_t *__restrict__ keys_out, const uint32_t *__restrict__ vals_in,
     uint32_t *__restrict__ vals_out, const uint32_t *__restrict__ spine, const uint16_t *__restrict__ prefix16,
@@ -276,7 +277,14 @@ __device__ __forceinline__ void downsweep_tile(DownsweepSmem<HAS_VALUES, OFF64> 
     GS_PHASE(1);                                   // load wait
 #pragma unroll
     for (int i = 0; i < LSB_KPT; ++i) key[i] = tw_in(key[i]);
-    {
+    if constexpr (RANK_FREE) {
+        // cursor mode, where the finish sorts every group: any order inside a digit run will do, so a key's rank is what one returning
+        // add on the wave's own counter gives -- no 32-instruction ballot match per key, which is what makes this kernel VALU-bound
+        // (gs_lsb_plan.hip, GS_PLAN_RANK_FREE; DESIGN.md section 3 has the measurement)
+        static_assert(!RANK_FREE || CURSOR, "only the cursor scatter is free to rank in any order");
+#pragma unroll
+        for (int i = 0; i < LSB_KPT; ++i) pos[i] = __hip_atomic_fetch_add(&my[digit(key[i])], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    } else {
         uint32_t d_prev = 0, plo = 0, phi = 0;
 #pragma unroll
         for (int i = 0; i <= LSB_KPT; ++i) {

@@ -288,7 +288,11 @@ __global__ __launch_bounds__(RADIX) void lsb_plan_reduce_kernel(const uint32_t *
 // writes the decision: PLANNED if and only if no look workgroup reported a wrapped counter, the sizes add up to n and no
 // group exceeds the largest local sort.  The level records of the finish are (re)written here on every sort, so stale
 // lists of an earlier sort on the same workspace never run.
-__global__ __launch_bounds__(RADIX) void lsb_plan_decide_kernel(PlanBlock *__restrict__ plan, uint32_t n, uint32_t parts, uint32_t cursor_on)
+// `mailbox` (or null): the host's look at the decision (see PlanPeek) -- the plan block's head and the scatter mode, written to
+// a pinned host mailbox by the thread that decides; the host reads them behind an event recorded after this launch.
+constexpr int PLAN_PEEK_WORDS = 9;   // route, max_group, nonempty, tasks[4], total, cursor_mode
+__global__ __launch_bounds__(RADIX) void lsb_plan_decide_kernel(PlanBlock *__restrict__ plan, uint32_t n, uint32_t parts, uint32_t cursor_on,
+                                                                uint32_t *mailbox)
 {
     __shared__ uint32_t s_base, s_total, s_max, s_nz, s_cls[MSB_NCLASS], s_clsbase[MSB_NCLASS];
     const uint32_t tid = threadIdx.x, b = blockIdx.x;
@@ -336,20 +340,20 @@ __global__ __launch_bounds__(RADIX) void lsb_plan_decide_kernel(PlanBlock *__res
             plan->ups_skip[q] = planned && q != 1 ? 1u : 0u;   // PLANNED: slot 1 scans and scatters on the look's counts
         }
         plan->offsets[PLAN_GROUPS] = n;
-        plan->cursor_mode = planned && cursor_on ? 1u : 0u;
+        const uint32_t mode = planned && cursor_on ? 1u : 0u;
+        plan->cursor_mode = mode;
+        if (mailbox) {
+            mailbox[0] = planned ? PLAN_PLANNED : PLAN_CLASSIC;
+            mailbox[1] = s_max;
+            mailbox[2] = s_nz;
+            for (int c = 0; c < MSB_NCLASS; ++c) mailbox[3 + c] = planned ? s_cls[c] : 0u;
+            mailbox[3 + MSB_NCLASS] = s_total;
+            mailbox[PLAN_PEEK_WORDS - 1] = mode;
+            __threadfence_system();
+        }
     }
 }
-
-// The host's look at the decision (see PlanPeek): the plan block's head and the scatter mode, to a pinned host mailbox.
-constexpr int PLAN_PEEK_WORDS = 9;   // route, max_group, nonempty, tasks[4], total, cursor_mode
-static_assert(offsetof(PlanBlock, total) == (PLAN_PEEK_WORDS - 2) * sizeof(uint32_t), "the head is eight words");
-__global__ void lsb_plan_peek_kernel(const PlanBlock *__restrict__ plan, uint32_t *mailbox)
-{
-    const uint32_t *head = &plan->route;
-    for (int i = 0; i < PLAN_PEEK_WORDS - 1; ++i) mailbox[i] = head[i];
-    mailbox[PLAN_PEEK_WORDS - 1] = plan->cursor_mode;
-    __threadfence_system();
-}
+static_assert(offsetof(PlanBlock, total) == (PLAN_PEEK_WORDS - 2) * sizeof(uint32_t) && PLAN_PEEK_WORDS == 5 + MSB_NCLASS, "the head is eight words");
 
 // The finish's task lists: one task per non-empty group, in group order inside each class.  Nothing when CLASSIC.
 struct PlanLists { MsbTask *tasks[MSB_NCLASS]; uint32_t cap[MSB_NCLASS]; };
@@ -412,9 +416,8 @@ __global__ __launch_bounds__(LSB_THREADS, 6) void lsb_plan_downsweep_kernel(cons
 //             of the groups (d2, d1), and the list of straddling tiles to empty (its words are the look's flags, which the
 //             decide kernel's workgroups are still reading when the mode is written); no look at the keys;
 //   scatter   downsweep_tile in CURSOR mode on the full tiles; the partial tile's launch returns;
-//   irregular places the keys of the listed tiles (one workgroup each) and of the partial tile (the last workgroup), every
-//             key by an add of 1 on its group's cursor.  The keys of a wave that share a group share one add where that is
-//             cheap: the first two groups met are one add each (sorted input: one or two groups per tile).
+//   irregular places the keys of the listed tiles (one workgroup each) and of the partial tile (the last workgroup): see
+//             lsb_plan_irregular_kernel.
 template <bool PLAIN>
 __global__ __launch_bounds__(LSB_THREADS, GS_EXP_UPS_WPE) void lsb_plan_upsweep2_kernel(const uint32_t *__restrict__ keys,
                                                                         uint32_t *__restrict__ spine, uint16_t *__restrict__ prefix16,
@@ -462,46 +465,137 @@ __global__ __launch_bounds__(LSB_THREADS, 6) void lsb_plan_scatter2_kernel(const
     }
 }
 
-__global__ __launch_bounds__(LSB_THREADS) void lsb_plan_irregular_kernel(const uint32_t *__restrict__ keys_in, uint32_t *__restrict__ keys_out,
-                                                                         const PlanBlock *__restrict__ plan, uint32_t *__restrict__ cursor,
-                                                                         uint32_t n)
+// The cursor set-up and the scatter of a sort whose host has seen PLANNED and cursor mode before it enqueues the second slot
+// (lsb_plan_slot2_cursor): the set-up is the 65536 words and nothing else -- no workgroup per chunk, no upsweep LDS -- and the
+// scatter takes its digit position from the host and its mode from the template, so it reads nothing from the plan block
+// but the list of straddling tiles it appends to.  The partial tile is the follow-up kernel's.
+__global__ __launch_bounds__(LSB_THREADS) void lsb_plan_cursor_init_kernel(PlanBlock *__restrict__ plan, uint32_t *__restrict__ cursor)
 {
-    if (!plan->cursor_mode) return;
+    const uint32_t i = blockIdx.x * (uint32_t)LSB_THREADS + threadIdx.x;   // the grid covers the cursors exactly
+    if (i == 0) plan->irr[0] = 0;
+    cursor[i] = plan->offsets[((i & (uint32_t)(RADIX - 1)) << RADIX_BITS) | (i >> RADIX_BITS)];
+}
+static_assert(PLAN_GROUPS % LSB_THREADS == 0, "whole workgroups set the cursors");
+
+// GS_PLAN_RANK_FREE (default 1; 0: the stable ballot-match ranking, for A/B builds): the order of the keys inside a digit run
+// does not show in the result, so this scatter ranks with one returning add per key on the wave's own LDS counters.
+#ifndef GS_PLAN_RANK_FREE
+#define GS_PLAN_RANK_FREE 1
+#endif
+template <bool BIG>
+__global__ __launch_bounds__(LSB_THREADS, 6) void lsb_plan_scatter2_cursor_kernel(const uint32_t *__restrict__ keys_in, uint32_t *__restrict__ keys_out,
+                                                                                  uint32_t *__restrict__ irr, uint32_t *__restrict__ cursor,
+                                                                                  PassParams p)
+{
+    __shared__ __attribute__((aligned(16))) DownsweepSmem<false> sm;
+    const uint32_t full_tiles = p.n / (uint32_t)LSB_TILE;
+    if (blockIdx.x >= full_tiles) return;
+    const uint32_t t = tile_of_item_wide(blockIdx.x, full_tiles);
+    constexpr bool RANK_FREE = GS_PLAN_RANK_FREE != 0;
+    downsweep_tile<false, false, 0, BIG, false, false, true, RANK_FREE>(sm, t, keys_in, keys_out, nullptr, nullptr, nullptr, nullptr, nullptr, p, nullptr,
+                                                                        0u, nullptr, threadIdx.x, nullptr, cursor, irr, PLAN_IRR_CAP);
+}
+
+// The follow-up kernel: one workgroup per listed tile and one for the partial tile, LSB_KPT rounds of LSB_THREADS keys.  Every
+// key's place comes from an add on its group's cursor, and a round trip to the cursors is microseconds, so nothing here
+// waits for memory more than three times: all loads of the tile are issued (clamped indices for the partial tile), then all
+// claims, and only then are places computed and keys stored.
+// The tile is sorted on d1 (bits 16-23), and nearly always holds two values of it, so the groups of its first and of its last
+// d1 are counted in LDS -- a returning add per key gives its rank inside the tile's share of the group -- and claimed with one
+// add per group and tile: 512 adds on the cursors at the most, not 8192 (with an add per key the launch was bound by the
+// rate of the adds, not by their latency: 255 tiles of uniform keys, 2.1 M adds, took 71 us with all of them in flight
+// against 63 us one after the other).  Keys of a d1 in between (a tile with three and more values) claim for themselves;
+// the claims of a wave round there: the first two groups met are one add each, by their first lane, every lane left over
+// adds for itself -- so a lane issues at most one such add per round.
+constexpr int PLAN_IRR_ROUNDS = LSB_TILE / LSB_THREADS;
+static_assert(LSB_THREADS == 2 * RADIX, "the follow-up kernel: one thread per group of the tile's first and last d1");
+__global__ __launch_bounds__(LSB_THREADS, 4) void lsb_plan_irregular_kernel(const uint32_t *__restrict__ keys_in, uint32_t *__restrict__ keys_out,
+                                                                            const PlanBlock *__restrict__ plan, uint32_t *__restrict__ cursor,
+                                                                            uint32_t n)
+{
+    __shared__ uint32_t edge[2 * RADIX];           // [first d1 | last d1][d2]: keys of the tile, then the places claimed for them
+    // (the three words of the plan block in one round trip, not one behind the other)
+    const uint32_t mode = plan->cursor_mode, count = plan->irr[0], t = plan->irr[blockIdx.x < PLAN_IRR_CAP ? 1u + blockIdx.x : 1u];
+    asm volatile("" ::"s"(mode), "s"(count), "s"(t));   // (all three requested before the first is looked at)
+    if (!mode) return;
     const uint32_t full_tiles = n / (uint32_t)LSB_TILE;
     uint32_t lo, len;
     if (blockIdx.x == PLAN_IRR_CAP) {
         lo = full_tiles * (uint32_t)LSB_TILE;
         len = n - lo;
+        if (len == 0u) return;                     // (never launched then)
     } else {
-        const uint32_t listed = plan->irr[0] < PLAN_IRR_CAP ? plan->irr[0] : PLAN_IRR_CAP;
+        const uint32_t listed = count < PLAN_IRR_CAP ? count : PLAN_IRR_CAP;
         if (blockIdx.x >= listed) return;
-        const uint32_t t = plan->irr[1u + blockIdx.x];
         if (t >= full_tiles) return;
         lo = t * (uint32_t)LSB_TILE;
         len = (uint32_t)LSB_TILE;
     }
     const int lane = lane_id();
-    // (whole waves enter every round: i - lane is the wave's first index)
-    for (uint32_t i = threadIdx.x; i - (uint32_t)lane < len; i += (uint32_t)LSB_THREADS) {
-        const bool have = i < len;
-        const uint32_t k = have ? keys_in[lo + i] : 0u;
-        const uint32_t g = k >> 16, c = ((g & (uint32_t)(RADIX - 1)) << RADIX_BITS) | (g >> RADIX_BITS);   // cursor of group (d2, d1): [d1][d2]
-        unsigned long long rest = __builtin_amdgcn_ballot_w64(have);
-        uint32_t at = 0;
+    const uint32_t tid = threadIdx.x, last = len - 1u;
+    const uint32_t *src = keys_in + lo;
+    uint32_t k[PLAN_IRR_ROUNDS];
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            if (rest == 0ull) break;
-            const int lead = __builtin_amdgcn_readfirstlane(__builtin_ctzll(rest));
-            const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)c, lead);
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(have && c == c0) & rest;
-            uint32_t first = 0;
-            if (lane == lead) first = __hip_atomic_fetch_add(cursor + c0, (uint32_t)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            first = (uint32_t)__builtin_amdgcn_readlane((int)first, lead);
-            if ((m >> lane) & 1ull) at = first + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            rest &= ~m;
+    for (int r = 0; r < PLAN_IRR_ROUNDS; ++r) {
+        const uint32_t i = tid + (uint32_t)r * (uint32_t)LSB_THREADS;
+        k[r] = src[i < last ? i : last];
+    }
+    const uint32_t k_first = src[0], k_last = src[last];
+    asm volatile("" ::"s"(k_first), "s"(k_last));       // (both requested before either is looked at)
+    const uint32_t d1_first = (k_first >> 16) & (uint32_t)(RADIX - 1), d1_last = (k_last >> 16) & (uint32_t)(RADIX - 1);
+    edge[tid] = 0;
+    __syncthreads();
+    // per round, claim[r] = the lane whose add covers this key | this key's rank among that add's keys << 8 | what this lane
+    // itself adds to its own group's cursor << 16 (0: nothing; always 0 for a key counted in LDS); got[r] = what the lane's
+    // own add returned: the key's rank in `edge`, or the place claimed on the cursor
+    uint32_t claim[PLAN_IRR_ROUNDS], got[PLAN_IRR_ROUNDS];
+    auto cursor_of = [](uint32_t key) {            // cursor of group (d2, d1): [d1][d2]
+        const uint32_t g = key >> 16;
+        return ((g & (uint32_t)(RADIX - 1)) << RADIX_BITS) | (g >> RADIX_BITS);
+    };
+    auto edge_of = [&](uint32_t key) {             // the key's counter in `edge`, or 2 * RADIX: it has none
+        const uint32_t d1 = (key >> 16) & (uint32_t)(RADIX - 1);
+        return d1 == d1_first ? key >> 24 : d1 == d1_last ? (uint32_t)RADIX + (key >> 24) : 2u * (uint32_t)RADIX;
+    };
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int r = 0; r < PLAN_IRR_ROUNDS; ++r) {
+        const bool have = tid + (uint32_t)r * (uint32_t)LSB_THREADS < len;
+        const uint32_t e = edge_of(k[r]), c = cursor_of(k[r]);
+        const bool mid = have && e == 2u * (uint32_t)RADIX;
+        got[r] = 0;
+        if (have && !mid) got[r] = atomicAdd(&edge[e], 1u);
+        unsigned long long rest = __builtin_amdgcn_ballot_w64(mid);
+        uint32_t cl = (uint32_t)lane;
+        if (rest != 0ull) {                        // (wave-uniform; the usual tile has no such key)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {          // (nothing left: m = 0, and nothing happens)
+                const int lead = __builtin_amdgcn_readfirstlane(rest ? __builtin_ctzll(rest) : 0);
+                const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)c, lead);
+                const unsigned long long m = __builtin_amdgcn_ballot_w64(mid && c == c0) & rest;
+                if ((m >> lane) & 1ull) cl = (uint32_t)lead | ((uint32_t)__popcll(m & below) << 8) | (lane == lead ? (uint32_t)__popcll(m) << 16 : 0u);
+                rest &= ~m;
+            }
+            if ((rest >> lane) & 1ull) cl |= 1u << 16;
         }
-        if ((rest >> lane) & 1ull) at = __hip_atomic_fetch_add(cursor + c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (have && at < n) keys_out[at] = k;
+        claim[r] = cl;
+    }
+#pragma unroll
+    for (int r = 0; r < PLAN_IRR_ROUNDS; ++r)
+        if (claim[r] >> 16) got[r] = __hip_atomic_fetch_add(cursor + cursor_of(k[r]), claim[r] >> 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    {   // thread tid claims for the counter it zeroed, and leaves the place in its stead
+        const uint32_t mine = edge[tid], d1 = tid < (uint32_t)RADIX ? d1_first : d1_last;
+        if (mine) edge[tid] = __hip_atomic_fetch_add(cursor + ((d1 << RADIX_BITS) | (tid & (uint32_t)(RADIX - 1))), mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < PLAN_IRR_ROUNDS; ++r) {
+        const bool have = tid + (uint32_t)r * (uint32_t)LSB_THREADS < len;
+        const uint32_t e = edge_of(k[r]);
+        uint32_t at = (uint32_t)__shfl((int)got[r], (int)(claim[r] & 0xffu)) + ((claim[r] >> 8) & 0xffu);
+        if (e < 2u * (uint32_t)RADIX) at += edge[e];
+        if (have && at < n) keys_out[at] = k[r];
     }
 }
 
@@ -647,7 +741,7 @@ static int lsb_plan_slot2(const uint32_t *kin, uint32_t *kout, const LsbWorkspac
 // the look: one workgroup per CU at most, each with room for its 128 KiB table in the alternate buffer; its spine and
 // prefix16 are those of a pass at shift 16 (lsb_make_params' grid)
 static int lsb_plan_look(const uint32_t *keys, uint32_t *alt, const LsbWorkspace &ws, PlanBlock *plan, uint64_t n, const PassParams &tw,
-                         hipStream_t s)
+                         hipStream_t s, uint32_t *mailbox = nullptr)
 {
     const uint32_t parts = (uint32_t)(n / PLAN_WORDS < PLAN_LOOK_MAX_GRID ? n / PLAN_WORDS : PLAN_LOOK_MAX_GRID);
     const uint32_t chunks = lsb_make_params(n, 16, RADIX_BITS).grid;
@@ -655,13 +749,14 @@ static int lsb_plan_look(const uint32_t *keys, uint32_t *alt, const LsbWorkspace
     hipLaunchKernelGGL(lsb_plan_look_kernel, dim3(parts), dim3(PLAN_LOOK_THREADS), 0, s, keys, alt, plan, ws.spine, ws.prefix16, (uint32_t)n,
                        chunks, tw.f32_in, tw.xor_in);
     hipLaunchKernelGGL(lsb_plan_reduce_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, alt, plan, parts);
-    hipLaunchKernelGGL(lsb_plan_decide_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, plan, (uint32_t)n, parts, plan_cursor_enabled() ? 1u : 0u);
+    hipLaunchKernelGGL(lsb_plan_decide_kernel, dim3(PLAN_BLOCKS), dim3(RADIX), 0, s, plan, (uint32_t)n, parts, plan_cursor_enabled() ? 1u : 0u,
+                       mailbox);
     return (int)hipGetLastError();
 }
 
-// The second slot of a sort that the host has seen to be PLANNED in cursor mode: the cursor set-up, the scatter of the full
-// tiles and the follow-up kernel, which also places the partial tile.  No scan (nothing reads it) and no partial-tile launch
-// (it returns at once in this mode).
+// The second slot of a sort that the host has seen to be PLANNED in cursor mode: the cursor set-up and the scatter of the full
+// tiles, by the kernels that know their route, and the follow-up kernel, which also places the partial tile.  No scan (nothing
+// reads it) and no partial-tile launch (it returns at once in this mode).
 static int lsb_plan_slot2_cursor(const uint32_t *kin, uint32_t *kout, const LsbWorkspace &ws, PlanBlock *plan, uint32_t *cursor,
                                  const PassParams &p, hipStream_t s)
 {
@@ -669,16 +764,16 @@ static int lsb_plan_slot2_cursor(const uint32_t *kin, uint32_t *kout, const LsbW
     if ((char *)cursor < (char *)ws.prefix16) return hipErrorInvalidValue;
     {
         KernelTimer kt(GS_K_OTHER, s);
-        hipLaunchKernelGGL(lsb_plan_upsweep2_kernel<true>, dim3(p.grid), dim3(LSB_THREADS), 0, s, kin, ws.spine, ws.prefix16, plan, cursor, p);
+        hipLaunchKernelGGL(lsb_plan_cursor_init_kernel, dim3(PLAN_GROUPS / LSB_THREADS), dim3(LSB_THREADS), 0, s, plan, cursor);
     }
     if (p.n >= (uint32_t)LSB_TILE) {
         KernelTimer kt(GS_K_LSB_DOWNSWEEP, s);
+        PassParams q = p;
+        q.shift = 24;                                      // what the decide kernel wrote to shift[1] of a PLANNED sort
         if (p.n > (1u << 30))
-            hipLaunchKernelGGL((lsb_plan_scatter2_kernel<false, true>), dim3(p.ds_grid), dim3(LSB_THREADS), 0, s, kin, kout, ws.totals,
-                               ws.spine, ws.prefix16, plan, cursor, p);
+            hipLaunchKernelGGL((lsb_plan_scatter2_cursor_kernel<true>), dim3(p.ds_grid), dim3(LSB_THREADS), 0, s, kin, kout, plan->irr, cursor, q);
         else
-            hipLaunchKernelGGL((lsb_plan_scatter2_kernel<false, false>), dim3(p.ds_grid), dim3(LSB_THREADS), 0, s, kin, kout, ws.totals,
-                               ws.spine, ws.prefix16, plan, cursor, p);
+            hipLaunchKernelGGL((lsb_plan_scatter2_cursor_kernel<false>), dim3(p.ds_grid), dim3(LSB_THREADS), 0, s, kin, kout, plan->irr, cursor, q);
     }
     {
         KernelTimer kt(GS_K_OTHER, s);
@@ -691,8 +786,8 @@ static int lsb_plan_slot2_cursor(const uint32_t *kin, uint32_t *kout, const LsbW
 // ---- the host's look at the decision.  The fixed sequence pays for both routes: a PLANNED sort launches two pass slots and
 // up to eight local-sort kernels that find nothing, a CLASSIC one the cursor set-up, the follow-up kernel, the task builder
 // and a finish over empty lists -- 0.3 ms at 2^30 keys, mostly workgroups that load one word and leave.  So, when the stream
-// is not being captured: right after the look a one-thread kernel copies the decision to a pinned host mailbox and an event
-// is recorded; the first slot, which is the same on both routes, is enqueued (milliseconds of work), and only then the host
+// is not being captured: the look's decide kernel also writes the decision to a pinned host mailbox and an event is recorded
+// behind it; the first slot, which is the same on both routes, is enqueued (milliseconds of work), and only then the host
 // waits for the event and enqueues what the route needs.  The discipline is the MSB sort's (MsbPeek in gs_msb.hip): one
 // mailbox per calling thread and device, released when the thread ends; under capture, with GS_LSB_PLAN_PEEK=0 (read once per
 // process) and on any failure the fixed sequence runs, which is right for any data.
@@ -746,13 +841,18 @@ static PlanPeek *plan_peek_get(hipStream_t s)
     pk.armed = false;
     return &pk;
 }
-static void plan_peek_arm(PlanPeek *pk, const PlanBlock *plan, hipStream_t s)
+// before the look is enqueued: the words the decide kernel will write
+static uint32_t *plan_peek_clear(PlanPeek *pk)
+{
+    if (!pk) return nullptr;
+    for (int i = 0; i < PLAN_PEEK_WORDS; ++i) ((volatile uint32_t *)pk->host)[i] = 0;   // route 0: not plausible
+    return pk->dev;
+}
+// right behind the look's decide launch
+static void plan_peek_arm(PlanPeek *pk, hipStream_t s)
 {
     if (!pk) return;
-    for (int i = 0; i < PLAN_PEEK_WORDS; ++i) ((volatile uint32_t *)pk->host)[i] = 0;   // route 0: not plausible
-    KernelTimer kt(GS_K_OTHER, s);
-    hipLaunchKernelGGL(lsb_plan_peek_kernel, dim3(1), dim3(1), 0, s, plan, pk->dev);
-    pk->armed = hipGetLastError() == hipSuccess && hipEventRecord(pk->ev, s) == hipSuccess;
+    pk->armed = hipEventRecord(pk->ev, s) == hipSuccess;
     if (!pk->armed) (void)hipGetLastError();
 }
 struct PlanSeen { bool ok = false; uint32_t route = 0, tasks[MSB_NCLASS] = {0, 0, 0, 0}, cursor_mode = 0; };
@@ -785,6 +885,25 @@ static PlanSeen plan_peek_wait(PlanPeek *pk, uint64_t n)
     for (int c = 0; c < MSB_NCLASS; ++c) seen.tasks[c] = w[3 + c];
     return seen;
 }
+// The finish's two launches behind the one-pass local sort (few distinct values, flagged) usually find nothing left: a
+// workgroup per task, 16384 at 2^30 keys, then costs 23-29 us per launch for reading one word each.  They stride over the
+// lists, so they get PLAN_FINISH_CAP workgroups at the most: the largest of 512 / 1024 / 2048 whose empty launch stays within
+// 5 us (DESIGN.md section 3 has both ends: nothing left, and every group left).  GS_LSB_PLAN_FINISH_CAP=512|1024|2048
+// (measurements; read once per process) overrides it.
+#ifndef GS_PLAN_FINISH_CAP
+#define GS_PLAN_FINISH_CAP 2048
+#endif
+constexpr uint32_t PLAN_FINISH_CAP = GS_PLAN_FINISH_CAP;
+static_assert(PLAN_FINISH_CAP == 512 || PLAN_FINISH_CAP == 1024 || PLAN_FINISH_CAP == 2048, "the finish's cap");
+static uint32_t plan_finish_cap()
+{
+    static const uint32_t v = [] {
+        const char *e = getenv("GS_LSB_PLAN_FINISH_CAP");
+        const unsigned long x = e ? strtoul(e, nullptr, 10) : 0ul;
+        return x == 512ul || x == 1024ul || x == 2048ul ? (uint32_t)x : PLAN_FINISH_CAP;
+    }();
+    return v;
+}
 // gs_lsb_plan_peek_status: what the calling thread's last planned sort did
 static thread_local uint32_t plan_peek_last[4] = {0, 0, 0, 0};
 
@@ -802,9 +921,11 @@ int lsb_plan_sort(char *base, uint32_t *d_keys[2], int *selector, uint64_t n, in
     int sel = *selector, e;
     PassParams tw{};
     lsb_twiddle_masks(key_type, descending, true, true, tw);
-    if ((e = lsb_plan_look(d_keys[sel], d_keys[sel ^ 1], ws, plan, n, tw, s))) return e;
     PlanPeek *peek = plan_peek_get(s);
-    plan_peek_arm(peek, plan, s);
+    e = lsb_plan_look(d_keys[sel], d_keys[sel ^ 1], ws, plan, n, tw, s, plan_peek_clear(peek));
+    // (also when the look's launches failed: the decide kernel may have been enqueued and may still write the mailbox)
+    plan_peek_arm(peek, s);
+    if (e) return e;
     PlanSeen seen;   // (!ok: the fixed sequence)
     plan_peek_last[0] = plan_peek_last[1] = 0; plan_peek_last[2] = 4; plan_peek_last[3] = (1u << MSB_NCLASS) - 1u;
     // The buffer ping-pong counts four slots on every path: a slot that is not enqueued flips the selector like one that skips.
@@ -846,7 +967,7 @@ int lsb_plan_sort(char *base, uint32_t *d_keys[2], int *selector, uint64_t n, in
     }
     if ((e = (int)hipGetLastError())) return e;
     if ((e = msb_local_sorts_in_place(plan->level, lists.tasks, PLAN_GROUPS, PLAN_GROUPS, d_keys[sel], PLAN_SORT_BITS, n, tw.f32_out,
-                                      tw.xor_out, s, seen.ok ? seen.tasks : nullptr)))
+                                      tw.xor_out, s, seen.ok ? seen.tasks : nullptr, plan_finish_cap())))
         return e;
     *selector = sel;
     return hipSuccess;
@@ -905,6 +1026,8 @@ int gs_lsb_plan_peek_status(uint32_t out[4])
     memcpy(out, plan_peek_last, sizeof(plan_peek_last));
     return hipSuccess;
 }
+
+uint32_t gs_lsb_plan_finish_cap(void) { return plan_finish_cap(); }
 
 int gs_lsb_plan_look_only(void *d_temp, const void *d_keys, void *d_alt, uint64_t num_items, int key_type, int descending, void *stream)
 {

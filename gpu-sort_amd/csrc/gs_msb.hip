@@ -1236,8 +1236,30 @@ __global__ __launch_bounds__(THREADS, (THREADS == 1024 && !(HAS_VALUES && KPT > 
     auto fresh = [](uint32_t x) { asm volatile("" : "+v"(x)); return x; };
     static_assert(!(STABLE && MODE != LS_ALL), "the stable sort has one plan");
     // next task of this workgroup (stride gridDim.x) that this MODE processes; LS_ONEPASS flags the ones it leaves
+    // The two leftover plans (LS_FLAGGED, LS_DEDUPE) look at 64 records of the stride at a time, one per lane: nearly every record
+    // they meet belongs to nobody (uniform keys, 65536 tasks: the sample look flags one task in every other sort), two workgroups
+    // of the big class are resident per CU, and a record per round trip made each of the two launches a walk of 50 us for that one task.
     auto advance = [&](uint32_t from, MsbTask &out) {
         uint32_t t = from;
+        if constexpr (MODE == LS_FLAGGED || MODE == LS_DEDUPE) {
+            for (; t < ntasks; t += (uint32_t)WAVE * gridDim.x) {
+                const unsigned long long cand = (unsigned long long)t + (unsigned long long)lane * gridDim.x;
+                const bool in = cand < (unsigned long long)ntasks;
+                const MsbTask c = ws.tasks[cls][in ? (uint32_t)cand : t];
+                const bool mine = in && (MODE == LS_FLAGGED ? (c.pad & (LS_FLAG | LS_DONE)) == LS_FLAG
+                                                            : ((c.pad & LS_DD) != 0u && (c.pad & LS_FLAG) != 0u && c.sort_bits > (uint32_t)LOCAL_B1 && c.sort_bits <= 16u));
+                const unsigned long long m = __builtin_amdgcn_ballot_w64(mine);
+                if (m != 0ull) {
+                    const int first = __builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
+                    out.offset = (uint32_t)__builtin_amdgcn_readlane((int)c.offset, first);
+                    out.size = (uint32_t)__builtin_amdgcn_readlane((int)c.size, first);
+                    out.sort_bits = (uint32_t)__builtin_amdgcn_readlane((int)c.sort_bits, first);
+                    out.pad = (uint32_t)__builtin_amdgcn_readlane((int)c.pad, first);
+                    return t + (uint32_t)first * gridDim.x;
+                }
+            }
+            return ntasks;
+        }
         for (; t < ntasks; t += gridDim.x) {
             const MsbTask c = ws.tasks[cls][t];
             // (the samples were looked at by msb_task_sample_kernel: LS_FLAG = a value heavy enough to overflow the one-pass
@@ -1888,7 +1910,8 @@ static inline bool onepass_possible(int min_bits, int b1, int onepass_bits)
 template <bool HAS_VALUES, bool STABLE = false>
 static void launch_local_sorts(const MsbWs &ws, int L, uint32_t bound, const uint32_t *sk, uint32_t *dk, const uint32_t *sv,
                                uint32_t *dv, int f32_in, uint32_t xor_in, int f32_out, uint32_t xor_out, hipStream_t s,
-                               int min_bits = 0, uint64_t num_items = 0, const uint32_t *known_tasks = nullptr, bool maybe_skew = true)
+                               int min_bits = 0, uint64_t num_items = 0, const uint32_t *known_tasks = nullptr, bool maybe_skew = true,
+                               uint32_t leftover_cap = 0u)
 {
     KernelTimer kt(GS_K_MSB_LOCAL_SORT, s);
     // grid-stride over the task list; few blocks suffice for the big classes (empty launches are not free)
@@ -1905,13 +1928,19 @@ static void launch_local_sorts(const MsbWs &ws, int L, uint32_t bound, const uin
 #endif
         return (uint32_t)(b < MSB_LS_MAX_GRID ? (b ? b : 1) : MSB_LS_MAX_GRID);
     };
-#define GS_LS1P(C, HV, M, P) hipLaunchKernelGGL((msb_local_sort_kernel<msb_class_threads(C), msb_class_kpt(C), HV, STABLE, M, P>), dim3(grid_of(C)), \
-                                               dim3(msb_class_threads(C)), 0, s, ws, L, C, sk, dk, sv, dv, f32_in, xor_in, f32_out, xor_out)
+    // `leftover_cap` != 0 (the keys-only plan of the LSB sort): the grid of the two launches behind LS_ONEPASS, which usually find
+    // nothing left and whose workgroups then only read `flagged` and leave -- 16384 of them cost 23-29 us per launch.  Both kernels
+    // stride over the list by their grid.  The MSB sort passes 0: its leftover launches usually find work (Zipf: see below).
+    auto left_of = [&](int c) {
+        const uint32_t g = grid_of(c);
+        return leftover_cap && leftover_cap < g ? leftover_cap : g;
+    };
+#define GS_LS1G(C, HV, M, P, G) hipLaunchKernelGGL((msb_local_sort_kernel<msb_class_threads(C), msb_class_kpt(C), HV, STABLE, M, P>), dim3(G), \
+                                                  dim3(msb_class_threads(C)), 0, s, ws, L, C, sk, dk, sv, dv, f32_in, xor_in, f32_out, xor_out)
+#define GS_LS1P(C, HV, M, P) GS_LS1G(C, HV, M, P, grid_of(C))
 #define GS_LS1(C, HV, M) GS_LS1P(C, HV, M, false)
     // (a resident grid of 1024 workgroups striding over the list instead of one workgroup per task, up to 16384: Zipf local sorts 1.69 -> 1.84 ms)
-#define GS_LSDD(C, HV, M) hipLaunchKernelGGL((msb_local_sort_kernel<msb_class_threads(C), msb_class_kpt(C), HV, STABLE, M, false>),                \
-                                             dim3(grid_of(C)), dim3(msb_class_threads(C)), 0, s, ws, L, C, sk, dk, sv, dv,                             \
-                                             f32_in, xor_in, f32_out, xor_out)
+#define GS_LSDD(C, HV, M) GS_LS1G(C, HV, M, false, (M) == LS_DEDUPE ? left_of(C) : grid_of(C))
     const bool plain = !f32_in && !xor_in && !f32_out && !xor_out;
     // GS_MSB_DEDUPE=0 switches the few-distinct-values plan off (A/B measurements; read once per process)
     static const bool dedupe_on = [] { const char *e = getenv("GS_MSB_DEDUPE"); return !(e && e[0] == '0'); }();
@@ -1924,7 +1953,7 @@ static void launch_local_sorts(const MsbWs &ws, int L, uint32_t bound, const uin
         else if (!onepass_possible(min_bits, local_b1((int)msb_class_cap(C)), local_b1((int)msb_class_cap(C) * (HV ? 2 : 1)) + 2)) \
             { if constexpr (DD) { if (dd) GS_LSDD(C, HV, LS_DEDUPE_ALL); } GS_LS1(C, HV, LS_ALL); }                    \
         else { if (plain) GS_LS1P(C, HV, LS_ONEPASS, true); else GS_LS1(C, HV, LS_ONEPASS);                           \
-               if constexpr (DD) { if (dd) GS_LSDD(C, HV, LS_DEDUPE); } GS_LS1(C, HV, LS_FLAGGED); }                   \
+               if constexpr (DD) { if (dd) GS_LSDD(C, HV, LS_DEDUPE); } GS_LS1G(C, HV, LS_FLAGGED, false, left_of(C)); } \
     } while (0)
     auto wanted = [&](int c) { return !known_tasks || known_tasks[c] != 0u; };
     if constexpr (!STABLE) {
@@ -1943,13 +1972,15 @@ static void launch_local_sorts(const MsbWs &ws, int L, uint32_t bound, const uin
 #undef GS_LS
 #undef GS_LS1
 #undef GS_LS1P
+#undef GS_LS1G
 #undef GS_LSDD
 }
 
 // gs_msb_tasks.hpp: the local sorts over lists the caller wrote (the keys-only plan of the LSB sort).  Only the fields the
 // local-sort path reads are filled in: msb_task_sample_kernel and msb_local_sort_kernel use level, tasks, max_tasks and caps.
 int msb_local_sorts_in_place(MsbLevel *level, MsbTask *const tasks[MSB_NCLASS], uint32_t max_tasks, uint32_t bound, uint32_t *keys,
-                             int sort_bits, uint64_t num_items, int f32_out, uint32_t xor_out, hipStream_t s, const uint32_t *known_tasks)
+                             int sort_bits, uint64_t num_items, int f32_out, uint32_t xor_out, hipStream_t s, const uint32_t *known_tasks,
+                             uint32_t leftover_cap)
 {
     MsbWs ws{};
     ws.level = level;
@@ -1957,7 +1988,8 @@ int msb_local_sorts_in_place(MsbLevel *level, MsbTask *const tasks[MSB_NCLASS], 
     ws.max_tasks = max_tasks;
     ws.tile_shift = 13u;
     ws.key_bits = 32u;
-    launch_local_sorts<false>(ws, 0, bound, keys, keys, nullptr, nullptr, 0, 0u, f32_out, xor_out, s, sort_bits, num_items, known_tasks);
+    launch_local_sorts<false>(ws, 0, bound, keys, keys, nullptr, nullptr, 0, 0u, f32_out, xor_out, s, sort_bits, num_items, known_tasks, true,
+                              leftover_cap);
     return (int)hipGetLastError();
 }
 

@@ -185,6 +185,9 @@ int  gs_lsb_plan_cursor_status(void *d_temp, uint64_t num_items, uint32_t out[4]
  * sorts of size class c were enqueued (0xf without a look, 0 on route 2).  No device access, no
  * synchronisation; all zeros before the thread's first such sort.  Diagnostic: tests read it.      */
 int  gs_lsb_plan_peek_status(uint32_t out[4]);
+/* The most workgroups the plan's finish gives each of the two local-sort launches that take what the
+ * one-pass sort left over (they stride over the task lists): 512, 1024 or 2048.  Tests size by it.  */
+uint32_t gs_lsb_plan_finish_cap(void);
 /* Test hooks of the keys-only plan.  gs_lsb_plan_look_only runs the look alone (the fused look, the
  * reduction of its tables and the decision) on a workspace of gs_lsb_temp_bytes(num_items) bytes and
  * returns without sorting: d_keys is read, the first num_items * 4 bytes of d_alt are scratch.  What
