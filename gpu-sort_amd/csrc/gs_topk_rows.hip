@@ -5,6 +5,8 @@
 // gs_topk_segmented_u32 (section 10k), gs_topk_segmented_u16 (section 10l) and gs_topk_segmented_u64 (section 10o), the same for
 // ragged segments given by device offsets, follow them: they run the same device functions per record of lists that a classify
 // kernel fills (see "ragged segments" below), instantiated over the same three key-traits types.
+// gs_topk_rows_anyk_u32 (section 10p), the rows form without the cap on k, is at the end (see "any k" below): its selects stage
+// the k selected pairs of every row in the outputs and gs_segmented_sort_u32 finishes them.
 //
 // Row r of the result is what gs_topk_u32 writes for row r alone, bit for bit.  Every row has the same length, so the
 // launches are decided on the host from num_cols and k:
@@ -1279,6 +1281,455 @@ static int ts_status(void *d_temp, uint64_t num_items, uint32_t num_segments, ui
     return hipSuccess;
 }
 
+// ------------------------------------------------------------------- any k --
+// gs_topk_rows_anyk_u32: the k best of every row with no cap on k.  A select stages the k selected
+// (key, column) pairs of every row, unsorted but with equal keys in column order, at [r * k, r * k + k) of the outputs, and
+// gs_segmented_sort_u32 with the regular offsets r * k finishes them, stably, on all 32 bits.  Two selects, by num_cols alone:
+//
+//   path 1   num_cols <= CH: one workgroup per row, the row read once: tr_select for the k-th image, then the ordered two-group
+//            placement straight into the row's k slots in global memory.  No global atomic, no histogram in memory.
+//   path 2   longer rows: a radix select over all rows at once in three counting rounds on image bits 31-21, 20-10 and 9-0.  A
+//            count kernel, one workgroup per (row, slab of whole tiles of CH columns), histograms the round's digit in LDS over
+//            the elements that match the row's prefix so far and adds its non-zero bins to the row's histogram in memory
+//            (integer adds: the sums do not depend on their order); a pick kernel, one workgroup per row, scans the bins, picks
+//            the digit that holds the krem-th element, updates the row's record and clears the histogram.  Then per (row, tile)
+//            two counts (before / equal to the k-th image), a scan per row, and a scatter that places group A in column order
+//            at [r * k, r * k + less) and the first `take` of group B behind it, by ballot ranks on top of the scanned bases.
+//
+// No atomic decides a position and no kernel waits on another workgroup: a staged row is a function of the input alone.  Equal
+// keys land in ONE group in column order (section 10g), so the stable finish reproduces the definition.
+constexpr uint32_t TA_TILE = TR_CH;
+constexpr uint32_t TA_SLAB_TILES = 4;      // tiles one count workgroup histograms before it adds its bins (1, 4 and 16 measured: section 10p)
+constexpr uint32_t TA_BINS = 2048;         // rounds 0 and 1: 11 bits; round 2: 10 bits
+constexpr uint32_t TA_STATE_WORDS = 8;     // per row: k-th image (the prefix so far), less, take (krem), 0, matched after round 0, after round 1, 0, 0
+
+template <int ROUND> struct TaRound {
+    static constexpr uint32_t SHIFT = ROUND == 0 ? 21u : ROUND == 1 ? 10u : 0u;
+    static constexpr uint32_t BINS = ROUND == 2 ? 1024u : 2048u;
+    static constexpr uint32_t MASK = ROUND == 0 ? 0u : ROUND == 1 ? 0xffe00000u : 0xfffffc00u;   // the digits above this one
+};
+
+// One workgroup: a tile of up to CH elements of a row into registers as images, in the (wave, row, lane) order of the block kernel.
+template <typename KT>
+__device__ __forceinline__ void ta_load_tile(const typename KT::T *__restrict__ src, uint32_t first, uint32_t len, int flt,
+                                             typename KT::I x, typename KT::I (&img)[TR_KPT])
+{
+    using I = typename KT::I;
+#pragma unroll
+    for (int u = 0; u < TR_KPT; ++u) {
+        const uint32_t j = first + (uint32_t)u * WAVE;
+        img[u] = j < len ? (I)__builtin_nontemporal_load(src + j) : (I)0u;
+    }
+#pragma unroll
+    for (int u = 0; u < TR_KPT; ++u) img[u] = KT::in(img[u], flt, x);
+}
+
+// tr_compact_with for a destination in global memory that is shared by the tiles of a row: group A from baseA, group B from
+// baseB (both include what the tiles before this one place; baseB starts at `less`), B cut at kk.  Stores the caller's bit
+// pattern, and with HV the column col0 + j.  Ends with a workgroup barrier.
+template <typename KT, bool HV>
+__device__ __forceinline__ void ta_place(typename KT::I (&img)[TR_KPT], uint32_t first, uint32_t len, uint32_t kk, typename KT::I kth,
+                                         uint32_t less, uint32_t baseA, uint32_t baseB, uint32_t w, uint32_t lane,
+                                         uint32_t (&wcnt)[2][TR_WAVES], typename KT::T *__restrict__ dst_k, uint32_t *__restrict__ dst_c,
+                                         uint32_t col0, int flt, typename KT::I x)
+{
+    using T = typename KT::T;
+    uint32_t nA = 0, nB = 0, lenc = len;
+    asm volatile("" : "+v"(lenc));   // (range compares again, as in tr_compact_with)
+#pragma unroll
+    for (int u = 0; u < TR_KPT; ++u) {
+        const uint32_t j = first + (uint32_t)u * WAVE;
+        nA += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(j < lenc && img[u] < kth));
+        nB += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(j < lenc && img[u] == kth));
+    }
+    if (lane == 0) { wcnt[0][w] = nA; wcnt[1][w] = nB; }
+    __syncthreads();
+    for (uint32_t q = 0; q < w; ++q) { baseA += wcnt[0][q]; baseB += wcnt[1][q]; }
+    if (baseA < less || baseB < kk) {   // wave-uniform: this wave still has something to place
+        asm volatile("" : "+v"(lenc));
+#pragma unroll
+        for (int u = 0; u < TR_KPT; ++u) {
+            const uint32_t j = first + (uint32_t)u * WAVE;
+            asm volatile("" : "+v"(img[u]));
+            const bool a = j < lenc && img[u] < kth, b = j < lenc && img[u] == kth;
+            const unsigned long long mA = __builtin_amdgcn_ballot_w64(a), mB = __builtin_amdgcn_ballot_w64(b);
+            const uint32_t pos = a ? baseA + count_lower(mA) : baseB + count_lower(mB);
+            if ((a || b) && pos < kk) {   // (group A never passes `less`; group B is cut at kk = less + take)
+                dst_k[pos] = (T)KT::out(img[u], flt, x);
+                if (HV) dst_c[pos] = col0 + j;
+            }
+            baseA += (uint32_t)__popcll(mA);
+            baseB += (uint32_t)__popcll(mB);
+        }
+    }
+    __syncthreads();
+}
+
+// offsets[i] = i * k for i in [0, rows]: the regular segments of the finish.
+__global__ __launch_bounds__(256) void topk_anyk_offsets_kernel(int32_t *__restrict__ offsets, uint32_t rows, uint32_t k)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i <= rows) offsets[i] = (int32_t)(i * k);
+}
+
+// Path 1: one workgroup per row of up to CH columns.
+template <typename KT, bool HV>
+__global__ __launch_bounds__(TR_THREADS) void topk_anyk_block_kernel(const typename KT::T *__restrict__ keys, uint32_t stride, uint32_t cols,
+                                                                     uint32_t k, typename KT::T *__restrict__ dst_k,
+                                                                     uint32_t *__restrict__ dst_c, uint32_t *__restrict__ state, int flt,
+                                                                     uint32_t x32)
+{
+    using I = typename KT::I;
+    const I x = KT::xmask(x32);
+    __shared__ __attribute__((aligned(16))) uint32_t h[RADIX];
+    __shared__ uint32_t scratch[8];
+    __shared__ uint32_t sel[3];
+    __shared__ uint32_t wcnt[2][TR_WAVES];
+    const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t r = blockIdx.x;
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    I img[TR_KPT];
+    ta_load_tile<KT>(keys + (size_t)r * stride, first, cols, flt, x, img);
+    uint32_t less;
+    const I kth = tr_select<KT::BITS>(img, first, cols, k, tid, h, scratch, sel, less);
+    const size_t out0 = (size_t)r * k;
+    ta_place<KT, HV>(img, first, cols, k, kth, less, 0u, less, w, lane, wcnt, dst_k + out0, HV ? dst_c + out0 : nullptr, 0u, flt, x);
+    if (tid < TA_STATE_WORDS) state[(size_t)r * TA_STATE_WORDS + tid] = tid == 0 ? (uint32_t)kth : tid == 1 ? less : tid == 2 ? k - less : 0u;
+}
+
+// Path 2, a counting round: one workgroup per (row, slab of slab_tiles tiles).
+template <typename KT, int ROUND>
+__global__ __launch_bounds__(TR_THREADS) void topk_anyk_count_kernel(const typename KT::T *__restrict__ keys, uint32_t stride, uint32_t cols,
+                                                                     uint32_t tiles, uint32_t slabs, uint32_t slab_tiles,
+                                                                     const uint32_t *__restrict__ state, uint32_t *__restrict__ hist, int flt,
+                                                                     uint32_t x32)
+{
+    using I = typename KT::I;
+    using R = TaRound<ROUND>;
+    const I x = KT::xmask(x32);
+    __shared__ uint32_t h[TA_BINS];
+    const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t r = blockIdx.x / slabs, sl = blockIdx.x - r * slabs;
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    for (uint32_t i = tid; i < R::BINS; i += TR_THREADS) h[i] = 0;
+    const uint32_t prefix = ROUND == 0 ? 0u : state[(size_t)r * TA_STATE_WORDS];
+    __syncthreads();
+    const uint32_t t0 = sl * slab_tiles, t1 = t0 + slab_tiles < tiles ? t0 + slab_tiles : tiles;
+    for (uint32_t t = t0; t < t1; ++t) {
+        const uint32_t lo = t * TA_TILE, len = cols - lo < TA_TILE ? cols - lo : TA_TILE;
+        I img[TR_KPT];
+        ta_load_tile<KT>(keys + (size_t)r * stride + lo, first, len, flt, x, img);
+#pragma unroll
+        for (int u = 0; u < TR_KPT; ++u) {
+            const uint32_t j = first + (uint32_t)u * WAVE;
+            if (j < len && (((uint32_t)img[u] ^ prefix) & R::MASK) == 0u) hist_add(h, ((uint32_t)img[u] >> R::SHIFT) & (R::BINS - 1u));
+        }
+    }
+    __syncthreads();
+    uint32_t *__restrict__ g = hist + (size_t)r * TA_BINS;
+    for (uint32_t i = tid; i < R::BINS; i += TR_THREADS) {   // a wave over contiguous bins; only what this slab holds
+        const uint32_t c = h[i];
+        if (c) atomicAdd(g + i, c);
+    }
+}
+
+// Path 2, a pick: one workgroup of 256 per row scans the round's bins, picks the one that holds the krem-th element, updates the
+// row's record and clears the histogram for the next round (and the next call).
+template <int ROUND>
+__global__ __launch_bounds__(256) void topk_anyk_pick_kernel(uint32_t *__restrict__ state, uint32_t *__restrict__ hist, uint32_t k)
+{
+    using R = TaRound<ROUND>;
+    constexpr uint32_t PER = R::BINS / 256u;
+    __shared__ uint32_t scratch[8];
+    const uint32_t tid = threadIdx.x;
+    uint32_t *__restrict__ h = hist + (size_t)blockIdx.x * TA_BINS + tid * PER;
+    uint32_t *__restrict__ st = state + (size_t)blockIdx.x * TA_STATE_WORDS;
+    const uint32_t prefix = ROUND == 0 ? 0u : st[0], less = ROUND == 0 ? 0u : st[1], krem = ROUND == 0 ? k : st[2];
+    uint32_t c[PER], sum = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < PER; ++i) { c[i] = h[i]; sum += c[i]; }
+#pragma unroll
+    for (uint32_t i = 0; i < PER; ++i) h[i] = 0;
+    uint32_t ex = block_exclusive_scan_256(sum, scratch, nullptr);   // (its barriers: every thread has read the record before one writes it)
+#pragma unroll
+    for (uint32_t i = 0; i < PER; ++i) {
+        if (ex < krem && krem - ex <= c[i]) {   // one bin of the row: the counts of the bins sum to at least krem
+            st[0] = prefix | ((tid * PER + i) << R::SHIFT);
+            st[1] = less + ex;
+            st[2] = krem - ex;
+            if (ROUND < 2) st[4 + ROUND] = c[i];
+        }
+        ex += c[i];
+    }
+    if (ROUND == 0 && tid == 0) { st[3] = 0; st[6] = 0; st[7] = 0; }
+}
+
+// Path 2, the select's counts: per (row, tile) the elements before the k-th image and those equal to it.
+template <typename KT>
+__global__ __launch_bounds__(TR_THREADS) void topk_anyk_tilecount_kernel(const typename KT::T *__restrict__ keys, uint32_t stride,
+                                                                         uint32_t cols, uint32_t tiles, const uint32_t *__restrict__ state,
+                                                                         uint2 *__restrict__ counts, int flt, uint32_t x32)
+{
+    using I = typename KT::I;
+    const I x = KT::xmask(x32);
+    __shared__ uint32_t wcnt[2][TR_WAVES];
+    const uint32_t w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t r = blockIdx.x / tiles, t = blockIdx.x - r * tiles;
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    const uint32_t lo = t * TA_TILE, len = cols - lo < TA_TILE ? cols - lo : TA_TILE;
+    const I kth = (I)state[(size_t)r * TA_STATE_WORDS];
+    I img[TR_KPT];
+    ta_load_tile<KT>(keys + (size_t)r * stride + lo, first, len, flt, x, img);
+    uint32_t nA = 0, nB = 0;
+#pragma unroll
+    for (int u = 0; u < TR_KPT; ++u) {
+        const uint32_t j = first + (uint32_t)u * WAVE;
+        nA += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(j < len && img[u] < kth));
+        nB += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(j < len && img[u] == kth));
+    }
+    if (lane == 0) { wcnt[0][w] = nA; wcnt[1][w] = nB; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t a = 0, b = 0;
+        for (int q = 0; q < TR_WAVES; ++q) { a += wcnt[0][q]; b += wcnt[1][q]; }
+        counts[blockIdx.x] = make_uint2(a, b);
+    }
+}
+
+// Path 2, the select's scan: one workgroup of 256 per row turns its tiles' counts into bases, group A from 0, group B from less.
+__global__ __launch_bounds__(256) void topk_anyk_scan_kernel(const uint32_t *__restrict__ state, uint2 *__restrict__ counts, uint32_t tiles)
+{
+    __shared__ uint32_t scratch[8];
+    const uint32_t tid = threadIdx.x;
+    uint2 *__restrict__ c = counts + (size_t)blockIdx.x * tiles;
+    uint32_t carryA = 0, carryB = state[(size_t)blockIdx.x * TA_STATE_WORDS + 1];
+    for (uint32_t base = 0; base < tiles; base += 256u) {
+        const uint32_t i = base + tid;
+        const uint2 v = i < tiles ? c[i] : make_uint2(0u, 0u);
+        uint32_t totA, totB;
+        const uint32_t exA = block_exclusive_scan_256(v.x, scratch, &totA);
+        const uint32_t exB = block_exclusive_scan_256(v.y, scratch, &totB);
+        if (i < tiles) c[i] = make_uint2(carryA + exA, carryB + exB);
+        carryA += totA; carryB += totB;
+    }
+}
+
+// Path 2, the select's scatter: one workgroup per (row, tile) places its part of the two groups.
+template <typename KT, bool HV>
+__global__ __launch_bounds__(TR_THREADS) void topk_anyk_scatter_kernel(const typename KT::T *__restrict__ keys, uint32_t stride, uint32_t cols,
+                                                                       uint32_t tiles, uint32_t k, const uint32_t *__restrict__ state,
+                                                                       const uint2 *__restrict__ counts, typename KT::T *__restrict__ dst_k,
+                                                                       uint32_t *__restrict__ dst_c, int flt, uint32_t x32)
+{
+    using I = typename KT::I;
+    const I x = KT::xmask(x32);
+    __shared__ uint32_t wcnt[2][TR_WAVES];
+    const uint32_t w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t r = blockIdx.x / tiles, t = blockIdx.x - r * tiles;
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    const uint32_t lo = t * TA_TILE, len = cols - lo < TA_TILE ? cols - lo : TA_TILE;
+    const I kth = (I)state[(size_t)r * TA_STATE_WORDS];
+    const uint32_t less = state[(size_t)r * TA_STATE_WORDS + 1];
+    const uint2 base = counts[blockIdx.x];
+    if (base.x >= less && base.y >= k) return;   // workgroup-uniform: both groups are full before this tile
+    I img[TR_KPT];
+    ta_load_tile<KT>(keys + (size_t)r * stride + lo, first, len, flt, x, img);
+    const size_t out0 = (size_t)r * k;
+    ta_place<KT, HV>(img, first, len, k, kth, less, base.x, base.y, w, lane, wcnt, dst_k + out0, HV ? dst_c + out0 : nullptr, lo, flt, x);
+}
+
+// The pairs form's last step: vals_out[r * k + i] = vals_in[r * stride + column].
+__global__ __launch_bounds__(256) void topk_anyk_gather_kernel(const uint32_t *__restrict__ vals_in, const uint32_t *__restrict__ col,
+                                                               uint32_t *__restrict__ vals_out, uint32_t total, uint32_t k, uint32_t stride,
+                                                               uint32_t cols)
+{
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+        const uint32_t r = i / k, c = col[i];
+        vals_out[i] = vals_in[(size_t)r * stride + (c < cols ? c : cols - 1u)];
+    }
+}
+
+struct TaPlan { uint32_t path, launches, slab_tiles, slabs, tiles; };
+
+static inline bool ta_shape_ok(uint64_t rows, uint64_t cols, uint64_t k)
+{
+    if (k > cols) return false;
+    if (tr_mul_ge_2p32(rows, cols)) return false;
+    if (rows != 0 && k > 0x7fffffffull / rows) return false;   // num_rows * k >= 2^31: the finish has int offsets
+    return true;
+}
+
+static inline TaPlan ta_make_plan(uint64_t cols)
+{
+    TaPlan p{};
+    if (cols <= TR_CH) { p.path = 1; p.launches = 2; p.slab_tiles = 1; p.slabs = 1; p.tiles = 1; return p; }
+    p.path = 2;
+    p.launches = 11;   // zero, offsets, three times (count, pick), tile counts, scan, scatter
+    p.tiles = (uint32_t)((cols + TA_TILE - 1) / TA_TILE);
+    p.slab_tiles = TA_SLAB_TILES;
+    p.slabs = (p.tiles + p.slab_tiles - 1) / p.slab_tiles;
+    return p;
+}
+
+struct TaWs {
+    uint32_t *state;
+    int32_t *offsets;
+    uint32_t *hist;
+    uint2 *counts;
+    uint32_t *keys1, *cols1, *cols0;
+    char *seg;
+    size_t seg_bytes;
+};
+
+// The header's workspace formula, term by term; returns the bytes carved (without the slack).
+static size_t ta_carve(char *base, uint64_t rows, uint64_t cols, uint64_t k, bool hv, bool pairs, TaWs *ws)
+{
+    const TaPlan p = ta_make_plan(cols);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *q = base + off; off += gs_ws_align(bytes); return q; };
+    ws->state = (uint32_t *)take((size_t)4 * TA_STATE_WORDS * rows);
+    ws->offsets = (int32_t *)take((size_t)4 * (rows + 1));
+    ws->hist = nullptr; ws->counts = nullptr;
+    if (p.path == 2) {
+        ws->hist = (uint32_t *)take((size_t)4 * TA_BINS * rows);
+        ws->counts = (uint2 *)take((size_t)8 * rows * p.tiles);
+    }
+    ws->keys1 = (uint32_t *)take((size_t)4 * rows * k);
+    ws->cols1 = hv ? (uint32_t *)take((size_t)4 * rows * k) : nullptr;
+    ws->cols0 = pairs ? (uint32_t *)take((size_t)4 * rows * k) : nullptr;
+    ws->seg_bytes = gs_segmented_temp_bytes(rows * k, hv ? 1 : 0, (uint32_t)rows);
+    ws->seg = take(ws->seg_bytes);
+    return off;
+}
+
+// (The size query has no pointers to tell pairs from arguments: with values it holds the first half of the columns too.)
+static size_t ta_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values)
+{
+    if (!ta_shape_ok(num_rows, num_cols, k)) return 0;
+    if (num_rows == 0 || num_cols == 0 || k == 0) return 0;
+    TaWs ws;
+    return ta_carve(nullptr, num_rows, num_cols, k, has_values != 0, has_values != 0, &ws) + GS_WS_SLACK;
+}
+
+template <typename KT, bool HV>
+static void ta_launch_select(hipStream_t s, const TaPlan &p, const TaWs &ws, const typename KT::T *ki, typename KT::T *dk, uint32_t *dc,
+                             uint32_t rows, uint32_t cols, uint32_t stride, uint32_t k, int flt, uint32_t x)
+{
+    KernelTimer kt(GS_K_OTHER, s);
+    if (p.path == 1) {
+        hipLaunchKernelGGL((topk_anyk_block_kernel<KT, HV>), dim3(rows), dim3(TR_THREADS), 0, s, ki, stride, cols, k, dk, dc, ws.state, flt, x);
+        return;
+    }
+    const dim3 gslab(rows * p.slabs), gtile(rows * p.tiles), grow(rows), wg(TR_THREADS);
+#define GS_TA_ROUND(R)                                                                                                             \
+    do {                                                                                                                           \
+        hipLaunchKernelGGL((topk_anyk_count_kernel<KT, R>), gslab, wg, 0, s, ki, stride, cols, p.tiles, p.slabs, p.slab_tiles,     \
+                           (const uint32_t *)ws.state, ws.hist, flt, x);                                                           \
+        hipLaunchKernelGGL((topk_anyk_pick_kernel<R>), grow, dim3(256), 0, s, ws.state, ws.hist, k);                               \
+    } while (0)
+    GS_TA_ROUND(0);
+    GS_TA_ROUND(1);
+    GS_TA_ROUND(2);
+#undef GS_TA_ROUND
+    hipLaunchKernelGGL((topk_anyk_tilecount_kernel<KT>), gtile, wg, 0, s, ki, stride, cols, p.tiles, (const uint32_t *)ws.state, ws.counts, flt,
+                       x);
+    hipLaunchKernelGGL(topk_anyk_scan_kernel, grow, dim3(256), 0, s, (const uint32_t *)ws.state, ws.counts, p.tiles);
+    hipLaunchKernelGGL((topk_anyk_scatter_kernel<KT, HV>), gtile, wg, 0, s, ki, stride, cols, p.tiles, k, (const uint32_t *)ws.state,
+                       (const uint2 *)ws.counts, dk, dc, flt, x);
+}
+
+static int ta_run(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
+                  uint32_t *d_vals_out, uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, int descending, int key_type,
+                  void *stream)
+{
+    using KT = TrKey32;
+    GS_CLEAR_STALE_ERROR();
+    if (!ta_shape_ok(num_rows, num_cols, k)) return hipErrorInvalidValue;
+    if (row_stride < num_cols || tr_mul_ge_2p32(num_rows, row_stride)) return hipErrorInvalidValue;
+    if (!KT::type_ok(key_type)) return hipErrorInvalidValue;
+    if (d_vals_in && !d_vals_out) return hipErrorInvalidValue;
+    if (num_rows == 0 || num_cols == 0 || k == 0) return hipSuccess;
+    const bool hv = d_vals_out != nullptr, pairs = d_vals_in != nullptr;
+    if (!d_keys_in || !d_keys_out) return hipErrorInvalidValue;
+    if (!d_temp || temp_bytes < ta_temp_bytes(num_rows, num_cols, k, hv)) return hipErrorInvalidValue;
+    if ((((uintptr_t)d_keys_in | (uintptr_t)d_keys_out | (uintptr_t)d_vals_in | (uintptr_t)d_vals_out) & 3u) != 0) return hipErrorInvalidValue;
+    {
+        const size_t in_elems = (size_t)((num_rows - 1) * row_stride + num_cols), out_elems = (size_t)(num_rows * k);
+        const void *arr[4] = {d_keys_in, d_vals_in, d_keys_out, d_vals_out};
+        const size_t bytes[4] = {4 * in_elems, 4 * in_elems, 4 * out_elems, 4 * out_elems};
+        if (gs_any_overlap4(arr, bytes)) return hipErrorInvalidValue;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t rows = (uint32_t)num_rows, cols = (uint32_t)num_cols, stride = (uint32_t)row_stride, kk = (uint32_t)k;
+    const uint32_t total = rows * kk;
+    const int flt = KT::is_float(key_type);
+    const uint32_t x = KT::xor_of(key_type, descending);
+    const TaPlan p = ta_make_plan(num_cols);
+    TaWs ws;
+    ta_carve(gs_ws_base(d_temp), num_rows, num_cols, k, hv, pairs, &ws);
+
+    if (p.path == 2) {   // the histograms start at zero; every pick leaves them so
+        const hipError_t e = zero_async(ws.hist, (size_t)4 * TA_BINS * rows, s);
+        if (e != hipSuccess) return (int)e;
+    }
+    {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(topk_anyk_offsets_kernel, dim3(rows / 256u + 1u), dim3(256), 0, s, ws.offsets, rows, kk);
+    }
+    // the select stages row r's k (key, column) pairs at [r * k, r * k + k): the keys in d_keys_out, the columns in d_vals_out
+    // (arguments) or in the workspace (pairs)
+    uint32_t *col0 = !hv ? nullptr : pairs ? ws.cols0 : d_vals_out;
+    if (hv) ta_launch_select<KT, true>(s, p, ws, d_keys_in, d_keys_out, col0, rows, cols, stride, kk, flt, x);
+    else ta_launch_select<KT, false>(s, p, ws, d_keys_in, d_keys_out, col0, rows, cols, stride, kk, flt, x);
+    int err = (int)hipGetLastError();
+    if (err) return err;
+
+    // the finish: four passes over all 32 bits leave the result in half 0, where the pairs were staged
+    uint32_t *dk[2] = {d_keys_out, ws.keys1}, *dv[2] = {col0, ws.cols1};
+    int selector = 0;
+    err = gs_segmented_sort_u32(ws.seg, ws.seg_bytes, dk, hv ? dv : nullptr, &selector, total, rows, ws.offsets, ws.offsets + 1, 0, 32,
+                                descending, key_type, s);
+    if (err) return err;
+    if (selector != 0) return hipErrorUnknown;
+    if (pairs) {
+        KernelTimer kt(GS_K_OTHER, s);
+        const uint32_t g = (total + 255u) / 256u;
+        hipLaunchKernelGGL(topk_anyk_gather_kernel, dim3(g < 65536u ? g : 65536u), dim3(256), 0, s, d_vals_in, (const uint32_t *)ws.cols0,
+                           d_vals_out, total, kk, stride, cols);
+    }
+    return (int)hipGetLastError();
+}
+
+static int ta_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, uint32_t out[8])
+{
+    if (!out) return hipErrorInvalidValue;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!ta_shape_ok(num_rows, num_cols, k)) return hipErrorInvalidValue;
+    if (num_rows == 0 || num_cols == 0 || k == 0) return hipSuccess;   // such a call enqueues nothing
+    const TaPlan p = ta_make_plan(num_cols);
+    out[0] = p.path; out[1] = p.launches; out[2] = TR_CH; out[3] = TA_TILE; out[4] = p.slab_tiles; out[5] = p.slabs; out[6] = p.tiles;
+    return hipSuccess;
+}
+
+static int ta_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint64_t row, uint32_t out[8],
+                     void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (!out) return hipErrorInvalidValue;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!ta_shape_ok(num_rows, num_cols, k)) return hipErrorInvalidValue;
+    if (num_rows == 0 || num_cols == 0 || k == 0) return hipSuccess;   // such a call enqueued nothing
+    if (!d_temp || row >= num_rows) return hipErrorInvalidValue;
+    TaWs ws;
+    ta_carve(gs_ws_base(d_temp), num_rows, num_cols, k, has_values != 0, false, &ws);   // (only the records, the first term, are read)
+    uint32_t st[TA_STATE_WORDS];
+    hipError_t e = hipMemcpyAsync(st, ws.state + row * TA_STATE_WORDS, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    out[0] = ta_make_plan(num_cols).path; out[1] = st[0]; out[2] = st[1]; out[3] = st[2]; out[4] = st[4]; out[5] = st[5];
+    return hipSuccess;
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -1388,6 +1839,31 @@ int gs_topk_segmented_status(void *d_temp, uint64_t num_items, uint32_t num_segm
                              void *stream)
 {
     return ts_status(d_temp, num_items, num_segments, k, has_values, out, stream);
+}
+
+size_t gs_topk_rows_anyk_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values)
+{
+    return ta_temp_bytes(num_rows, num_cols, k, has_values);
+}
+
+int gs_topk_rows_anyk_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
+                          uint32_t *d_vals_out, uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, int descending,
+                          int key_type, void *stream)
+{
+    return ta_run(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, num_rows, num_cols, row_stride, k, descending, key_type,
+                  stream);
+}
+
+int gs_topk_rows_anyk_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint32_t out[8])
+{
+    (void)has_values;
+    return ta_plan(num_rows, num_cols, k, out);
+}
+
+int gs_topk_rows_anyk_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint64_t row, uint32_t out[8],
+                             void *stream)
+{
+    return ta_status(d_temp, num_rows, num_cols, k, has_values, row, out, stream);
 }
 
 }  // extern "C"

@@ -6,7 +6,8 @@ float16 / bfloat16) and DeviceTopK64 for 8-byte keys (gs_topk_u64: int64 / uint6
 (gs_topk_segmented_u32, and gs_topk_segmented_u16 for int16 / uint16 / float16 / bfloat16 keys); DeviceTopKSegmented64 /
 topk_segmented64() are the segmented form for 8-byte keys (gs_topk_segmented_u64: int64 / uint64 / float64).  DeviceTopKRows / topk_rows() are the same for every row of a matrix (gs_topk_rows_u32, and
 gs_topk_rows_u16 for int16 / uint16 / float16 / bfloat16 keys, in the order of GS_KEY_F16 / BF16 at the enum); DeviceTopKRows64 /
-topk_rows64() are the rows form for 8-byte keys (gs_topk_rows_u64: int64 / uint64 / float64).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
+topk_rows64() are the rows form for 8-byte keys (gs_topk_rows_u64: int64 / uint64 / float64); DeviceTopKRowsAnyK /
+topk_rows_anyk() are the rows form for 32-bit keys and any k up to the row length (gs_topk_rows_anyk_u32).  The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs
 (descending for the Max forms) on the same input: stable, keys in the caller's bit patterns, floats in the order of
 GS_KEY_F32 (negative NaNs first, positive NaNs last ascending; -0.0 before +0.0).
 """
@@ -441,6 +442,121 @@ def topk_rows64(keys, k, largest=False, values=None, indices=False, stream=None)
     if stream is not None:
         temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
     DeviceTopKRows64._run(temp, nbytes, keys, keys_out, values, values_out, rows, cols, stride, k, largest, has_values, stream, None)
+    return keys_out, values_out
+
+
+class DeviceTopKRowsAnyK:
+    """DeviceTopKRows without the cap at MaxK() (gs_topk_rows_anyk_u32): MinKeys / MaxKeys / MinPairs / MaxPairs / Plan / Status
+    for 32-bit keys and any 1 <= k <= num_cols.
+
+    Each row's result is what DeviceTopK gives for that row alone; for k <= DeviceTopKRows.MaxK() it is DeviceTopKRows' result,
+    and that class remains the faster one there.  Two-phase: d_temp_storage=None returns the size, 0 for a shape the entry
+    point refuses (k > num_cols, num_rows * k >= 2^31, ...).  Keys of any other width raise TypeError."""
+
+    @staticmethod
+    def _run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols, row_stride,
+             k, descending, has_values, stream, key_type):
+        need = lib.gs_topk_rows_anyk_temp_bytes(num_rows, num_cols, k, int(has_values))
+        if d_temp_storage is None:
+            return need
+        if not isinstance(d_keys_in, torch.Tensor) or d_keys_in.element_size() != 4:
+            raise TypeError("DeviceTopKRowsAnyK: 32-bit keys only")
+        key_type = _key_type_of(d_keys_in, key_type)
+        _check_rows_in(d_keys_in, "d_keys_in")
+        _check_buf(d_keys_out, num_rows * k, "d_keys_out")
+        if has_values:
+            if d_values_in is not None:
+                _check_rows_in(d_values_in, "d_values_in")
+            _check_buf(d_values_out, num_rows * k, "d_values_out")
+        err = lib.gs_topk_rows_anyk_u32(C.c_void_p(d_temp_storage.data_ptr()),
+                                        min(temp_storage_bytes, d_temp_storage.numel() * d_temp_storage.element_size()),
+                                        d_keys_in.data_ptr(), d_values_in.data_ptr() if d_values_in is not None else None,
+                                        d_keys_out.data_ptr(), d_values_out.data_ptr() if has_values else None,
+                                        num_rows, num_cols, row_stride, k, int(descending), key_type, _stream_ptr(stream))
+        check(err, "gs_topk_rows_anyk_u32")
+        return need
+
+    @staticmethod
+    def MinKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_rows, num_cols, row_stride, k, stream=None,
+                key_type=None):
+        return DeviceTopKRowsAnyK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_rows, num_cols,
+                                       row_stride, k, False, False, stream, key_type)
+
+    @staticmethod
+    def MaxKeys(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, num_rows, num_cols, row_stride, k, stream=None,
+                key_type=None):
+        return DeviceTopKRowsAnyK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, None, None, num_rows, num_cols,
+                                       row_stride, k, True, False, stream, key_type)
+
+    @staticmethod
+    def MinPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols,
+                 row_stride, k, stream=None, key_type=None):
+        return DeviceTopKRowsAnyK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out,
+                                       num_rows, num_cols, row_stride, k, False, True, stream, key_type)
+
+    @staticmethod
+    def MaxPairs(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows, num_cols,
+                 row_stride, k, stream=None, key_type=None):
+        return DeviceTopKRowsAnyK._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out,
+                                       num_rows, num_cols, row_stride, k, True, True, stream, key_type)
+
+    @staticmethod
+    def Plan(num_rows, num_cols, k, has_values=False):
+        """gs_topk_rows_anyk_plan: [path, kernel launches before the finish, CH, tile, tiles per slab, slabs per row, tiles per
+        row, 0]; a pure host function.  Raises for a refused shape."""
+        out = (C.c_uint32 * 8)()
+        check(lib.gs_topk_rows_anyk_plan(num_rows, num_cols, k, int(has_values), out), "gs_topk_rows_anyk_plan")
+        return [int(x) for x in out]
+
+    @staticmethod
+    def Status(d_temp_storage, num_rows, num_cols, k, has_values, row, stream=None):
+        """gs_topk_rows_anyk_status: [path, image of row `row`'s k-th element, elements before it, taken from its tie run,
+        elements that matched the prefix after round one, after round two, 0, 0] of the last call on d_temp_storage.
+        Synchronises the stream."""
+        out = (C.c_uint32 * 8)()
+        check(lib.gs_topk_rows_anyk_status(C.c_void_p(d_temp_storage.data_ptr()), num_rows, num_cols, k, int(has_values), row, out,
+                                           _stream_ptr(stream)), "gs_topk_rows_anyk_status")
+        return [int(x) for x in out]
+
+
+def topk_rows_anyk(keys, k, largest=False, values=None, indices=False, stream=None):
+    """topk_rows() for any 0 <= k <= cols in one batched call (gs_topk_rows_anyk_u32): the k smallest (largest=True: largest)
+    of every row of the 2-D tensor `keys` of 4-byte elements, sorted, as (keys_out, values_out) of shape [rows, k].
+
+    The checks and the return shapes are topk_rows()': the last dimension contiguous, rows at any stride >= cols, values a
+    4-byte tensor of the same shape and strides, indices=True for the column indices as int32 bit patterns of u32.  Any other
+    key width raises TypeError.  For k <= DeviceTopKRows.MaxK() topk_rows() gives the same result faster."""
+    if values is not None and indices:
+        raise ValueError("topk_rows_anyk: give values or indices=True, not both")
+    if keys.dim() != 2:
+        raise ValueError("topk_rows_anyk: a 2-D tensor, not %d-D" % keys.dim())
+    rows, cols = keys.shape
+    if cols > 1 and keys.stride(1) != 1:
+        raise ValueError("topk_rows_anyk: the last dimension must be contiguous")
+    if not 0 <= k <= cols:
+        raise ValueError(f"topk_rows_anyk: need 0 <= k <= {cols}")
+    stride = keys.stride(0) if rows > 1 else cols
+    if rows > 1 and stride < cols:
+        raise ValueError("topk_rows_anyk: rows overlap (stride %d < %d columns)" % (stride, cols))
+    if values is not None and (values.shape != keys.shape or values.element_size() != 4 or
+                               (cols > 1 and values.stride(1) != 1) or (rows > 1 and values.stride(0) != stride)):
+        raise ValueError("topk_rows_anyk: values must have the keys' shape and strides and 4-byte elements")
+    if keys.element_size() != 4:
+        raise TypeError("topk_rows_anyk: 32-bit keys only (int32, float32, uint32)")
+    has_values = values is not None or indices
+    keys_out = torch.empty((rows, k), dtype=keys.dtype, device=keys.device)
+    values_out = None
+    if has_values:
+        values_out = torch.empty((rows, k), dtype=values.dtype if values is not None else torch.int32, device=keys.device)
+    if k == 0 or rows == 0:
+        return keys_out, values_out
+    nbytes = lib.gs_topk_rows_anyk_temp_bytes(rows, cols, k, int(has_values))
+    if nbytes == 0 or rows * stride >= (1 << 32):
+        raise ValueError("topk_rows_anyk: the entry point refuses this shape (rows * stride below 2^32, rows * k below 2^31)")
+    temp = torch.empty(nbytes, dtype=torch.uint8, device=keys.device)
+    if stream is not None:
+        temp.record_stream(stream)   # the workspace is freed on return: keep it until the stream has used it
+    DeviceTopKRowsAnyK._run(temp, nbytes, keys, keys_out, values, values_out, rows, cols, stride, k, largest, has_values, stream, None)
     return keys_out, values_out
 
 

@@ -384,6 +384,61 @@ struct DeviceTopKRows {
     }
 };
 
+// DeviceTopKRows without the cap at gs_topk_rows_max_k() (gs_topk_rows_anyk_u32): 32-bit keys (unsigned int, int, float), any
+// 1 <= k <= num_cols, 32-bit values at the same row_stride.  Each row's result is what DeviceTopK gives for that row alone; for
+// k <= gs_topk_rows_max_k() it is DeviceTopKRows' result, and that struct remains the faster one there.  A size query of 0
+// with a non-empty shape means the shape is refused (k > num_cols, num_rows * k >= 2^31, ...).
+struct DeviceTopKRowsAnyK {
+    template <typename KeyT, typename ValueT>
+    static hipError_t Dispatch(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                               const ValueT *d_values_in, ValueT *d_values_out, uint64_t num_rows, uint64_t num_cols,
+                               uint64_t row_stride, uint64_t k, bool descending, hipStream_t stream)
+    {
+        static_assert(sizeof(KeyT) == 4 && KeyTraits<KeyT>::type <= GS_KEY_F32, "unsigned int, int or float keys");
+        static_assert(sizeof(ValueT) == 4, "32-bit values only");
+        const bool has_values = d_values_out != nullptr;
+        if (d_temp_storage == nullptr) {
+            temp_storage_bytes = gs_topk_rows_anyk_temp_bytes(num_rows, num_cols, k, has_values);
+            return hipSuccess;
+        }
+        return static_cast<hipError_t>(gs_topk_rows_anyk_u32(
+            d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint32_t *>(d_keys_in),
+            reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint32_t *>(d_keys_out),
+            reinterpret_cast<uint32_t *>(d_values_out), num_rows, num_cols, row_stride, k, descending ? 1 : 0, KeyTraits<KeyT>::type,
+            stream));
+    }
+    template <typename KeyT>
+    static hipError_t MinKeys(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                              uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, uint32_t>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, nullptr, nullptr, num_rows, num_cols,
+                                        row_stride, k, false, stream);
+    }
+    template <typename KeyT>
+    static hipError_t MaxKeys(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                              uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, uint32_t>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, nullptr, nullptr, num_rows, num_cols,
+                                        row_stride, k, true, stream);
+    }
+    template <typename KeyT, typename ValueT>
+    static hipError_t MinPairs(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                               const ValueT *d_values_in, ValueT *d_values_out, uint64_t num_rows, uint64_t num_cols,
+                               uint64_t row_stride, uint64_t k, hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, ValueT>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows,
+                                      num_cols, row_stride, k, false, stream);
+    }
+    template <typename KeyT, typename ValueT>
+    static hipError_t MaxPairs(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                               const ValueT *d_values_in, ValueT *d_values_out, uint64_t num_rows, uint64_t num_cols,
+                               uint64_t row_stride, uint64_t k, hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, ValueT>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, num_rows,
+                                      num_cols, row_stride, k, true, stream);
+    }
+};
+
 // The k best of every ragged segment of a flat array (gs_topk_segmented_u32): segment s is d_keys_in[d_begin_offsets[s] ..
 // d_end_offsets[s]) (device offsets, clamped to [0, num_items] on the device), its min(k, length) best -- what DeviceTopK gives
 // for that segment alone -- go to d_keys_out[s * k ..) and the same range of d_values_out, and d_counts_out[s] (may be nullptr)
