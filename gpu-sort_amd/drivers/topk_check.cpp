@@ -2,20 +2,7 @@
 // unsigned int / int / float keys, sort a copy of the input with the stable pair sort and take the top k of the original,
 // in all four call shapes (Min / Max, keys / pairs with the input indices as values); the first k must agree bit for bit.
 //   usage: topk_check [num_items]     prints OK and exits 0 iff every case matches
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
-#include <vector>
-
-#include "gpusort.hpp"
-
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %d at %s:%d\n", (int)e_, __FILE__, __LINE__); exit(2); } } while (0)
-
-template <typename T> static const char *name_of();
-template <> const char *name_of<unsigned int>() { return "u32"; }
-template <> const char *name_of<int>() { return "i32"; }
-template <> const char *name_of<float>() { return "f32"; }
+#include "topk_check_common.hpp"
 
 template <typename KeyT>
 static int test_case(size_t n, size_t k, bool descending, int spread)
@@ -78,11 +65,7 @@ static int test_case(size_t n, size_t k, bool descending, int spread)
         const unsigned int *vin = mode == 1 ? d_idx : nullptr;
         d_temp = nullptr; temp_bytes = 0;
         auto run = [&]() -> hipError_t {
-            if (mode == 0)
-                return descending ? gpusort::DeviceTopK::MaxKeys(d_temp, temp_bytes, d_in, d_top, n, k)
-                                  : gpusort::DeviceTopK::MinKeys(d_temp, temp_bytes, d_in, d_top, n, k);
-            return descending ? gpusort::DeviceTopK::MaxPairs(d_temp, temp_bytes, d_in, d_top, vin, d_top_idx, n, k)
-                              : gpusort::DeviceTopK::MinPairs(d_temp, temp_bytes, d_in, d_top, vin, d_top_idx, n, k);
+            return top<gpusort::DeviceTopK>(mode, descending, d_temp, temp_bytes, d_in, d_top, vin, d_top_idx, n, k);
         };
         HIP_OK(run());
         HIP_OK(hipMalloc(&d_temp, temp_bytes));
@@ -94,8 +77,8 @@ static int test_case(size_t n, size_t k, bool descending, int spread)
         int b = memcmp(got_k.data(), want_k.data(), k * 4) != 0;
         if (mode && memcmp(got_i.data(), want_i.data(), k * 4) != 0) b = 1;
         bad += b;
-        printf("%s keys, %s, n=%zu, k=%zu, %s, input %d: %s\n", name_of<KeyT>(), mode == 0 ? "keys" : mode == 1 ? "pairs" : "arguments",
-               n, k, descending ? "max" : "min", spread, b ? "FAIL" : "CORRECT");
+        printf("%s keys, %s, n=%zu, k=%zu, %s, input %d: %s\n", name_of<KeyT>(), mode_name(mode), n, k, descending ? "max" : "min", spread,
+               b ? "FAIL" : "CORRECT");
     }
     HIP_OK(hipFree(d_in)); HIP_OK(hipFree(d_sorted)); HIP_OK(hipFree(d_top));
     HIP_OK(hipFree(d_idx)); HIP_OK(hipFree(d_idx_sorted)); HIP_OK(hipFree(d_top_idx));

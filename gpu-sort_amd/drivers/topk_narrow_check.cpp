@@ -4,36 +4,10 @@
 // (GS_KEY_F32's map at width 16 for the float types).  The key input starts one element into its allocation in every second
 // case, so its base alternates between 4- and 2-byte alignment.
 //   usage: topk_narrow_check     prints OK and exits 0 iff every case matches
-#include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <numeric>
-#include <random>
-#include <vector>
+#include "topk_check_common.hpp"
 
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <hip/hip_bf16.h>
-
-#include "gpusort.hpp"
-
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %d at %s:%d\n", (int)e_, __FILE__, __LINE__); exit(2); } } while (0)
-
-template <typename T> static const char *name_of();
-template <> const char *name_of<unsigned short>() { return "u16"; }
-template <> const char *name_of<short>() { return "i16"; }
-template <> const char *name_of<_Float16>() { return "f16"; }
-template <> const char *name_of<__hip_bfloat16>() { return "bf16"; }
-
-// the order-preserving 16-bit image of a key's bit pattern
-static uint16_t image16(uint16_t k, int key_type, bool descending)
-{
-    if (key_type == GS_KEY_I16) k ^= 0x8000u;
-    else if (key_type == GS_KEY_F16 || key_type == GS_KEY_BF16) k = (k & 0x8000u) ? (uint16_t)~k : (uint16_t)(k ^ 0x8000u);
-    return descending ? (uint16_t)~k : k;
-}
+// input 1: one top byte, past 65536 elements the input is re-read; input 2: eight values
+static const Inputs<uint16_t> INPUTS = {0x00ffu, 0x3f00u, 0x8003u, 0, 0, {}};
 
 template <typename KeyT>
 static int test_case(size_t n, size_t k, bool descending, int spread, size_t in_off)
@@ -42,13 +16,7 @@ static int test_case(size_t n, size_t k, bool descending, int spread, size_t in_
     std::mt19937_64 rng(2024 + n * 7 + k * 3 + spread);
     std::vector<uint16_t> h_keys(n);
     std::vector<unsigned int> h_vals(n);
-    for (size_t i = 0; i < n; ++i) {
-        uint16_t bits = (uint16_t)rng();
-        if (spread == 1) bits = (uint16_t)((bits & 0x00ffu) | 0x3f00u);   // one top byte: past 65536 elements the input is re-read
-        if (spread == 2) bits &= 0x8003u;                                  // eight values: the cut falls inside a run of equal keys
-        h_keys[i] = bits;
-        h_vals[i] = (unsigned int)rng();
-    }
+    fill(rng, spread, INPUTS, h_keys, h_vals);
     uint16_t *d_alloc;
     KeyT *d_out;
     unsigned int *d_vin, *d_vout;
@@ -62,7 +30,7 @@ static int test_case(size_t n, size_t k, bool descending, int spread, size_t in_
     std::vector<uint32_t> order(n);
     std::iota(order.begin(), order.end(), 0u);
     std::stable_sort(order.begin(), order.end(),
-                     [&](uint32_t a, uint32_t b) { return image16(h_keys[a], kt, descending) < image16(h_keys[b], kt, descending); });
+                     [&](uint32_t a, uint32_t b) { return image_of(h_keys[a], kt, descending) < image_of(h_keys[b], kt, descending); });
 
     int bad = 0;
     std::vector<uint16_t> got_k(k);
@@ -72,13 +40,7 @@ static int test_case(size_t n, size_t k, bool descending, int spread, size_t in_
         const unsigned int *vin = mode == 1 ? d_vin : nullptr;
         void *d_temp = nullptr;
         size_t temp_bytes = 0;
-        auto run = [&]() -> hipError_t {
-            if (mode == 0)
-                return descending ? gpusort::DeviceTopK::MaxKeys(d_temp, temp_bytes, d_in, d_out, n, k)
-                                  : gpusort::DeviceTopK::MinKeys(d_temp, temp_bytes, d_in, d_out, n, k);
-            return descending ? gpusort::DeviceTopK::MaxPairs(d_temp, temp_bytes, d_in, d_out, vin, d_vout, n, k)
-                              : gpusort::DeviceTopK::MinPairs(d_temp, temp_bytes, d_in, d_out, vin, d_vout, n, k);
-        };
+        auto run = [&]() -> hipError_t { return top<gpusort::DeviceTopK>(mode, descending, d_temp, temp_bytes, d_in, d_out, vin, d_vout, n, k); };
         HIP_OK(run());
         if (temp_bytes == 0 || temp_bytes != gs_topk_u16_temp_bytes(n, k, mode != 0)) { printf("the shim asked another size query\n"); return 1; }
         HIP_OK(hipMalloc(&d_temp, temp_bytes));
@@ -96,11 +58,10 @@ static int test_case(size_t n, size_t k, bool descending, int spread, size_t in_
             if (mode == 1 && got_v[i] != h_vals[j]) b = 1;
             if (mode == 2 && got_v[i] != j) b = 1;
         }
-        if (st[1] != image16(h_keys[order[k - 1]], kt, descending) || st[2] + st[3] != k) b = 1;
+        if (st[1] != image_of(h_keys[order[k - 1]], kt, descending) || st[2] + st[3] != k) b = 1;
         bad += b;
-        printf("%s keys, %s, n=%zu, k=%zu, %s, input %d, offset %zu, route %u: %s\n", name_of<KeyT>(),
-               mode == 0 ? "keys" : mode == 1 ? "pairs" : "arguments", n, k, descending ? "max" : "min", spread, in_off, st[0],
-               b ? "FAIL" : "CORRECT");
+        printf("%s keys, %s, n=%zu, k=%zu, %s, input %d, offset %zu, route %u: %s\n", name_of<KeyT>(), mode_name(mode), n, k,
+               descending ? "max" : "min", spread, in_off, st[0], b ? "FAIL" : "CORRECT");
     }
     HIP_OK(hipFree(d_alloc)); HIP_OK(hipFree(d_vin)); HIP_OK(hipFree(d_out)); HIP_OK(hipFree(d_vout));
     return bad;

@@ -5,39 +5,14 @@
 // long / long long / double keys; every segment's first count elements and the counts must agree bit for bit, and the slots
 // behind a segment's count must keep their fill.
 //   usage: topk_segmented_wide_check     prints OK and exits 0 iff every case matches; stops at the first mismatch
-#include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <numeric>
-#include <random>
-#include <vector>
+#include "topk_check_common.hpp"
 
-#include <hip/hip_runtime.h>
-
-#include "gpusort.hpp"
-
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %d at %s:%d\n", (int)e_, __FILE__, __LINE__); exit(2); } } while (0)
-
-template <typename T> static const char *name_of();
-template <> const char *name_of<unsigned long long>() { return "u64"; }
-template <> const char *name_of<long long>() { return "i64"; }
-template <> const char *name_of<double>() { return "f64"; }
-
-// the order-preserving image of a key's bit pattern (the maps stated at the GS_KEY_* enum), complemented when descending
-template <typename T> static uint64_t image_of(uint64_t bits, bool descending);
-template <> uint64_t image_of<unsigned long long>(uint64_t b, bool d) { return d ? ~b : b; }
-template <> uint64_t image_of<long long>(uint64_t b, bool d) { b ^= 0x8000000000000000ull; return d ? ~b : b; }
-template <> uint64_t image_of<double>(uint64_t b, bool d)
-{
-    b = (b >> 63) ? ~b : b ^ 0x8000000000000000ull;
-    return d ? ~b : b;
-}
-
-static const uint64_t SPECIALS[] = {0x7ff8000000000001ull, 0xfff8000000000001ull, 0xffffffffffffffffull, 0x7ff0000000000000ull,
-                                    0xfff0000000000000ull, 0x0000000000000000ull, 0x8000000000000000ull, 0x0000000000000001ull,
-                                    0x7fffffffffffffffull, 0x3ff0000000000000ull, 0xbff0000000000000ull};
+// input 0: every third key a special value; input 1: integers below 2^24, five bytes are constant; input 2: eight values, the
+// cut falls inside a tie run
+static const Inputs<uint64_t> INPUTS = {0xffffffull, 0, 0x8000000000000003ull, 0x3ff0000000000000ull, 3,
+                                        {0x7ff8000000000001ull, 0xfff8000000000001ull, 0xffffffffffffffffull, 0x7ff0000000000000ull,
+                                         0xfff0000000000000ull, 0x0000000000000000ull, 0x8000000000000000ull, 0x0000000000000001ull,
+                                         0x7fffffffffffffffull, 0x3ff0000000000000ull, 0xbff0000000000000ull}};
 
 static const size_t CLASS_LENS[6][4] = {{1, 40, 64, 0}, {65, 200, 256, 0}, {257, 400, 512, 0}, {513, 900, 1024, 0},
                                         {1025, 3000, 8192, 0}, {8193, 20000, 0, 0}};
@@ -46,6 +21,7 @@ template <typename KeyT>
 static int test_case(int cls, int mode, bool descending, size_t k, int spread)
 {
     static_assert(sizeof(KeyT) == 8, "64-bit keys");
+    constexpr int kt = gpusort::KeyTraits<KeyT>::type;
     std::vector<int> begin, end;
     size_t n = 3;
     for (int j = 0; j < 4 && CLASS_LENS[cls][j]; ++j) {
@@ -64,14 +40,7 @@ static int test_case(int cls, int mode, bool descending, size_t k, int spread)
     std::mt19937_64 rng(7121 + 31 * cls + 7 * mode + k + spread);
     std::vector<uint64_t> h_keys(n);
     std::vector<unsigned int> h_vals(n);
-    for (size_t i = 0; i < n; ++i) {
-        uint64_t bits = rng();
-        if (spread == 1) bits &= 0xffffffull;                                 // integers below 2^24: five bytes are constant
-        if (spread == 2) bits = (bits & 0x8000000000000003ull) | 0x3ff0000000000000ull;   // eight values: the cut falls inside a tie run
-        if (spread == 0 && (i % 3) == 0) bits = SPECIALS[(i / 3) % (sizeof(SPECIALS) / sizeof(SPECIALS[0]))];
-        h_keys[i] = bits;
-        h_vals[i] = (unsigned int)rng();
-    }
+    fill(rng, spread, INPUTS, h_keys, h_vals);
     KeyT *d_in, *d_out;
     unsigned int *d_vin, *d_vout, *d_counts;
     int *d_begin, *d_end;
@@ -88,12 +57,8 @@ static int test_case(int cls, int mode, bool descending, size_t k, int spread)
     void *d_temp = nullptr;
     size_t temp_bytes = 0;
     auto run = [&]() -> hipError_t {
-        using D = gpusort::DeviceTopKSegmented;
-        if (mode == 0)
-            return descending ? D::MaxKeys(d_temp, temp_bytes, d_in, d_out, d_counts, n, (uint32_t)S, d_begin, d_end, k)
-                              : D::MinKeys(d_temp, temp_bytes, d_in, d_out, d_counts, n, (uint32_t)S, d_begin, d_end, k);
-        return descending ? D::MaxPairs(d_temp, temp_bytes, d_in, d_out, vin, d_vout, d_counts, n, (uint32_t)S, d_begin, d_end, k)
-                          : D::MinPairs(d_temp, temp_bytes, d_in, d_out, vin, d_vout, d_counts, n, (uint32_t)S, d_begin, d_end, k);
+        return top<gpusort::DeviceTopKSegmented>(mode, descending, d_temp, temp_bytes, d_in, d_out, vin, d_vout, d_counts, n, (uint32_t)S,
+                                                 d_begin, d_end, k);
     };
     HIP_OK(run());
     if (temp_bytes == 0 || temp_bytes != gs_topk_segmented_u64_temp_bytes(n, (uint32_t)S, k, mode != 0)) {
@@ -118,7 +83,7 @@ static int test_case(int cls, int mode, bool descending, size_t k, int spread)
         std::vector<unsigned int> order(len);
         std::iota(order.begin(), order.end(), 0u);
         std::stable_sort(order.begin(), order.end(), [&](unsigned int x, unsigned int y) {
-            return image_of<KeyT>(h_keys[lo + x], descending) < image_of<KeyT>(h_keys[lo + y], descending);
+            return image_of(h_keys[lo + x], kt, descending) < image_of(h_keys[lo + y], kt, descending);
         });
         for (size_t i = 0; i < kept; ++i) {
             want_k[s * k + i] = h_keys[lo + order[i]];
@@ -128,8 +93,8 @@ static int test_case(int cls, int mode, bool descending, size_t k, int spread)
     // the reference buffers keep the fill behind every count, so whole-buffer equality also proves the unwritten slots
     if (memcmp(got_k.data(), want_k.data(), S * k * 8) != 0) b = 1;
     if (memcmp(got_v.data(), want_v.data(), S * k * 4) != 0) b = 1;
-    printf("%s keys, %s, list %d, segments=%zu, items=%zu, k=%zu, %s, input %d: %s\n", name_of<KeyT>(),
-           mode == 0 ? "keys" : mode == 1 ? "pairs" : "arguments", cls, S, n, k, descending ? "max" : "min", spread, b ? "FAIL" : "CORRECT");
+    printf("%s keys, %s, list %d, segments=%zu, items=%zu, k=%zu, %s, input %d: %s\n", name_of<KeyT>(), mode_name(mode), cls, S, n, k,
+           descending ? "max" : "min", spread, b ? "FAIL" : "CORRECT");
     HIP_OK(hipFree(d_in)); HIP_OK(hipFree(d_vin)); HIP_OK(hipFree(d_out)); HIP_OK(hipFree(d_vout));
     HIP_OK(hipFree(d_counts)); HIP_OK(hipFree(d_begin)); HIP_OK(hipFree(d_end));
     return b;

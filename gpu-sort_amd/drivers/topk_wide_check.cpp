@@ -4,33 +4,11 @@
 // Min and Max, and check the result against a stable sort on the host of the 64-bit image.  The key input starts one element
 // into its allocation in every second case.
 //   usage: topk_wide_check     prints OK and exits 0 iff every case matches
-#include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <numeric>
-#include <random>
-#include <vector>
+#include "topk_check_common.hpp"
 
-#include <hip/hip_runtime.h>
-
-#include "gpusort.hpp"
-
-#define HIP_OK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %d at %s:%d\n", (int)e_, __FILE__, __LINE__); exit(2); } } while (0)
-
-template <typename T> static const char *name_of();
-template <> const char *name_of<unsigned long long>() { return "u64"; }
-template <> const char *name_of<long long>() { return "i64"; }
-template <> const char *name_of<double>() { return "f64"; }
-
-// the order-preserving 64-bit image of a key's bit pattern
-static uint64_t image64(uint64_t k, int key_type, bool descending)
-{
-    if (key_type == GS_KEY_I64) k ^= 0x8000000000000000ull;
-    else if (key_type == GS_KEY_F64) k = (k >> 63) ? ~k : (k ^ 0x8000000000000000ull);
-    return descending ? ~k : k;
-}
+// input 1: integers below 2^24, bytes 6..3 are skipped; input 2: four values, the cut falls inside a run of equal keys (route
+// 2 once a run is longer than the candidate list)
+static const Inputs<uint64_t> INPUTS = {0xffffffull, 0, 0x8000000000000001ull, 0, 0, {}};
 
 template <typename KeyT>
 static int test_case(size_t n, size_t k, bool descending, int spread, size_t in_off)
@@ -39,14 +17,7 @@ static int test_case(size_t n, size_t k, bool descending, int spread, size_t in_
     std::mt19937_64 rng(2024 + n * 7 + k * 3 + spread);
     std::vector<uint64_t> h_keys(n);
     std::vector<unsigned int> h_vals(n);
-    for (size_t i = 0; i < n; ++i) {
-        uint64_t bits = rng();
-        if (spread == 1) bits &= 0xffffffull;                  // integers below 2^24: bytes 6..3 are skipped
-        if (spread == 2) bits &= 0x8000000000000001ull;        // four values: the cut falls inside a run of equal keys (route 2
-                                                               // once a run is longer than the candidate list)
-        h_keys[i] = bits;
-        h_vals[i] = (unsigned int)rng();
-    }
+    fill(rng, spread, INPUTS, h_keys, h_vals);
     uint64_t *d_alloc;
     KeyT *d_out;
     unsigned int *d_vin, *d_vout;
@@ -60,7 +31,7 @@ static int test_case(size_t n, size_t k, bool descending, int spread, size_t in_
     std::vector<uint32_t> order(n);
     std::iota(order.begin(), order.end(), 0u);
     std::stable_sort(order.begin(), order.end(),
-                     [&](uint32_t a, uint32_t b) { return image64(h_keys[a], kt, descending) < image64(h_keys[b], kt, descending); });
+                     [&](uint32_t a, uint32_t b) { return image_of(h_keys[a], kt, descending) < image_of(h_keys[b], kt, descending); });
 
     int bad = 0;
     std::vector<uint64_t> got_k(k);
@@ -70,13 +41,7 @@ static int test_case(size_t n, size_t k, bool descending, int spread, size_t in_
         const unsigned int *vin = mode == 1 ? d_vin : nullptr;
         void *d_temp = nullptr;
         size_t temp_bytes = 0;
-        auto run = [&]() -> hipError_t {
-            if (mode == 0)
-                return descending ? gpusort::DeviceTopK::MaxKeys(d_temp, temp_bytes, d_in, d_out, n, k)
-                                  : gpusort::DeviceTopK::MinKeys(d_temp, temp_bytes, d_in, d_out, n, k);
-            return descending ? gpusort::DeviceTopK::MaxPairs(d_temp, temp_bytes, d_in, d_out, vin, d_vout, n, k)
-                              : gpusort::DeviceTopK::MinPairs(d_temp, temp_bytes, d_in, d_out, vin, d_vout, n, k);
-        };
+        auto run = [&]() -> hipError_t { return top<gpusort::DeviceTopK>(mode, descending, d_temp, temp_bytes, d_in, d_out, vin, d_vout, n, k); };
         HIP_OK(run());
         if (temp_bytes == 0 || temp_bytes != gs_topk_u64_temp_bytes(n, k, mode != 0)) { printf("the shim asked another size query\n"); return 1; }
         HIP_OK(hipMalloc(&d_temp, temp_bytes));
@@ -94,13 +59,12 @@ static int test_case(size_t n, size_t k, bool descending, int spread, size_t in_
             if (mode == 1 && got_v[i] != h_vals[j]) b = 1;
             if (mode == 2 && got_v[i] != j) b = 1;
         }
-        const uint64_t kth = image64(h_keys[order[k - 1]], kt, descending);
+        const uint64_t kth = image_of(h_keys[order[k - 1]], kt, descending);
         if (st[1] != (uint32_t)kth || st[2] != (uint32_t)(kth >> 32) || st[3] + st[4] != k) b = 1;
         if (st[6] != (st[5] == 1 ? 2u : st[5] + 2u)) b = 1;
         bad += b;
-        printf("%s keys, %s, n=%zu, k=%zu, %s, input %d, offset %zu, route %u, D %u: %s\n", name_of<KeyT>(),
-               mode == 0 ? "keys" : mode == 1 ? "pairs" : "arguments", n, k, descending ? "max" : "min", spread, in_off, st[0], st[5],
-               b ? "FAIL" : "CORRECT");
+        printf("%s keys, %s, n=%zu, k=%zu, %s, input %d, offset %zu, route %u, D %u: %s\n", name_of<KeyT>(), mode_name(mode), n, k,
+               descending ? "max" : "min", spread, in_off, st[0], st[5], b ? "FAIL" : "CORRECT");
     }
     HIP_OK(hipFree(d_alloc)); HIP_OK(hipFree(d_vin)); HIP_OK(hipFree(d_out)); HIP_OK(hipFree(d_vout));
     return bad;
