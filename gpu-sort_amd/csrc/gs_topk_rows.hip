@@ -5,8 +5,9 @@
 // gs_topk_segmented_u32 (section 10k), gs_topk_segmented_u16 (section 10l) and gs_topk_segmented_u64 (section 10o), the same for
 // ragged segments given by device offsets, follow them: they run the same device functions per record of lists that a classify
 // kernel fills (see "ragged segments" below), instantiated over the same three key-traits types.
-// gs_topk_rows_anyk_u32 (section 10p), the rows form without the cap on k, is at the end (see "any k" below): its selects stage
-// the k selected pairs of every row in the outputs and gs_segmented_sort_u32 finishes them.
+// gs_topk_rows_anyk_u32 (section 10p) and gs_topk_rows_anyk_u16 (section 10q), the rows form without the cap on k, are at the end
+// (see "any k" below): their selects stage the k selected pairs of every row in the outputs and gs_segmented_sort_u32 /
+// gs_segmented_sort_narrow finishes them.
 //
 // Row r of the result is what gs_topk_u32 writes for row r alone, bit for bit.  Every row has the same length, so the
 // launches are decided on the host from num_cols and k:
@@ -1298,16 +1299,52 @@ static int ts_status(void *d_temp, uint64_t num_items, uint32_t num_segments, ui
 //
 // No atomic decides a position and no kernel waits on another workgroup: a staged row is a function of the input alone.  Equal
 // keys land in ONE group in column order (section 10g), so the stable finish reproduces the definition.
+//
+// gs_topk_rows_anyk_u16 (section 10q) is the same host code and the same kernels at TrKey16: path 2 runs two counting rounds on
+// image bits 15-8 and 7-0 with 256 bins (TaWidth / TaRound below), and the finish is gs_segmented_sort_narrow on bits 0 .. 16.
 constexpr uint32_t TA_TILE = TR_CH;
 constexpr uint32_t TA_SLAB_TILES = 4;      // tiles one count workgroup histograms before it adds its bins (1, 4 and 16 measured: section 10p)
-constexpr uint32_t TA_BINS = 2048;         // rounds 0 and 1: 11 bits; round 2: 10 bits
+constexpr uint32_t TA_LDS_WORDS = 2048;    // the count kernel's LDS histogram at either width
 constexpr uint32_t TA_STATE_WORDS = 8;     // per row: k-th image (the prefix so far), less, take (krem), 0, matched after round 0, after round 1, 0, 0
 
-template <int ROUND> struct TaRound {
+// What the image width changes in the counting rounds of path 2 (gs_topk_rows_anyk_u16, section 10q, is the 16-bit one).
+// ROUNDS: how many; BINS: the words of a row's histogram in memory (the widest round's bins); COPIES: the LDS histogram of a count
+// workgroup holds that many interleaved copies of every bin, TA_LDS_WORDS words in all, and a lane adds to copy lane % COPIES.
+//   32 bits   three rounds on image bits 31-21, 20-10 and 9-0: 2048, 2048 and 1024 bins, one copy.
+//   16 bits   two rounds on image bits 15-8 and 7-0: 256 bins, eight copies.  The top byte of a half or bfloat16 score is its sign
+//             and most of its exponent: a wave's 64 images fall into a handful of bins, and same-address lanes of an LDS atomic
+//             serialise (see hist_add).  Eight copies cut such a run of lanes by eight in the LDS the 32-bit rounds use anyway.
+template <int BITS> struct TaWidth;
+template <> struct TaWidth<32> { static constexpr int ROUNDS = 3; static constexpr uint32_t BINS = 2048u, COPIES = 1u; };
+template <> struct TaWidth<16> { static constexpr int ROUNDS = 2; static constexpr uint32_t BINS = 256u, COPIES = 8u; };
+static_assert(TaWidth<32>::BINS * TaWidth<32>::COPIES == TA_LDS_WORDS && TaWidth<16>::BINS * TaWidth<16>::COPIES == TA_LDS_WORDS, "one LDS budget");
+
+template <int BITS, int ROUND> struct TaRound;
+template <int ROUND> struct TaRound<32, ROUND> {
     static constexpr uint32_t SHIFT = ROUND == 0 ? 21u : ROUND == 1 ? 10u : 0u;
     static constexpr uint32_t BINS = ROUND == 2 ? 1024u : 2048u;
     static constexpr uint32_t MASK = ROUND == 0 ? 0u : ROUND == 1 ? 0xffe00000u : 0xfffffc00u;   // the digits above this one
 };
+template <int ROUND> struct TaRound<16, ROUND> {
+    static_assert(ROUND < 2, "two rounds");
+    static constexpr uint32_t SHIFT = ROUND == 0 ? 8u : 0u;
+    static constexpr uint32_t BINS = 256u;
+    static constexpr uint32_t MASK = ROUND == 0 ? 0u : 0xff00u;   // (a 16-bit image has zeros above bit 15)
+};
+
+// hist_add into copy lane % COPIES of bin d.  One copy: hist_add itself.  A wave of one digit still adds once.
+template <uint32_t COPIES>
+__device__ __forceinline__ void ta_hist_add(uint32_t *hist, uint32_t d, uint32_t lane)
+{
+    if (COPIES == 1u) { hist_add(hist, d); return; }
+    const unsigned long long act = __builtin_amdgcn_ballot_w64(true);
+    const uint32_t d0 = __builtin_amdgcn_readfirstlane(d);
+    if (__builtin_amdgcn_ballot_w64(d == d0) == act) {
+        if (count_lower_mask(act) == 0) atomicAdd(&hist[d0 * COPIES], (uint32_t)__popcll(act));
+    } else {
+        atomicAdd(&hist[d * COPIES + (lane & (COPIES - 1u))], 1u);
+    }
+}
 
 // One workgroup: a tile of up to CH elements of a row into registers as images, in the (wave, row, lane) order of the block kernel.
 template <typename KT>
@@ -1405,13 +1442,14 @@ __global__ __launch_bounds__(TR_THREADS) void topk_anyk_count_kernel(const typen
                                                                      uint32_t x32)
 {
     using I = typename KT::I;
-    using R = TaRound<ROUND>;
+    using W = TaWidth<KT::BITS>;
+    using R = TaRound<KT::BITS, ROUND>;
     const I x = KT::xmask(x32);
-    __shared__ uint32_t h[TA_BINS];
+    __shared__ uint32_t h[TA_LDS_WORDS];
     const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
     const uint32_t r = blockIdx.x / slabs, sl = blockIdx.x - r * slabs;
     const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
-    for (uint32_t i = tid; i < R::BINS; i += TR_THREADS) h[i] = 0;
+    for (uint32_t i = tid; i < R::BINS * W::COPIES; i += TR_THREADS) h[i] = 0;
     const uint32_t prefix = ROUND == 0 ? 0u : state[(size_t)r * TA_STATE_WORDS];
     __syncthreads();
     const uint32_t t0 = sl * slab_tiles, t1 = t0 + slab_tiles < tiles ? t0 + slab_tiles : tiles;
@@ -1422,27 +1460,31 @@ __global__ __launch_bounds__(TR_THREADS) void topk_anyk_count_kernel(const typen
 #pragma unroll
         for (int u = 0; u < TR_KPT; ++u) {
             const uint32_t j = first + (uint32_t)u * WAVE;
-            if (j < len && (((uint32_t)img[u] ^ prefix) & R::MASK) == 0u) hist_add(h, ((uint32_t)img[u] >> R::SHIFT) & (R::BINS - 1u));
+            if (j < len && (((uint32_t)img[u] ^ prefix) & R::MASK) == 0u)
+                ta_hist_add<W::COPIES>(h, ((uint32_t)img[u] >> R::SHIFT) & (R::BINS - 1u), lane);
         }
     }
     __syncthreads();
-    uint32_t *__restrict__ g = hist + (size_t)r * TA_BINS;
+    uint32_t *__restrict__ g = hist + (size_t)r * W::BINS;
     for (uint32_t i = tid; i < R::BINS; i += TR_THREADS) {   // a wave over contiguous bins; only what this slab holds
-        const uint32_t c = h[i];
+        uint32_t c = h[i * W::COPIES];
+#pragma unroll
+        for (uint32_t q = 1; q < W::COPIES; ++q) c += h[i * W::COPIES + q];
         if (c) atomicAdd(g + i, c);
     }
 }
 
 // Path 2, a pick: one workgroup of 256 per row scans the round's bins, picks the one that holds the krem-th element, updates the
 // row's record and clears the histogram for the next round (and the next call).
-template <int ROUND>
+template <int BITS, int ROUND>
 __global__ __launch_bounds__(256) void topk_anyk_pick_kernel(uint32_t *__restrict__ state, uint32_t *__restrict__ hist, uint32_t k)
 {
-    using R = TaRound<ROUND>;
+    using W = TaWidth<BITS>;
+    using R = TaRound<BITS, ROUND>;
     constexpr uint32_t PER = R::BINS / 256u;
     __shared__ uint32_t scratch[8];
     const uint32_t tid = threadIdx.x;
-    uint32_t *__restrict__ h = hist + (size_t)blockIdx.x * TA_BINS + tid * PER;
+    uint32_t *__restrict__ h = hist + (size_t)blockIdx.x * W::BINS + tid * PER;
     uint32_t *__restrict__ st = state + (size_t)blockIdx.x * TA_STATE_WORDS;
     const uint32_t prefix = ROUND == 0 ? 0u : st[0], less = ROUND == 0 ? 0u : st[1], krem = ROUND == 0 ? k : st[2];
     uint32_t c[PER], sum = 0;
@@ -1457,11 +1499,14 @@ __global__ __launch_bounds__(256) void topk_anyk_pick_kernel(uint32_t *__restric
             st[0] = prefix | ((tid * PER + i) << R::SHIFT);
             st[1] = less + ex;
             st[2] = krem - ex;
-            if (ROUND < 2) st[4 + ROUND] = c[i];
+            if (ROUND + 1 < W::ROUNDS) st[4 + ROUND] = c[i];
         }
         ex += c[i];
     }
-    if (ROUND == 0 && tid == 0) { st[3] = 0; st[6] = 0; st[7] = 0; }
+    if (ROUND == 0 && tid == 0) {   // (the words no pick writes: with two rounds word 5 as well)
+        st[3] = 0; st[6] = 0; st[7] = 0;
+        if (W::ROUNDS < 3) st[5] = 0;
+    }
 }
 
 // Path 2, the select's counts: per (row, tile) the elements before the k-th image and those equal to it.
@@ -1559,60 +1604,99 @@ static inline bool ta_shape_ok(uint64_t rows, uint64_t cols, uint64_t k)
     return true;
 }
 
+template <typename KT>
 static inline TaPlan ta_make_plan(uint64_t cols)
 {
     TaPlan p{};
     if (cols <= TR_CH) { p.path = 1; p.launches = 2; p.slab_tiles = 1; p.slabs = 1; p.tiles = 1; return p; }
     p.path = 2;
-    p.launches = 11;   // zero, offsets, three times (count, pick), tile counts, scan, scatter
+    p.launches = 5u + 2u * (uint32_t)TaWidth<KT::BITS>::ROUNDS;   // zero, offsets, ROUNDS times (count, pick), tile counts, scan, scatter
     p.tiles = (uint32_t)((cols + TA_TILE - 1) / TA_TILE);
     p.slab_tiles = TA_SLAB_TILES;
     p.slabs = (p.tiles + p.slab_tiles - 1) / p.slab_tiles;
     return p;
 }
 
+// The finish by key width: the segmented sort of the staged pairs on the whole image, and its size query.
+template <typename KT> struct TaFinish;
+template <> struct TaFinish<TrKey32> {
+    static size_t temp_bytes(uint64_t items, bool hv, uint64_t rows) { return gs_segmented_temp_bytes(items, hv ? 1 : 0, (uint32_t)rows); }
+    static int sort(void *ws, size_t ws_bytes, uint32_t *dk[2], uint32_t *dv[2], int *selector, uint32_t items, uint32_t rows,
+                    const int32_t *offsets, int descending, int key_type, hipStream_t s)
+    {
+        return gs_segmented_sort_u32(ws, ws_bytes, dk, dv, selector, items, rows, offsets, offsets + 1, 0, 32, descending, key_type, s);
+    }
+};
+template <> struct TaFinish<TrKey16> {
+    static size_t temp_bytes(uint64_t items, bool hv, uint64_t rows)
+    {
+        return gs_segmented_narrow_temp_bytes(items, GS_KEY_U16, hv ? 4 : 0, (uint32_t)rows);
+    }
+    static int sort(void *ws, size_t ws_bytes, uint16_t *dk[2], uint32_t *dv[2], int *selector, uint32_t items, uint32_t rows,
+                    const int32_t *offsets, int descending, int key_type, hipStream_t s)
+    {
+        void *k2[2] = {dk[0], dk[1]}, *v2[2] = {dv ? dv[0] : nullptr, dv ? dv[1] : nullptr};
+        return gs_segmented_sort_narrow(ws, ws_bytes, k2, dv ? v2 : nullptr, selector, items, rows, offsets, offsets + 1, key_type,
+                                        dv ? 4 : 0, 0, 16, descending, s);
+    }
+};
+
+template <typename KT>
 struct TaWs {
     uint32_t *state;
     int32_t *offsets;
     uint32_t *hist;
     uint2 *counts;
-    uint32_t *keys1, *cols1, *cols0;
+    typename KT::T *keys1;
+    uint32_t *cols1, *cols0;
     char *seg;
     size_t seg_bytes;
 };
 
 // The header's workspace formula, term by term; returns the bytes carved (without the slack).
-static size_t ta_carve(char *base, uint64_t rows, uint64_t cols, uint64_t k, bool hv, bool pairs, TaWs *ws)
+template <typename KT>
+static size_t ta_carve(char *base, uint64_t rows, uint64_t cols, uint64_t k, bool hv, bool pairs, TaWs<KT> *ws)
 {
-    const TaPlan p = ta_make_plan(cols);
+    using T = typename KT::T;
+    const TaPlan p = ta_make_plan<KT>(cols);
     size_t off = 0;
     auto take = [&](size_t bytes) { char *q = base + off; off += gs_ws_align(bytes); return q; };
     ws->state = (uint32_t *)take((size_t)4 * TA_STATE_WORDS * rows);
     ws->offsets = (int32_t *)take((size_t)4 * (rows + 1));
     ws->hist = nullptr; ws->counts = nullptr;
     if (p.path == 2) {
-        ws->hist = (uint32_t *)take((size_t)4 * TA_BINS * rows);
+        ws->hist = (uint32_t *)take((size_t)4 * TaWidth<KT::BITS>::BINS * rows);
         ws->counts = (uint2 *)take((size_t)8 * rows * p.tiles);
     }
-    ws->keys1 = (uint32_t *)take((size_t)4 * rows * k);
+    ws->keys1 = (T *)take(sizeof(T) * rows * k);
     ws->cols1 = hv ? (uint32_t *)take((size_t)4 * rows * k) : nullptr;
     ws->cols0 = pairs ? (uint32_t *)take((size_t)4 * rows * k) : nullptr;
-    ws->seg_bytes = gs_segmented_temp_bytes(rows * k, hv ? 1 : 0, (uint32_t)rows);
+    ws->seg_bytes = TaFinish<KT>::temp_bytes(rows * k, hv, rows);
     ws->seg = take(ws->seg_bytes);
     return off;
 }
 
 // (The size query has no pointers to tell pairs from arguments: with values it holds the first half of the columns too.)
+template <typename KT>
 static size_t ta_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values)
 {
     if (!ta_shape_ok(num_rows, num_cols, k)) return 0;
     if (num_rows == 0 || num_cols == 0 || k == 0) return 0;
-    TaWs ws;
-    return ta_carve(nullptr, num_rows, num_cols, k, has_values != 0, has_values != 0, &ws) + GS_WS_SLACK;
+    TaWs<KT> ws;
+    return ta_carve<KT>(nullptr, num_rows, num_cols, k, has_values != 0, has_values != 0, &ws) + GS_WS_SLACK;
+}
+
+template <typename KT, int ROUND>
+static void ta_launch_round(hipStream_t s, const TaPlan &p, const TaWs<KT> &ws, const typename KT::T *ki, uint32_t rows, uint32_t cols,
+                            uint32_t stride, uint32_t k, int flt, uint32_t x)
+{
+    hipLaunchKernelGGL((topk_anyk_count_kernel<KT, ROUND>), dim3(rows * p.slabs), dim3(TR_THREADS), 0, s, ki, stride, cols, p.tiles, p.slabs,
+                       p.slab_tiles, (const uint32_t *)ws.state, ws.hist, flt, x);
+    hipLaunchKernelGGL((topk_anyk_pick_kernel<KT::BITS, ROUND>), dim3(rows), dim3(256), 0, s, ws.state, ws.hist, k);
 }
 
 template <typename KT, bool HV>
-static void ta_launch_select(hipStream_t s, const TaPlan &p, const TaWs &ws, const typename KT::T *ki, typename KT::T *dk, uint32_t *dc,
+static void ta_launch_select(hipStream_t s, const TaPlan &p, const TaWs<KT> &ws, const typename KT::T *ki, typename KT::T *dk, uint32_t *dc,
                              uint32_t rows, uint32_t cols, uint32_t stride, uint32_t k, int flt, uint32_t x)
 {
     KernelTimer kt(GS_K_OTHER, s);
@@ -1620,17 +1704,10 @@ static void ta_launch_select(hipStream_t s, const TaPlan &p, const TaWs &ws, con
         hipLaunchKernelGGL((topk_anyk_block_kernel<KT, HV>), dim3(rows), dim3(TR_THREADS), 0, s, ki, stride, cols, k, dk, dc, ws.state, flt, x);
         return;
     }
-    const dim3 gslab(rows * p.slabs), gtile(rows * p.tiles), grow(rows), wg(TR_THREADS);
-#define GS_TA_ROUND(R)                                                                                                             \
-    do {                                                                                                                           \
-        hipLaunchKernelGGL((topk_anyk_count_kernel<KT, R>), gslab, wg, 0, s, ki, stride, cols, p.tiles, p.slabs, p.slab_tiles,     \
-                           (const uint32_t *)ws.state, ws.hist, flt, x);                                                           \
-        hipLaunchKernelGGL((topk_anyk_pick_kernel<R>), grow, dim3(256), 0, s, ws.state, ws.hist, k);                               \
-    } while (0)
-    GS_TA_ROUND(0);
-    GS_TA_ROUND(1);
-    GS_TA_ROUND(2);
-#undef GS_TA_ROUND
+    const dim3 gtile(rows * p.tiles), grow(rows), wg(TR_THREADS);
+    ta_launch_round<KT, 0>(s, p, ws, ki, rows, cols, stride, k, flt, x);
+    ta_launch_round<KT, 1>(s, p, ws, ki, rows, cols, stride, k, flt, x);
+    if constexpr (TaWidth<KT::BITS>::ROUNDS == 3) ta_launch_round<KT, 2>(s, p, ws, ki, rows, cols, stride, k, flt, x);
     hipLaunchKernelGGL((topk_anyk_tilecount_kernel<KT>), gtile, wg, 0, s, ki, stride, cols, p.tiles, (const uint32_t *)ws.state, ws.counts, flt,
                        x);
     hipLaunchKernelGGL(topk_anyk_scan_kernel, grow, dim3(256), 0, s, (const uint32_t *)ws.state, ws.counts, p.tiles);
@@ -1638,11 +1715,12 @@ static void ta_launch_select(hipStream_t s, const TaPlan &p, const TaWs &ws, con
                        (const uint2 *)ws.counts, dk, dc, flt, x);
 }
 
-static int ta_run(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
+template <typename KT>
+static int ta_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_in, const uint32_t *d_vals_in, typename KT::T *d_keys_out,
                   uint32_t *d_vals_out, uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, int descending, int key_type,
                   void *stream)
 {
-    using KT = TrKey32;
+    using T = typename KT::T;
     GS_CLEAR_STALE_ERROR();
     if (!ta_shape_ok(num_rows, num_cols, k)) return hipErrorInvalidValue;
     if (row_stride < num_cols || tr_mul_ge_2p32(num_rows, row_stride)) return hipErrorInvalidValue;
@@ -1651,12 +1729,13 @@ static int ta_run(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, co
     if (num_rows == 0 || num_cols == 0 || k == 0) return hipSuccess;
     const bool hv = d_vals_out != nullptr, pairs = d_vals_in != nullptr;
     if (!d_keys_in || !d_keys_out) return hipErrorInvalidValue;
-    if (!d_temp || temp_bytes < ta_temp_bytes(num_rows, num_cols, k, hv)) return hipErrorInvalidValue;
-    if ((((uintptr_t)d_keys_in | (uintptr_t)d_keys_out | (uintptr_t)d_vals_in | (uintptr_t)d_vals_out) & 3u) != 0) return hipErrorInvalidValue;
+    if (!d_temp || temp_bytes < ta_temp_bytes<KT>(num_rows, num_cols, k, hv)) return hipErrorInvalidValue;
+    if ((((uintptr_t)d_keys_in | (uintptr_t)d_keys_out) & (sizeof(T) - 1)) != 0) return hipErrorInvalidValue;
+    if ((((uintptr_t)d_vals_in | (uintptr_t)d_vals_out) & 3u) != 0) return hipErrorInvalidValue;
     {
         const size_t in_elems = (size_t)((num_rows - 1) * row_stride + num_cols), out_elems = (size_t)(num_rows * k);
         const void *arr[4] = {d_keys_in, d_vals_in, d_keys_out, d_vals_out};
-        const size_t bytes[4] = {4 * in_elems, 4 * in_elems, 4 * out_elems, 4 * out_elems};
+        const size_t bytes[4] = {sizeof(T) * in_elems, 4 * in_elems, sizeof(T) * out_elems, 4 * out_elems};
         if (gs_any_overlap4(arr, bytes)) return hipErrorInvalidValue;
     }
     hipStream_t s = (hipStream_t)stream;
@@ -1664,12 +1743,12 @@ static int ta_run(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, co
     const uint32_t total = rows * kk;
     const int flt = KT::is_float(key_type);
     const uint32_t x = KT::xor_of(key_type, descending);
-    const TaPlan p = ta_make_plan(num_cols);
-    TaWs ws;
-    ta_carve(gs_ws_base(d_temp), num_rows, num_cols, k, hv, pairs, &ws);
+    const TaPlan p = ta_make_plan<KT>(num_cols);
+    TaWs<KT> ws;
+    ta_carve<KT>(gs_ws_base(d_temp), num_rows, num_cols, k, hv, pairs, &ws);
 
     if (p.path == 2) {   // the histograms start at zero; every pick leaves them so
-        const hipError_t e = zero_async(ws.hist, (size_t)4 * TA_BINS * rows, s);
+        const hipError_t e = zero_async(ws.hist, (size_t)4 * TaWidth<KT::BITS>::BINS * rows, s);
         if (e != hipSuccess) return (int)e;
     }
     {
@@ -1684,11 +1763,12 @@ static int ta_run(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, co
     int err = (int)hipGetLastError();
     if (err) return err;
 
-    // the finish: four passes over all 32 bits leave the result in half 0, where the pairs were staged
-    uint32_t *dk[2] = {d_keys_out, ws.keys1}, *dv[2] = {col0, ws.cols1};
+    // the finish: an even number of passes over the whole image (four of 32 bits, two of 16) leaves the result in half 0, where
+    // the pairs were staged
+    T *dk[2] = {d_keys_out, ws.keys1};
+    uint32_t *dv[2] = {col0, ws.cols1};
     int selector = 0;
-    err = gs_segmented_sort_u32(ws.seg, ws.seg_bytes, dk, hv ? dv : nullptr, &selector, total, rows, ws.offsets, ws.offsets + 1, 0, 32,
-                                descending, key_type, s);
+    err = TaFinish<KT>::sort(ws.seg, ws.seg_bytes, dk, hv ? dv : nullptr, &selector, total, rows, ws.offsets, descending, key_type, s);
     if (err) return err;
     if (selector != 0) return hipErrorUnknown;
     if (pairs) {
@@ -1700,17 +1780,19 @@ static int ta_run(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, co
     return (int)hipGetLastError();
 }
 
+template <typename KT>
 static int ta_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, uint32_t out[8])
 {
     if (!out) return hipErrorInvalidValue;
     for (int i = 0; i < 8; ++i) out[i] = 0;
     if (!ta_shape_ok(num_rows, num_cols, k)) return hipErrorInvalidValue;
     if (num_rows == 0 || num_cols == 0 || k == 0) return hipSuccess;   // such a call enqueues nothing
-    const TaPlan p = ta_make_plan(num_cols);
+    const TaPlan p = ta_make_plan<KT>(num_cols);
     out[0] = p.path; out[1] = p.launches; out[2] = TR_CH; out[3] = TA_TILE; out[4] = p.slab_tiles; out[5] = p.slabs; out[6] = p.tiles;
     return hipSuccess;
 }
 
+template <typename KT>
 static int ta_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint64_t row, uint32_t out[8],
                      void *stream)
 {
@@ -1720,13 +1802,13 @@ static int ta_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_
     if (!ta_shape_ok(num_rows, num_cols, k)) return hipErrorInvalidValue;
     if (num_rows == 0 || num_cols == 0 || k == 0) return hipSuccess;   // such a call enqueued nothing
     if (!d_temp || row >= num_rows) return hipErrorInvalidValue;
-    TaWs ws;
-    ta_carve(gs_ws_base(d_temp), num_rows, num_cols, k, has_values != 0, false, &ws);   // (only the records, the first term, are read)
+    TaWs<KT> ws;
+    ta_carve<KT>(gs_ws_base(d_temp), num_rows, num_cols, k, has_values != 0, false, &ws);   // (only the records, the first term, are read)
     uint32_t st[TA_STATE_WORDS];
     hipError_t e = hipMemcpyAsync(st, ws.state + row * TA_STATE_WORDS, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
-    out[0] = ta_make_plan(num_cols).path; out[1] = st[0]; out[2] = st[1]; out[3] = st[2]; out[4] = st[4]; out[5] = st[5];
+    out[0] = ta_make_plan<KT>(num_cols).path; out[1] = st[0]; out[2] = st[1]; out[3] = st[2]; out[4] = st[4]; out[5] = st[5];
     return hipSuccess;
 }
 
@@ -1843,27 +1925,52 @@ int gs_topk_segmented_status(void *d_temp, uint64_t num_items, uint32_t num_segm
 
 size_t gs_topk_rows_anyk_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values)
 {
-    return ta_temp_bytes(num_rows, num_cols, k, has_values);
+    return ta_temp_bytes<TrKey32>(num_rows, num_cols, k, has_values);
 }
 
 int gs_topk_rows_anyk_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
                           uint32_t *d_vals_out, uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, int descending,
                           int key_type, void *stream)
 {
-    return ta_run(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, num_rows, num_cols, row_stride, k, descending, key_type,
-                  stream);
+    return ta_run<TrKey32>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, num_rows, num_cols, row_stride, k, descending,
+                           key_type, stream);
 }
 
 int gs_topk_rows_anyk_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint32_t out[8])
 {
     (void)has_values;
-    return ta_plan(num_rows, num_cols, k, out);
+    return ta_plan<TrKey32>(num_rows, num_cols, k, out);
 }
 
 int gs_topk_rows_anyk_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint64_t row, uint32_t out[8],
                              void *stream)
 {
-    return ta_status(d_temp, num_rows, num_cols, k, has_values, row, out, stream);
+    return ta_status<TrKey32>(d_temp, num_rows, num_cols, k, has_values, row, out, stream);
+}
+
+size_t gs_topk_rows_anyk_u16_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values)
+{
+    return ta_temp_bytes<TrKey16>(num_rows, num_cols, k, has_values);
+}
+
+int gs_topk_rows_anyk_u16(void *d_temp, size_t temp_bytes, const uint16_t *d_keys_in, const uint32_t *d_vals_in, uint16_t *d_keys_out,
+                          uint32_t *d_vals_out, uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, int descending,
+                          int key_type, void *stream)
+{
+    return ta_run<TrKey16>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, num_rows, num_cols, row_stride, k, descending,
+                           key_type, stream);
+}
+
+int gs_topk_rows_anyk_u16_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint32_t out[8])
+{
+    (void)has_values;
+    return ta_plan<TrKey16>(num_rows, num_cols, k, out);
+}
+
+int gs_topk_rows_anyk_u16_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint64_t row,
+                                 uint32_t out[8], void *stream)
+{
+    return ta_status<TrKey16>(d_temp, num_rows, num_cols, k, has_values, row, out, stream);
 }
 
 }  // extern "C"

@@ -8,12 +8,13 @@
                             gs_topk_rows_u16          int16, uint16, float16, bfloat16
     DeviceTopKRows64        gs_topk_rows_u64          int64, float64, uint64
     DeviceTopKRowsAnyK      gs_topk_rows_anyk_u32     int32, float32, uint32; any k up to the row length
+    DeviceTopKRowsAnyK16    gs_topk_rows_anyk_u16     int16, uint16, float16, bfloat16; any k up to the row length
     DeviceTopKSegmented     gs_topk_segmented_u32     int32, float32, uint32
                             gs_topk_segmented_u16     int16, uint16, float16, bfloat16
     DeviceTopKSegmented64   gs_topk_segmented_u64     int64, float64, uint64
 
 The classes are two-phase like DeviceRadixSort (d_temp_storage=None returns the size); topk(), topk_rows(), topk_rows64(),
-topk_rows_anyk(), topk_segmented() and topk_segmented64() allocate outputs and workspace, topk() for any of the three widths.
+topk_rows_anyk(), topk_rows_anyk16(), topk_segmented() and topk_segmented64() allocate outputs and workspace, topk() for any of the three widths.
 The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs (descending for the Max forms) on the same
 input (the whole array, every row of a matrix, every ragged segment given by device offsets): stable, keys in the caller's bit
 patterns, floats in the order of GS_KEY_F32 (negative NaNs first, positive NaNs last ascending; -0.0 before +0.0), float16 /
@@ -318,20 +319,37 @@ class DeviceTopKRowsAnyK(_TopKRows):
     point refuses (k > num_cols, num_rows * k >= 2^31, ...).  Keys of any other width raise TypeError."""
 
     _entries = {_W32: ("gs_topk_rows_anyk_u32", "gs_topk_rows_anyk_temp_bytes")}
+    _plan, _status = "gs_topk_rows_anyk_plan", "gs_topk_rows_anyk_status"
 
-    @staticmethod
-    def Plan(num_rows, num_cols, k, has_values=False):
+    @classmethod
+    def Plan(cls, num_rows, num_cols, k, has_values=False):
         """gs_topk_rows_anyk_plan: [path, kernel launches before the finish, CH, tile, tiles per slab, slabs per row, tiles per
         row, 0]; a pure host function.  Raises for a refused shape."""
-        return _eight_words("gs_topk_rows_anyk_plan", num_rows, num_cols, k, int(has_values))
+        return _eight_words(cls._plan, num_rows, num_cols, k, int(has_values))
 
-    @staticmethod
-    def Status(d_temp_storage, num_rows, num_cols, k, has_values, row, stream=None):
+    @classmethod
+    def Status(cls, d_temp_storage, num_rows, num_cols, k, has_values, row, stream=None):
         """gs_topk_rows_anyk_status: [path, image of row `row`'s k-th element, elements before it, taken from its tie run,
         elements that matched the prefix after round one, after round two, 0, 0] of the last call on d_temp_storage.
         Synchronises the stream."""
-        return _eight_words("gs_topk_rows_anyk_status", C.c_void_p(d_temp_storage.data_ptr()), num_rows, num_cols, k,
-                            int(has_values), row, stream=(_stream_ptr(stream),))
+        return _eight_words(cls._status, C.c_void_p(d_temp_storage.data_ptr()), num_rows, num_cols, k, int(has_values), row,
+                            stream=(_stream_ptr(stream),))
+
+
+class DeviceTopKRowsAnyK16(DeviceTopKRowsAnyK):
+    """DeviceTopKRowsAnyK for a matrix of 16-bit keys (gs_topk_rows_anyk_u16): MinKeys / MaxKeys / MinPairs / MaxPairs / Plan /
+    Status for any 1 <= k <= num_cols.
+
+    The key type comes from the tensor's dtype (int16, uint16, float16, bfloat16) or from an explicit 16-bit key_type; each
+    row's result is what DeviceTopK16 gives for that row alone, and for k <= DeviceTopKRows.MaxK() it is DeviceTopKRows' result
+    on the same keys, that class remaining the faster one there.  Values and column indices are 4 bytes.  Plan() is
+    gs_topk_rows_anyk_u16_plan (two counting rounds: 9 launches before the finish on path 2, the geometry words those of
+    DeviceTopKRowsAnyK), Status() gs_topk_rows_anyk_u16_status: [path, 16-bit image of the k-th element, elements before it,
+    taken from its tie run, elements sharing its top byte, 0, 0, 0].  Keys of any other width and any other key_type raise
+    TypeError."""
+
+    _entries = {_W16: ("gs_topk_rows_anyk_u16", "gs_topk_rows_anyk_u16_temp_bytes")}
+    _plan, _status = "gs_topk_rows_anyk_u16_plan", "gs_topk_rows_anyk_u16_status"
 
 
 def _rows_call(who, front, keys, k, values, indices, stream):
@@ -357,8 +375,8 @@ def _rows_call(who, front, keys, k, values, indices, stream):
     if w is None:
         raise TypeError("%s: %s only%s" % ((who,) + front._accepts()))
     key_type = _key_type_of(keys, None, w, who)
-    if w is _W16 and k > lib.gs_topk_rows_max_k():
-        raise ValueError("%s: 16-bit keys need k <= %d; loop topk() over the rows for more" % (who, lib.gs_topk_rows_max_k()))
+    if w is _W16 and hasattr(front, "MaxK") and k > lib.gs_topk_rows_max_k():   # (a front without a cap takes any k)
+        raise ValueError("%s: 16-bit keys need k <= %d; topk_rows_anyk16() serves more" % (who, lib.gs_topk_rows_max_k()))
     has_values, keys_out, values_out = _outputs((rows, k), keys, values, indices)
     nbytes = None
     if k != 0 and rows != 0:
@@ -394,7 +412,7 @@ def topk_rows(keys, k, largest=False, values=None, indices=False, stream=None):
     values: a 4-byte tensor of the same shape and strides, carried with the keys.  indices=True (without values): values_out
     holds the column indices as int32 bit patterns of u32.  Neither: values_out is None.  Allocates outputs and workspace.
     A k above DeviceTopKRows.MaxK() is served by gs_topk_u32 row by row.  2-byte keys (int16, uint16, float16, bfloat16) take
-    gs_topk_rows_u16; for them a k above MaxK() raises ValueError: such callers loop topk() over the rows."""
+    gs_topk_rows_u16; for them a k above MaxK() raises ValueError: such callers use topk_rows_anyk16()."""
     return _topk_rows("topk_rows", DeviceTopKRows, DeviceTopK, keys, k, largest, values, indices, stream)
 
 
@@ -415,14 +433,30 @@ def topk_rows_anyk(keys, k, largest=False, values=None, indices=False, stream=No
     The checks and the return shapes are topk_rows()': the last dimension contiguous, rows at any stride >= cols, values a
     4-byte tensor of the same shape and strides, indices=True for the column indices as int32 bit patterns of u32.  Any other
     key width raises TypeError.  For k <= DeviceTopKRows.MaxK() topk_rows() gives the same result faster."""
-    key_type, rows, cols, stride, has_values, keys_out, values_out, nbytes = _rows_call("topk_rows_anyk", DeviceTopKRowsAnyK, keys, k,
-                                                                                       values, indices, stream)
+    return _topk_rows_anyk("topk_rows_anyk", DeviceTopKRowsAnyK, keys, k, largest, values, indices, stream)
+
+
+def topk_rows_anyk16(keys, k, largest=False, values=None, indices=False, stream=None):
+    """topk_rows_anyk() for a 2-D tensor of 2-byte keys (int16, uint16, float16, bfloat16): the k smallest (largest=True:
+    largest) of every row for any 0 <= k <= cols in one batched call, sorted, as (keys_out, values_out) of shape [rows, k],
+    through gs_topk_rows_anyk_u16.
+
+    The checks and the return shapes are topk_rows()': the last dimension contiguous, rows at any stride >= cols, values a
+    4-byte tensor of the same shape and strides, indices=True for the column indices as int32 bit patterns of u32.  The keys
+    come back in the input dtype, float16 / bfloat16 in the order of GS_KEY_F16 / BF16 at the enum.  Any other key width raises
+    TypeError.  For k <= DeviceTopKRows.MaxK() topk_rows() gives the same result faster."""
+    return _topk_rows_anyk("topk_rows_anyk16", DeviceTopKRowsAnyK16, keys, k, largest, values, indices, stream)
+
+
+def _topk_rows_anyk(who, front, keys, k, largest, values, indices, stream):
+    """topk_rows_anyk() and topk_rows_anyk16(): the argument checks in the name of `who`, the outputs, and `front`'s call."""
+    key_type, rows, cols, stride, has_values, keys_out, values_out, nbytes = _rows_call(who, front, keys, k, values, indices, stream)
     if nbytes is None:
         return keys_out, values_out
     if nbytes == 0 or rows * stride >= (1 << 32):
-        raise ValueError("topk_rows_anyk: the entry point refuses this shape (rows * stride below 2^32, rows * k below 2^31)")
+        raise ValueError(f"{who}: the entry point refuses this shape (rows * stride below 2^32, rows * k below 2^31)")
     temp = _workspace(nbytes, keys.device, stream)
-    DeviceTopKRowsAnyK._run(temp, nbytes, keys, keys_out, values, values_out, rows, cols, stride, k, largest, has_values, stream, key_type)
+    front._run(temp, nbytes, keys, keys_out, values, values_out, rows, cols, stride, k, largest, has_values, stream, key_type)
     return keys_out, values_out
 
 

@@ -719,6 +719,75 @@ int      gs_topk_rows_anyk_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k
 int      gs_topk_rows_anyk_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values,
                                   uint64_t row, uint32_t out[8], void *stream);
 
+/* ------------------------------------- top k of every row, any k, 16-bit keys --
+ * gs_topk_rows_anyk_u32 for 16-bit keys, its kernels instantiated for them (gs_topk_rows.hip): a wide
+ * nucleus over bfloat16 logits, the 2000 ... 12000 half scores a detector keeps per image, a few thousand candidates per query,
+ * without widening the matrix and without a loop of gs_topk_u16 over the rows.  key_type is GS_KEY_U16, GS_KEY_I16, GS_KEY_F16 or
+ * GS_KEY_BF16, in the order stated at the enum for gs_lsb_sort_narrow (GS_KEY_F32's map at width 16: negative NaNs first,
+ * positive NaNs last, -0 before +0).  1 <= k <= num_cols; everything else is gs_topk_rows_anyk_u32's contract word for word,
+ * with 2-byte keys.  Row r of the result is bit for bit what gs_topk_u16 writes for that row alone: the first k of the stable
+ * sort on the 16-bit order-preserving image (complemented at 16 bits when descending), the lowest column indices where the cut
+ * falls inside a run of equal keys, the caller's bit patterns kept (NaN payloads included).  Equivalently it is what
+ * gs_topk_rows_anyk_u32 gives on the matrix (uint32_t)key << 16 with the key type widened (U16 -> U32, I16 -> I32, F16 / BF16 ->
+ * F32), the returned keys shifted right by 16, values and column indices unchanged.  A k of 1024 and below is served too, with
+ * gs_topk_rows_u16's bytes; that call remains the faster one there.
+ * Forms: keys only; pairs; arguments (d_vals_in == NULL, d_vals_out != NULL: the u32 column index).  Values are u32 and sit at
+ * the same row_stride counted in elements (row r's values start at d_vals_in + r * row_stride); the outputs are dense with
+ * stride k.  The inputs and the stride gap are never written, the gap's contents never influence a result, nothing outside
+ * [0, num_rows * k) of the outputs and the workspace is written, d_temp anywhere, enqueue-only (no host read-back, allocation or
+ * synchronisation), the launches are a function of the arguments alone (gs_topk_rows_anyk_u16_plan reports them), so the call
+ * may be captured into a HIP graph on one plain stream; calls may follow each other on one stream with one workspace; two runs
+ * give identical bytes.  num_rows == 0, num_cols == 0 or k == 0 returns 0, writes nothing and needs no workspace (the query
+ * returns 0).
+ * Errors (hipErrorInvalidValue, checked before anything is enqueued, nothing written; the size query returns 0 and the plan
+ * zeros for a refused shape; the checks run in gs_topk_rows_anyk_u32's order): k > num_cols, row_stride < num_cols,
+ * num_rows * row_stride >= 2^32 (the size query and the plan, which have no stride, refuse num_rows * num_cols >= 2^32),
+ * num_rows * k >= 2^31 (the finish has int offsets), a key_type other than GS_KEY_U16 / I16 / F16 / BF16, d_vals_in without
+ * d_vals_out, a NULL key pointer, a NULL or too-small workspace, a key array not aligned to 2 bytes or a value array not
+ * aligned to 4, arrays that share a byte (inputs at (num_rows - 1) * row_stride + num_cols elements, outputs at num_rows * k;
+ * 2 bytes per key, 4 per value).  A key pointer at 2 mod 4 and an odd row_stride are served like any other: every key is read
+ * and written with one 2-byte access, as in gs_topk_rows_u16.
+ * Paths, by num_cols alone, with gs_topk_rows_anyk_u32's geometry (CH = tile = 8192, four tiles per slab).  Path 1, num_cols <=
+ * 8192: one workgroup reads the row once, selects the k-th image in registers and LDS in two byte rounds and places the k
+ * selected (key, column) pairs, equal keys in column order, into the row's k output slots.  Path 2, longer rows: a radix select
+ * over all rows at once in two counting rounds on image bits 15-8 and 7-0 (one workgroup per row and slab adds its LDS
+ * histogram to the row's 256 bins; one workgroup per row picks the bin), then per (row, tile) two counts, a scan per row and a
+ * scatter in column order: four reads of the matrix at 2 bytes a key.  The integer adds of the histograms are the only global
+ * atomics; none decides a position.  Both paths finish with gs_segmented_sort_narrow on the num_rows * k staged pairs with the
+ * regular offsets r * k, bits 0 .. 16, in the caller's key_type and direction.
+ * Workspace: a pure host function of its arguments, a multiple of 256, monotone in each of them.  With T = ceil(num_cols /
+ * 8192), hv = 1 with has_values else 0, p2 = 1 if num_cols > 8192 else 0, and every term rounded up to 256 bytes:
+ *   32 * num_rows                             a record per row: k-th image (low 16 bits), less, take, 0, matched after round one, 0, 0, 0
+ * + 4 * (num_rows + 1)                        the offsets r * k of the finish
+ * + p2 * 4 * 256 * num_rows                   the rows' histograms
+ * + p2 * 8 * num_rows * T                     two u32 counts per (row, tile)
+ * + 2 * num_rows * k                          the second half of the staged keys (the first is d_keys_out)
+ * + hv * 4 * num_rows * k                     the second half of the columns (the first is d_vals_out in the arguments form)
+ * + hv * 4 * num_rows * k                     the first half of the columns, used by the pairs form
+ * + gs_segmented_narrow_temp_bytes(num_rows * k, GS_KEY_U16, 4 with has_values else 0, num_rows)
+ * + 256 bytes of alignment slack.
+ * Never more than gs_topk_rows_anyk_temp_bytes of the same arguments.  No element of the matrix is copied into it except the
+ * k selected per row.                                                                                                      */
+size_t   gs_topk_rows_anyk_u16_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values);
+int      gs_topk_rows_anyk_u16(void *d_temp, size_t temp_bytes,
+                               const uint16_t *d_keys_in, const uint32_t *d_vals_in,
+                               uint16_t *d_keys_out, uint32_t *d_vals_out,
+                               uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k,
+                               int descending, int key_type, void *stream);
+/* What gs_topk_rows_anyk_u16 launches for a shape: a pure host function.  out[0] = path (1 or 2), out[1] = kernel launches
+ * before the finish (path 1: 2, offsets and select; path 2: 9, zero, offsets, twice count and pick, tile counts, scan,
+ * scatter), out[2..6] = gs_topk_rows_anyk_plan's geometry words (CH, the tile, tiles per slab, slabs per row, tiles per row),
+ * out[7] = 0.  A refused shape (k > num_cols, num_rows * num_cols >= 2^32, num_rows * k >= 2^31) returns hipErrorInvalidValue
+ * and all zeros; a no-op shape returns 0 and all zeros.                                                                    */
+int      gs_topk_rows_anyk_u16_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint32_t out[8]);
+/* What the select found for one row of the last gs_topk_rows_anyk_u16 on d_temp with these arguments (read back after
+ * synchronising `stream`; no kernel runs).  out[0] = path, out[1] = the 16-bit image of that row's k-th element, out[2] =
+ * elements whose image sorts strictly before it, out[3] = k - out[2], out[4] = elements that share its top byte (matched after
+ * round one; path 2, 0 on path 1), out[5..7] = 0.  All zeros for a no-op shape; hipErrorInvalidValue for a refused shape,
+ * row >= num_rows, or a NULL d_temp or out.                                                                                 */
+int      gs_topk_rows_anyk_u16_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values,
+                                      uint64_t row, uint32_t out[8], void *stream);
+
 /* ------------------------------------------------ top k of every ragged segment --
  * The k best of every segment of a flat array, the segments given by device offsets (gs_topk_rows.hip, DESIGN.md section
  * 10k): per-query candidate lists, variable-length sequences, per-image box scores, the neighbour lists of a CSR graph.
