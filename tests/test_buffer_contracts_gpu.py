@@ -396,6 +396,24 @@ def row_shard_partition(gs, A, tag, n, kind, var, pl, fill, seed):
     return Call(gs.lib.gs_msb_temp_bytes(n, int(pairs)), launch, verify)
 
 
+def row_shard_histogram(gs, A, tag, n, kind, var, pl, fill, seed):
+    """gs_shard_histogram_u32 takes no workspace (query 0).  The variant's flag picks the width: 12 bits or 11.  Under P1 the
+    keys lie three elements off a 16-byte boundary, which is the scalar kernel.  Asked for a short workspace (-1 bytes),
+    the row makes the call that is refused for its width instead, 13 bits: the histogram must stay as it was."""
+    kt, wide = var
+    bits = SHARD_BITS if wide else SHARD_BITS - 1
+    keys = gen_keys(kt, kind, n, seed)
+    A.add(tag + "kin", 4 * n, data_off(pl, 4), data=keys, const=True).add(tag + "hist", 8 << bits, data_off(pl, 8), fill)
+
+    def launch(ws, nbytes):
+        return gs.lib.gs_shard_histogram_u32(A.ptr(tag + "kin"), n, bits if nbytes >= 0 else SHARD_BITS + 1, A.ptr(tag + "hist"), kt, None)
+
+    def verify(A):
+        want = np.bincount(ordmap(keys, kt).astype(np.uint32) >> np.uint32(32 - bits), minlength=1 << bits).astype(np.uint64)
+        assert np.array_equal(A.read(tag + "hist", np.uint64), want), "histogram"
+    return Call(0, launch, verify)
+
+
 LSB_VARS = [(U32, False, (0, 32), 0), (I32, True, (0, 32), 0), (F32, True, (0, 32), 1), (U32, True, (3, 29), 0),
             (F32, False, (0, 32), 0), (I32, False, (5, 21), 1)]
 WIDE_LSB_VARS = [(U64, 0, (0, 64), 0), (I64, 4, (0, 64), 1), (F64, 8, (0, 64), 0), (F32, 8, (0, 32), 0), (U64, 8, (7, 45), 0),
@@ -426,6 +444,7 @@ ROWS = {
     "gs_msb_first_pass_u32": (row_first_pass, FP_VARS, U32_SIZES),
     "gs_msb_finish_u32": (row_finish, FP_VARS, U32_SIZES),
     "gs_shard_partition_u32": (row_shard_partition, SHARD_VARS, U32_SIZES),
+    "gs_shard_histogram_u32": (row_shard_histogram, FP_VARS, U32_SIZES),
 }
 
 
@@ -436,7 +455,7 @@ def run(gs, cuda, row, calls, pl, fill, seed, short=False):
     A = Arena(cuda, seed=seed, all_const=short)
     prepared = [fn(gs, A, "c%d_" % i, n, kind, var, pl, fill, seed + 7 * i) for i, (n, kind, var) in enumerate(calls)]
     wsz = max(c.query for c in prepared)
-    A.add("ws", wsz - 1 if short else wsz, PLACEMENTS[pl], fill)
+    A.add("ws", max(wsz - 1, 0) if short else wsz, PLACEMENTS[pl], fill)        # (a row without a workspace queries 0)
     A.build()
     what = "%s %s fill=%s calls=%s" % (row, pl, fill, [(n, k, v) for n, k, v in calls])
     for c in prepared:
