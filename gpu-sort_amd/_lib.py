@@ -48,6 +48,7 @@ SIGNATURES = {
     "gs_lsb_plan_cursor_status": (i32, [vp, u64, C.POINTER(C.c_uint32), vp]),
     "gs_lsb_plan_peek_status": (i32, [C.POINTER(C.c_uint32)]),
     "gs_lsb_plan_finish_cap": (C.c_uint32, []),
+    "gs_lsb_plan_onepass_grid": (C.c_uint32, []),
     "gs_lsb_plan_look_only": (i32, [vp, vp, vp, u64, i32, i32, vp]),
     "gs_lsb_plan_layout": (i32, [u64, C.POINTER(C.c_uint64)]),
     "gs_lsb_upsweep_u32": (i32, [vp, sz, vp, u64, i32, i32, i32, i32, vp]),

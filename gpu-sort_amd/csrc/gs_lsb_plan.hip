@@ -904,6 +904,28 @@ static uint32_t plan_finish_cap()
     }();
     return v;
 }
+// The one-pass launch of the finish gets PLAN_ONEPASS_GRID workgroups at the most (gs_msb.hip, launch_local_sorts); with fewer
+// workgroups than tasks they stride over the list.  Measured at 2^30 uniform keys, 65536 tasks of class 3, parent and new
+// alternating in one process (tools/lookahead_ab.py): every value below the local sorts' own 16384 is
+// slower, 32768 is no faster, and a workgroup per task -- 65536, the most groups there are -- is 0.13-0.15 ms faster.
+// GS_LSB_PLAN_ONEPASS_GRID=512|1024|...|65536 (a power of two; measurements and tests; read once per process) overrides it;
+// any other value is ignored.  gs_lsb_plan_onepass_grid() returns the value in force.  GS_PLAN_ONEPASS_GRID=16384 builds the
+// launch as it was.
+#ifndef GS_PLAN_ONEPASS_GRID
+#define GS_PLAN_ONEPASS_GRID 65536
+#endif
+constexpr uint32_t PLAN_ONEPASS_GRID = GS_PLAN_ONEPASS_GRID;
+static constexpr bool plan_onepass_grid_ok(unsigned long x) { return x >= 512ul && x <= 65536ul && (x & (x - 1ul)) == 0ul; }
+static_assert(plan_onepass_grid_ok(PLAN_ONEPASS_GRID), "the one-pass launch's grid");
+static uint32_t plan_onepass_grid()
+{
+    static const uint32_t v = [] {
+        const char *e = getenv("GS_LSB_PLAN_ONEPASS_GRID");
+        const unsigned long x = e ? strtoul(e, nullptr, 10) : 0ul;
+        return plan_onepass_grid_ok(x) ? (uint32_t)x : PLAN_ONEPASS_GRID;
+    }();
+    return v;
+}
 // gs_lsb_plan_peek_status: what the calling thread's last planned sort did
 static thread_local uint32_t plan_peek_last[4] = {0, 0, 0, 0};
 
@@ -967,7 +989,7 @@ int lsb_plan_sort(char *base, uint32_t *d_keys[2], int *selector, uint64_t n, in
     }
     if ((e = (int)hipGetLastError())) return e;
     if ((e = msb_local_sorts_in_place(plan->level, lists.tasks, PLAN_GROUPS, PLAN_GROUPS, d_keys[sel], PLAN_SORT_BITS, n, tw.f32_out,
-                                      tw.xor_out, s, seen.ok ? seen.tasks : nullptr, plan_finish_cap())))
+                                      tw.xor_out, s, seen.ok ? seen.tasks : nullptr, plan_finish_cap(), plan_onepass_grid())))
         return e;
     *selector = sel;
     return hipSuccess;
@@ -1028,6 +1050,8 @@ int gs_lsb_plan_peek_status(uint32_t out[4])
 }
 
 uint32_t gs_lsb_plan_finish_cap(void) { return plan_finish_cap(); }
+
+uint32_t gs_lsb_plan_onepass_grid(void) { return plan_onepass_grid(); }
 
 int gs_lsb_plan_look_only(void *d_temp, const void *d_keys, void *d_alt, uint64_t num_items, int key_type, int descending, void *stream)
 {

@@ -1911,29 +1911,39 @@ template <bool HAS_VALUES, bool STABLE = false>
 static void launch_local_sorts(const MsbWs &ws, int L, uint32_t bound, const uint32_t *sk, uint32_t *dk, const uint32_t *sv,
                                uint32_t *dv, int f32_in, uint32_t xor_in, int f32_out, uint32_t xor_out, hipStream_t s,
                                int min_bits = 0, uint64_t num_items = 0, const uint32_t *known_tasks = nullptr, bool maybe_skew = true,
-                               uint32_t leftover_cap = 0u)
+                               uint32_t leftover_cap = 0u, uint32_t onepass_cap = 0u)
 {
     KernelTimer kt(GS_K_MSB_LOCAL_SORT, s);
     // grid-stride over the task list; few blocks suffice for the big classes (empty launches are not free)
     // `known_tasks` (the host has looked, see MsbPeek): tasks per class -- empty classes are not launched at all
-    auto grid_of = [&](int c) {
+    auto grid_upto = [&](int c, uint32_t most) {
         uint64_t b = bound;
         if (known_tasks && known_tasks[c] < b) b = known_tasks[c];
         if (num_items && c > 0) {
             const uint64_t lim = num_items / msb_class_cap(c - 1) + RADIX;     // a class-c task holds > cap(c-1) keys
             if (lim < b) b = lim;
         }
+        return (uint32_t)(b < most ? (b ? b : 1) : most);
+    };
 #ifndef MSB_LS_MAX_GRID
 #define MSB_LS_MAX_GRID MSB_MAX_GRID
 #endif
-        return (uint32_t)(b < MSB_LS_MAX_GRID ? (b ? b : 1) : MSB_LS_MAX_GRID);
-    };
+    auto grid_of = [&](int c) { return grid_upto(c, MSB_LS_MAX_GRID); };
     // `leftover_cap` != 0 (the keys-only plan of the LSB sort): the grid of the two launches behind LS_ONEPASS, which usually find
     // nothing left and whose workgroups then only read `flagged` and leave -- 16384 of them cost 23-29 us per launch.  Both kernels
     // stride over the list by their grid.  The MSB sort passes 0: its leftover launches usually find work (Zipf: see below).
     auto left_of = [&](int c) {
         const uint32_t g = grid_of(c);
         return leftover_cap && leftover_cap < g ? leftover_cap : g;
+    };
+    // `onepass_cap` != 0 (the keys-only plan again): the most workgroups of the LS_ONEPASS launch itself, in place of MSB_LS_MAX_GRID;
+    // it may lie above it.  On 65536 even tasks the launch was the slower the fewer workgroups strode over the list (2.36 ms at 512,
+    // 2.06 at 16384) and fastest with a workgroup per task (1.90-1.95 ms): the dispatcher hands a task to whichever CU is free,
+    // a strided list does not, and the cold start of a task hides behind the other workgroup of its CU.  Above MSB_LS_MAX_GRID only
+    // when the host knows the task counts: a worst-case grid of that size would mostly be workgroups that find no task (stream
+    // capture, GS_LSB_PLAN_PEEK=0).  The MSB sort passes 0.
+    auto onepass_of = [&](int c) {
+        return onepass_cap && (known_tasks || onepass_cap <= MSB_LS_MAX_GRID) ? grid_upto(c, onepass_cap) : grid_of(c);
     };
 #define GS_LS1G(C, HV, M, P, G) hipLaunchKernelGGL((msb_local_sort_kernel<msb_class_threads(C), msb_class_kpt(C), HV, STABLE, M, P>), dim3(G), \
                                                   dim3(msb_class_threads(C)), 0, s, ws, L, C, sk, dk, sv, dv, f32_in, xor_in, f32_out, xor_out)
@@ -1952,7 +1962,7 @@ static void launch_local_sorts(const MsbWs &ws, int L, uint32_t bound, const uin
         if constexpr (STABLE) { GS_LS1(C, HV, LS_ALL); }                                                              \
         else if (!onepass_possible(min_bits, local_b1((int)msb_class_cap(C)), local_b1((int)msb_class_cap(C) * (HV ? 2 : 1)) + 2)) \
             { if constexpr (DD) { if (dd) GS_LSDD(C, HV, LS_DEDUPE_ALL); } GS_LS1(C, HV, LS_ALL); }                    \
-        else { if (plain) GS_LS1P(C, HV, LS_ONEPASS, true); else GS_LS1(C, HV, LS_ONEPASS);                           \
+        else { if (plain) GS_LS1G(C, HV, LS_ONEPASS, true, onepass_of(C)); else GS_LS1G(C, HV, LS_ONEPASS, false, onepass_of(C)); \
                if constexpr (DD) { if (dd) GS_LSDD(C, HV, LS_DEDUPE); } GS_LS1G(C, HV, LS_FLAGGED, false, left_of(C)); } \
     } while (0)
     auto wanted = [&](int c) { return !known_tasks || known_tasks[c] != 0u; };
@@ -1980,7 +1990,7 @@ static void launch_local_sorts(const MsbWs &ws, int L, uint32_t bound, const uin
 // local-sort path reads are filled in: msb_task_sample_kernel and msb_local_sort_kernel use level, tasks, max_tasks and caps.
 int msb_local_sorts_in_place(MsbLevel *level, MsbTask *const tasks[MSB_NCLASS], uint32_t max_tasks, uint32_t bound, uint32_t *keys,
                              int sort_bits, uint64_t num_items, int f32_out, uint32_t xor_out, hipStream_t s, const uint32_t *known_tasks,
-                             uint32_t leftover_cap)
+                             uint32_t leftover_cap, uint32_t onepass_cap)
 {
     MsbWs ws{};
     ws.level = level;
@@ -1989,7 +1999,7 @@ int msb_local_sorts_in_place(MsbLevel *level, MsbTask *const tasks[MSB_NCLASS], 
     ws.tile_shift = 13u;
     ws.key_bits = 32u;
     launch_local_sorts<false>(ws, 0, bound, keys, keys, nullptr, nullptr, 0, 0u, f32_out, xor_out, s, sort_bits, num_items, known_tasks, true,
-                              leftover_cap);
+                              leftover_cap, onepass_cap);
     return (int)hipGetLastError();
 }
 

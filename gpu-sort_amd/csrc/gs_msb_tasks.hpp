@@ -50,9 +50,10 @@ struct MsbLevel {
 // output twiddle is applied on the way out.  No host wait: worst-case grids (`bound` tasks per class at most), blocks
 // that find no task exit.  `known_tasks`: the caller has read level[0].task_count on the host -- classes without tasks are
 // not launched and the grids are exact.  `leftover_cap` != 0: at most that many workgroups for each of the two launches
-// that take what the one-pass sort left (they stride over the lists); 0: no cap.
+// that take what the one-pass sort left (they stride over the lists); 0: no cap.  `onepass_cap` != 0: the most workgroups of
+// the one-pass launch itself, in place of the local sorts' own 16384 (a value above that counts only with `known_tasks`).
 int msb_local_sorts_in_place(MsbLevel *level, MsbTask *const tasks[MSB_NCLASS], uint32_t max_tasks, uint32_t bound, uint32_t *keys,
                              int sort_bits, uint64_t num_items, int f32_out, uint32_t xor_out, hipStream_t s,
-                             const uint32_t *known_tasks = nullptr, uint32_t leftover_cap = 0u);
+                             const uint32_t *known_tasks = nullptr, uint32_t leftover_cap = 0u, uint32_t onepass_cap = 0u);
 
 }  // namespace gs

@@ -188,6 +188,13 @@ int  gs_lsb_plan_peek_status(uint32_t out[4]);
 /* The most workgroups the plan's finish gives each of the two local-sort launches that take what the
  * one-pass sort left over (they stride over the task lists): 512, 1024 or 2048.  Tests size by it.  */
 uint32_t gs_lsb_plan_finish_cap(void);
+/* The most workgroups the plan's finish gives the one-pass local-sort launch itself (with fewer than
+ * tasks they stride over the task lists): a power of two from 512 to 65536; built in is 65536, a
+ * workgroup per task.  A value above 16384 counts only in sorts whose host has read the plan's
+ * decision (not under stream capture or GS_LSB_PLAN_PEEK=0, which launch worst-case grids).
+ * GS_LSB_PLAN_ONEPASS_GRID (read once per process) overrides the built-in value with one of these
+ * eight; any other value is ignored.  Tests size by it.                                             */
+uint32_t gs_lsb_plan_onepass_grid(void);
 /* Test hooks of the keys-only plan.  gs_lsb_plan_look_only runs the look alone (the fused look, the
  * reduction of its tables and the decision) on a workspace of gs_lsb_temp_bytes(num_items) bytes and
  * returns without sorting: d_keys is read, the first num_items * 4 bytes of d_alt are scratch.  What

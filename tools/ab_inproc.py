@@ -1,7 +1,8 @@
 """A/B of library builds INSIDE one process on the SAME buffers (the placement of the arrays changes a kernel's time by several
 percent from one allocation to the next, profiles/README.md round 3): every build is loaded with ctypes and runs the LSB sort of
 2^30 keys (or pairs) alternately, per-kernel times from each build's own event hook.
-python tools/ab_inproc.py [pairs|msb|msbzipf] libA.so libB.so ...   (names inside gpu-sort_amd/lib)"""
+python tools/ab_inproc.py [pairs|msb|msbzipf] libA.so libB.so ...   (names inside gpu-sort_amd/lib)
+ROUNDS=k: k timed rounds after the warm-up round (default 4); msb modes also print the local sorts' fastest and slowest round."""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -64,7 +65,7 @@ for name in args:
     libs.append((name, L, C.c_void_p(L.gs_profile_create())))
 res = {f"{i}:{name}": [] for i, (name, _, _) in enumerate(libs)}
 stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-for rnd in range(5):
+for rnd in range(int(os.environ.get("ROUNDS", "4")) + 1):   # (the first round is a warm-up)
     for i, (name, L, prof) in enumerate(libs):
         a.copy_(src)
         if pairs:
@@ -93,7 +94,8 @@ med = lambda xs: sorted(xs)[len(xs) // 2]
 for name, v in res.items():
     if msb:
         cols = [med([x[k] for x in v]) for k in range(6)]
-        print(f"{name:28s} per sort: lsb_up {cols[0]:.3f} lsb_down {cols[1]:.3f} msb_hist {cols[2]:.3f} classify {cols[3]:.3f} partition {cols[4]:.3f} local {cols[5]:.3f}  sum {sum(cols):.3f} ms", flush=True)
+        loc = sorted(x[5] for x in v)
+        print(f"{name:28s} per sort: lsb_up {cols[0]:.3f} lsb_down {cols[1]:.3f} msb_hist {cols[2]:.3f} classify {cols[3]:.3f} partition {cols[4]:.3f} local {cols[5]:.3f} (min {loc[0]:.3f} max {loc[-1]:.3f})  sum {sum(cols):.3f} ms", flush=True)
         continue
     ups = sorted(x[0] for x in v); dss = sorted(x[1] for x in v)
     print(f"{name:28s} upsweep median {ups[len(ups)//2]:.4f}  downsweep median {dss[len(dss)//2]:.4f} min {dss[0]:.4f} max {dss[-1]:.4f} ms/launch", flush=True)
