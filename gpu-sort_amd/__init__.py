@@ -16,6 +16,7 @@ Names follow the reference:
   DeviceTopKRows64, topk_rows64 (the same for every row of a matrix of int64 / uint64 / float64 keys: gs_topk_rows_u64)
   DeviceTopKRowsAnyK, topk_rows_anyk   (every row of a matrix of 32-bit keys for any k <= columns: gs_topk_rows_anyk_u32)
   DeviceTopKRowsAnyK16, topk_rows_anyk16   (the same for int16 / uint16 / float16 / bfloat16 keys: gs_topk_rows_anyk_u16)
+  DeviceTopKRowsAnyK64, topk_rows_anyk64   (the same for int64 / uint64 / float64 keys: gs_topk_rows_anyk_u64)
   DeviceTopKSegmented, topk_segmented   (the same for every ragged segment given by device offsets; 32-bit keys, and int16 / uint16 / float16 / bfloat16)
   DeviceTopKSegmented64, topk_segmented64   (the same for ragged segments of int64 / uint64 / float64 keys: gs_topk_segmented_u64)
   sortKeysGPU / sortPairsGPU    (lsb/sort.cu:25-76)
@@ -27,6 +28,7 @@ from ._lib import (GpuSortError, GS_KEY_U32, GS_KEY_I32, GS_KEY_F32, GS_KEY_U64,
                    GS_GEN_ENTROPY_AND, GS_GEN_ENUMERATED, LIB_PATH, lib, KernelProfile)
 from .lsb import DoubleBuffer, DeviceRadixSort, DeviceRadixSortLarge, DeviceSegmentedRadixSort, sortKeysGPU, sortPairsGPU, lsb_pass_kernels
 from .select import (DeviceTopK, DeviceTopK16, DeviceTopK64, DeviceTopKRows, DeviceTopKRows64, DeviceTopKRowsAnyK, DeviceTopKRowsAnyK16,
+                     DeviceTopKRowsAnyK64, topk_rows_anyk64,
                      DeviceTopKSegmented, DeviceTopKSegmented64, topk, topk_rows, topk_rows64, topk_rows_anyk, topk_rows_anyk16, topk_segmented,
                      topk_segmented64)
 from .datagen import (generate_random_keys, generate_uniform_keys, generate_zipf_keys, generate_enumerated_values,

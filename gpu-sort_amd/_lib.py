@@ -91,6 +91,10 @@ SIGNATURES = {
     "gs_topk_rows_anyk_u16": (i32, [vp, sz, vp, vp, vp, vp, u64, u64, u64, u64, i32, i32, vp]),
     "gs_topk_rows_anyk_u16_plan": (i32, [u64, u64, u64, i32, C.POINTER(C.c_uint32)]),
     "gs_topk_rows_anyk_u16_status": (i32, [vp, u64, u64, u64, i32, u64, C.POINTER(C.c_uint32), vp]),
+    "gs_topk_rows_anyk_u64_temp_bytes": (sz, [u64, u64, u64, i32]),
+    "gs_topk_rows_anyk_u64": (i32, [vp, sz, vp, vp, vp, vp, u64, u64, u64, u64, i32, i32, vp]),
+    "gs_topk_rows_anyk_u64_plan": (i32, [u64, u64, u64, i32, C.POINTER(C.c_uint32)]),
+    "gs_topk_rows_anyk_u64_status": (i32, [vp, u64, u64, u64, i32, u64, C.POINTER(C.c_uint32), vp]),
     "gs_topk_segmented_temp_bytes": (sz, [u64, C.c_uint32, u64, i32]),
     "gs_topk_segmented_u32": (i32, [vp, sz, vp, vp, vp, vp, vp, u64, C.c_uint32, vp, vp, u64, i32, i32, vp]),
     "gs_topk_segmented_u16_temp_bytes": (sz, [u64, C.c_uint32, u64, i32]),

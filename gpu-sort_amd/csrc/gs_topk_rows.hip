@@ -7,7 +7,8 @@
 // kernel fills (see "ragged segments" below), instantiated over the same three key-traits types.
 // gs_topk_rows_anyk_u32 (section 10p) and gs_topk_rows_anyk_u16 (section 10q), the rows form without the cap on k, are at the end
 // (see "any k" below): their selects stage the k selected pairs of every row in the outputs and gs_segmented_sort_u32 /
-// gs_segmented_sort_narrow finishes them.
+// gs_segmented_sort_narrow finishes them.  gs_topk_rows_anyk_u64 (section 10r) follows them: path 1 is the same kernel at
+// TrKey64, path 2 a descent of its own (see "any k, 64-bit keys" below), and gs_segmented_sort_wide finishes.
 //
 // Row r of the result is what gs_topk_u32 writes for row r alone, bit for bit.  Every row has the same length, so the
 // launches are decided on the host from num_cols and k:
@@ -1317,6 +1318,7 @@ constexpr uint32_t TA_STATE_WORDS = 8;     // per row: k-th image (the prefix so
 template <int BITS> struct TaWidth;
 template <> struct TaWidth<32> { static constexpr int ROUNDS = 3; static constexpr uint32_t BINS = 2048u, COPIES = 1u; };
 template <> struct TaWidth<16> { static constexpr int ROUNDS = 2; static constexpr uint32_t BINS = 256u, COPIES = 8u; };
+template <> struct TaWidth<64> { static constexpr int ROUNDS = 6; static constexpr uint32_t BINS = 2048u, COPIES = 1u; };   // (a descent of its own: see "any k, 64-bit keys")
 static_assert(TaWidth<32>::BINS * TaWidth<32>::COPIES == TA_LDS_WORDS && TaWidth<16>::BINS * TaWidth<16>::COPIES == TA_LDS_WORDS, "one LDS budget");
 
 template <int BITS, int ROUND> struct TaRound;
@@ -1345,6 +1347,17 @@ __device__ __forceinline__ void ta_hist_add(uint32_t *hist, uint32_t d, uint32_t
         atomicAdd(&hist[d * COPIES + (lane & (COPIES - 1u))], 1u);
     }
 }
+
+// The row record by image width: its words, the word that holds `less`, and the k-th image from it.  Eight words with the image
+// in word 0 at 16 and 32 bits; sixteen with the image in words 0 (low) and 1 (high) at 64 (see "any k, 64-bit keys" below).
+template <typename KT> struct TaRec {
+    static constexpr uint32_t WORDS = TA_STATE_WORDS, LESS = 1;
+    static __device__ __forceinline__ uint32_t kth(const uint32_t *__restrict__ rec) { return rec[0]; }
+};
+template <> struct TaRec<TrKey64> {
+    static constexpr uint32_t WORDS = 16, LESS = 2;
+    static __device__ __forceinline__ uint64_t kth(const uint32_t *__restrict__ rec) { return ((uint64_t)rec[1] << 32) | rec[0]; }
+};
 
 // One workgroup: a tile of up to CH elements of a row into registers as images, in the (wave, row, lane) order of the block kernel.
 template <typename KT>
@@ -1431,7 +1444,13 @@ __global__ __launch_bounds__(TR_THREADS) void topk_anyk_block_kernel(const typen
     const I kth = tr_select<KT::BITS>(img, first, cols, k, tid, h, scratch, sel, less);
     const size_t out0 = (size_t)r * k;
     ta_place<KT, HV>(img, first, cols, k, kth, less, 0u, less, w, lane, wcnt, dst_k + out0, HV ? dst_c + out0 : nullptr, 0u, flt, x);
-    if (tid < TA_STATE_WORDS) state[(size_t)r * TA_STATE_WORDS + tid] = tid == 0 ? (uint32_t)kth : tid == 1 ? less : tid == 2 ? k - less : 0u;
+    if constexpr (KT::BITS == 64) {   // the sixteen-word record of gs_topk_rows_anyk_u64: both halves of the image, mode 0
+        if (tid < TaRec<KT>::WORDS)
+            state[(size_t)r * TaRec<KT>::WORDS + tid] =
+                tid == 0 ? (uint32_t)kth : tid == 1 ? (uint32_t)(kth >> 32) : tid == TaRec<KT>::LESS ? less : tid == 3 ? k - less : 0u;
+    } else {
+        if (tid < TA_STATE_WORDS) state[(size_t)r * TA_STATE_WORDS + tid] = tid == 0 ? (uint32_t)kth : tid == 1 ? less : tid == 2 ? k - less : 0u;
+    }
 }
 
 // Path 2, a counting round: one workgroup per (row, slab of slab_tiles tiles).
@@ -1522,7 +1541,7 @@ __global__ __launch_bounds__(TR_THREADS) void topk_anyk_tilecount_kernel(const t
     const uint32_t r = blockIdx.x / tiles, t = blockIdx.x - r * tiles;
     const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
     const uint32_t lo = t * TA_TILE, len = cols - lo < TA_TILE ? cols - lo : TA_TILE;
-    const I kth = (I)state[(size_t)r * TA_STATE_WORDS];
+    const I kth = TaRec<KT>::kth(state + (size_t)r * TaRec<KT>::WORDS);
     I img[TR_KPT];
     ta_load_tile<KT>(keys + (size_t)r * stride + lo, first, len, flt, x, img);
     uint32_t nA = 0, nB = 0;
@@ -1558,6 +1577,23 @@ __global__ __launch_bounds__(256) void topk_anyk_scan_kernel(const uint32_t *__r
         carryA += totA; carryB += totB;
     }
 }
+// The same scan over the sixteen-word records of the 64-bit call (a kernel of its own: the one above keeps its code).
+__global__ __launch_bounds__(256) void topk_anyk_wide_scan_kernel(const uint32_t *__restrict__ state, uint2 *__restrict__ counts, uint32_t tiles)
+{
+    __shared__ uint32_t scratch[8];
+    const uint32_t tid = threadIdx.x;
+    uint2 *__restrict__ c = counts + (size_t)blockIdx.x * tiles;
+    uint32_t carryA = 0, carryB = state[(size_t)blockIdx.x * TaRec<TrKey64>::WORDS + TaRec<TrKey64>::LESS];
+    for (uint32_t base = 0; base < tiles; base += 256u) {
+        const uint32_t i = base + tid;
+        const uint2 v = i < tiles ? c[i] : make_uint2(0u, 0u);
+        uint32_t totA, totB;
+        const uint32_t exA = block_exclusive_scan_256(v.x, scratch, &totA);
+        const uint32_t exB = block_exclusive_scan_256(v.y, scratch, &totB);
+        if (i < tiles) c[i] = make_uint2(carryA + exA, carryB + exB);
+        carryA += totA; carryB += totB;
+    }
+}
 
 // Path 2, the select's scatter: one workgroup per (row, tile) places its part of the two groups.
 template <typename KT, bool HV>
@@ -1573,8 +1609,8 @@ __global__ __launch_bounds__(TR_THREADS) void topk_anyk_scatter_kernel(const typ
     const uint32_t r = blockIdx.x / tiles, t = blockIdx.x - r * tiles;
     const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
     const uint32_t lo = t * TA_TILE, len = cols - lo < TA_TILE ? cols - lo : TA_TILE;
-    const I kth = (I)state[(size_t)r * TA_STATE_WORDS];
-    const uint32_t less = state[(size_t)r * TA_STATE_WORDS + 1];
+    const I kth = TaRec<KT>::kth(state + (size_t)r * TaRec<KT>::WORDS);
+    const uint32_t less = state[(size_t)r * TaRec<KT>::WORDS + TaRec<KT>::LESS];
     const uint2 base = counts[blockIdx.x];
     if (base.x >= less && base.y >= k) return;   // workgroup-uniform: both groups are full before this tile
     I img[TR_KPT];
@@ -1594,7 +1630,237 @@ __global__ __launch_bounds__(256) void topk_anyk_gather_kernel(const uint32_t *_
     }
 }
 
-struct TaPlan { uint32_t path, launches, slab_tiles, slabs, tiles; };
+// ------------------------------------------------------ any k, 64-bit keys --
+// gs_topk_rows_anyk_u64.  Path 1 is topk_anyk_block_kernel at TrKey64.  Path 2 is a descent of its own:
+// counting rounds on 11-bit digits that go straight to the bits that can differ, and that stop reading the matrix for a row as
+// soon as the bucket of its k-th element fits the row's list.  Every launch of the worst case (six rounds) is always enqueued; a
+// workgroup whose row is decided reads the row's record and returns.
+//
+//   a round at shift s (53 first)   a count workgroup per (row, slab) histograms (image >> s) & 2047 in LDS over the elements whose
+//            image matches the row's prefix on the bits at and above s + 11, and reduces the OR of those images and the OR of their
+//            complements (AND = ~that; a zeroed word is neutral for both): per wave, then in LDS, then one pair of 64-bit atomic ORs
+//            per workgroup into the record.  The adds and ORs are commutative: their results do not depend on their order.
+//   a pick   one workgroup per row takes the bin d of the krem-th element, puts d into prefix bits [s, s + 11), updates less and
+//            krem, and with c the bin's count and v = (AND ^ OR) below s -- AND and OR are those of the round's matched set, a
+//            superset of the bucket -- decides:  s == 0 or v == 0: every element of the bucket equals prefix | (AND below s), the
+//            row is decided (mode 2, a tie run cut at krem);  else c <= L: the bucket goes to the row's list (mode 1);  else, with
+//            hb the highest set bit of v, bits (hb, s) are constant over the matched set and come from the AND, and the next round
+//            runs at max(hb - 10, 0).  The shifts fall by at least 11 until they reach 0: 53, <= 42, <= 31, <= 20, <= 9, 0.
+//   collect  one workgroup per (row, tile), rows in mode 1: appends the images that match the prefix at and above s to the row's
+//            list.  A workgroup claims its range from the row's cursor with one atomic add.  That atomic decides positions IN THE
+//            LIST only; the list is read as a multiset (an image and two counts come out of it) and never reaches an output position.
+//   list select   one workgroup per row in mode 1 loads the <= L images as path 1 loads a row and runs tr_select with k = krem.
+//   then the tile counts, the per-row scan and the scatter of the 32-bit call, at TrKey64.
+//
+// The record, sixteen words per row: k-th image (the prefix so far) low, high; less; krem / take; mode (0 descending or path 1,
+// 1 list, 2 tie run); D, the rounds taken; the shift of the next round (of the last one once decided); the list's cursor; the
+// OR word low, high; the OR-of-complements word low, high; c of the last pick; three zero words.
+constexpr uint32_t TA64_TAKE = 3, TA64_MODE = 4, TA64_D = 5, TA64_SHIFT = 6, TA64_LIST = 7, TA64_OR = 8, TA64_ORN = 10, TA64_C = 12;
+constexpr uint32_t TA64_DIGIT = 11, TA64_BINS = 2048, TA64_SHIFT0 = 53, TA64_ROUNDS = 6;
+static_assert(TA64_BINS == TA_LDS_WORDS && (1u << TA64_DIGIT) == TA64_BINS && TA64_SHIFT0 + TA64_DIGIT == 64, "one LDS budget, whole image");
+
+__global__ __launch_bounds__(TR_THREADS) void topk_anyk_wide_count_kernel(const uint64_t *__restrict__ keys, uint32_t stride, uint32_t cols,
+                                                                          uint32_t tiles, uint32_t slabs, uint32_t slab_tiles,
+                                                                          uint32_t *__restrict__ state, uint32_t *__restrict__ hist, int flt,
+                                                                          uint32_t x32, int first_round)
+{
+    using KT = TrKey64;
+    const uint64_t x = KT::xmask(x32);
+    __shared__ uint32_t h[TA_LDS_WORDS];
+    __shared__ unsigned long long red[2];
+    const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t r = blockIdx.x / slabs, sl = blockIdx.x - r * slabs;
+    uint32_t *__restrict__ rec = state + (size_t)r * TaRec<KT>::WORDS;
+    uint32_t shift = TA64_SHIFT0;
+    uint64_t prefix = 0;
+    if (!first_round) {
+        if (rec[TA64_MODE] != 0u) return;   // workgroup-uniform: the row is decided
+        shift = (uint32_t)__builtin_amdgcn_readfirstlane(rec[TA64_SHIFT]);
+        prefix = uniform64(rec[0], rec[1]);
+    }
+    const uint64_t mask = shift >= TA64_SHIFT0 ? 0ull : ~0ull << (shift + TA64_DIGIT);   // the bits above this digit
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    for (uint32_t i = tid; i < TA64_BINS; i += TR_THREADS) h[i] = 0;
+    if (tid < 2u) red[tid] = 0ull;
+    __syncthreads();
+    uint64_t all_or = 0ull, all_orn = 0ull;
+    const uint32_t t0 = sl * slab_tiles, t1 = t0 + slab_tiles < tiles ? t0 + slab_tiles : tiles;
+    for (uint32_t t = t0; t < t1; ++t) {
+        const uint32_t lo = t * TA_TILE, len = cols - lo < TA_TILE ? cols - lo : TA_TILE;
+        uint64_t img[TR_KPT];
+        ta_load_tile<KT>(keys + (size_t)r * stride + lo, first, len, flt, x, img);
+#pragma unroll
+        for (int u = 0; u < TR_KPT; ++u) {
+            const uint32_t j = first + (uint32_t)u * WAVE;
+            if (j < len && ((img[u] ^ prefix) & mask) == 0ull) {
+                hist_add(h, (uint32_t)(img[u] >> shift) & (TA64_BINS - 1u));
+                all_or |= img[u];
+                all_orn |= ~img[u];
+            }
+        }
+    }
+    {   // OR over the wave, then one LDS atomic pair per wave that matched something
+        uint32_t ol = (uint32_t)all_or, oh = (uint32_t)(all_or >> 32), nl = (uint32_t)all_orn, nh = (uint32_t)(all_orn >> 32);
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            ol |= __shfl_xor(ol, d, WAVE); oh |= __shfl_xor(oh, d, WAVE);
+            nl |= __shfl_xor(nl, d, WAVE); nh |= __shfl_xor(nh, d, WAVE);
+        }
+        if (lane == 0u && (ol | oh | nl | nh) != 0u) {
+            atomicOr(&red[0], ((unsigned long long)oh << 32) | ol);
+            atomicOr(&red[1], ((unsigned long long)nh << 32) | nl);
+        }
+    }
+    __syncthreads();
+    uint32_t *__restrict__ g = hist + (size_t)r * TA64_BINS;
+    for (uint32_t i = tid; i < TA64_BINS; i += TR_THREADS) {   // a wave over contiguous bins; only what this slab holds
+        const uint32_t c = h[i];
+        if (c) atomicAdd(g + i, c);
+    }
+    if (tid == 0u && (red[0] | red[1]) != 0ull) {   // (the record is 64 bytes at a 256-byte base: the words are 8-byte aligned)
+        atomicOr(reinterpret_cast<unsigned long long *>(rec + TA64_OR), red[0]);
+        atomicOr(reinterpret_cast<unsigned long long *>(rec + TA64_ORN), red[1]);
+    }
+}
+
+// A pick of the 64-bit descent: see the rule above.  Clears the bins and the reduction words for the next round and the next call.
+__global__ __launch_bounds__(256) void topk_anyk_wide_pick_kernel(uint32_t *__restrict__ state, uint32_t *__restrict__ hist, uint32_t k,
+                                                                  uint32_t list_cap, int first_round)
+{
+    constexpr uint32_t PER = TA64_BINS / 256u;
+    __shared__ uint32_t scratch[8];
+    const uint32_t tid = threadIdx.x;
+    uint32_t *__restrict__ h = hist + (size_t)blockIdx.x * TA64_BINS + tid * PER;
+    uint32_t *__restrict__ st = state + (size_t)blockIdx.x * TaRec<TrKey64>::WORDS;
+    if (!first_round && st[TA64_MODE] != 0u) return;   // workgroup-uniform: decided, and its bins are clear
+    const uint32_t shift = first_round ? TA64_SHIFT0 : st[TA64_SHIFT];
+    const uint64_t prefix = first_round ? 0ull : ((uint64_t)st[1] << 32) | st[0];
+    const uint32_t less = first_round ? 0u : st[TaRec<TrKey64>::LESS], krem = first_round ? k : st[TA64_TAKE];
+    const uint32_t rounds = first_round ? 0u : st[TA64_D];
+    const uint64_t all_or = ((uint64_t)st[TA64_OR + 1] << 32) | st[TA64_OR];
+    const uint64_t all_and = ~(((uint64_t)st[TA64_ORN + 1] << 32) | st[TA64_ORN]);
+    uint32_t c[PER], sum = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < PER; ++i) { c[i] = h[i]; sum += c[i]; }
+#pragma unroll
+    for (uint32_t i = 0; i < PER; ++i) h[i] = 0;
+    uint32_t ex = block_exclusive_scan_256(sum, scratch, nullptr);   // (its barriers: every thread has read the record before one writes it)
+#pragma unroll
+    for (uint32_t i = 0; i < PER; ++i) {
+        if (ex < krem && krem - ex <= c[i]) {   // one bin of the row: the counts of the bins sum to at least krem
+            const uint64_t low = shift ? (1ull << shift) - 1ull : 0ull;
+            const uint64_t v = (all_and ^ all_or) & low;
+            uint64_t p = prefix | ((uint64_t)(tid * PER + i) << shift);
+            uint32_t mode = 0u, next = shift;
+            if (shift == 0u || v == 0ull) {
+                p |= all_and & low;
+                mode = 2u;
+            } else if (c[i] <= list_cap) {
+                mode = 1u;
+            } else {
+                const uint32_t hb = 63u - (uint32_t)__builtin_clzll(v);   // hb < shift
+                p |= all_and & low & ~((2ull << hb) - 1ull);              // bits (hb, shift): the same in every matched image
+                next = hb >= TA64_DIGIT - 1u ? hb - (TA64_DIGIT - 1u) : 0u;
+            }
+            st[0] = (uint32_t)p; st[1] = (uint32_t)(p >> 32);
+            st[TaRec<TrKey64>::LESS] = less + ex;
+            st[TA64_TAKE] = krem - ex;
+            st[TA64_MODE] = mode;
+            st[TA64_D] = rounds + 1u;
+            st[TA64_SHIFT] = next;
+            st[TA64_LIST] = 0u;
+            st[TA64_OR] = 0u; st[TA64_OR + 1] = 0u; st[TA64_ORN] = 0u; st[TA64_ORN + 1] = 0u;
+            st[TA64_C] = c[i];
+            st[13] = 0u; st[14] = 0u; st[15] = 0u;
+        }
+        ex += c[i];
+    }
+}
+
+// Collect: one workgroup per (row, tile) of a row in mode 1 appends its images of the bucket to the row's list.
+__global__ __launch_bounds__(TR_THREADS) void topk_anyk_wide_collect_kernel(const uint64_t *__restrict__ keys, uint32_t stride, uint32_t cols,
+                                                                            uint32_t tiles, uint32_t *__restrict__ state,
+                                                                            uint64_t *__restrict__ lists, uint32_t list_cap, int flt,
+                                                                            uint32_t x32)
+{
+    using KT = TrKey64;
+    const uint64_t x = KT::xmask(x32);
+    __shared__ uint32_t wcnt[TR_WAVES];
+    __shared__ uint32_t claimed;
+    const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t r = blockIdx.x / tiles, t = blockIdx.x - r * tiles;
+    uint32_t *__restrict__ rec = state + (size_t)r * TaRec<KT>::WORDS;
+    if (rec[TA64_MODE] != 1u) return;   // workgroup-uniform
+    const uint32_t shift = (uint32_t)__builtin_amdgcn_readfirstlane(rec[TA64_SHIFT]);   // 1 .. 53 in mode 1
+    const uint64_t prefix = uniform64(rec[0], rec[1]);
+    const uint64_t mask = ~0ull << shift;
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    const uint32_t lo = t * TA_TILE, len = cols - lo < TA_TILE ? cols - lo : TA_TILE;
+    uint64_t img[TR_KPT];
+    ta_load_tile<KT>(keys + (size_t)r * stride + lo, first, len, flt, x, img);
+    uint32_t n = 0;
+#pragma unroll
+    for (int u = 0; u < TR_KPT; ++u) {
+        const uint32_t j = first + (uint32_t)u * WAVE;
+        n += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(j < len && ((img[u] ^ prefix) & mask) == 0ull));
+    }
+    if (lane == 0u) wcnt[w] = n;
+    __syncthreads();
+    uint32_t base = 0, total = 0;
+    for (uint32_t q = 0; q < (uint32_t)TR_WAVES; ++q) { if (q < w) base += wcnt[q]; total += wcnt[q]; }
+    if (total == 0u) return;   // workgroup-uniform
+    if (tid == 0u) claimed = atomicAdd(rec + TA64_LIST, total);
+    __syncthreads();
+    base += claimed;
+    uint64_t *__restrict__ dst = lists + (size_t)r * list_cap;
+#pragma unroll
+    for (int u = 0; u < TR_KPT; ++u) {
+        const uint32_t j = first + (uint32_t)u * WAVE;
+        const bool m = j < len && ((img[u] ^ prefix) & mask) == 0ull;
+        const unsigned long long mm = __builtin_amdgcn_ballot_w64(m);
+        const uint32_t pos = base + count_lower(mm);
+        if (m && pos < list_cap) dst[pos] = img[u];   // (the bucket holds c <= list_cap elements: the bound never cuts)
+        base += (uint32_t)__popcll(mm);
+    }
+}
+
+// List select: one workgroup per row in mode 1 finds the krem-th image of the row's list.
+__global__ __launch_bounds__(TR_THREADS) void topk_anyk_wide_listselect_kernel(uint32_t *__restrict__ state,
+                                                                               const uint64_t *__restrict__ lists, uint32_t list_cap)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t h[RADIX];
+    __shared__ uint32_t scratch[8];
+    __shared__ uint32_t sel[3];
+    const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    uint32_t *__restrict__ rec = state + (size_t)blockIdx.x * TaRec<TrKey64>::WORDS;
+    if (rec[TA64_MODE] != 1u) return;   // workgroup-uniform
+    const uint32_t c = rec[TA64_C], n = c < list_cap ? c : list_cap;
+    const uint32_t less0 = rec[TaRec<TrKey64>::LESS], krem = rec[TA64_TAKE];
+    const uint64_t *__restrict__ src = lists + (size_t)blockIdx.x * list_cap;
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    uint64_t img[TR_KPT];
+#pragma unroll
+    for (int u = 0; u < TR_KPT; ++u) {
+        const uint32_t j = first + (uint32_t)u * WAVE;
+        img[u] = j < n ? src[j] : 0ull;
+    }
+    uint32_t less;
+    const uint64_t kth = tr_select<64>(img, first, n, krem, tid, h, scratch, sel, less);   // (its barriers: the record is read before it is written)
+    if (tid == 0u) {
+        rec[0] = (uint32_t)kth; rec[1] = (uint32_t)(kth >> 32);
+        rec[TaRec<TrKey64>::LESS] = less0 + less;
+        rec[TA64_TAKE] = krem - less;
+    }
+}
+
+struct TaPlan { uint32_t path, launches, slab_tiles, slabs, tiles, list_cap; };
+
+// L, the capacity of a row's list in the 64-bit descent: an eighth of the row, at least 1024, at most one tile.
+static inline uint32_t ta_list_cap(uint64_t cols)
+{
+    const uint64_t e = cols / 8;
+    return (uint32_t)(e < 1024 ? 1024 : e > TR_CH ? TR_CH : e);
+}
 
 static inline bool ta_shape_ok(uint64_t rows, uint64_t cols, uint64_t k)
 {
@@ -1611,6 +1877,7 @@ static inline TaPlan ta_make_plan(uint64_t cols)
     if (cols <= TR_CH) { p.path = 1; p.launches = 2; p.slab_tiles = 1; p.slabs = 1; p.tiles = 1; return p; }
     p.path = 2;
     p.launches = 5u + 2u * (uint32_t)TaWidth<KT::BITS>::ROUNDS;   // zero, offsets, ROUNDS times (count, pick), tile counts, scan, scatter
+    if (KT::BITS == 64) { p.launches += 2u; p.list_cap = ta_list_cap(cols); }   // collect and list select
     p.tiles = (uint32_t)((cols + TA_TILE - 1) / TA_TILE);
     p.slab_tiles = TA_SLAB_TILES;
     p.slabs = (p.tiles + p.slab_tiles - 1) / p.slab_tiles;
@@ -1641,12 +1908,25 @@ template <> struct TaFinish<TrKey16> {
     }
 };
 
+template <> struct TaFinish<TrKey64> {
+    static size_t temp_bytes(uint64_t items, bool hv, uint64_t rows) { return gs_segmented_wide_temp_bytes(items, 8, hv ? 4 : 0, (uint32_t)rows); }
+    static int sort(void *ws, size_t ws_bytes, uint64_t *dk[2], uint32_t *dv[2], int *selector, uint32_t items, uint32_t rows,
+                    const int32_t *offsets, int descending, int key_type, hipStream_t s)
+    {
+        void *k2[2] = {dk[0], dk[1]}, *v2[2] = {dv ? dv[0] : nullptr, dv ? dv[1] : nullptr};
+        return gs_segmented_sort_wide(ws, ws_bytes, k2, dv ? v2 : nullptr, selector, items, rows, offsets, offsets + 1, 8, dv ? 4 : 0, 0, 64,
+                                      descending, key_type, s);
+    }
+};
+
 template <typename KT>
 struct TaWs {
     uint32_t *state;
     int32_t *offsets;
     uint32_t *hist;
     uint2 *counts;
+    uint64_t *lists;   // (64-bit keys, path 2)
+    size_t zero_bytes; // from `state`: the records, the offsets and the histograms are one area
     typename KT::T *keys1;
     uint32_t *cols1, *cols0;
     char *seg;
@@ -1661,12 +1941,14 @@ static size_t ta_carve(char *base, uint64_t rows, uint64_t cols, uint64_t k, boo
     const TaPlan p = ta_make_plan<KT>(cols);
     size_t off = 0;
     auto take = [&](size_t bytes) { char *q = base + off; off += gs_ws_align(bytes); return q; };
-    ws->state = (uint32_t *)take((size_t)4 * TA_STATE_WORDS * rows);
+    ws->state = (uint32_t *)take((size_t)4 * TaRec<KT>::WORDS * rows);
     ws->offsets = (int32_t *)take((size_t)4 * (rows + 1));
-    ws->hist = nullptr; ws->counts = nullptr;
+    ws->hist = nullptr; ws->counts = nullptr; ws->lists = nullptr; ws->zero_bytes = 0;
     if (p.path == 2) {
         ws->hist = (uint32_t *)take((size_t)4 * TaWidth<KT::BITS>::BINS * rows);
+        ws->zero_bytes = off;
         ws->counts = (uint2 *)take((size_t)8 * rows * p.tiles);
+        if (KT::BITS == 64) ws->lists = (uint64_t *)take((size_t)8 * p.list_cap * rows);
     }
     ws->keys1 = (T *)take(sizeof(T) * rows * k);
     ws->cols1 = hv ? (uint32_t *)take((size_t)4 * rows * k) : nullptr;
@@ -1705,12 +1987,23 @@ static void ta_launch_select(hipStream_t s, const TaPlan &p, const TaWs<KT> &ws,
         return;
     }
     const dim3 gtile(rows * p.tiles), grow(rows), wg(TR_THREADS);
-    ta_launch_round<KT, 0>(s, p, ws, ki, rows, cols, stride, k, flt, x);
-    ta_launch_round<KT, 1>(s, p, ws, ki, rows, cols, stride, k, flt, x);
-    if constexpr (TaWidth<KT::BITS>::ROUNDS == 3) ta_launch_round<KT, 2>(s, p, ws, ki, rows, cols, stride, k, flt, x);
+    if constexpr (KT::BITS == 64) {   // the worst case of the descent, always: a decided row's workgroups return at once
+        for (uint32_t round = 0; round < TA64_ROUNDS; ++round) {
+            hipLaunchKernelGGL(topk_anyk_wide_count_kernel, dim3(rows * p.slabs), wg, 0, s, ki, stride, cols, p.tiles, p.slabs, p.slab_tiles,
+                               ws.state, ws.hist, flt, x, round == 0 ? 1 : 0);
+            hipLaunchKernelGGL(topk_anyk_wide_pick_kernel, grow, dim3(256), 0, s, ws.state, ws.hist, k, p.list_cap, round == 0 ? 1 : 0);
+        }
+        hipLaunchKernelGGL(topk_anyk_wide_collect_kernel, gtile, wg, 0, s, ki, stride, cols, p.tiles, ws.state, ws.lists, p.list_cap, flt, x);
+        hipLaunchKernelGGL(topk_anyk_wide_listselect_kernel, grow, wg, 0, s, ws.state, (const uint64_t *)ws.lists, p.list_cap);
+    } else {
+        ta_launch_round<KT, 0>(s, p, ws, ki, rows, cols, stride, k, flt, x);
+        ta_launch_round<KT, 1>(s, p, ws, ki, rows, cols, stride, k, flt, x);
+        if constexpr (TaWidth<KT::BITS>::ROUNDS == 3) ta_launch_round<KT, 2>(s, p, ws, ki, rows, cols, stride, k, flt, x);
+    }
     hipLaunchKernelGGL((topk_anyk_tilecount_kernel<KT>), gtile, wg, 0, s, ki, stride, cols, p.tiles, (const uint32_t *)ws.state, ws.counts, flt,
                        x);
-    hipLaunchKernelGGL(topk_anyk_scan_kernel, grow, dim3(256), 0, s, (const uint32_t *)ws.state, ws.counts, p.tiles);
+    if constexpr (KT::BITS == 64) hipLaunchKernelGGL(topk_anyk_wide_scan_kernel, grow, dim3(256), 0, s, (const uint32_t *)ws.state, ws.counts, p.tiles);
+    else hipLaunchKernelGGL(topk_anyk_scan_kernel, grow, dim3(256), 0, s, (const uint32_t *)ws.state, ws.counts, p.tiles);
     hipLaunchKernelGGL((topk_anyk_scatter_kernel<KT, HV>), gtile, wg, 0, s, ki, stride, cols, p.tiles, k, (const uint32_t *)ws.state,
                        (const uint2 *)ws.counts, dk, dc, flt, x);
 }
@@ -1748,7 +2041,9 @@ static int ta_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_
     ta_carve<KT>(gs_ws_base(d_temp), num_rows, num_cols, k, hv, pairs, &ws);
 
     if (p.path == 2) {   // the histograms start at zero; every pick leaves them so
-        const hipError_t e = zero_async(ws.hist, (size_t)4 * TaWidth<KT::BITS>::BINS * rows, s);
+        // (64-bit keys: the records, whose cursors and reduction words must start at zero, sit in one area with them)
+        const hipError_t e = KT::BITS == 64 ? zero_async(ws.state, ws.zero_bytes, s)
+                                            : zero_async(ws.hist, (size_t)4 * TaWidth<KT::BITS>::BINS * rows, s);
         if (e != hipSuccess) return (int)e;
     }
     {
@@ -1763,7 +2058,7 @@ static int ta_run(void *d_temp, size_t temp_bytes, const typename KT::T *d_keys_
     int err = (int)hipGetLastError();
     if (err) return err;
 
-    // the finish: an even number of passes over the whole image (four of 32 bits, two of 16) leaves the result in half 0, where
+    // the finish: an even number of passes over the whole image (eight of 64 bits, four of 32, two of 16) leaves the result in half 0, where
     // the pairs were staged
     T *dk[2] = {d_keys_out, ws.keys1};
     uint32_t *dv[2] = {col0, ws.cols1};
@@ -1789,6 +2084,7 @@ static int ta_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, uint32_t ou
     if (num_rows == 0 || num_cols == 0 || k == 0) return hipSuccess;   // such a call enqueues nothing
     const TaPlan p = ta_make_plan<KT>(num_cols);
     out[0] = p.path; out[1] = p.launches; out[2] = TR_CH; out[3] = TA_TILE; out[4] = p.slab_tiles; out[5] = p.slabs; out[6] = p.tiles;
+    out[7] = p.list_cap;   // (0 at 16 and 32 bits and on path 1)
     return hipSuccess;
 }
 
@@ -1804,11 +2100,17 @@ static int ta_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_
     if (!d_temp || row >= num_rows) return hipErrorInvalidValue;
     TaWs<KT> ws;
     ta_carve<KT>(gs_ws_base(d_temp), num_rows, num_cols, k, has_values != 0, false, &ws);   // (only the records, the first term, are read)
-    uint32_t st[TA_STATE_WORDS];
-    hipError_t e = hipMemcpyAsync(st, ws.state + row * TA_STATE_WORDS, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    uint32_t st[TaRec<KT>::WORDS];
+    hipError_t e = hipMemcpyAsync(st, ws.state + row * TaRec<KT>::WORDS, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
-    out[0] = ta_make_plan<KT>(num_cols).path; out[1] = st[0]; out[2] = st[1]; out[3] = st[2]; out[4] = st[4]; out[5] = st[5];
+    out[0] = ta_make_plan<KT>(num_cols).path;
+    if (KT::BITS == 64) {
+        out[1] = st[0]; out[2] = st[1]; out[3] = st[TaRec<KT>::LESS]; out[4] = st[TA64_TAKE]; out[5] = st[TA64_D]; out[6] = st[TA64_MODE];
+        out[7] = st[TA64_MODE] == 1u ? st[TA64_LIST] : 0u;
+    } else {
+        out[1] = st[0]; out[2] = st[1]; out[3] = st[2]; out[4] = st[4]; out[5] = st[5];
+    }
     return hipSuccess;
 }
 
@@ -1971,6 +2273,31 @@ int gs_topk_rows_anyk_u16_status(void *d_temp, uint64_t num_rows, uint64_t num_c
                                  uint32_t out[8], void *stream)
 {
     return ta_status<TrKey16>(d_temp, num_rows, num_cols, k, has_values, row, out, stream);
+}
+
+size_t gs_topk_rows_anyk_u64_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values)
+{
+    return ta_temp_bytes<TrKey64>(num_rows, num_cols, k, has_values);
+}
+
+int gs_topk_rows_anyk_u64(void *d_temp, size_t temp_bytes, const uint64_t *d_keys_in, const uint32_t *d_vals_in, uint64_t *d_keys_out,
+                          uint32_t *d_vals_out, uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k, int descending,
+                          int key_type, void *stream)
+{
+    return ta_run<TrKey64>(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, num_rows, num_cols, row_stride, k, descending,
+                           key_type, stream);
+}
+
+int gs_topk_rows_anyk_u64_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint32_t out[8])
+{
+    (void)has_values;
+    return ta_plan<TrKey64>(num_rows, num_cols, k, out);
+}
+
+int gs_topk_rows_anyk_u64_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint64_t row,
+                                 uint32_t out[8], void *stream)
+{
+    return ta_status<TrKey64>(d_temp, num_rows, num_cols, k, has_values, row, out, stream);
 }
 
 }  // extern "C"

@@ -9,12 +9,13 @@
     DeviceTopKRows64        gs_topk_rows_u64          int64, float64, uint64
     DeviceTopKRowsAnyK      gs_topk_rows_anyk_u32     int32, float32, uint32; any k up to the row length
     DeviceTopKRowsAnyK16    gs_topk_rows_anyk_u16     int16, uint16, float16, bfloat16; any k up to the row length
+    DeviceTopKRowsAnyK64    gs_topk_rows_anyk_u64     int64, float64, uint64; any k up to the row length
     DeviceTopKSegmented     gs_topk_segmented_u32     int32, float32, uint32
                             gs_topk_segmented_u16     int16, uint16, float16, bfloat16
     DeviceTopKSegmented64   gs_topk_segmented_u64     int64, float64, uint64
 
 The classes are two-phase like DeviceRadixSort (d_temp_storage=None returns the size); topk(), topk_rows(), topk_rows64(),
-topk_rows_anyk(), topk_rows_anyk16(), topk_segmented() and topk_segmented64() allocate outputs and workspace, topk() for any of the three widths.
+topk_rows_anyk(), topk_rows_anyk16(), topk_rows_anyk64(), topk_segmented() and topk_segmented64() allocate outputs and workspace, topk() for any of the three widths.
 The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs (descending for the Max forms) on the same
 input (the whole array, every row of a matrix, every ragged segment given by device offsets): stable, keys in the caller's bit
 patterns, floats in the order of GS_KEY_F32 (negative NaNs first, positive NaNs last ascending; -0.0 before +0.0), float16 /
@@ -352,6 +353,35 @@ class DeviceTopKRowsAnyK16(DeviceTopKRowsAnyK):
     _plan, _status = "gs_topk_rows_anyk_u16_plan", "gs_topk_rows_anyk_u16_status"
 
 
+class DeviceTopKRowsAnyK64(DeviceTopKRowsAnyK):
+    """DeviceTopKRowsAnyK for a matrix of 64-bit keys (gs_topk_rows_anyk_u64): MinKeys / MaxKeys / MinPairs / MaxPairs / Plan /
+    Status for any 1 <= k <= num_cols.
+
+    The key type comes from the tensor's dtype (int64, float64, uint64) or from an explicit GS_KEY_U64 / I64 / F64; each row's
+    result is what DeviceTopK64 gives for that row alone, float64 in the order of GS_KEY_F32 at the enum, and for
+    k <= DeviceTopKRows64.MaxK() it is DeviceTopKRows64's result, that class remaining the faster one there.  Values and column
+    indices are 4 bytes.  Keys of any other width and any other key_type raise TypeError."""
+
+    _entries = {_W64: ("gs_topk_rows_anyk_u64", "gs_topk_rows_anyk_u64_temp_bytes")}
+    _plan, _status = "gs_topk_rows_anyk_u64_plan", "gs_topk_rows_anyk_u64_status"
+
+    @classmethod
+    def Plan(cls, num_rows, num_cols, k, has_values=False):
+        """gs_topk_rows_anyk_u64_plan: [path, kernel launches before the finish (2 on path 1, 19 on path 2), CH, tile, tiles
+        per slab, slabs per row, tiles per row, L: the capacity of a row's list (0 on path 1)]; a pure host function.  Raises
+        for a refused shape."""
+        return _eight_words(cls._plan, num_rows, num_cols, k, int(has_values))
+
+    @classmethod
+    def Status(cls, d_temp_storage, num_rows, num_cols, k, has_values, row, stream=None):
+        """gs_topk_rows_anyk_u64_status: [path, low word of the image of row `row`'s k-th element, its high word, elements
+        before it, taken from its tie run, D: the counting rounds the row took (0 on path 1), how its descent ended (0 path 1,
+        1 from the row's list, 2 a tie run), elements put on the list (0 otherwise)] of the last call on d_temp_storage.
+        Synchronises the stream."""
+        return _eight_words(cls._status, C.c_void_p(d_temp_storage.data_ptr()), num_rows, num_cols, k, int(has_values), row,
+                            stream=(_stream_ptr(stream),))
+
+
 def _rows_call(who, front, keys, k, values, indices, stream):
     """The argument checks of the topk_rows*() forms, in the name of `who`, the [rows, k] outputs and the answer of `front`'s
     size query (None where k or the number of rows is 0 and the outputs are the whole result), as (key_type, rows, cols,
@@ -448,8 +478,20 @@ def topk_rows_anyk16(keys, k, largest=False, values=None, indices=False, stream=
     return _topk_rows_anyk("topk_rows_anyk16", DeviceTopKRowsAnyK16, keys, k, largest, values, indices, stream)
 
 
+def topk_rows_anyk64(keys, k, largest=False, values=None, indices=False, stream=None):
+    """topk_rows_anyk() for a 2-D tensor of 8-byte keys (int64, float64, uint64): the k smallest (largest=True: largest) of
+    every row for any 0 <= k <= cols in one batched call, sorted, as (keys_out, values_out) of shape [rows, k], through
+    gs_topk_rows_anyk_u64.
+
+    The checks and the return shapes are topk_rows()': the last dimension contiguous, rows at any stride >= cols, values a
+    4-byte tensor of the same shape and strides, indices=True for the column indices as int32 bit patterns of u32.  float64 is
+    in the order of GS_KEY_F32 at the enum.  Any other key width raises TypeError.  For k <= DeviceTopKRows64.MaxK()
+    topk_rows64() gives the same result faster."""
+    return _topk_rows_anyk("topk_rows_anyk64", DeviceTopKRowsAnyK64, keys, k, largest, values, indices, stream)
+
+
 def _topk_rows_anyk(who, front, keys, k, largest, values, indices, stream):
-    """topk_rows_anyk() and topk_rows_anyk16(): the argument checks in the name of `who`, the outputs, and `front`'s call."""
+    """topk_rows_anyk(), topk_rows_anyk16() and topk_rows_anyk64(): the argument checks in the name of `who`, the outputs, and `front`'s call."""
     key_type, rows, cols, stride, has_values, keys_out, values_out, nbytes = _rows_call(who, front, keys, k, values, indices, stream)
     if nbytes is None:
         return keys_out, values_out

@@ -795,6 +795,99 @@ int      gs_topk_rows_anyk_u16_plan(uint64_t num_rows, uint64_t num_cols, uint64
 int      gs_topk_rows_anyk_u16_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values,
                                       uint64_t row, uint32_t out[8], void *stream);
 
+/* ------------------------------------- top k of every row, any k, 64-bit keys --
+ * gs_topk_rows_anyk_u32 for 64-bit keys (gs_topk_rows.hip): a matrix of int64 ids or timestamps, double
+ * scores or 64-bit hashes and more than gs_topk_rows_max_k() of every row -- a per-group ORDER BY ... LIMIT 5000, a few thousand
+ * candidates per query scored in double precision, a k-way merge of per-shard lists -- without a segmented sort of a copy of
+ * the whole matrix and without a loop of gs_topk_u64 over the rows.  key_type is GS_KEY_U64, GS_KEY_I64 or GS_KEY_F64 (doubles
+ * in the order of GS_KEY_F32 at width 64: negative NaNs first, positive NaNs last ascending, -0 before +0).  1 <= k <= num_cols;
+ * everything else is gs_topk_rows_anyk_u32's contract word for word, with 8-byte keys.  Row r of the result is bit for bit what
+ * gs_topk_u64 writes for that row alone: the first k of the stable sort on the 64-bit order-preserving image (complemented
+ * when descending), the lowest column indices where the cut falls inside a run of equal keys, the caller's bit patterns kept
+ * (NaN payloads included).  A k of 1024 and below is served too, with gs_topk_rows_u64's bytes; that call remains the faster
+ * one there.
+ * Forms: keys only; pairs; arguments (d_vals_in == NULL, d_vals_out != NULL: the u32 column index).  Values are u32 and sit at
+ * the same row_stride counted in elements; the outputs are dense with stride k.  The inputs and the stride gap are never
+ * written, the gap is never read, nothing outside [0, num_rows * k) of the outputs and the workspace is written, d_temp
+ * anywhere, enqueue-only (no host read-back, allocation or synchronisation), the launches are a function of the arguments
+ * alone (gs_topk_rows_anyk_u64_plan reports them), so the call may be captured into a HIP graph on one plain stream; calls may
+ * follow each other on one stream with one workspace; two runs give identical output bytes (the order inside a row's list in
+ * the workspace may differ: see collect below).  num_rows == 0, num_cols == 0 or k == 0 returns 0, writes nothing and needs no
+ * workspace (the query returns 0).
+ * Errors (hipErrorInvalidValue, checked before anything is enqueued, nothing written; the size query returns 0 and the plan
+ * zeros for a refused shape; the checks run in gs_topk_rows_anyk_u32's order): k > num_cols, row_stride < num_cols,
+ * num_rows * row_stride >= 2^32 (the size query and the plan, which have no stride, refuse num_rows * num_cols >= 2^32),
+ * num_rows * k >= 2^31 (the finish has int offsets), a key_type other than GS_KEY_U64 / I64 / F64, d_vals_in without
+ * d_vals_out, a NULL key pointer, a NULL or too-small workspace, a key array not aligned to 8 bytes or a value array not
+ * aligned to 4, arrays that share a byte (inputs at (num_rows - 1) * row_stride + num_cols elements, outputs at num_rows * k;
+ * 8 bytes per key, 4 per value).
+ * Paths, by num_cols alone, with gs_topk_rows_anyk_u32's geometry (CH = tile = 8192, four tiles per slab).
+ * Path 1, num_cols <= 8192: one workgroup reads the row once, selects the k-th image in registers and LDS (a byte round only
+ * for a byte in which two images of the row differ) and places the k selected (key, column) pairs, equal keys in column order,
+ * into the row's k output slots.  2 launches before the finish: offsets, select.
+ * Path 2, longer rows: a radix select over all rows at once on 11-bit digits (2048 bins, 8 KB of LDS per count workgroup), with
+ * a decision per row on the device.  L = min(8192, max(1024, num_cols / 8)) is the capacity of a row's list.
+ *   A counting round at shift s (the first has s = 53): one workgroup per (row, slab) histograms (image >> s) & 2047 over the
+ *   elements of the row whose image matches the row's prefix on the bits at and above s + 11, and reduces the OR of those
+ *   images and the OR of their complements (the AND is the complement of the latter; a zeroed word is neutral for both): per
+ *   wave, in LDS, then one pair of 64-bit atomic ORs per workgroup.  The bins are added to the row's histogram with integer
+ *   atomic adds.  Neither result depends on the order of the atomics.
+ *   A pick, one workgroup per row: take the bin d that holds the krem-th element; set prefix bits [s, s + 11) to d; update less
+ *   and krem; let c be the bin's count and v = (AND ^ OR) restricted to the bits below s -- AND and OR are those of the round's
+ *   matched set, not of the bucket.  If s == 0 or v == 0, every element of the bucket equals the k-th image, whose bits below s
+ *   come from the AND: the row is decided (a tie run, mode 2).  Else if c <= L the bucket goes to the row's list (mode 1).
+ *   Else, with hb the highest set bit of v, the bits between hb and s are constant over the bucket and come from the AND, and
+ *   the next round runs at s' = max(hb - 10, 0).  The pick clears the bins and the two reduction words.
+ *   The shifts fall by at least 11 until they reach 0, so six rounds are the worst case: 53, <= 42, <= 31, <= 20, <= 9, 0.  All
+ *   six (count, pick) pairs are always enqueued; a workgroup whose row is decided reads the row's record and returns at once.
+ *   Collect, one workgroup per (row, tile), rows in mode 1 only: appends the images of the elements that match the full prefix
+ *   to the row's list.  A workgroup claims its range from the row's cursor with ONE atomic add: that atomic decides positions
+ *   in the list only; the list is read as a multiset and never reaches an output position.
+ *   List select, one workgroup per row in mode 1: loads the <= L images as path 1 loads a row, selects the krem-th among them
+ *   and writes the k-th image, less and take into the record.
+ *   Then per (row, tile) two counts (before / equal to the k-th image), a scan per row and a scatter: group A in column order
+ *   from 0, the first `take` of the tie run in column order from `less`.  No atomic decides an output position.
+ *   19 launches before the finish: zero (records, offsets and histograms are one area), offsets, six times (count, pick),
+ *   collect, list select, tile counts, scan, scatter.  A row that took D rounds is read D + 3 times in list mode and D + 2
+ *   times for a tie run: uniform u64 D = 1; N(0, 1) doubles, int64 below 2^24 and the timestamps of one day D = 2 (their first
+ *   round only learns AND and OR); a row of one key D = 1, a tie run.
+ * Both paths finish with gs_segmented_sort_wide on the num_rows * k staged pairs with the regular offsets r * k, key_bytes 8,
+ * val_bytes 0 or 4, bits 0 .. 64, in the caller's key_type and direction: eight passes end in the half they started from.
+ * Workspace: a pure host function of its arguments, a multiple of 256, monotone in each of them.  With T = ceil(num_cols /
+ * 8192), hv = 1 with has_values else 0, p2 = 1 if num_cols > 8192 else 0, L as above, and every term rounded up to 256 bytes:
+ *   64 * num_rows                             a record of sixteen words per row: the k-th image low, high; less; krem / take; the
+ *                                             mode; D; the next shift; the list count; the OR word low, high; the OR of the
+ *                                             complements low, high; c of the last pick; three zero words
+ * + 4 * (num_rows + 1)                        the offsets r * k of the finish
+ * + p2 * 4 * 2048 * num_rows                  the rows' histograms
+ * + p2 * 8 * num_rows * T                     two u32 counts per (row, tile)
+ * + p2 * 8 * L * num_rows                     the rows' lists (images only): never above an eighth of the dense matrix bytes
+ * + 8 * num_rows * k                          the second half of the staged keys (the first is d_keys_out)
+ * + hv * 4 * num_rows * k                     the second half of the columns (the first is d_vals_out in the arguments form)
+ * + hv * 4 * num_rows * k                     the first half of the columns, used by the pairs form
+ * + gs_segmented_wide_temp_bytes(num_rows * k, 8, 4 with has_values else 0, num_rows)
+ * + 256 bytes of alignment slack.                                                                                          */
+size_t   gs_topk_rows_anyk_u64_temp_bytes(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values);
+int      gs_topk_rows_anyk_u64(void *d_temp, size_t temp_bytes,
+                               const uint64_t *d_keys_in, const uint32_t *d_vals_in,
+                               uint64_t *d_keys_out, uint32_t *d_vals_out,
+                               uint64_t num_rows, uint64_t num_cols, uint64_t row_stride, uint64_t k,
+                               int descending, int key_type, void *stream);
+/* What gs_topk_rows_anyk_u64 launches for a shape: a pure host function.  out[0] = path (1 or 2), out[1] = kernel launches
+ * before the finish (path 1: 2; path 2: 19, as listed above), out[2..6] = gs_topk_rows_anyk_plan's geometry words (CH, the
+ * tile, tiles per slab, slabs per row, tiles per row), out[7] = L, the capacity of a row's list (0 on path 1).  A refused shape
+ * (k > num_cols, num_rows * num_cols >= 2^32, num_rows * k >= 2^31) returns hipErrorInvalidValue and all zeros; a no-op shape
+ * returns 0 and all zeros.                                                                                                  */
+int      gs_topk_rows_anyk_u64_plan(uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values, uint32_t out[8]);
+/* What the select found for one row of the last gs_topk_rows_anyk_u64 on d_temp with these arguments (read back after
+ * synchronising `stream`; no kernel runs).  out[0] = path, out[1], out[2] = the low and the high word of the image of that
+ * row's k-th element, out[3] = elements whose image sorts strictly before it, out[4] = k - out[3], out[5] = D, the counting
+ * rounds the row took (0 on path 1), out[6] = how the descent ended (0 path 1, 1 from the row's list, 2 a tie run), out[7] =
+ * elements put on the list (0 otherwise).  All zeros for a no-op shape; hipErrorInvalidValue for a refused shape,
+ * row >= num_rows, or a NULL d_temp or out.                                                                                 */
+int      gs_topk_rows_anyk_u64_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_t k, int has_values,
+                                      uint64_t row, uint32_t out[8], void *stream);
+
 /* ------------------------------------------------ top k of every ragged segment --
  * The k best of every segment of a flat array, the segments given by device offsets (gs_topk_rows.hip, DESIGN.md section
  * 10k): per-query candidate lists, variable-length sequences, per-image box scores, the neighbour lists of a CSR graph.

@@ -389,17 +389,29 @@ struct DeviceTopKRows {
 // k <= gs_topk_rows_max_k() it is DeviceTopKRows' result, and that struct remains the faster one there.  A size query of 0
 // with a non-empty shape means the shape is refused (k > num_cols, num_rows * k >= 2^31, ...).
 // 2-byte keys (unsigned short, short, _Float16, __half, __hip_bfloat16) go to gs_topk_rows_anyk_u16 and its size query: the same
-// definition on the 16-bit image.  8-byte keys are not served: a static_assert.
+// definition on the 16-bit image.  8-byte keys (unsigned long long, long long, double and their fixed-width names) go to
+// gs_topk_rows_anyk_u64 and its size query: the same definition on the 64-bit image, double in GS_KEY_F32's order at width 64.
 struct DeviceTopKRowsAnyK {
     template <typename KeyT, typename ValueT>
     static hipError_t Dispatch(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
                                const ValueT *d_values_in, ValueT *d_values_out, uint64_t num_rows, uint64_t num_cols,
                                uint64_t row_stride, uint64_t k, bool descending, hipStream_t stream)
     {
-        static_assert(sizeof(KeyT) == 4 || sizeof(KeyT) == 2, "32-bit keys (unsigned int, int, float) or 16-bit keys");
+        static_assert(sizeof(KeyT) == 8 || sizeof(KeyT) == 4 || sizeof(KeyT) == 2, "64-bit, 32-bit or 16-bit keys");
         static_assert(sizeof(ValueT) == 4, "32-bit values only");
         const bool has_values = d_values_out != nullptr;
-        if constexpr (sizeof(KeyT) == 2) {   // unsigned short, short, _Float16, __half, __hip_bfloat16: gs_topk_rows_anyk_u16
+        if constexpr (sizeof(KeyT) == 8) {   // unsigned long long, long long, double: gs_topk_rows_anyk_u64
+            constexpr int kt = KeyTraits<KeyT>::type;
+            static_assert(kt == GS_KEY_U64 || kt == GS_KEY_I64 || kt == GS_KEY_F64, "a 64-bit key type");
+            if (d_temp_storage == nullptr) {
+                temp_storage_bytes = gs_topk_rows_anyk_u64_temp_bytes(num_rows, num_cols, k, has_values);
+                return hipSuccess;
+            }
+            return static_cast<hipError_t>(gs_topk_rows_anyk_u64(
+                d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint64_t *>(d_keys_in),
+                reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint64_t *>(d_keys_out),
+                reinterpret_cast<uint32_t *>(d_values_out), num_rows, num_cols, row_stride, k, descending ? 1 : 0, kt, stream));
+        } else if constexpr (sizeof(KeyT) == 2) {   // unsigned short, short, _Float16, __half, __hip_bfloat16: gs_topk_rows_anyk_u16
             constexpr int kt = KeyTraits<KeyT>::type;
             static_assert(kt == GS_KEY_U16 || kt == GS_KEY_I16 || kt == GS_KEY_F16 || kt == GS_KEY_BF16, "a 16-bit key type");
             if (d_temp_storage == nullptr) {
