@@ -19,6 +19,7 @@ Names follow the reference:
   DeviceTopKRowsAnyK64, topk_rows_anyk64   (the same for int64 / uint64 / float64 keys: gs_topk_rows_anyk_u64)
   DeviceTopKSegmented, topk_segmented   (the same for every ragged segment given by device offsets; 32-bit keys, and int16 / uint16 / float16 / bfloat16)
   DeviceTopKSegmented64, topk_segmented64   (the same for ragged segments of int64 / uint64 / float64 keys: gs_topk_segmented_u64)
+  DeviceTopKSegmentedAnyK, topk_segmented_anyk   (ragged segments of 32-bit keys for any k: gs_topk_segmented_anyk_u32)
   sortKeysGPU / sortPairsGPU    (lsb/sort.cu:25-76)
   rdxsrt_unstable_sort, rdxsrt_unstable_sort_keys/_pairs, RDXSRT_SortedSequence
                                 (msb/src/sort/gpu_radix_sort.h:31-34,197,511,544)
@@ -30,7 +31,7 @@ from .lsb import DoubleBuffer, DeviceRadixSort, DeviceRadixSortLarge, DeviceSegm
 from .select import (DeviceTopK, DeviceTopK16, DeviceTopK64, DeviceTopKRows, DeviceTopKRows64, DeviceTopKRowsAnyK, DeviceTopKRowsAnyK16,
                      DeviceTopKRowsAnyK64, topk_rows_anyk64,
                      DeviceTopKSegmented, DeviceTopKSegmented64, topk, topk_rows, topk_rows64, topk_rows_anyk, topk_rows_anyk16, topk_segmented,
-                     topk_segmented64)
+                     topk_segmented64, DeviceTopKSegmentedAnyK, topk_segmented_anyk)
 from .datagen import (generate_random_keys, generate_uniform_keys, generate_zipf_keys, generate_enumerated_values,
                       check_sorted, check_pairs_enumerated)
 from .msb import (RDXSRT_SortedSequence, rdxsrt_unstable_sort, rdxsrt_unstable_sort_keys, rdxsrt_unstable_sort_pairs,

@@ -103,6 +103,10 @@ SIGNATURES = {
     "gs_topk_segmented_u64": (i32, [vp, sz, vp, vp, vp, vp, vp, u64, C.c_uint32, vp, vp, u64, i32, i32, vp]),
     "gs_topk_segmented_plan": (i32, [u64, C.c_uint32, u64, i32, C.POINTER(C.c_uint32)]),
     "gs_topk_segmented_status": (i32, [vp, u64, C.c_uint32, u64, i32, C.POINTER(C.c_uint32), vp]),
+    "gs_topk_segmented_anyk_temp_bytes": (sz, [u64, C.c_uint32, u64, i32]),
+    "gs_topk_segmented_anyk_u32": (i32, [vp, sz, vp, vp, vp, vp, vp, u64, C.c_uint32, vp, vp, u64, i32, i32, vp]),
+    "gs_topk_segmented_anyk_plan": (i32, [u64, C.c_uint32, u64, i32, C.POINTER(C.c_uint32)]),
+    "gs_topk_segmented_anyk_status": (i32, [vp, u64, C.c_uint32, u64, i32, C.POINTER(C.c_uint32), vp]),
     "gs_msb_census": (i32, [vp, u64, i32, vp, vp]),
     "gs_msb_wide_census": (i32, [vp, u64, i32, i32, vp, vp]),
     "gs_msb_capacities": (None, [u64, i32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -9,6 +9,8 @@
 // (see "any k" below): their selects stage the k selected pairs of every row in the outputs and gs_segmented_sort_u32 /
 // gs_segmented_sort_narrow finishes them.  gs_topk_rows_anyk_u64 (section 10r) follows them: path 1 is the same kernel at
 // TrKey64, path 2 a descent of its own (see "any k, 64-bit keys" below), and gs_segmented_sort_wide finishes.
+// gs_topk_segmented_anyk_u32 (section 10s), the ragged form without the cap on k, is the last (see "any k, ragged segments"): the
+// classify, expand and wave kernels of the ragged form as they are, the any-k selects per record and per (record, tile) task.
 //
 // Row r of the result is what gs_topk_u32 writes for row r alone, bit for bit.  Every row has the same length, so the
 // launches are decided on the host from num_cols and k:
@@ -2114,6 +2116,491 @@ static int ta_status(void *d_temp, uint64_t num_rows, uint64_t num_cols, uint64_
     return hipSuccess;
 }
 
+// ----------------------------------------------------- any k, ragged segments --
+// gs_topk_segmented_anyk_u32: the k best of every ragged segment with no cap on k.  The workspace begins
+// with the TsWs layout, so topk_seg_classify_kernel sorts the segments into the same six lists, with the same Lmax / Tmax bounds
+// and the same drop rule, and topk_seg_expand_kernel writes the (record, tile) tasks of the long ones.  Then, by length:
+//
+//   <= 1024   the four topk_seg_wave_kernel launches as they are: k is their output stride and min(k, len) their cut.  What they
+//             write is final and sorted; these segments skip the finish.
+//   <= CH     one workgroup per record of the block list: topk_anyk_block_kernel's body (tr_select, then ta_place at seg * k).
+//   longer    path 2 of gs_topk_rows_anyk_u32 over all long segments at once, (row, tile) = blockIdx replaced by a lookup in the
+//             task list: three counting rounds into 2048 bins per long record, a pick per record after each, two counts per task, a
+//             scan per record and a scatter in position order.  A count workgroup takes the slab of TA_SLAB_TILES consecutive
+//             tiles that starts at its task (a segment's tasks are consecutive slots); the others go on to their next slot.
+//
+// The selects stage the kept (key, position) pairs of a segment, unsorted but with equal keys in position order, at
+// [seg * k, seg * k + kept), and write seg * k + kept into the end array of the finish: gs_segmented_sort_u32 over the
+// num_segments * k slots with begin = seg * k.  The end array starts equal to the begin array, so an empty, a wave-class or a
+// dropped segment is an empty range of the finish and none of its slots is touched.  Every record and task read from the
+// workspace is clamped against the arguments before it becomes an address; no atomic decides an output position.
+struct TsaWs {
+    uint32_t *state;             // eight words per long record: k-th image (the prefix so far), less, take, 0, matched after round 0, 1, 0, 0
+    uint32_t *hist;              // TaWidth<32>::BINS per long record
+    uint2 *counts;               // per task slot
+    int32_t *begin, *end;        // the finish's offsets
+    uint32_t *keys1, *pos1, *pos0;
+    char *seg;
+    size_t seg_bytes;
+};
+
+__device__ __forceinline__ uint32_t tsa_task_count(const TsWs &ws)
+{   // the cursor, not the count of completed claims: a dropped segment leaves a hole behind it
+    const uint32_t c = ws.state[TS_TASK_CUR + 1] != 0u ? ws.tmax : ws.state[TS_TASK_CUR];
+    return __builtin_amdgcn_readfirstlane(c > ws.tmax ? ws.tmax : c);
+}
+__device__ __forceinline__ uint32_t tsa_rec_count(const TsWs &ws)
+{
+    const uint32_t c = ws.state[TS_REC_CUR];
+    return __builtin_amdgcn_readfirstlane(c > ws.lmax ? ws.lmax : c);
+}
+
+// a long record, clamped; false when nothing of it may be touched (an empty record is a dropped segment's)
+__device__ __forceinline__ bool tsa_load_long(const TsWs &ws, uint32_t rec, uint32_t num_items, uint32_t &base, uint32_t &slen, uint32_t &seg,
+                                              uint32_t &row, uint32_t &chunks)
+{
+    if (!ts_load_rec(ws.list[TS_LONG], rec, num_items, ws.nseg, num_items, base, slen, seg, row)) return false;
+    chunks = (slen + TA_TILE - 1u) / TA_TILE;
+    return !__builtin_amdgcn_readfirstlane(row >= ws.tmax || chunks > ws.tmax - row);
+}
+
+// task slot t: its record and tile, and the record's fields.  A slot whose claim was dropped was never written by the expand
+// kernel: whatever it holds is not the task of this slot.  Everything returned is uniform.
+__device__ __forceinline__ bool tsa_load_task(const TsWs &ws, uint32_t t, uint32_t nrec, uint32_t num_items, uint32_t &rec, uint32_t &c,
+                                              uint32_t &base, uint32_t &slen, uint32_t &seg, uint32_t &chunks)
+{
+    const TsTask task = ws.tasks[t];
+    rec = __builtin_amdgcn_readfirstlane(task.rec); c = __builtin_amdgcn_readfirstlane(task.chunk);
+    if (__builtin_amdgcn_readfirstlane(rec >= nrec)) return false;
+    uint32_t row;
+    if (!tsa_load_long(ws, rec, num_items, base, slen, seg, row, chunks)) return false;
+    return !__builtin_amdgcn_readfirstlane(c >= chunks || row + c != t);
+}
+
+// begin[s] = end[s] = s * k: every segment starts as an empty range of the finish.
+__global__ __launch_bounds__(256) void topk_seganyk_offsets_kernel(int32_t *__restrict__ begin, int32_t *__restrict__ end, uint32_t nseg,
+                                                                   uint32_t k)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < nseg) { begin[i] = (int32_t)(i * k); end[i] = (int32_t)(i * k); }
+}
+
+// Segments of 1025 .. CH elements: one workgroup per record of the block list, topk_anyk_block_kernel's body.
+template <typename KT, bool HV>
+__global__ __launch_bounds__(TR_THREADS) void topk_seganyk_block_kernel(TsWs ws, const typename KT::T *__restrict__ keys,
+                                                                        typename KT::T *__restrict__ dst_k, uint32_t *__restrict__ dst_c,
+                                                                        int32_t *__restrict__ end, uint32_t num_items, uint32_t k, int flt,
+                                                                        uint32_t x32)
+{
+    using I = typename KT::I;
+    const I x = KT::xmask(x32);
+    __shared__ __attribute__((aligned(16))) uint32_t h[RADIX];
+    __shared__ uint32_t scratch[8];
+    __shared__ uint32_t sel[3];
+    __shared__ uint32_t wcnt[2][TR_WAVES];
+    const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    uint32_t count = ws.state[TS_BLOCK];
+    if (count > ws.nseg) count = ws.nseg;
+    for (uint32_t t = blockIdx.x; t < count; t += gridDim.x) {   // (t and everything decided from it are uniform: the barriers are safe)
+        uint32_t base, len, seg, row;
+        if (!ts_load_rec(ws.list[TS_BLOCK], t, num_items, ws.nseg, TR_CH, base, len, seg, row)) continue;
+        const uint32_t kept = k < len ? k : len;
+        I img[TR_KPT];
+        ta_load_tile<KT>(keys + base, first, len, flt, x, img);
+        uint32_t less;
+        const I kth = tr_select<KT::BITS>(img, first, len, kept, tid, h, scratch, sel, less);
+        const size_t out0 = (size_t)seg * k;
+        ta_place<KT, HV>(img, first, len, kept, kth, less, 0u, less, w, lane, wcnt, dst_k + out0, HV ? dst_c + out0 : nullptr, 0u, flt, x);
+        if (tid == 0u) end[seg] = (int32_t)(seg * k + kept);
+    }
+}
+
+// The histograms of the long records in use start at zero; every pick leaves them so for the next round.
+__global__ __launch_bounds__(256) void topk_seganyk_clear_kernel(TsWs ws, uint32_t *__restrict__ hist)
+{
+    const uint32_t nrec = tsa_rec_count(ws);
+    for (uint32_t r = blockIdx.x; r < nrec; r += gridDim.x) {
+        uint4 *__restrict__ h = reinterpret_cast<uint4 *>(hist + (size_t)r * TaWidth<32>::BINS);
+        for (uint32_t i = threadIdx.x; i < TaWidth<32>::BINS / 4u; i += 256u) h[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+// A counting round: the workgroup that meets the first task of a slab histograms the slab's tiles in LDS and adds its non-zero
+// bins to the record's histogram (integer adds: the sums do not depend on their order).
+template <typename KT, int ROUND>
+__global__ __launch_bounds__(TR_THREADS) void topk_seganyk_count_kernel(TsWs ws, const typename KT::T *__restrict__ keys,
+                                                                        const uint32_t *__restrict__ state, uint32_t *__restrict__ hist,
+                                                                        uint32_t num_items, int flt, uint32_t x32)
+{
+    using I = typename KT::I;
+    using R = TaRound<KT::BITS, ROUND>;
+    const I x = KT::xmask(x32);
+    __shared__ uint32_t h[TA_LDS_WORDS];
+    const uint32_t tid = threadIdx.x, w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    const uint32_t count = tsa_task_count(ws), nrec = tsa_rec_count(ws);
+    // Workgroup b starts at slot (b % q) * TA_SLAB_TILES + b / q, q a TA_SLAB_TILES-th of the grid (a multiple of it): where every
+    // segment is a whole number of slabs, the slots that start a slab are those of the first q workgroups -- consecutive ones,
+    // which the dispatcher spreads over all dies -- and not every TA_SLAB_TILES-th one.
+    const uint32_t q = gridDim.x / TA_SLAB_TILES;
+    for (uint32_t t = (blockIdx.x % q) * TA_SLAB_TILES + blockIdx.x / q; t < count; t += gridDim.x) {
+        uint32_t rec, c, base, slen, seg, chunks;
+        if (!tsa_load_task(ws, t, nrec, num_items, rec, c, base, slen, seg, chunks)) continue;
+        if (c % TA_SLAB_TILES != 0u) continue;   // the slab belongs to the workgroup of its first task
+        for (uint32_t i = tid; i < R::BINS; i += TR_THREADS) h[i] = 0;
+        const uint32_t prefix = ROUND == 0 ? 0u : state[(size_t)rec * TA_STATE_WORDS];
+        __syncthreads();
+        const uint32_t c1 = c + TA_SLAB_TILES < chunks ? c + TA_SLAB_TILES : chunks;
+        for (uint32_t tile = c; tile < c1; ++tile) {
+            const uint32_t lo = tile * TA_TILE, len = slen - lo < TA_TILE ? slen - lo : TA_TILE;
+            I img[TR_KPT];
+            ta_load_tile<KT>(keys + (size_t)base + lo, first, len, flt, x, img);
+#pragma unroll
+            for (int u = 0; u < TR_KPT; ++u) {
+                const uint32_t j = first + (uint32_t)u * WAVE;
+                if (j < len && (((uint32_t)img[u] ^ prefix) & R::MASK) == 0u) hist_add(h, ((uint32_t)img[u] >> R::SHIFT) & (R::BINS - 1u));
+            }
+        }
+        __syncthreads();
+        uint32_t *__restrict__ g = hist + (size_t)rec * TaWidth<KT::BITS>::BINS;
+        for (uint32_t i = tid; i < R::BINS; i += TR_THREADS) {   // a wave over contiguous bins; only what this slab holds
+            const uint32_t v = h[i];
+            if (v) atomicAdd(g + i, v);
+        }
+        __syncthreads();   // h is read before the next slab clears it
+    }
+}
+
+// A pick: one workgroup of 256 per long record, topk_anyk_pick_kernel's body with krem = min(k, len) in the first round.
+template <int BITS, int ROUND>
+__global__ __launch_bounds__(256) void topk_seganyk_pick_kernel(TsWs ws, uint32_t *__restrict__ state, uint32_t *__restrict__ hist,
+                                                                uint32_t num_items, uint32_t k)
+{
+    using W = TaWidth<BITS>;
+    using R = TaRound<BITS, ROUND>;
+    constexpr uint32_t PER = R::BINS / 256u;
+    __shared__ uint32_t scratch[8];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nrec = tsa_rec_count(ws);
+    for (uint32_t r = blockIdx.x; r < nrec; r += gridDim.x) {
+        uint32_t base, slen, seg, row, chunks;
+        if (!tsa_load_long(ws, r, num_items, base, slen, seg, row, chunks)) continue;
+        uint32_t *__restrict__ h = hist + (size_t)r * W::BINS + tid * PER;
+        uint32_t *__restrict__ st = state + (size_t)r * TA_STATE_WORDS;
+        const uint32_t prefix = ROUND == 0 ? 0u : st[0], less = ROUND == 0 ? 0u : st[1], krem = ROUND == 0 ? (k < slen ? k : slen) : st[2];
+        uint32_t c[PER], sum = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < PER; ++i) { c[i] = h[i]; sum += c[i]; }
+#pragma unroll
+        for (uint32_t i = 0; i < PER; ++i) h[i] = 0;
+        uint32_t ex = block_exclusive_scan_256(sum, scratch, nullptr);   // (its barriers: every thread has read the record before one writes it)
+#pragma unroll
+        for (uint32_t i = 0; i < PER; ++i) {
+            if (ex < krem && krem - ex <= c[i]) {   // one bin of the record: the counts of the bins sum to at least krem
+                st[0] = prefix | ((tid * PER + i) << R::SHIFT);
+                st[1] = less + ex;
+                st[2] = krem - ex;
+                if (ROUND + 1 < W::ROUNDS) st[4 + ROUND] = c[i];
+            }
+            ex += c[i];
+        }
+        if (ROUND == 0 && tid == 0) { st[3] = 0; st[6] = 0; st[7] = 0; }
+    }
+}
+
+// The select's counts: per task the elements of its tile before the k-th image and those equal to it.
+template <typename KT>
+__global__ __launch_bounds__(TR_THREADS) void topk_seganyk_tilecount_kernel(TsWs ws, const typename KT::T *__restrict__ keys,
+                                                                            const uint32_t *__restrict__ state, uint2 *__restrict__ counts,
+                                                                            uint32_t num_items, int flt, uint32_t x32)
+{
+    using I = typename KT::I;
+    const I x = KT::xmask(x32);
+    __shared__ uint32_t wcnt[2][TR_WAVES];
+    const uint32_t w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    const uint32_t count = tsa_task_count(ws), nrec = tsa_rec_count(ws);
+    for (uint32_t t = blockIdx.x; t < count; t += gridDim.x) {
+        uint32_t rec, c, base, slen, seg, chunks;
+        if (!tsa_load_task(ws, t, nrec, num_items, rec, c, base, slen, seg, chunks)) continue;
+        const uint32_t lo = c * TA_TILE, len = slen - lo < TA_TILE ? slen - lo : TA_TILE;
+        const I kth = state[(size_t)rec * TA_STATE_WORDS];
+        I img[TR_KPT];
+        ta_load_tile<KT>(keys + (size_t)base + lo, first, len, flt, x, img);
+        uint32_t nA = 0, nB = 0;
+#pragma unroll
+        for (int u = 0; u < TR_KPT; ++u) {
+            const uint32_t j = first + (uint32_t)u * WAVE;
+            nA += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(j < len && img[u] < kth));
+            nB += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(j < len && img[u] == kth));
+        }
+        if (lane == 0) { wcnt[0][w] = nA; wcnt[1][w] = nB; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t a = 0, b = 0;
+            for (int q = 0; q < TR_WAVES; ++q) { a += wcnt[0][q]; b += wcnt[1][q]; }
+            counts[t] = make_uint2(a, b);
+        }
+        __syncthreads();   // wcnt is read before the next task writes it
+    }
+}
+
+// The select's scan: one workgroup of 256 per long record turns its tasks' counts into bases, group A from 0, group B from less,
+// and writes the end of the segment's range of the finish -- here, for the records that found room, and nowhere else.
+__global__ __launch_bounds__(256) void topk_seganyk_scan_kernel(TsWs ws, const uint32_t *__restrict__ state, uint2 *__restrict__ counts,
+                                                                int32_t *__restrict__ end, uint32_t num_items, uint32_t k)
+{
+    __shared__ uint32_t scratch[8];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t nrec = tsa_rec_count(ws);
+    for (uint32_t r = blockIdx.x; r < nrec; r += gridDim.x) {
+        uint32_t base0, slen, seg, row, tiles;
+        if (!tsa_load_long(ws, r, num_items, base0, slen, seg, row, tiles)) continue;
+        uint2 *__restrict__ c = counts + row;
+        uint32_t carryA = 0, carryB = state[(size_t)r * TA_STATE_WORDS + 1];
+        for (uint32_t base = 0; base < tiles; base += 256u) {
+            const uint32_t i = base + tid;
+            const uint2 v = i < tiles ? c[i] : make_uint2(0u, 0u);
+            uint32_t totA, totB;
+            const uint32_t exA = block_exclusive_scan_256(v.x, scratch, &totA);
+            const uint32_t exB = block_exclusive_scan_256(v.y, scratch, &totB);
+            if (i < tiles) c[i] = make_uint2(carryA + exA, carryB + exB);
+            carryA += totA; carryB += totB;
+        }
+        if (tid == 0u) end[seg] = (int32_t)(seg * k + (k < slen ? k : slen));
+    }
+}
+
+// The select's scatter: per task, its tile's part of the two groups, at the scanned bases.
+template <typename KT, bool HV>
+__global__ __launch_bounds__(TR_THREADS) void topk_seganyk_scatter_kernel(TsWs ws, const typename KT::T *__restrict__ keys,
+                                                                          const uint32_t *__restrict__ state, const uint2 *__restrict__ counts,
+                                                                          typename KT::T *__restrict__ dst_k, uint32_t *__restrict__ dst_c,
+                                                                          uint32_t num_items, uint32_t k, int flt, uint32_t x32)
+{
+    using I = typename KT::I;
+    const I x = KT::xmask(x32);
+    __shared__ uint32_t wcnt[2][TR_WAVES];
+    const uint32_t w = (uint32_t)wave_id(), lane = (uint32_t)lane_id();
+    const uint32_t first = w * (uint32_t)(WAVE * TR_KPT) + lane;
+    const uint32_t count = tsa_task_count(ws), nrec = tsa_rec_count(ws);
+    for (uint32_t t = blockIdx.x; t < count; t += gridDim.x) {
+        uint32_t rec, c, base, slen, seg, chunks;
+        if (!tsa_load_task(ws, t, nrec, num_items, rec, c, base, slen, seg, chunks)) continue;
+        const uint32_t lo = c * TA_TILE, len = slen - lo < TA_TILE ? slen - lo : TA_TILE, kept = k < slen ? k : slen;
+        const I kth = state[(size_t)rec * TA_STATE_WORDS];
+        const uint32_t less = __builtin_amdgcn_readfirstlane(state[(size_t)rec * TA_STATE_WORDS + 1]);
+        const uint2 at = counts[t];
+        if (__builtin_amdgcn_readfirstlane(at.x >= less && at.y >= kept)) continue;   // both groups are full before this tile
+        I img[TR_KPT];
+        ta_load_tile<KT>(keys + (size_t)base + lo, first, len, flt, x, img);
+        const size_t out0 = (size_t)seg * k;
+        ta_place<KT, HV>(img, first, len, kept, kth, less, at.x, at.y, w, lane, wcnt, dst_k + out0, HV ? dst_c + out0 : nullptr, lo, flt, x);
+    }
+}
+
+// The pairs form's last step, over the ranges of the finish only: vals_out[seg * k + i] = vals_in[b + position], b the
+// segment's clamped begin.  (A wave-class segment's range is empty: its slots already hold values.)
+__global__ __launch_bounds__(256) void topk_seganyk_gather_kernel(const uint32_t *__restrict__ vals_in, const uint32_t *__restrict__ pos,
+                                                                  uint32_t *__restrict__ vals_out, const int32_t *__restrict__ end,
+                                                                  const int *__restrict__ seg_begin, uint32_t nseg, uint32_t num_items,
+                                                                  uint32_t k)
+{
+    for (uint32_t s = blockIdx.x; s < nseg; s += gridDim.x) {
+        const uint32_t out0 = s * k, e = (uint32_t)end[s];
+        if (e <= out0) continue;
+        const uint32_t cnt = e - out0 < k ? e - out0 : k;
+        int lo = seg_begin[s];
+        if (lo < 0) lo = 0;
+        if ((uint32_t)lo >= num_items) continue;
+        const uint32_t last = num_items - 1u - (uint32_t)lo;
+        for (uint32_t i = threadIdx.x; i < cnt; i += 256u) {
+            const uint32_t p = pos[out0 + i];
+            vals_out[out0 + i] = vals_in[(size_t)lo + (p < last ? p : last)];
+        }
+    }
+}
+
+// ---- host
+static inline bool tsa_shape_ok(uint64_t num_items, uint64_t num_segments, uint64_t k)
+{
+    if (num_items >= (1ull << 31)) return false;
+    if (num_segments != 0 && k > 0x7fffffffull / num_segments) return false;   // num_segments * k >= 2^31: the finish has int offsets
+    return true;
+}
+
+// The header's workspace formula, term by term, behind the TsWs front (without candidate rows); returns the bytes carved.
+static size_t tsa_carve(char *base, uint64_t num_items, uint64_t num_segments, uint64_t k, bool hv, bool pairs, TsWs *front, TsaWs *ws)
+{
+    size_t off = ts_carve(base, num_items, num_segments, 0, false, 4, front);
+    const TsGeom g = ts_geom(num_items, num_segments);
+    auto take = [&](size_t bytes) { char *q = (char *)((uintptr_t)base + off); off += gs_ws_align(bytes); return q; };
+    ws->state = (uint32_t *)take((size_t)4 * TA_STATE_WORDS * g.lmax);
+    ws->hist = (uint32_t *)take((size_t)4 * TaWidth<32>::BINS * g.lmax);
+    ws->counts = (uint2 *)take((size_t)8 * g.tmax);
+    ws->begin = (int32_t *)take((size_t)4 * num_segments);
+    ws->end = (int32_t *)take((size_t)4 * num_segments);
+    ws->keys1 = (uint32_t *)take((size_t)4 * num_segments * k);
+    ws->pos1 = hv ? (uint32_t *)take((size_t)4 * num_segments * k) : nullptr;
+    ws->pos0 = pairs ? (uint32_t *)take((size_t)4 * num_segments * k) : nullptr;
+    ws->seg_bytes = gs_segmented_temp_bytes(num_segments * k, hv ? 1 : 0, (uint32_t)num_segments);
+    ws->seg = take(ws->seg_bytes);
+    return off;
+}
+
+// (The size query has no pointers to tell pairs from arguments: with values it holds the first half of the positions too.)
+static size_t tsa_temp_bytes(uint64_t num_items, uint64_t num_segments, uint64_t k, int has_values)
+{
+    if (!tsa_shape_ok(num_items, num_segments, k)) return 0;
+    if (num_items == 0 || num_segments == 0 || k == 0) return 0;
+    TsWs front;
+    TsaWs ws;
+    return tsa_carve(nullptr, num_items, num_segments, k, has_values != 0, has_values != 0, &front, &ws) + GS_WS_SLACK;
+}
+
+// launches before the finish: zero, classify and four wave kernels; offsets and the block kernel; expand, clear, three times
+// (count, pick), tile counts, scan and scatter
+static inline uint32_t tsa_launches(uint32_t groups) { return 6u + ((groups & 2u) ? 2u : 0u) + ((groups & 4u) ? 11u : 0u); }
+
+template <typename KT, int ROUND>
+static void tsa_launch_round(hipStream_t s, const TsWs &front, const TsaWs &ws, uint32_t gt, uint32_t gl, const typename KT::T *ki, uint32_t n,
+                             uint32_t k, int flt, uint32_t x)
+{
+    const uint32_t gc = (gt + TA_SLAB_TILES - 1u) / TA_SLAB_TILES * TA_SLAB_TILES;   // (a workgroup past the last slot returns at once)
+    hipLaunchKernelGGL((topk_seganyk_count_kernel<KT, ROUND>), dim3(gc), dim3(TR_THREADS), 0, s, front, ki, (const uint32_t *)ws.state, ws.hist,
+                       n, flt, x);
+    hipLaunchKernelGGL((topk_seganyk_pick_kernel<KT::BITS, ROUND>), dim3(gl), dim3(256), 0, s, front, ws.state, ws.hist, n, k);
+}
+
+template <typename KT, bool HV>
+static void tsa_launch_select(hipStream_t s, const TsWs &front, const TsaWs &ws, uint32_t groups, const typename KT::T *ki,
+                              typename KT::T *dk, uint32_t *dc, uint32_t n, uint32_t k, int flt, uint32_t x)
+{
+    KernelTimer kt(GS_K_OTHER, s);
+    const uint32_t gb = front.nseg < TS_MAX_GRID ? front.nseg : TS_MAX_GRID;
+    hipLaunchKernelGGL(topk_seganyk_offsets_kernel, dim3((front.nseg + 255u) / 256u), dim3(256), 0, s, ws.begin, ws.end, front.nseg, k);
+    hipLaunchKernelGGL((topk_seganyk_block_kernel<KT, HV>), dim3(gb), dim3(TR_THREADS), 0, s, front, ki, dk, dc, ws.end, n, k, flt, x);
+    if (!(groups & 4u)) return;
+    const uint32_t gl = front.lmax < TS_MAX_GRID ? front.lmax : TS_MAX_GRID, gt = front.tmax < TS_MAX_GRID ? front.tmax : TS_MAX_GRID;
+    hipLaunchKernelGGL(topk_seg_expand_kernel, dim3(gl), dim3(256), 0, s, front, n);
+    hipLaunchKernelGGL(topk_seganyk_clear_kernel, dim3(gl), dim3(256), 0, s, front, ws.hist);
+    tsa_launch_round<KT, 0>(s, front, ws, gt, gl, ki, n, k, flt, x);
+    tsa_launch_round<KT, 1>(s, front, ws, gt, gl, ki, n, k, flt, x);
+    tsa_launch_round<KT, 2>(s, front, ws, gt, gl, ki, n, k, flt, x);
+    hipLaunchKernelGGL((topk_seganyk_tilecount_kernel<KT>), dim3(gt), dim3(TR_THREADS), 0, s, front, ki, (const uint32_t *)ws.state, ws.counts, n,
+                       flt, x);
+    hipLaunchKernelGGL(topk_seganyk_scan_kernel, dim3(gl), dim3(256), 0, s, front, (const uint32_t *)ws.state, ws.counts, ws.end, n, k);
+    hipLaunchKernelGGL((topk_seganyk_scatter_kernel<KT, HV>), dim3(gt), dim3(TR_THREADS), 0, s, front, ki, (const uint32_t *)ws.state,
+                       (const uint2 *)ws.counts, dk, dc, n, k, flt, x);
+}
+
+static int tsa_run(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
+                   uint32_t *d_vals_out, uint32_t *d_counts_out, uint64_t num_items, uint32_t num_segments, const int32_t *d_begin_offsets,
+                   const int32_t *d_end_offsets, uint64_t k, int descending, int key_type, void *stream)
+{
+    using KT = TrKey32;
+    GS_CLEAR_STALE_ERROR();
+    if (!tsa_shape_ok(num_items, num_segments, k)) return hipErrorInvalidValue;
+    if (!KT::type_ok(key_type)) return hipErrorInvalidValue;
+    if (d_vals_in && !d_vals_out) return hipErrorInvalidValue;
+    if (num_items == 0 || num_segments == 0 || k == 0) return hipSuccess;
+    const bool hv = d_vals_out != nullptr, pairs = d_vals_in != nullptr;
+    if (!d_keys_in || !d_keys_out || !d_begin_offsets || !d_end_offsets) return hipErrorInvalidValue;
+    if (!d_temp || temp_bytes < tsa_temp_bytes(num_items, num_segments, k, hv)) return hipErrorInvalidValue;
+    if ((((uintptr_t)d_keys_in | (uintptr_t)d_keys_out | (uintptr_t)d_vals_in | (uintptr_t)d_vals_out | (uintptr_t)d_counts_out |
+          (uintptr_t)d_begin_offsets | (uintptr_t)d_end_offsets) & 3u) != 0)
+        return hipErrorInvalidValue;
+    {   // no array may share a byte with another, except that the two offset arrays (both only read) may: begin + 1 == end is usual
+        const size_t out_elems = (size_t)num_segments * k;
+        const void *arr[7] = {d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_counts_out, d_begin_offsets, d_end_offsets};
+        const size_t bytes[7] = {4 * num_items, 4 * num_items, 4 * out_elems, 4 * out_elems, (size_t)4 * num_segments, (size_t)4 * num_segments,
+                                 (size_t)4 * num_segments};
+        for (int i = 0; i < 7; ++i)
+            for (int j = i + 1; j < 7; ++j)
+                if (!(i == 5 && j == 6) && gs_ranges_overlap(arr[i], bytes[i], arr[j], bytes[j])) return hipErrorInvalidValue;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t n = (uint32_t)num_items, kk = (uint32_t)k;
+    const int flt = KT::is_float(key_type);
+    const uint32_t x = KT::xor_of(key_type, descending);
+    TsWs front;
+    TsaWs ws;
+    tsa_carve(gs_ws_base(d_temp), num_items, num_segments, k, hv, pairs, &front, &ws);
+    const uint32_t groups = ts_groups(num_items);
+
+    hipError_t e = zero_async(front.state, TS_STATE_BYTES, s);
+    if (e != hipSuccess) return (int)e;
+    { KernelTimer kt(GS_K_OTHER, s);
+      const uint32_t g = (num_segments + 1023u) / 1024u;
+      hipLaunchKernelGGL(topk_seg_classify_kernel, dim3(g < 4096u ? g : 4096u), dim3(256), 0, s, front, d_begin_offsets, d_end_offsets, n, kk,
+                         d_counts_out); }
+    {
+        const uint32_t wg = (num_segments + 3u) / 4u, grid = wg < TS_MAX_GRID ? wg : TS_MAX_GRID;
+#define GS_TSA_WAVE(W)                                                                                                    \
+    do {                                                                                                                  \
+        if (hv) ts_launch_wave<KT, W, true>(s, front, grid, d_keys_in, d_vals_in, d_keys_out, d_vals_out, n, kk, flt, x); \
+        else ts_launch_wave<KT, W, false>(s, front, grid, d_keys_in, d_vals_in, d_keys_out, d_vals_out, n, kk, flt, x);   \
+    } while (0)
+        GS_TSA_WAVE(1); GS_TSA_WAVE(4); GS_TSA_WAVE(8); GS_TSA_WAVE(16);
+#undef GS_TSA_WAVE
+    }
+    int err = (int)hipGetLastError();
+    if (err || !(groups & 2u)) return err;   // (num_items <= 1024: every segment is of a wave class, and final)
+
+    // the selects stage a segment's kept (key, position) pairs at [seg * k, seg * k + kept): the keys in d_keys_out, the positions
+    // in d_vals_out (arguments) or in the workspace (pairs)
+    uint32_t *pos0 = !hv ? nullptr : pairs ? ws.pos0 : d_vals_out;
+    if (hv) tsa_launch_select<KT, true>(s, front, ws, groups, d_keys_in, d_keys_out, pos0, n, kk, flt, x);
+    else tsa_launch_select<KT, false>(s, front, ws, groups, d_keys_in, d_keys_out, pos0, n, kk, flt, x);
+    err = (int)hipGetLastError();
+    if (err) return err;
+
+    // the finish: four passes over the whole image leave the result in half 0, where the pairs were staged
+    uint32_t *dk[2] = {d_keys_out, ws.keys1};
+    uint32_t *dv[2] = {pos0, ws.pos1};
+    int selector = 0;
+    err = gs_segmented_sort_u32(ws.seg, ws.seg_bytes, dk, hv ? dv : nullptr, &selector, (uint64_t)num_segments * kk, num_segments, ws.begin,
+                                ws.end, 0, 32, descending, key_type, s);
+    if (err) return err;
+    if (selector != 0) return hipErrorUnknown;
+    if (pairs) {
+        KernelTimer kt(GS_K_OTHER, s);
+        hipLaunchKernelGGL(topk_seganyk_gather_kernel, dim3(num_segments < TS_MAX_GRID ? num_segments : TS_MAX_GRID), dim3(256), 0, s, d_vals_in,
+                           (const uint32_t *)ws.pos0, d_vals_out, (const int32_t *)ws.end, d_begin_offsets, num_segments, n, kk);
+    }
+    return (int)hipGetLastError();
+}
+
+static int tsa_plan(uint64_t num_items, uint32_t num_segments, uint64_t k, uint32_t out[8])
+{
+    if (!out) return hipErrorInvalidValue;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!tsa_shape_ok(num_items, num_segments, k)) return hipErrorInvalidValue;
+    if (num_items == 0 || num_segments == 0 || k == 0) return hipSuccess;   // such a call enqueues nothing
+    const TsGeom g = ts_geom(num_items, num_segments);
+    out[0] = ts_groups(num_items); out[1] = tsa_launches(out[0]); out[2] = TR_CH; out[3] = TA_TILE; out[4] = TA_SLAB_TILES;
+    out[5] = (uint32_t)g.lmax; out[6] = (uint32_t)g.tmax;
+    return hipSuccess;
+}
+
+static int tsa_status(void *d_temp, uint64_t num_items, uint32_t num_segments, uint64_t k, uint32_t out[8], void *stream)
+{
+    GS_CLEAR_STALE_ERROR();
+    if (!out) return hipErrorInvalidValue;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (!tsa_shape_ok(num_items, num_segments, k)) return hipErrorInvalidValue;
+    if (num_items == 0 || num_segments == 0 || k == 0) return hipSuccess;   // such a call enqueued nothing
+    if (!d_temp) return hipErrorInvalidValue;
+    uint32_t st[16];   // the state block is the first term of the workspace
+    hipError_t e = hipMemcpyAsync(st, gs_ws_base(d_temp), sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    for (int q = 0; q < 5; ++q) out[q] = st[q];
+    out[5] = st[TS_LONG_OK]; out[6] = st[TS_TASKS_OK]; out[7] = st[TS_DROPPED];
+    return hipSuccess;
+}
+
 }  // namespace gs
 
 using namespace gs;
@@ -2298,6 +2785,33 @@ int gs_topk_rows_anyk_u64_status(void *d_temp, uint64_t num_rows, uint64_t num_c
                                  uint32_t out[8], void *stream)
 {
     return ta_status<TrKey64>(d_temp, num_rows, num_cols, k, has_values, row, out, stream);
+}
+
+size_t gs_topk_segmented_anyk_temp_bytes(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values)
+{
+    return tsa_temp_bytes(num_items, num_segments, k, has_values);
+}
+
+int gs_topk_segmented_anyk_u32(void *d_temp, size_t temp_bytes, const uint32_t *d_keys_in, const uint32_t *d_vals_in, uint32_t *d_keys_out,
+                               uint32_t *d_vals_out, uint32_t *d_counts_out, uint64_t num_items, uint32_t num_segments,
+                               const int32_t *d_begin_offsets, const int32_t *d_end_offsets, uint64_t k, int descending, int key_type,
+                               void *stream)
+{
+    return tsa_run(d_temp, temp_bytes, d_keys_in, d_vals_in, d_keys_out, d_vals_out, d_counts_out, num_items, num_segments, d_begin_offsets,
+                   d_end_offsets, k, descending, key_type, stream);
+}
+
+int gs_topk_segmented_anyk_plan(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values, uint32_t out[8])
+{
+    (void)has_values;
+    return tsa_plan(num_items, num_segments, k, out);
+}
+
+int gs_topk_segmented_anyk_status(void *d_temp, uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values, uint32_t out[8],
+                                  void *stream)
+{
+    (void)has_values;
+    return tsa_status(d_temp, num_items, num_segments, k, out, stream);
 }
 
 }  // extern "C"

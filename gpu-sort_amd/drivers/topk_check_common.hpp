@@ -1,7 +1,7 @@
 // topk_check_common.hpp -- what the topk_*_check programs share: the HIP_OK macro, the printed names of the ten key types, the
 // order-preserving image of a key at its width, the generator of a case's input, and the two cases that more than one program
 // runs: the rows case against std::stable_sort (topk_rows_narrow / _wide / _anyk_check) and the segmented case against
-// gpusort::DeviceTopK (topk_segmented_check / _narrow_check).  The programs with a reference of their own keep their case and
+// gpusort::DeviceTopK (topk_segmented_check / _narrow_check / _anyk_check).  The programs with a reference of their own keep their case and
 // take the rest from here; every program states its types, shapes, k's, directions, inputs and seed itself.
 #pragma once
 #include <algorithm>
@@ -151,11 +151,13 @@ static int rows_case(size_t rows, size_t cols, size_t k, bool descending, int sp
 // The ragged set of the segmented case, as int32 begins and ends into n keys: every list of the classify kernel (empty, one
 // wave of each class, one workgroup, chunked), laid out in the order listed with a gap of 5 between them, so that segments
 // start at odd elements, but the longest one first in memory; then a repeat, two segments that need clamping and one whose
-// end lies before its begin.
-static size_t ragged_segments(std::vector<int> &begin, std::vector<int> &end)
+// end lies before its begin.  more: two further segments in front of the longest, of 8193 elements and of 3 tiles + 1.
+static size_t ragged_segments(std::vector<int> &begin, std::vector<int> &end, bool more = false)
 {
-    const size_t lens[] = {0, 1, 64, 65, 256, 300, 512, 700, 1024, 1025, 5000, 8192, 8193, 20000, 40000};
-    const size_t S0 = sizeof(lens) / sizeof(lens[0]);
+    std::vector<size_t> lens = {0, 1, 64, 65, 256, 300, 512, 700, 1024, 1025, 5000, 8192, 8193, 20000};
+    if (more) { lens.push_back(8193); lens.push_back(3 * 8192 + 1); }
+    lens.push_back(40000);
+    const size_t S0 = lens.size();
     std::vector<size_t> at(S0);
     at[S0 - 1] = 3;
     size_t n = 3 + lens[S0 - 1] + 5;
@@ -171,13 +173,15 @@ static size_t ragged_segments(std::vector<int> &begin, std::vector<int> &end)
 // The segmented case: ragged_segments() through gpusort::DeviceTopKSegmented in one call and segment by segment through
 // gpusort::DeviceTopK at k = min(k, length), in the keys, pairs and arguments forms.  Every segment's first count elements and
 // the counts must agree bit for bit, the slots behind a segment's count must keep their fill, and the size the shim asks for
-// must be that of `size_query`.  Prints one line per form and returns the number that failed.
-template <typename KeyT, typename SizeQuery>
-static int segmented_case(size_t k, bool descending, int spread, uint64_t seed, const Inputs<word_of<KeyT>> &in, SizeQuery size_query)
+// must be that of `size_query`.  Prints one line per form and returns the number that failed.  D: the shim class of the one
+// call (gpusort::DeviceTopKSegmentedAnyK in topk_segmented_anyk_check, which also asks for the longer ragged set).
+template <typename KeyT, typename SizeQuery, typename D = gpusort::DeviceTopKSegmented>
+static int segmented_case(size_t k, bool descending, int spread, uint64_t seed, const Inputs<word_of<KeyT>> &in, SizeQuery size_query,
+                          D = D(), bool more = false)
 {
     typedef word_of<KeyT> W;
     std::vector<int> begin, end;
-    const size_t n = ragged_segments(begin, end), S = begin.size();
+    const size_t n = ragged_segments(begin, end, more), S = begin.size();
     std::mt19937_64 rng(seed);
     std::vector<W> h_keys(n);
     std::vector<unsigned int> h_vals(n);
@@ -205,8 +209,7 @@ static int segmented_case(size_t k, bool descending, int spread, uint64_t seed, 
         void *d_temp = nullptr;
         size_t temp_bytes = 0;
         auto run = [&]() -> hipError_t {
-            return top<gpusort::DeviceTopKSegmented>(mode, descending, d_temp, temp_bytes, d_in, d_seg, vin, d_seg_v, d_counts, n, (uint32_t)S,
-                                                     d_begin, d_end, k);
+            return top<D>(mode, descending, d_temp, temp_bytes, d_in, d_seg, vin, d_seg_v, d_counts, n, (uint32_t)S, d_begin, d_end, k);
         };
         HIP_OK(run());
         if (temp_bytes == 0) { printf("size query refused n=%zu S=%zu k=%zu\n", n, S, k); return 1; }

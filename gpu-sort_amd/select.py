@@ -13,9 +13,10 @@
     DeviceTopKSegmented     gs_topk_segmented_u32     int32, float32, uint32
                             gs_topk_segmented_u16     int16, uint16, float16, bfloat16
     DeviceTopKSegmented64   gs_topk_segmented_u64     int64, float64, uint64
+    DeviceTopKSegmentedAnyK gs_topk_segmented_anyk_u32  int32, float32, uint32; any k
 
 The classes are two-phase like DeviceRadixSort (d_temp_storage=None returns the size); topk(), topk_rows(), topk_rows64(),
-topk_rows_anyk(), topk_rows_anyk16(), topk_rows_anyk64(), topk_segmented() and topk_segmented64() allocate outputs and workspace, topk() for any of the three widths.
+topk_rows_anyk(), topk_rows_anyk16(), topk_rows_anyk64(), topk_segmented(), topk_segmented64() and topk_segmented_anyk() allocate outputs and workspace, topk() for any of the three widths.
 The result is exactly the first k elements of DeviceRadixSort.SortKeys / SortPairs (descending for the Max forms) on the same
 input (the whole array, every row of a matrix, every ragged segment given by device offsets): stable, keys in the caller's bit
 patterns, floats in the order of GS_KEY_F32 (negative NaNs first, positive NaNs last ascending; -0.0 before +0.0), float16 /
@@ -502,23 +503,8 @@ def _topk_rows_anyk(who, front, keys, k, largest, values, indices, stream):
     return keys_out, values_out
 
 
-class DeviceTopKSegmented(_Front):
-    """MinKeys / MaxKeys / MinPairs / MaxPairs for every segment of a flat array (gs_topk_segmented_u32): segment s is
-    d_keys_in[d_begin_offsets[s] .. d_end_offsets[s]) (int32 offsets on the device, clamped to [0, num_items] there), and its
-    min(k, length) smallest (largest), sorted, go to d_keys_out[s * k ..) with their values; d_counts_out[s] (may be None) gets
-    that number, and the slots behind it are not written.
-
-    d_values_in=None in the pairs forms writes the elements' positions within their segment (u32 bit patterns).  Each
-    segment's result is what DeviceTopK gives for that segment alone.  Two-phase like DeviceTopKRows: d_temp_storage=None
-    returns the size, which is 0 for a shape the entry point refuses (k > MaxK(), num_items >= 2^31, ...).
-
-    2-byte key tensors (int16, uint16, float16, bfloat16, or an explicit 16-bit key_type) go to gs_topk_segmented_u16: the same
-    definition on the 16-bit image, values, counts and offsets still 4 bytes.  The size query (d_temp_storage=None) sees no
-    tensor: with a 16-bit key_type it answers for gs_topk_segmented_u16, without one for gs_topk_segmented_u32, which is never
-    the smaller of the two.  Plan() and Status() serve both widths."""
-
-    _entries = {_W32: ("gs_topk_segmented_u32", "gs_topk_segmented_temp_bytes"),
-                _W16: ("gs_topk_segmented_u16", "gs_topk_segmented_u16_temp_bytes")}
+class _TopKSegmented(_Front):
+    """The ragged shape: the call and its four forms, for the classes that state the entry points."""
 
     @classmethod
     def _run(cls, d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, d_counts_out, num_items,
@@ -571,6 +557,25 @@ class DeviceTopKSegmented(_Front):
         return cls._run(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out, d_counts_out, num_items,
                         num_segments, d_begin_offsets, d_end_offsets, k, True, True, stream, key_type)
 
+
+class DeviceTopKSegmented(_TopKSegmented):
+    """MinKeys / MaxKeys / MinPairs / MaxPairs for every segment of a flat array (gs_topk_segmented_u32): segment s is
+    d_keys_in[d_begin_offsets[s] .. d_end_offsets[s]) (int32 offsets on the device, clamped to [0, num_items] there), and its
+    min(k, length) smallest (largest), sorted, go to d_keys_out[s * k ..) with their values; d_counts_out[s] (may be None) gets
+    that number, and the slots behind it are not written.
+
+    d_values_in=None in the pairs forms writes the elements' positions within their segment (u32 bit patterns).  Each
+    segment's result is what DeviceTopK gives for that segment alone.  Two-phase like DeviceTopKRows: d_temp_storage=None
+    returns the size, which is 0 for a shape the entry point refuses (k > MaxK(), num_items >= 2^31, ...).
+
+    2-byte key tensors (int16, uint16, float16, bfloat16, or an explicit 16-bit key_type) go to gs_topk_segmented_u16: the same
+    definition on the 16-bit image, values, counts and offsets still 4 bytes.  The size query (d_temp_storage=None) sees no
+    tensor: with a 16-bit key_type it answers for gs_topk_segmented_u16, without one for gs_topk_segmented_u32, which is never
+    the smaller of the two.  Plan() and Status() serve both widths."""
+
+    _entries = {_W32: ("gs_topk_segmented_u32", "gs_topk_segmented_temp_bytes"),
+                _W16: ("gs_topk_segmented_u16", "gs_topk_segmented_u16_temp_bytes")}
+
     MaxK = staticmethod(DeviceTopKRows.MaxK)
 
     @staticmethod
@@ -600,8 +605,33 @@ class DeviceTopKSegmented64(DeviceTopKSegmented):
     _entries = {_W64: ("gs_topk_segmented_u64", "gs_topk_segmented_u64_temp_bytes")}
 
 
+class DeviceTopKSegmentedAnyK(_TopKSegmented):
+    """DeviceTopKSegmented without the cap at MaxK() (gs_topk_segmented_anyk_u32): MinKeys / MaxKeys / MinPairs / MaxPairs /
+    Plan / Status for 32-bit keys and any k >= 1, which may exceed every segment's length.
+
+    Each segment's result is what DeviceTopK gives for that segment alone at min(k, length); for k <= DeviceTopKSegmented.MaxK()
+    it is DeviceTopKSegmented's result.  d_counts_out[s] (may be None) gets min(k, length), and the slots behind it are not
+    written.  Two-phase: d_temp_storage=None returns the size, 0 for a shape the entry point refuses (num_items >= 2^31,
+    num_segments * k >= 2^31).  Keys of any other width raise TypeError."""
+
+    _entries = {_W32: ("gs_topk_segmented_anyk_u32", "gs_topk_segmented_anyk_temp_bytes")}
+
+    @staticmethod
+    def Plan(num_items, num_segments, k, has_values=False):
+        """gs_topk_segmented_anyk_plan: [launch groups (bit 0 wave, 1 workgroup, 2 long), kernel launches before the finish, CH,
+        tile, tiles per slab, Lmax, Tmax, 0]; a pure host function.  Raises for a refused shape."""
+        return _eight_words("gs_topk_segmented_anyk_plan", num_items, num_segments, k, int(has_values))
+
+    @staticmethod
+    def Status(d_temp_storage, num_items, num_segments, k, has_values, stream=None):
+        """gs_topk_segmented_anyk_status: [segments in the four wave lists, the workgroup list, the long list, tile tasks,
+        dropped segments] of the last call on d_temp_storage.  Synchronises the stream."""
+        return _eight_words("gs_topk_segmented_anyk_status", C.c_void_p(d_temp_storage.data_ptr()), num_items, num_segments, k,
+                            int(has_values), stream=(_stream_ptr(stream),))
+
+
 def _topk_segmented(who, front, keys, offsets, k, largest, values, indices, stream, end_offsets):
-    """topk_segmented() and topk_segmented64(): the argument checks in the name of `who`, the outputs, and `front`'s call."""
+    """topk_segmented(), topk_segmented64() and topk_segmented_anyk(): the argument checks in the name of `who`, the outputs, and `front`'s call."""
     if values is not None and indices:
         raise ValueError(f"{who}: give values or indices=True, not both")
     w = next((w for w in front._entries if w.elem == keys.element_size()), None)
@@ -628,6 +658,8 @@ def _topk_segmented(who, front, keys, offsets, k, largest, values, indices, stre
     if k == 0 or segs == 0 or n == 0:
         return keys_out, values_out, counts
     nbytes = front._run(None, 0, None, None, None, None, None, n, segs, None, None, k, largest, has_values, stream, key_type)
+    if nbytes == 0 and not hasattr(front, "MaxK"):   # (a front without a cap takes any k)
+        raise ValueError(f"{who}: the entry point refuses this shape (fewer than 2^31 keys, segments * k below 2^31)")
     if nbytes == 0:
         raise ValueError("%s: the entry point refuses this shape (k <= %d, fewer than 2^31 keys, segments * k below 2^32)"
                          % (who, lib.gs_topk_rows_max_k()))
@@ -658,3 +690,16 @@ def topk_segmented64(keys, offsets, k, largest=False, values=None, indices=False
     and end_offsets; values a 4-byte tensor of the keys' length; indices=True for the positions within the segment as int32
     bit patterns of u32.  The keys come back in the input dtype.  Any other key width raises TypeError."""
     return _topk_segmented("topk_segmented64", DeviceTopKSegmented64, keys, offsets, k, largest, values, indices, stream, end_offsets)
+
+
+def topk_segmented_anyk(keys, offsets, k, largest=False, values=None, indices=False, stream=None, end_offsets=None):
+    """topk_segmented() for any k >= 0 in one call (gs_topk_segmented_anyk_u32): the k smallest (largest=True: largest) of every
+    segment of the 1-D tensor `keys` of 4-byte elements, sorted, as (keys_out [S, k], values_out [S, k] or None, counts [S]
+    int32).  k may exceed every segment's length: counts[s] = min(k, length of segment s), and the slots of row s past
+    counts[s] are unspecified.
+
+    The arguments, the checks and the return shapes are topk_segmented()'s: int32 device offsets of S + 1 elements, or begins
+    and end_offsets; values a 4-byte tensor of the keys' length; indices=True for the positions within the segment as int32
+    bit patterns of u32.  2- and 8-byte keys raise TypeError."""
+    return _topk_segmented("topk_segmented_anyk", DeviceTopKSegmentedAnyK, keys, offsets, k, largest, values, indices, stream,
+                           end_offsets)

@@ -962,6 +962,94 @@ int    gs_topk_segmented_plan(uint64_t num_items, uint32_t num_segments, uint64_
 int    gs_topk_segmented_status(void *d_temp, uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values,
                                 uint32_t out[8], void *stream);
 
+/* ----------------------------------------- top k of every ragged segment, any k --
+ * gs_topk_segmented_u32 without the cap at gs_topk_rows_max_k() (gs_topk_rows.hip): the 2000 ... 12000
+ * box scores a detector keeps per image, a few thousand candidates per query, a per-group ORDER BY ... LIMIT 5000, where the
+ * lists rarely have equal lengths.  1 <= k; everything else is gs_topk_segmented_u32's contract word for word.
+ * Segment s is d_keys_in[b .. e) with b = max(d_begin_offsets[s], 0) and e = min(d_end_offsets[s], num_items); it is empty
+ * when e <= b.  The clamping happens on the device.  With len = e - b and kept = min(k, len), d_keys_out[s * k .. s * k + kept)
+ * and the same range of d_vals_out are exactly what gs_topk_u32 writes for that sub-array alone with k = kept, bit for bit:
+ * the first kept of the stable sort on key_type's 32-bit image (GS_KEY_U32 / I32 / F32; complemented when descending), the
+ * lowest positions where the cut falls inside a run of equal keys, the caller's bit patterns kept (the NaN order of the
+ * GS_KEY_F32 note included).  d_counts_out[s] = kept (u32); the array may be NULL.  Output slots [s * k + kept, (s + 1) * k)
+ * are NOT written.
+ * Forms: keys only; pairs (d_vals_out gets d_vals_in[b + position]: d_vals_in is flat and indexed like the keys);
+ * arguments (d_vals_in == NULL, d_vals_out != NULL), where the value written is the element's position within its segment,
+ * counted from the clamped b, as u32.
+ * Segments may come in any order, leave gaps, repeat and, up to CH = 8192 elements each, overlap freely (the input is only
+ * read).  The lengths of the segments LONGER than CH must together not exceed num_items, which holds whenever those segments
+ * do not overlap.  Where they do exceed it, a long segment that finds no room in the workspace is DROPPED: d_counts_out[s] =
+ * 0, nothing of it is written, and gs_topk_segmented_anyk_status counts it (the room is claimed from cursors that only grow:
+ * after one dropped segment, later long ones may be dropped as well).
+ * Plain pointers, inputs and offsets are never written, nothing is written outside [0, num_segments * k) of the outputs,
+ * [0, num_segments) of the counts and the workspace, d_temp anywhere, enqueue-only (no host read-back, allocation or
+ * synchronisation); the launches are a function of (num_items, num_segments, k, has_values) alone
+ * (gs_topk_segmented_anyk_plan reports them without a device), so the call may be captured into a HIP graph on one plain
+ * stream; calls may follow each other on one stream with one workspace; two runs give identical output bytes (the
+ * workspace bytes may differ: the lists are filled in device order); no atomic decides an output position.  num_items == 0,
+ * num_segments == 0 or k == 0 returns 0, writes nothing and needs no workspace (the query returns 0).
+ * Errors (hipErrorInvalidValue, checked before anything is enqueued, nothing written; the size query returns 0 for a
+ * refused shape): num_items >= 2^31 (int offsets), num_segments * k >= 2^31 (the finish has int offsets), a key_type other
+ * than GS_KEY_U32 / I32 / F32, d_vals_in without d_vals_out, NULL keys or NULL offsets, a NULL or too-small workspace, an array
+ * not aligned to 4 bytes, arrays that share a byte (inputs at num_items elements, outputs at num_segments * k, the counts
+ * and the offsets at num_segments; the two offset arrays, both only read, may share bytes with each other, as in
+ * end = begin + 1).  k may exceed num_items or any segment's length: that is what kept is for.  A k of 1024 and below is
+ * served too, with gs_topk_segmented_u32's bytes; gs_topk_segmented_u32 itself keeps refusing k > 1024.
+ * Paths, decided on the device per segment by its length; one classify kernel sorts the segments into gs_topk_segmented_u32's
+ * six lists, with the same Lmax / Tmax bounds and the same drop rule.  Up to 1024 elements: the four wave kernels of
+ * gs_topk_segmented_u32 as they are; their output is final and sorted, and these segments skip the finish.  1025 .. CH: one
+ * workgroup per segment reads it once, selects the kept-th image in registers and LDS and places the kept (key, position)
+ * pairs, equal keys in position order, at s * k.  Longer: one radix select over all long segments at once on their
+ * (segment, tile of 8192) tasks -- three counting rounds on image bits 31-21, 20-10 and 9-0 into 2048 bins per long segment
+ * (a workgroup histograms a slab of consecutive tiles of one segment in LDS before it adds to the bins; one workgroup per
+ * segment picks the bin), then two counts per task, a scan per segment and a scatter in position order: five reads of a
+ * long segment.  The finish is gs_segmented_sort_u32 on the num_segments * k slots, all 32 bits, with the begin offsets s * k
+ * and the end offsets s * k + kept that the two selects wrote (equal to the begin for empty, wave-class and dropped
+ * segments, whose slots it therefore never touches); the pairs form ends with a gather over those ranges.  The host leaves
+ * out only what the arguments exclude: the workgroup kernel, the long-segment kernels and the finish when num_items <= 1024,
+ * the long-segment kernels when num_items <= CH.
+ * Workspace: a pure host function of its arguments, a multiple of 256, monotone in each of them.  With S = num_segments,
+ * n = num_items, Lmax = min(S, n / (CH + 1)), Tmax = n / CH + Lmax (0 when Lmax is 0), hv = 1 with has_values else 0, and
+ * every term rounded up to 256 bytes:
+ *   4096                                      the state block: list counts, the long segments' claim, the dropped word
+ * + 5 * (16 * S)                              the four wave lists and the workgroup list, each sized for S records
+ * + 16 * Lmax                                 the long records
+ * + 8 * Tmax                                  the tile tasks
+ * + 32 * Lmax                                 a record per long segment: k-th image, less, take, 0, matched after rounds one and two, 0, 0
+ * + 4 * 2048 * Lmax                           the long segments' histograms
+ * + 8 * Tmax                                  two u32 counts per task
+ * + 2 * (4 * S)                               the begin and the end offsets of the finish
+ * + 4 * S * k                                 the second half of the staged keys (the first is d_keys_out)
+ * + hv * 4 * S * k                            the second half of the positions (the first is d_vals_out in the arguments form)
+ * + hv * 4 * S * k                            the first half of the positions, used by the pairs form
+ * + gs_segmented_temp_bytes(S * k, has_values, S)
+ * + 256 bytes of alignment slack.
+ * The histograms are at most about one byte per key (4 * 2048 * Lmax <= 8192 * n / 8193); only those of the long segments
+ * in use are zeroed, on the device.  The long-segment areas vanish when n <= CH (Lmax = Tmax = 0).  No element of the input is
+ * copied into the workspace except the kept ones.                                                                          */
+size_t gs_topk_segmented_anyk_temp_bytes(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values);
+int    gs_topk_segmented_anyk_u32(void *d_temp, size_t temp_bytes,
+                                  const uint32_t *d_keys_in, const uint32_t *d_vals_in,
+                                  uint32_t *d_keys_out, uint32_t *d_vals_out, uint32_t *d_counts_out,
+                                  uint64_t num_items, uint32_t num_segments,
+                                  const int32_t *d_begin_offsets, const int32_t *d_end_offsets,
+                                  uint64_t k, int descending, int key_type, void *stream);
+/* What gs_topk_segmented_anyk_u32 launches for a shape: a pure host function (no device, no workspace, no synchronisation).
+ * out[0] = bit mask of the launch groups the call enqueues (bit 0 the wave kernels, bit 1 the workgroup kernel, bit 2 the
+ * long-segment kernels; by num_items, as in gs_topk_segmented_plan), out[1] = kernel launches before the finish (6: the
+ * zeroing, the classify kernel and four wave kernels; 8 with the offsets and the workgroup kernel; 19 with the long segments'
+ * tasks, the clearing of their histograms, three times count and pick, tile counts, scan and scatter), out[2] = CH, out[3] =
+ * the tile (8192), out[4] = tiles per slab, out[5] = Lmax, out[6] = Tmax, out[7] = 0.  A refused shape (num_items >= 2^31,
+ * num_segments * k >= 2^31) returns hipErrorInvalidValue and all zeros; a no-op shape returns 0 and all zeros.             */
+int    gs_topk_segmented_anyk_plan(uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values, uint32_t out[8]);
+/* What the last gs_topk_segmented_anyk_u32 on d_temp (same num_items, num_segments, k and has_values) decided, after
+ * synchronising `stream`, aggregated like gs_topk_segmented_status: out[0..3] = segments in the four wave lists (<= 64,
+ * <= 256, <= 512, <= 1024 elements), out[4] = the workgroup list (1025 .. CH), out[5] = the long list (> CH, dropped ones not
+ * counted), out[6] = tile tasks, out[7] = dropped segments.  All zeros for a no-op shape; hipErrorInvalidValue for a refused
+ * shape or a NULL d_temp or out.  Diagnostic: tests and benches read it.                                                   */
+int    gs_topk_segmented_anyk_status(void *d_temp, uint64_t num_items, uint32_t num_segments, uint64_t k, int has_values,
+                                     uint32_t out[8], void *stream);
+
 /* -------------------------------- top k of every ragged segment, 16-bit keys --
  * gs_topk_segmented_u32 for 16-bit keys, its kernels instantiated for them (gs_topk_rows.hip): bfloat16 or
  * half candidate scores, logits of variable-length sequences, box scores, CSR weights, without widening them.  key_type is

@@ -559,6 +559,67 @@ struct DeviceTopKSegmented {
     }
 };
 
+// DeviceTopKSegmented without the cap at gs_topk_rows_max_k() (gs_topk_segmented_anyk_u32): 32-bit keys (unsigned int, int,
+// float), any k >= 1, which may exceed every segment's length; 32-bit values.  Each segment's result is what DeviceTopK gives for
+// that segment alone at min(k, length); for k <= gs_topk_rows_max_k() it is DeviceTopKSegmented's result.  The forms, the two
+// phases, the counts and the unwritten slots are DeviceTopKSegmented's.  A size query of 0 with a non-empty shape means the
+// shape is refused (num_items >= 2^31, num_segments * k >= 2^31).
+struct DeviceTopKSegmentedAnyK {
+    template <typename KeyT, typename ValueT>
+    static hipError_t Dispatch(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                               const ValueT *d_values_in, ValueT *d_values_out, uint32_t *d_counts_out, uint64_t num_items,
+                               uint32_t num_segments, const int *d_begin_offsets, const int *d_end_offsets, uint64_t k,
+                               bool descending, hipStream_t stream)
+    {
+        static_assert(sizeof(KeyT) == 4 && KeyTraits<KeyT>::type <= GS_KEY_F32, "unsigned int, int or float keys");
+        static_assert(sizeof(ValueT) == 4, "32-bit values only");
+        const bool has_values = d_values_out != nullptr;
+        if (d_temp_storage == nullptr) {
+            temp_storage_bytes = gs_topk_segmented_anyk_temp_bytes(num_items, num_segments, k, has_values);
+            return hipSuccess;
+        }
+        return static_cast<hipError_t>(gs_topk_segmented_anyk_u32(
+            d_temp_storage, temp_storage_bytes, reinterpret_cast<const uint32_t *>(d_keys_in),
+            reinterpret_cast<const uint32_t *>(d_values_in), reinterpret_cast<uint32_t *>(d_keys_out),
+            reinterpret_cast<uint32_t *>(d_values_out), d_counts_out, num_items, num_segments, d_begin_offsets, d_end_offsets, k,
+            descending ? 1 : 0, KeyTraits<KeyT>::type, stream));
+    }
+    template <typename KeyT>
+    static hipError_t MinKeys(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                              uint32_t *d_counts_out, uint64_t num_items, uint32_t num_segments, const int *d_begin_offsets,
+                              const int *d_end_offsets, uint64_t k, hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, uint32_t>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, nullptr, nullptr, d_counts_out,
+                                        num_items, num_segments, d_begin_offsets, d_end_offsets, k, false, stream);
+    }
+    template <typename KeyT>
+    static hipError_t MaxKeys(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                              uint32_t *d_counts_out, uint64_t num_items, uint32_t num_segments, const int *d_begin_offsets,
+                              const int *d_end_offsets, uint64_t k, hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, uint32_t>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, nullptr, nullptr, d_counts_out,
+                                        num_items, num_segments, d_begin_offsets, d_end_offsets, k, true, stream);
+    }
+    template <typename KeyT, typename ValueT>
+    static hipError_t MinPairs(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                               const ValueT *d_values_in, ValueT *d_values_out, uint32_t *d_counts_out, uint64_t num_items,
+                               uint32_t num_segments, const int *d_begin_offsets, const int *d_end_offsets, uint64_t k,
+                               hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, ValueT>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out,
+                                      d_counts_out, num_items, num_segments, d_begin_offsets, d_end_offsets, k, false, stream);
+    }
+    template <typename KeyT, typename ValueT>
+    static hipError_t MaxPairs(void *d_temp_storage, size_t &temp_storage_bytes, const KeyT *d_keys_in, KeyT *d_keys_out,
+                               const ValueT *d_values_in, ValueT *d_values_out, uint32_t *d_counts_out, uint64_t num_items,
+                               uint32_t num_segments, const int *d_begin_offsets, const int *d_end_offsets, uint64_t k,
+                               hipStream_t stream = 0)
+    {
+        return Dispatch<KeyT, ValueT>(d_temp_storage, temp_storage_bytes, d_keys_in, d_keys_out, d_values_in, d_values_out,
+                                      d_counts_out, num_items, num_segments, d_begin_offsets, d_end_offsets, k, true, stream);
+    }
+};
+
 // The stable sort of 2^32 elements and more (gs_lsb_sort_large, num_items < 2^40): DeviceRadixSort's DoubleBuffer overloads
 // with a uint64_t count, for 32- or 64-bit keys with no, 32-bit or 64-bit values, and (gs_lsb_sort_narrow_large) 8- and 16-bit
 // keys with no values or values of 1, 2, 4, 8 or 16 bytes, whose result lands in the alternate buffer.  A struct of its own rather than uint64_t
